@@ -1,16 +1,24 @@
 #!/usr/bin/env python3
 """bench.py -- headline metric of BASELINE.json on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload config3|config4|config5]
+    python bench.py --gpus N --steps K --warmup W [--workload config3|config4|config5] [--full] [--dump-outputs DIR]
 
 `--gpus N` with N > 1 and no launcher around it (no WORLD_SIZE in the environment) starts the N ranks
 itself: N fresh child processes of this script, one per GPU, before this process has touched the GPU;
 rank 0's JSON line is relayed. Under `python -m torch.distributed.run --nproc-per-node N` the ranks
 are the launcher's. Every rank checks that the world it finds is the `--gpus` it was given.
 
-The default (config 3) line also carries `other_workloads`: short runs of config 5 and config 4 in
-the same process, outside config 3's timed region, each with its own value / ms_per_step / roofline /
-cpu_baseline and the same SHA-256 checks (`--no-others` leaves them out, e.g. under rocprofv3).
+A plain run of the default workload does what its headline figure needs: it sets up, warms up, times
+the K steps and prints the line. `--full` adds everything else the line has carried: the first step's
+SHA-256 against the compiled reference's, the sustained run, the drop-in API's rate, the CPU baselines,
+the ranks' PCM checksum and `other_workloads` -- short runs of config 5, config 4, the carrier-FM bank
+and config 2 in the same process, outside config 3's timed region, each with its own value / ms_per_step /
+roofline / cpu_baseline and the same SHA-256 checks (`--no-others` leaves them out, e.g. under rocprofv3).
+
+`--dump-outputs DIR` writes, after the timed steps, the PCM of the last timed step -- what a caller of
+the path would have fetched -- as DIR/pcm.npy (float32, rank 0's; a fixed, seeded sample where it
+would exceed 32 MB). The inputs depend on the arguments only, so two builds can be compared output
+for output.
 
 One step = one pass of the generator hot path over one batch, program state, block buffers and PCM
 resident in HBM:
@@ -238,6 +246,26 @@ def sha256(a):
     return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
 
 
+DUMP_MAX_VALUES = 8 << 20  # 32 MB of float32
+
+
+def dump_outputs(args, R, batch, frames):
+    """--dump-outputs: the PCM of stream 0 as the batch's last run left it in HBM -- the int16 mono frames that run would have
+    fetched -- written as DIR/pcm.npy in float32 (exact), by rank 0. Call after the batch has been synchronised and before it
+    renders again. Longer PCM is cut to a fixed, seeded sample of DUMP_MAX_VALUES frames, in frame order."""
+    if not args.dump_outputs or R.rank != 0:
+        return
+    import numpy as np
+    if not R.cuda:
+        raise SystemExit("--dump-outputs reads the PCM where the device left it: not on a test backend")
+    from saugns_amd import shard
+    pcm = shard.device_pcm_tensor(batch, 0, frames).cpu().numpy().astype(np.float32)
+    if pcm.size > DUMP_MAX_VALUES:
+        pcm = pcm[np.sort(np.random.default_rng(0).choice(pcm.size, DUMP_MAX_VALUES, replace=False))]
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    np.save(os.path.join(args.dump_outputs, "pcm.npy"), pcm)
+
+
 # tests/tools/bench_seqexec.py (tests/test_dist.py) imports this module, sets HARNESS to {"new_batch": fn} and calls main():
 # the N-rank logic of this script -- launcher, sharding, barriers, reductions -- then runs on a box without GPUs over the
 # tests' sequential plan executor. Lines produced that way say so in `data` and measure nothing. Nothing in this file
@@ -413,6 +441,8 @@ def run_bank(args, R, sa, tabs, name, steps=20, warmup=2):
     R.barrier([batch])
     dt = R.max(time.perf_counter() - t0)
     tm = batch.timing_ex()
+    if args.workload == name:  # (not for the same bank among config 3's other_workloads)
+        dump_outputs(args, R, batch, frames)
     batch.close()
     if R.rank != 0:
         return None
@@ -455,13 +485,17 @@ def run_config3(args, R, sa, tabs):
     from saugns_amd import voicebank
     index = json.load(open(os.path.join(GOLDEN, "index.json")))
     sustain = 0 if test_backend() else max(0, args.sustain)
+    # (the script is long enough for the sustained run whether or not it runs: a plain run renders what --full renders)
     seconds = max(1, (args.frames * (args.steps + args.warmup + sustain + 2)) // 44100 + 2)
+    if not args.full:
+        sustain = 0
+    full_size = args.voices == 1024 and args.frames == 441000
     prg = voicebank.config3(n=args.voices, seconds=seconds)
     batch = new_batch(sa, [prg])
-    # what is about to be timed is the reference's render: the first step (the script's first 10 s)
+    # what is about to be timed is the reference's render: the first step (the script's first 10 s), checked with --full
     verified = None
-    pcm = batch.run(args.frames, stereo=False)[0]
-    if args.voices == 1024 and args.frames == 441000:
+    pcm = batch.run(args.frames, stereo=False, fetch=args.full)[0]
+    if args.full and full_size:
         got, want = sha256(pcm[0]), index["configs"]["config3"]["sha256"]
         if got != want:
             raise SystemExit(f"rank {R.rank}: first step's PCM {got[:16]} is not the reference's {want[:16]}")
@@ -478,6 +512,7 @@ def run_config3(args, R, sa, tabs):
     dt_mine = time.perf_counter() - t0
     dt = R.max(dt_mine)
     tm = batch.timing_ex()
+    dump_outputs(args, R, batch, args.frames)
     ranks = R.identity(sa, dt_mine / args.steps * 1e3)
     frames_total = args.frames * args.steps * R.world
     # The same step a thousand times over, a few seconds of nothing but these kernels: what the timed K steps give
@@ -495,13 +530,15 @@ def run_config3(args, R, sa, tabs):
         sustained = {"steps": sustain, "seconds": ds, "ms_per_step": ds / sustain * 1e3,
                      "value": args.frames * sustain * R.world / ds}
     # the only exchange of the whole job is this after-the-fact reduction of
-    # {frames rendered, PCM checksum} for the scaling report (outside the timed region)
-    pcm = batch.run(args.frames, stereo=False)[0]
-    mine = [args.frames * args.steps, int(np.asarray(pcm, dtype=np.int64).sum() & 0x7FFFFFFF)]
-    tally = R.sum(mine)
-    if tally[0] != frames_total or tally[1] != mine[1] * R.world:
-        raise SystemExit(f"rank {R.rank}: ranks disagree on the rendered PCM ({tally} vs {mine} x {R.world})")
-    dropin = dropin_rate(sa, args) if R.world == 1 and not test_backend() and not args.no_dropin else None
+    # {frames rendered, PCM checksum} for the scaling report (outside the timed region; --full)
+    tally = [frames_total, None]
+    if args.full:
+        pcm = batch.run(args.frames, stereo=False)[0]
+        mine = [args.frames * args.steps, int(np.asarray(pcm, dtype=np.int64).sum() & 0x7FFFFFFF)]
+        tally = R.sum(mine)
+        if tally[0] != frames_total or tally[1] != mine[1] * R.world:
+            raise SystemExit(f"rank {R.rank}: ranks disagree on the rendered PCM ({tally} vs {mine} x {R.world})")
+    dropin = dropin_rate(sa, args) if args.full and R.world == 1 and not test_backend() and not args.no_dropin else None
     if R.rank != 0:
         return None
     n_ops = args.voices * 4
@@ -510,7 +547,7 @@ def run_config3(args, R, sa, tabs):
     alg_bytes = (n_ops * 8 + 2) * args.frames
     launch_s = (tm["fast_ms"] / 1e3) / max(1, tm["segments"])
     achieved = alg_bytes / launch_s / 1e9 if launch_s > 0 else 0.0
-    traffic, source, valu, step_bytes = profile_traffic("config3", "fast_kernel<") if verified else (None, None, None, None)
+    traffic, source, valu, step_bytes = profile_traffic("config3", "fast_kernel<") if full_size else (None, None, None, None)
     # What binds this kernel (DESIGN.md 4.1 *Roofline*): vector-instruction issue. `valu` comes from the
     # hash-matched PMC summary (tools/collect_profile.py): SQ_INSTS_VALU_* split the launch's vector instructions by class, each
     # class is priced with the issue cost tools/valu_probe.hip measured on this part (profiles/r05_valu_costs.json; four waves
@@ -556,7 +593,7 @@ def run_config3(args, R, sa, tabs):
                      "hbm_real": {"bytes_per_step": step_bytes, "frac": hbm_real_frac,
                                   "is": "HBM bytes of every kernel of one step (PMC: FETCH_SIZE x 2 + WRITE_SIZE) over the step time, against 8 TB/s"}},
         # the same facts as top-level scalars (the driver's record keeps no nested objects: VERDICT r04 item 6)
-        "first_step_sha_ok": bool(verified), "valu_frac": valu_frac, "hbm_real_frac": hbm_real_frac,
+        "first_step_sha_ok": bool(verified) if args.full else None, "valu_frac": valu_frac, "hbm_real_frac": hbm_real_frac,
         "algorithmic_hbm_frac": achieved / 8000.0,
         "dropin_frames_per_s": dropin["value"] if dropin else None,
         "dropin_create_ms": dropin["phases_ms"]["create"] if dropin else None,
@@ -566,7 +603,7 @@ def run_config3(args, R, sa, tabs):
         "sustained_frames_per_s": sustained["value"] if sustained else None,
         "ranks": ranks,
     }
-    if not args.no_cpu and R.world == 1:
+    if args.full and not args.no_cpu and R.world == 1:
         out["cpu_baseline"] = cpu_reference(lambda: voicebank.config3(n=args.voices, seconds=30),
                                             f"config 3 ({args.voices} voices x depth-3 PM)", args.voices, 4,
                                             tabs, all_cores=True)
@@ -1000,8 +1037,8 @@ def main():
     ap.add_argument("--voices5", type=int, default=4096, help="config5: voices")
     ap.add_argument("--c4-run", type=int, default=0, help="config4: frames per engine run (default: the whole 60 s)")
     ap.add_argument("--c4-frames", type=int, default=0, help="config4 (tests): render only the first frames of each script")
-    ap.add_argument("--sustain", type=int, default=1000, help="config3: steps of the sustained run after the timed region "
-                    "(reported under `sustained`, never `value`; 0: none)")
+    ap.add_argument("--sustain", type=int, default=1000, help="config3 with --full: steps of the sustained run after the timed "
+                    "region (reported under `sustained`, never `value`; 0: none)")
     ap.add_argument("--c5-serial", action="store_true", help="(accepted for old command lines: the default)")
     ap.add_argument("--c5-ordered", action="store_true", help="config5: also measure the steps with script k + 1 issued while script k renders, ordered behind it")
     ap.add_argument("--no-cpu", action="store_true")
@@ -1010,7 +1047,14 @@ def main():
     ap.add_argument("--no-dropin", action="store_true", help="config3: skip the drop-in API's PCIe-inclusive rate")
     ap.add_argument("--no-others", action="store_true", help="config3: no short config 5 / config 4 runs after it")
     ap.add_argument("--force-others", action="store_true", help="tests: the other workloads also beside a reduced config 3")
+    ap.add_argument("--full", action="store_true",
+                    help="config3: also the first step's SHA-256 check, the sustained run, the drop-in rate, the CPU baselines, "
+                         "the ranks' PCM checksum and the other workloads (a plain run times the steps and nothing else)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's PCM as DIR/pcm.npy (float32; config3, config2, fm)")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload in ("config4", "config5"):
+        ap.error("--dump-outputs: --workload config3, config2 or fm (a config 4 or config 5 step ends with its batch closed)")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch_ranks(args.gpus)  # before anything touches the GPU
     defaults = {"config3": (500, 20), "config4": (5, 1), "config5": (5, 1), "config2": (20, 2), "fm": (20, 2)}[args.workload]
@@ -1031,7 +1075,8 @@ def main():
     else:
         out = {"config3": run_config3, "config4": run_config4, "config5": run_config5}[args.workload](args, R, sa, tabs)
     others = {}
-    if args.workload == "config3" and not args.no_others and ((args.voices == 1024 and args.frames == 441000) or args.force_others):
+    if args.workload == "config3" and args.full and not args.no_others and \
+            ((args.voices == 1024 and args.frames == 441000) or args.force_others):
         # the other two BASELINE workloads, every rank alike (their barriers are collective), short runs
         for name, fn in (("config5", run_config5), ("config4", run_config4)):
             if name == "config5" and test_backend():

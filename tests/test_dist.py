@@ -102,11 +102,12 @@ def test_bench_gpus_2_starts_two_ranks_config4(seqexec):
 
 
 def test_bench_gpus_2_starts_two_ranks_config3(seqexec):
+    # (--full: the ranks' after-the-fact PCM checksum is one of the extras of a full line)
     j = _line(_bench(["--gpus", "2", "--voices", "8", "--frames", "4410", "--steps", "2", "--warmup", "1",
-                      "--no-cpu"], seqexec))
+                      "--no-cpu", "--full"], seqexec))
     assert j["n_gpus"] == 2 and j["steps"] == 2 and j["config"]["frames_all_ranks"] == 2 * 2 * 4410
     one = _line(_bench(["--gpus", "1", "--voices", "8", "--frames", "4410", "--steps", "2", "--warmup", "1",
-                        "--no-cpu"], seqexec))
+                        "--no-cpu", "--full"], seqexec))
     assert one["n_gpus"] == 1 and one["config"]["frames_all_ranks"] == 2 * 4410
     # the same bank on every rank: the all-rank checksum is the single rank's, twice
     assert j["config"]["pcm_checksum_all_ranks"] == 2 * one["config"]["pcm_checksum_all_ranks"]
@@ -171,15 +172,28 @@ dist.destroy_process_group()
 def test_bench_gpus_2_default_workload_carries_config4_sharded(seqexec):
     """With N > 1 the default command's line has the north star's multi-GPU case at its top: config 4, 64 renders per GPU
     sharded by seed (here 2 per rank, heads only), next to config 3's value."""
-    j = _line(_bench(["--gpus", "2", "--voices", "8", "--frames", "4410", "--steps", "1", "--warmup", "0", "--no-cpu",
+    j = _line(_bench(["--gpus", "2", "--voices", "8", "--frames", "4410", "--steps", "1", "--warmup", "0", "--no-cpu", "--full",
                       "--force-others", "--renders", "2", "--c4-frames", "11025"], seqexec))
     c4 = j["config4_sharded"]
     assert c4["n_gpus"] == 2 and c4["renders_all_ranks"] == 4 and c4["frames_all_ranks"] == 8 * 4 * 11025  # (eight timed steps of the side workload)
     assert c4["scaling"] == "weak" and c4["value"] > 0
     assert j["other_workloads"]["config4"]["config"]["renders_all_ranks"] == 4
-    one = _line(_bench(["--gpus", "1", "--voices", "8", "--frames", "4410", "--steps", "1", "--warmup", "0", "--no-cpu",
+    one = _line(_bench(["--gpus", "1", "--voices", "8", "--frames", "4410", "--steps", "1", "--warmup", "0", "--no-cpu", "--full",
                         "--force-others", "--renders", "2", "--c4-frames", "11025"], seqexec))
     assert "config4_sharded" not in one and one["other_workloads"]["config4"]["config"]["renders_all_ranks"] == 2
+
+
+def test_bench_plain_line_times_the_steps_and_nothing_else(seqexec):
+    """Without --full the line holds the timed steps' figures and none of the extras: no reference check, sustained run,
+    drop-in rate, CPU baseline, PCM checksum or other workloads (--no-cpu is not given: a plain run has no CPU baseline)."""
+    j = _line(_bench(["--gpus", "1", "--voices", "8", "--frames", "4410", "--steps", "3", "--warmup", "1"], seqexec))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert j[k] is not None, k
+    assert j["steps"] == 3 and j["warmup"] == 1 and j["ms_per_step"] > 0 and j["config"]["frames_all_ranks"] == 3 * 4410
+    assert "cpu_baseline" not in j and "other_workloads" not in j
+    c = j["config"]
+    assert c["first_step_verified"] is None and c["sustained"] is None and c["dropin_value"] is None
+    assert c["pcm_checksum_all_ranks"] is None and j["first_step_sha_ok"] is None
 
 
 def test_bench_under_a_launcher_and_world_mismatch(seqexec):
@@ -228,6 +242,6 @@ def test_bench_gpus_2_on_one_gpu_box_with_cpu_rendezvous():
     g = run(["--gpus", "1", "--workload", "config4", "--renders", "3", "--steps", "1", "--warmup", "0", "--no-cpu", "--gather-pcm"])
     assert g["config"]["pcm_gather"]["renders"] == 3 and g["config"]["pcm_gather"]["backend"] == "nccl"
     env["SAU_BENCH_BACKEND"] = "gloo"
-    k = run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu", "--no-others"])
+    k = run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu", "--no-others", "--full"])
     assert k["n_gpus"] == 2 and k["config"]["frames_all_ranks"] == 2 * 3 * 441000
     assert k["config"]["first_step_verified"]["sha256"].startswith("3211740aca595248")

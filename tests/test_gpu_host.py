@@ -23,8 +23,7 @@ from conftest import need_ref  # noqa: E402
 @pytest.fixture(autouse=True)
 def _hosts_are_here(request):
     """The two host binaries travel to the GPU box prebuilt; without them these tests FAIL (a missing checker must not look
-    like a pass: VERDICT r04 item 6) -- except the one that needs the reference's script files, which exist in the build
-    container only and which says so itself."""
+    like a pass: VERDICT r04 item 6) -- except the parser-crash one, which skips itself without them."""
     if not have_hosts and "crash_the_reference_parser" not in request.node.name:
         pytest.fail("oracle/_ref/saugns_cpu / saugns_gpu are not here: `make -C oracle hosts` where /root/reference exists")
 
@@ -144,16 +143,17 @@ def test_two_generators_at_two_rates(tmp_path):
         assert len(dg) > len(pg)  # 48 kHz against 44.1 kHz
 
 
-REF_SRC = "/root/reference"
+# the reference's script files, stored as they are under tests/golden/scripts/ with their paths in its tree
+SCRIPTS_DIR = os.path.join(ROOT, "tests", "golden", "scripts")
 PARSER_CRASHERS = ("devtests/crashes/testbindmultiple.sau", "devtests/crashes/testbindmultiple2.sau",
                    "devtests/crashes/testbindmultiple3.sau", "devtests/warning/label_without_operator.sau")
 
 
-@pytest.mark.skipif(not have_hosts or not os.path.isdir(os.path.join(REF_SRC, "devtests")),
-                    reason="needs the reference hosts and the reference's script files (build container only)")
+@pytest.mark.skipif(not have_hosts, reason="needs the reference hosts (oracle/_ref/saugns_cpu, saugns_gpu)")
 def test_scripts_that_crash_the_reference_parser_end_both_hosts_alike(tmp_path):
-    """Four scripts of the reference's corpus are outside every fixture because its parser crashes on them (devtests/crashes/
-    is its collection of such cases; no program ever reaches a generator). The parser stays the reference's (SURVEY section 2,
+    """Four scripts of the reference's corpus are outside every program fixture because its parser crashes on them
+    (devtests/crashes/ is its collection of such cases; no program ever reaches a generator); the script files themselves
+    are fixtures under tests/golden/scripts/. The parser stays the reference's (SURVEY section 2,
     out of scope), so the host linked against this library must end exactly as the reference's own does: same signal, no
     output file. No GPU needed -- the crash comes before sau_create_Generator. (The fifth script that used to be skipped,
     alarm-25m, is an ordinary corpus fixture since round 4.)"""
@@ -161,7 +161,7 @@ def test_scripts_that_crash_the_reference_parser_end_both_hosts_alike(tmp_path):
         rc = {}
         for name, exe in (("cpu", CPU), ("gpu", GPU)):
             path = str(tmp_path / f"{name}.wav")
-            out = run(exe, ["-m", "-d", "-r", "44100", "-o", path, os.path.join(REF_SRC, rel)])
+            out = run(exe, ["-m", "-d", "-r", "44100", "-o", path, os.path.join(SCRIPTS_DIR, rel)])
             rc[name] = out.returncode
             assert not os.path.exists(path) or os.path.getsize(path) <= 44, (rel, name)
         assert rc["cpu"] < 0 and rc["gpu"] == rc["cpu"], (rel, rc)  # (negative: ended by a signal -- SIGSEGV here)

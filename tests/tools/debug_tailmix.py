@@ -1,6 +1,6 @@
 """tailmix on / off on a small config-4 batch: where do the PCMs differ?"""
 import os, sys, subprocess
-ROOT = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 import numpy as np
 if len(sys.argv) > 1:

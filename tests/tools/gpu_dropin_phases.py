@@ -1,9 +1,10 @@
 import sys, time, os
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
 import numpy as np
 import saugns_amd as sa
 from saugns_amd import voicebank
-tabs = np.fromfile(os.path.join(os.environ.get("GRAFT_REPO_ROOT", "/root/repo"), "tests/golden/piluts_ref.f32"), dtype="<f4").reshape(12, 2048)
+tabs = np.fromfile(os.path.join(ROOT, "tests/golden/piluts_ref.f32"), dtype="<f4").reshape(12, 2048)
 sa.lib(); sa.set_piluts(tabs)
 prg = voicebank.config3()
 buf = np.zeros(11289, np.int16)

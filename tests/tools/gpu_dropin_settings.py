@@ -1,7 +1,7 @@
 """The drop-in generator's wall time on BASELINE config 3 (create -> 11289-frame calls -> destroy) under its read-ahead settings:
     python tests/tools/gpu_dropin_settings.py            (runs itself once per setting: the settings are read at creation)"""
 import os, subprocess, sys, time
-ROOT = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 if len(sys.argv) > 1 and sys.argv[1] == "one":
     sys.path.insert(0, ROOT)
     import numpy as np

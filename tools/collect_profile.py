@@ -1,7 +1,8 @@
-"""Turn one round's rocprofv3 outputs under gpurun_out/ into the summaries kept in profiles/:
-    python tools/collect_profile.py r01e r01_e
-expects gpurun_out/prof_<tag>/<tag>_kernel_stats.csv, gpurun_out/bench_<tag>.json and the PMC
-passes gpurun_out/pmc_<tag>_{fetch,write,sq,inst}/*_counter_collection.csv."""
+"""Turn one round's rocprofv3 outputs in the folder OUT (tools/profile_round.sh <tag> [OUT]; default profile_out) into the
+summaries kept in profiles/:
+    python tools/collect_profile.py r01e r01_e [OUT]
+expects OUT/prof_<tag>/<tag>_kernel_stats.csv, OUT/bench_<tag>.json and the PMC
+passes OUT/pmc_<tag>_{fetch,write,sq,inst}/*_counter_collection.csv."""
 import collections
 import csv
 import json
@@ -9,8 +10,9 @@ import shutil
 import sys
 
 tag, name = sys.argv[1], sys.argv[2]
-shutil.copy(f"gpurun_out/prof_{tag}/{tag}_kernel_stats.csv", f"profiles/{name}_bench_kernel_stats.csv")
-bench_line = open(f"gpurun_out/bench_{tag}.json").read().strip().splitlines()[-1]
+OUT = sys.argv[3] if len(sys.argv) > 3 else "profile_out"
+shutil.copy(f"{OUT}/prof_{tag}/{tag}_kernel_stats.csv", f"profiles/{name}_bench_kernel_stats.csv")
+bench_line = open(f"{OUT}/bench_{tag}.json").read().strip().splitlines()[-1]
 open(f"profiles/{name}_bench.json", "w").write(bench_line + "\n")
 bench = json.loads(bench_line)
 frames_per_step = bench["config"]["frames_per_step"]
@@ -93,7 +95,7 @@ def valu_side(v, kernel=""):
 
 
 for d, f in (("fetch", "f"), ("write", "w"), ("sq", "s"), ("inst", "i"), ("grbm", "g"), ("cls_a", "a"), ("cls_b", "b")):
-    src = f"gpurun_out/pmc_{tag}_{d}/{f}_counter_collection.csv"
+    src = f"{OUT}/pmc_{tag}_{d}/{f}_counter_collection.csv"
     if not os.path.exists(src):
         continue
     shutil.copy(src, f"profiles/{name}_pmc_{d}_counter_collection.csv")
@@ -116,14 +118,14 @@ for k, v in out["kernels"].items():
         v["valu"] = vs
 json.dump(out, open(f"profiles/{name}_pmc_summary.json", "w"), indent=1)
 # the other workloads' bench lines and kernel statistics, when the round measured them
-if os.path.exists(f"gpurun_out/bench_{tag}_full.json"):
-    open(f"profiles/{name}_bench_full.json", "w").write(open(f"gpurun_out/bench_{tag}_full.json").read().strip().splitlines()[-1] + "\n")
+if os.path.exists(f"{OUT}/bench_{tag}_full.json"):
+    open(f"profiles/{name}_bench_full.json", "w").write(open(f"{OUT}/bench_{tag}_full.json").read().strip().splitlines()[-1] + "\n")
 for wl in ("c5", "c4"):
-    b = f"gpurun_out/bench_{tag}_{wl}.json"
+    b = f"{OUT}/bench_{tag}_{wl}.json"
     if os.path.exists(b):
         line = open(b).read().strip().splitlines()[-1]
         open(f"profiles/{name}_{wl}_bench.json", "w").write(line + "\n")
-    st = f"gpurun_out/prof_{tag}_{wl}/{tag}_{wl}_kernel_stats.csv"
+    st = f"{OUT}/prof_{tag}_{wl}/{tag}_{wl}_kernel_stats.csv"
     if os.path.exists(st):
         shutil.copy(st, f"profiles/{name}_{wl}_kernel_stats.csv")
 # configs 5 and 4: per-kernel HBM bytes and instruction counts (averages per launch), and the bytes of one step --
@@ -131,7 +133,7 @@ for wl in ("c5", "c4"):
 for wl, wname in (("c5", "config5"), ("c4", "config4"), ("fmbank", "fm"), ("config2", "config2")):
     ks = {}
     for d, f in ((wl + "_fetch", "m"), (wl + "_write", "m"), (wl + "_inst", "i"), (wl + "_cls_a", "a"), (wl + "_cls_b", "b"), (wl + "_grbm", "g")):
-        src = f"gpurun_out/pmc_{tag}_{d}/{f}_counter_collection.csv"
+        src = f"{OUT}/pmc_{tag}_{d}/{f}_counter_collection.csv"
         if not os.path.exists(src):
             continue
         agg = collections.defaultdict(lambda: collections.defaultdict(list))
@@ -162,11 +164,11 @@ for wl, wname in (("c5", "config5"), ("c4", "config4"), ("fmbank", "fm"), ("conf
                "hbm_bytes_per_step_corrected": total / 2 if total else None,
                "kernels": ks}, open(f"profiles/{name}_{wl}_pmc_summary.json", "w"), indent=1)
 # running-sum workloads: the sweep's lines, kernel statistics, instruction counts per launch of the single-pass build
-if os.path.exists(f"gpurun_out/sweep_{tag}_fm.txt"):
-    shutil.copy(f"gpurun_out/sweep_{tag}_fm.txt", f"profiles/{name}_fm_sweep.txt")
-if os.path.exists(f"gpurun_out/prof_{tag}_fm/{tag}_fm_kernel_stats.csv"):
-    shutil.copy(f"gpurun_out/prof_{tag}_fm/{tag}_fm_kernel_stats.csv", f"profiles/{name}_fm_kernel_stats.csv")
-src = f"gpurun_out/pmc_{tag}_fm_inst/i_counter_collection.csv"
+if os.path.exists(f"{OUT}/sweep_{tag}_fm.txt"):
+    shutil.copy(f"{OUT}/sweep_{tag}_fm.txt", f"profiles/{name}_fm_sweep.txt")
+if os.path.exists(f"{OUT}/prof_{tag}_fm/{tag}_fm_kernel_stats.csv"):
+    shutil.copy(f"{OUT}/prof_{tag}_fm/{tag}_fm_kernel_stats.csv", f"profiles/{name}_fm_kernel_stats.csv")
+src = f"{OUT}/pmc_{tag}_fm_inst/i_counter_collection.csv"
 if os.path.exists(src):
     agg = collections.defaultdict(lambda: collections.defaultdict(list))
     for r in csv.DictReader(open(src)):
