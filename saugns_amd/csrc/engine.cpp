@@ -73,6 +73,7 @@ Engine *Engine::create(const sauProgram *const *prgs, size_t n_prgs, uint32_t sr
 	if (const char *lt = getenv("SAU_AMD_LOOP_TAILS")) e->loop_tails_ = atoi(lt) != 0;
 	e->plan_cache_ = tune_env("SAU_AMD_NO_PLAN_CACHE") == nullptr;
 	e->plan_check_ = tune_env("SAU_AMD_PLAN_CHECK") != nullptr; /* tests: every cached plan against a fresh compile */
+	e->poison_ = tune_env("SAU_AMD_POISON") != nullptr; /* tests: PCM and voice rows filled with a pattern ahead of every run */
 	e->plan_refs_.resize(vo_base);
 	BackendConfig cfg;
 	cfg.srate = srate;
@@ -627,6 +628,7 @@ bool Engine::run(int16_t *const *host_bufs, size_t buf_len, bool stereo,
 		reserved_frames_ = want;
 		reserved_stereo_ = stereo || reserved_stereo_;
 	}
+	if (poison_ && !backend_->poison_run(total, stereo, err)) return false;
 	/* (generator.c:911-914, the buffer cleared ahead of the call: render_segment clears what the mixers leave) */
 	for (Stream &st : streams_) { st.call_gen = 0; st.part_start = 0; st.part_gen = 0; }
 	{

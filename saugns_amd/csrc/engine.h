@@ -112,6 +112,10 @@ public:
 	 * behind a stream's last voice and the segments nothing sounds in are cleared, ordered with the rendering like any device work) */
 	virtual bool zero_pcm(uint32_t first_stream, uint32_t n_streams, uint32_t first_frame, uint32_t n_frames, bool stereo,
 			std::string &err) = 0;
+	/* tests (SAU_AMD_POISON): a run of `frames` frames is about to start -- fill the streams' whole PCM rows with a pattern
+	 * no mixer writes (0x5a5a), so that a frame that is neither mixed nor cleared by zero_pcm shows in the PCM instead of the
+	 * previous run's, usually correct, data. Called after any reserve_frames and before the run's first segment. */
+	virtual bool poison_run(uint32_t frames, bool stereo, std::string &err) { (void)frames; (void)stereo; (void)err; return true; }
 	virtual bool render(const SegmentDesc &seg, std::string &err) = 0;
 	/* copy stream `s` PCM [0, frames) to host memory (blocks until done) */
 	virtual bool fetch_pcm(uint32_t stream, int16_t *dst, uint32_t frames,
@@ -265,6 +269,7 @@ private:
 	uint64_t rebuilds_ = 0;
 	bool plan_cache_ = true, plan_check_ = false;
 	bool loop_tails_ = true;
+	bool poison_ = false; /* SAU_AMD_POISON (tests): Backend::poison_run ahead of every run */
 	struct Stream {
 		const sauProgram *prg = nullptr;
 		std::vector<EventNode> events;

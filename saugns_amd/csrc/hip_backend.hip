@@ -402,6 +402,7 @@ public:
 		xcd_queues_ = tune_env("SAU_AMD_NO_XCD_QUEUES") == nullptr;
 		inmix_taper_ = tune_env("SAU_AMD_INMIX_TAPER") != nullptr;
 		inmix_report_ = tune_env("SAU_AMD_INMIX_REPORT") != nullptr;
+		poison_ = tune_env("SAU_AMD_POISON") != nullptr;
 		if (const char *ia = tune_env("SAU_AMD_INMIX_AT")) inmix_at_ = (uint32_t)atoi(ia) & 15u;
 		if (const char *mv = tune_env("SAU_AMD_INMIX_MIN_VOICES")) inmix_min_voices_ = (uint32_t)atoi(mv);
 		if (const char *ms = tune_env("SAU_AMD_INMIX_MIN_STEPS")) inmix_min_steps_ = (uint32_t)atoi(ms);
@@ -496,6 +497,15 @@ public:
 		return true;
 	}
 
+	/* (SAU_AMD_POISON, tests) every stream's whole row, the frames behind the run's length included: those are never handed out
+	 * and must still read 0x5a5a afterwards. On the one stream, so behind the previous run's fetch_pcm_async copies. */
+	bool poison_run(uint32_t frames, bool stereo, std::string &err) override {
+		(void)frames; (void)stereo;
+		use_device();
+		if (pcm_.p) HIP_OK(hipMemsetD16Async((hipDeviceptr_t)pcm_.p, 0x5a5a, pcm_row_ * cfg_.n_streams, stream_));
+		return true;
+	}
+
 	bool zero_pcm(uint32_t first_stream, uint32_t n_streams, uint32_t first_frame, uint32_t n_frames, bool stereo,
 			std::string &err) override {
 		use_device();
@@ -585,6 +595,14 @@ public:
 			S.vout_rows = seg.n_voices;
 		}
 		if (seg.n_pan_rows && !S.pan.ensure((size_t)seg.n_pan_rows * row_stride_, err)) return false;
+		/* (SAU_AMD_POISON, tests) the voice and pan rows before the segment's first launch, with a finite value (about 0.32: a
+		 * NaN may come out of the float-to-int16 clamp as 0 and hide the very frames this is meant to show). Nothing in them
+		 * outlives a segment: every kernel that reads a row (the mixers, the launches that mix tiles themselves) reads what this
+		 * segment's launches stored in it, and what a feedback chain carries over lives in chain_rows_, not here. */
+		if (poison_) {
+			HIP_OK(hipMemsetD32Async((hipDeviceptr_t)S.vout.p, 0x3ea5a5a5, (size_t)seg.n_voices * row_stride_, stream_));
+			if (seg.n_pan_rows) HIP_OK(hipMemsetD32Async((hipDeviceptr_t)S.pan.p, 0x3ea5a5a5, (size_t)seg.n_pan_rows * row_stride_, stream_));
+		}
 		if (!S.mstreams.ensure(seg.n_streams, err)) return false;
 		/* descriptors go through page-locked staging that is reused once the
 		 * previous segment's copies have left it */
@@ -1661,6 +1679,7 @@ private:
 	                                   * slower on config 3 (2.04 -> 2.08 ms per step, the launch 1.91 -> 1.94: profiles/r06_ab.txt): off */
 	uint32_t inmix_at_ = 13;           /* which of a chunk's tasks mix the chunk before: from this many sixteenths into it (SAU_AMD_INMIX_AT) */
 	bool inmix_report_ = false;       /* SAU_AMD_INMIX_REPORT: a line on stderr per such segment (tests) */
+	bool poison_ = false;             /* SAU_AMD_POISON: voice and pan rows filled with 0x3ea5a5a5 ahead of every segment (tests) */
 	DevBuf<uint32_t> inmix_ctl_;
 	DevBuf<uint32_t> tail_ok_;        /* [stream]: the look-back launch mixes this stream itself (k_fast_types.h: FastParams.tail_ok) */
 	bool tailmix_enabled_ = false;    /* SAU_AMD_TAILMIX: the look-back launch mixes few-voice streams itself. Exact (357 GPU tests with it on), and

@@ -56,6 +56,12 @@ struct SeqBackend : public Backend {
 		for (auto &p : pcm) p.assign((size_t)n * 2, (int16_t)0x5a5a);
 		return true;
 	}
+	/* (SAU_AMD_POISON: poisoned again ahead of every run, not only when the rows grow -- a frame a later run neither mixes nor
+	 * clears would otherwise show the earlier run's data) */
+	bool poison_run(uint32_t, bool, std::string &) override {
+		for (auto &p : pcm) std::fill(p.begin(), p.end(), (int16_t)0x5a5a);
+		return true;
+	}
 	bool upload_plans(const Step *s, const FastIds *, size_t ns, const uint32_t *ids, size_t ni, std::string &) override {
 		steps.assign(s, s + ns); op_ids.assign(ids, ids + ni);
 		return true;

@@ -64,6 +64,7 @@ def test_a_bank_of_both_kinds(sa, oracle, capfd, monkeypatch, stereo):
     split at 2 and at 14 look-back waves of a workgroup's 16 all give the oracle's PCM."""
     oracle.oracle().ora_set_fastmath_forms(ORACLE_FORMS)
     monkeypatch.setenv("SAU_AMD_DEBUG_DUO", "1")
+    monkeypatch.setenv("SAU_AMD_POISON", "1")  # (a later leg cannot pass on what an earlier one left in the pool's blocks)
     voices = []
     for i in range(48):
         voices += [_pm_voice(2 * i, 3000), _fm_voice(i, 3000) if i % 3 else _r_voice(i, 3000), _pm_voice(2 * i + 1, 3000)]
@@ -90,6 +91,7 @@ def test_a_batch_of_small_scripts(sa, oracle, capfd, monkeypatch):
     lengths, so that later segments hold fewer voices of either kind."""
     oracle.oracle().ora_set_fastmath_forms(ORACLE_FORMS)
     monkeypatch.setenv("SAU_AMD_DEBUG_DUO", "1")
+    monkeypatch.setenv("SAU_AMD_POISON", "1")
     # (config 4's scripts use five wave tables, which leaves its closed-form voices 8 rows per pass on narrow table blocks; these
     #  use one, and would get 12 rows on wide blocks in a launch of their own)
     monkeypatch.setenv("SAU_AMD_MORE_ROWS", "0")
@@ -178,3 +180,60 @@ def test_two_batches_in_flight(sa, oracle, monkeypatch):
                 assert hip.hipMemcpy(got.ctypes.data, b.device_pcm(i), got.nbytes, 2) == 0
                 assert (got == w).all(), (rep, i)
             b.close()
+
+
+def _bank_of_both_kinds():
+    voices = []
+    for i in range(48):
+        voices += [_pm_voice(2 * i, 2000 - 9 * i), _fm_voice(i, 2000) if i % 3 else _r_voice(i, 1900), _pm_voice(2 * i + 1, 2000)]
+    return vb.build_program(voices)
+
+
+def _small_scripts():
+    prgs = []
+    for k in range(12):
+        ms = 1500 + 250 * (k % 5)
+        voices = [_pm_voice(3 * k, ms), _r_voice(k, ms) if k % 2 else _fm_voice(2 * k, ms), _pm_voice(3 * k + 3, ms - 400)]
+        prgs.append(vb.build_program(voices))
+    return prgs
+
+
+@pytest.mark.parametrize("grid, xcd", [(32, False), (64, False), (128, False), (37, True), (255, True)])
+def test_launches_of_partition_sized_and_odd_grids(sa, oracle, capfd, monkeypatch, grid, xcd):
+    """The joint launch's grid follows the device's CUs (hip_backend.hip: fk_grid_): a CPX, QPX or DPX partition gives 32, 64 or
+    128 workgroups and no per-XCD queues (SAU_AMD_NO_XCD_QUEUES: apart from the grid the only thing the CU count changes), a
+    CU-masked device any count -- here 37 and 255. At each, the bank of both kinds and the batch of small scripts in the split
+    duo_kernel picks, at 3 and 7 look-back waves of a workgroup's 16 (SAU_AMD_DUO_LW), and apart (SAU_AMD_NO_DUO: fast_kernel<8, 2>):
+    the oracle's PCM, with every PCM, voice and pan row poisoned ahead of the render (SAU_AMD_POISON). Which wave takes which
+    look-back voice at these grids: tests/test_lookback_waves_model.py."""
+    oracle.oracle().ora_set_fastmath_forms(ORACLE_FORMS)
+    monkeypatch.setenv("SAU_AMD_DEBUG_DUO", "1")
+    monkeypatch.setenv("SAU_AMD_POISON", "1")
+    monkeypatch.setenv("SAU_AMD_FK_GRID", str(grid))
+    if not xcd:
+        monkeypatch.setenv("SAU_AMD_NO_XCD_QUEUES", "1")
+    monkeypatch.setenv("SAU_AMD_MORE_ROWS", "0")
+    monkeypatch.setenv("SAU_AMD_NO_WIDE_TABS", "1")
+    bank, small = _bank_of_both_kinds(), _small_scripts()
+    want_bank = oracle.oracle_render(bank.ptr, 44100, False, chunk=88200)
+    want_small = [oracle.oracle_render(p.ptr, 44100, False, chunk=66150) for p in small]
+    for leg in ("", "3", "7", "apart"):
+        monkeypatch.delenv("SAU_AMD_DUO_LW", raising=False)
+        if leg == "apart":
+            monkeypatch.setenv("SAU_AMD_NO_DUO", "1")
+        elif leg:
+            monkeypatch.setenv("SAU_AMD_DUO_LW", leg)
+        batch = sa.Batch([bank], 44100)
+        got = batch.render(stereo=False, chunk=88200)[0]
+        batch.close()
+        assert len(got) == len(want_bank) and (got == want_bank).all(), (grid, leg)
+        batch = sa.Batch(small, 44100)
+        got = batch.render(stereo=False, chunk=66150)
+        batch.close()
+        for k, (g, w) in enumerate(zip(got, want_small)):
+            assert len(g) == len(w) and (np.asarray(g) == w).all(), (grid, leg, k)
+        d = _duos(capfd)
+        if leg == "apart":
+            assert 1 not in d
+        else:
+            assert 1 in d, f"the joint launch did not run ({grid}, {leg}): " + d.text

@@ -87,6 +87,7 @@ def test_the_same_pcm_whoever_mixes_and_however_tasks_are_dealt(sa, oracle, capf
     from saugns_amd import voicebank as vb
     monkeypatch.setenv("SAU_AMD_FK_GRID", "16")
     monkeypatch.setenv("SAU_AMD_INMIX_REPORT", "1")
+    monkeypatch.setenv("SAU_AMD_POISON", "1")  # (a later leg cannot pass on what an earlier one left in the pool's blocks)
     oracle.oracle().ora_set_fastmath_forms(ORACLE_FORMS)
     prg = vb.config3(96, 4)
     want = oracle.oracle_render(prg.ptr, 44100, False, chunk=176400)
@@ -114,6 +115,7 @@ def test_edge_groups_and_inner_groups_in_launches_of_their_own(sa, oracle, repor
     in runs that cut the voices' groups elsewhere."""
     from saugns_amd import voicebank as vb
     oracle.oracle().ora_set_fastmath_forms(ORACLE_FORMS)
+    monkeypatch.setenv("SAU_AMD_POISON", "1")
     voices = vb.config3_voices(80, 5)
     for i, v in enumerate(voices):
         v.time_ms = 5000 - 37 * (i % 23)  # (different last groups)

@@ -664,3 +664,41 @@ def test_product_library_exports_only_the_abi():
     declared = set(re.findall(r"\b(sauAmd_\w+|sau_create_Generator|sau_destroy_Generator|sauGenerator_run|sauNoise_names)\s*[\(\[]", hdr))
     exported = {x for x in names if x.startswith(("sauAmd_", "sau_", "sauGenerator_", "sauNoise_"))}
     assert exported == declared, (sorted(exported - declared), sorted(declared - exported))
+
+
+def _ending_streams(vb, ms_scale=1.0):
+    """Streams for consecutive runs of one engine: voices that sound through one run and end inside the next (frames that were
+    sound there must be zero now), two identical streams (one zero_pcm span of two rows), others that end elsewhere (spans of
+    their own), one that ends inside the first run, and a script whose events leave segments with nothing sounding."""
+    def v(i, ms):
+        m = vb.Op("sin", freq=vb.Line(float(1 + i % 3), ratio=True), amp=vb._f32(0.5))
+        return vb.Op(("sin", "tri", "sqr")[i % 3], freq=vb._num(".3f", 150.0 + 31.7 * i), time_ms=int(ms * ms_scale),
+                     pan=vb.Line(vb._num(".2f", ((i * 37) % 100) / 100.0)), mods={vb.POP_PMOD: [m]})
+    long_ = vb.build_program([v(0, 1700), v(1, 900), v(2, 1250)])
+    return [long_, long_, vb.build_program([v(3, 1300), v(4, 600)]), vb.build_program([v(5, 400)]),
+            vb.build_program([v(6, 1550 + 60 * k) for k in range(3)])]
+
+
+@pytest.mark.parametrize("stereo", [False, True])
+def test_consecutive_runs_clear_what_an_earlier_run_left(sa, oracle, seqexec, monkeypatch, stereo):
+    """Engine::render_segment's zero accounting (engine.cpp: every frame of a run is mixed or cleared by zero_pcm), on the
+    sequential executor with its PCM poisoned ahead of EVERY run (SAU_AMD_POISON): runs of 7001 frames, each run's whole buffer --
+    the frames behind a stream's end included -- equals the oracle's PCM followed by zeros, in a batch whose streams end in the
+    same run at the same frame, at different frames, in the first run, and one run after all have ended."""
+    from saugns_amd import voicebank as vb
+    oracle.oracle().ora_set_fastmath_forms(ORACLE_FORMS)
+    monkeypatch.setenv("SAU_AMD_POISON", "1")
+    prgs = _ending_streams(vb) + [load_program(sa, "examples__tests__scales")]
+    R, ch = 7001, 2 if stereo else 1
+    want = [oracle.oracle_render(p.ptr, 12000, stereo, chunk=R) for p in prgs]
+    runs = max(len(w) // ch for w in want) // R + 2  # (the last one after every stream has ended)
+    b = sa.Batch(prgs, 12000, backend=seqexec.seq_backend_create(1016))
+    for k in range(runs):
+        pcm, more, lens = b.run(R, stereo)
+        for s, w in enumerate(want):
+            exp = np.zeros(R * ch, np.int16)
+            part = w[k * R * ch:(k + 1) * R * ch]
+            exp[:len(part)] = part
+            assert (pcm[s] == exp).all(), (k, s, np.flatnonzero(pcm[s] != exp)[:4] // ch)
+            assert more[s] == (len(w) > (k + 1) * R * ch), (k, s)
+    b.close()
