@@ -238,7 +238,7 @@ __device__ __forceinline__ void chain_feed(const ChainDesc &cd, bool live, int l
 					}
 					if (!__any(big)) {
 #pragma unroll
-						for (uint32_t j = 0; j < HB; ++j) incs[j] = (uint32_t)__double2loint((double)x[j] + 0x1.8p52);
+						for (uint32_t j = 0; j < HB; ++j) incs[j] = rint32w_small(x[j]);
 					} else {
 #pragma unroll
 						for (uint32_t j = 0; j < HB; ++j) incs[j] = rint32w(x[j]);
@@ -281,7 +281,7 @@ __device__ __forceinline__ void chain_feed(const ChainDesc &cd, bool live, int l
 				/* llrintf(x) mod 2^32 (wosc.h:145): one test per four frames for the rounding form */
 				if (!__any(big)) {
 #pragma unroll
-					for (uint32_t j = 0; j < 4; ++j) incs[j] = (uint32_t)__double2loint((double)x[j] + 0x1.8p52);
+					for (uint32_t j = 0; j < 4; ++j) incs[j] = rint32w_small(x[j]);
 				} else {
 #pragma unroll
 					for (uint32_t j = 0; j < 4; ++j) incs[j] = rint32w(x[j]);

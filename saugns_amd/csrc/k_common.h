@@ -217,3 +217,9 @@ template <bool LDS> __device__ __forceinline__ unsigned long long lookback64(uns
 __device__ __forceinline__ uint32_t rint32w_p31_small(float p) {
 	return (uint32_t)__double2loint((double)p + 0x1.8p21);
 }
+/* llrintf(x) wrapped to 32 bits (a phase increment, wosc.h:145) for |x| < 2^51: adding 1.5 * 2^52 in f64 rounds
+ * to the nearest integer (half to even) and leaves it, mod 2^32, in the low word of the significand. The callers
+ * test |x| < 2^50 and take rint32w() otherwise. */
+__device__ __forceinline__ uint32_t rint32w_small(float x) {
+	return (uint32_t)__double2loint((double)x + 0x1.8p52);
+}

@@ -180,9 +180,8 @@
 											const float v = freq_at(k, t);
 											fv[k] = v;
 											const float x = fa.coeff * v;
-											/* llrintf(x) mod 2^32 (wosc.h:145): adding 1.5 * 2^52 in f64 rounds to the nearest
-											 * integer and leaves it in the low word; exact while |x| < 2^51 */
-											r = fabsf(x) < 0x1p50f ? (uint32_t)__double2loint((double)x + 0x1.8p52) : rint32w(x);
+											/* llrintf(x) mod 2^32 (wosc.h:145): the short form (k_common.h) is exact while |x| < 2^51 */
+											r = fabsf(x) < 0x1p50f ? rint32w_small(x) : rint32w(x);
 											if (inc_write && l >= (int)H && in_seg(t)) irow[t] = r;
 										}
 										const uint32_t inc = in_seg(t) ? r : 0u;
@@ -201,7 +200,7 @@
 									uint32_t r[T];
 									if (!__any(big)) {
 #pragma unroll
-										for (int k = 0; k < T; ++k) r[k] = (uint32_t)__double2loint((double)x[k] + 0x1.8p52);
+										for (int k = 0; k < T; ++k) r[k] = rint32w_small(x[k]);
 									} else {
 #pragma unroll
 										for (int k = 0; k < T; ++k) r[k] = rint32w(x[k]);

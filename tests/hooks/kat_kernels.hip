@@ -8,6 +8,11 @@
 
 using namespace saudev;
 
+/* the kernels' wave-level helpers and short rounding forms, as hip_backend.hip includes them (inside a namespace there) */
+namespace katk {
+#include "../../saugns_amd/csrc/k_common.h"
+}
+
 /* div_diff_scale(a, b) against IEEE a / b for every f32 b with 1 <= |b| <= 2^31 (a superset of the rounded integers the
  * differentiator divides by). Thread t takes the bit patterns t, t + stride, ... */
 __global__ void kat_div_kernel(float a, int variant, unsigned long long *mismatches, uint32_t *first_bad) {
@@ -20,6 +25,8 @@ __global__ void kat_div_kernel(float a, int variant, unsigned long long *mismatc
 			float got;
 			if (variant == 0) {
 				got = div_diff_scale(a, b);
+			} else if (variant == 2) { /* the unmodulated rows' one division per group (k_fast_group.h) */
+				got = div_f32_normal(a, b);
 			} else { /* no correction: the probe must be able to see this fail */
 				got = a * __builtin_amdgcn_rcpf(b);
 			}
@@ -144,6 +151,84 @@ bool kat_rint64(int scattered, unsigned long long *mismatches, uint32_t *first_b
 			hipMemcpy(first_bad, d_f, sizeof *d_f, hipMemcpyDeviceToHost) == hipSuccess;
 	}
 	if (d_m) (void)hipFree(d_m);
+	if (d_f) (void)hipFree(d_f);
+	return ok;
+}
+
+/* The 32-bit rounding forms of phase offsets, increments and cycle counts (sau_dev_math.h, k_common.h) for EVERY f32 bit
+ * pattern against independent formulations in f64 (kat_rint64_ref for llrintf; cvttss2si and the reference build's floorf
+ * below), in kat_rint64_kernel's two lane orders: the wave-wide guards in front of the short forms see waves of alike and
+ * of mixed magnitudes. `fn`:
+ *   0 rint32w(x)            == low word of llrintf(x), every x (NaN, infinities and |x| >= 2^63 give 0 on the host)
+ *   1 rint32w_p31(p)        == low word of llrintf(p * 0x1p31f), the product rounded in f32 as the host rounds it
+ *   2 rint32w_p31_small(p)  == the same for |p| < 2^20; counted apart: [2^20, 2^21) and (-2^21, -2^20], where it is wrong
+ *   3 rint32w_small(x)      == low word of llrintf(x) for |x| < 2^50; counted apart: [2^51, 2^52), where it is wrong
+ *   4 f2i_x86(x)            == cvttss2si: truncation, 0x80000000 out of range and for NaN
+ *   5 floor_i32_ref(x)      == cvttss2si, then one off where that lies above x, in 32-bit arithmetic (below -2^31: INT32_MAX)
+ * n[0]: mismatches where the form must hold, n[1] / n[2]: mismatches in the positive / negative control range. */
+__device__ __forceinline__ int32_t kat_cvtt_ref(float x) {
+	const double d = (double)x;
+	if (!(d >= -0x1p31 && d < 0x1p31)) return (int32_t)0x80000000u; /* (NaN too) */
+	return (int32_t)trunc(d);
+}
+__device__ __forceinline__ int32_t kat_floor_ref(float x) {
+	const double d = (double)x;
+	if (d < -0x1p31) return INT32_MAX; /* truncation gave 0x80000000 = -2^31, above x: minus one wraps */
+	if (!(d < 0x1p31)) return (int32_t)0x80000000u; /* (NaN too) */
+	return (int32_t)floor(d);
+}
+__global__ void kat_round32_kernel(int fn, int scattered, unsigned long long *n, uint32_t *first_bad) {
+	unsigned long long bad = 0, ctrl_pos = 0, ctrl_neg = 0;
+	const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x, nt = gridDim.x * blockDim.x; /* nt divides 2^32 */
+	for (uint32_t k = 0; k < (uint32_t)(0x100000000ull / nt); ++k) {
+		uint32_t bits = k * nt + tid;
+		if (scattered) bits *= 0x9e3779b1u;
+		const float x = bits_f(bits);
+		const float ax = fabsf(x);
+		uint32_t got, want;
+		bool in = true;
+		int ctrl = 0; /* +1 / -1: x lies in the positive / negative control range */
+		switch (fn) {
+		case 0: got = rint32w(x); want = (uint32_t)kat_rint64_ref(x); break;
+		case 1: got = rint32w_p31(x); want = (uint32_t)kat_rint64_ref(x * 0x1p31f); break;
+		case 2:
+			got = katk::rint32w_p31_small(x); want = (uint32_t)kat_rint64_ref(x * 0x1p31f);
+			in = ax < 0x1p20f;
+			ctrl = (ax >= 0x1p20f && ax < 0x1p21f) ? (x > 0 ? 1 : -1) : 0;
+			break;
+		case 3:
+			got = katk::rint32w_small(x); want = (uint32_t)kat_rint64_ref(x);
+			in = ax < 0x1p50f;
+			ctrl = (x >= 0x1p51f && x < 0x1p52f) ? 1 : 0;
+			break;
+		case 4: got = (uint32_t)f2i_x86(x); want = (uint32_t)kat_cvtt_ref(x); break;
+		default: got = (uint32_t)floor_i32_ref(x); want = (uint32_t)kat_floor_ref(x); break;
+		}
+		if (got != want) {
+			if (in) { ++bad; atomicMin(first_bad, bits); }
+			else if (ctrl > 0) ++ctrl_pos;
+			else if (ctrl < 0) ++ctrl_neg;
+		}
+	}
+	if (bad) atomicAdd(&n[0], bad);
+	if (ctrl_pos) atomicAdd(&n[1], ctrl_pos);
+	if (ctrl_neg) atomicAdd(&n[2], ctrl_neg);
+}
+bool kat_round32(int fn, int scattered, unsigned long long *counts, uint32_t *first_bad) {
+	unsigned long long *d_n = nullptr;
+	uint32_t *d_f = nullptr;
+	bool ok = hipMalloc((void **)&d_n, 3 * sizeof *d_n) == hipSuccess && hipMalloc((void **)&d_f, sizeof *d_f) == hipSuccess;
+	if (ok) {
+		const uint32_t none = 0xffffffffu;
+		ok = hipMemset(d_n, 0, 3 * sizeof *d_n) == hipSuccess && hipMemcpy(d_f, &none, sizeof none, hipMemcpyHostToDevice) == hipSuccess;
+	}
+	if (ok) {
+		hipLaunchKernelGGL(kat_round32_kernel, dim3(4096), dim3(256), 0, 0, fn, scattered, d_n, d_f);
+		ok = hipDeviceSynchronize() == hipSuccess &&
+			hipMemcpy(counts, d_n, 3 * sizeof *d_n, hipMemcpyDeviceToHost) == hipSuccess &&
+			hipMemcpy(first_bad, d_f, sizeof *d_f, hipMemcpyDeviceToHost) == hipSuccess;
+	}
+	if (d_n) (void)hipFree(d_n);
 	if (d_f) (void)hipFree(d_f);
 	return ok;
 }

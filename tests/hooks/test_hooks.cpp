@@ -6,7 +6,8 @@
  *     (tests/seqexec: the sequential plan executor) -- host logic without a GPU
  *   sauAmd_Generator_rewinds: how often a changed call size / channel layout took a generator's read-ahead back
  *   sauAmd_kat_line_device / _host, sauAmd_kat_div_device: the shared arithmetic as compiled for the device and the host
- *   sauAmd_kat_scan64_device: the kernels' 64-bit wave scan and sum (k_wave_scan.h) over caller-supplied values */
+ *   sauAmd_kat_scan64_device: the kernels' 64-bit wave scan and sum (k_wave_scan.h) over caller-supplied values
+ *   sauAmd_kat_round32_device: the 32-bit rounding forms of phases (sau_dev_math.h, k_common.h) on every bit pattern */
 #include "../../saugns_amd/csrc/capi_internal.h"
 #include "../../saugns_amd/csrc/sau_dev_ops.h"
 #include <stdio.h>
@@ -19,6 +20,7 @@ bool kat_div(float a, int variant, unsigned long long *mismatches, uint32_t *fir
 bool kat_line(const saudev::LineState &st, uint32_t len, const float *mul, float *out, saudev::LineState *st_out);
 bool kat_scan64(const unsigned long long *in, unsigned long long *scan, unsigned long long *sum, uint32_t n_waves);
 bool kat_rint64(int scattered, unsigned long long *mismatches, uint32_t *first_bad);
+bool kat_round32(int fn, int scattered, unsigned long long *counts, uint32_t *first_bad);
 #endif
 
 HOOK sauGenerator *sauAmd_create_Generator_with_backend(const sauProgram *prg, uint32_t srate, void *backend) {
@@ -55,7 +57,8 @@ HOOK int sauAmd_kat_line_device(uint32_t *state, uint32_t len, const float *mul,
 	return 1;
 }
 /* for wave id w: how many divisors make div_diff_scale differ from IEEE division (and the first such bit pattern);
- * variant 1 is the uncorrected product a * rcp(b), which the probe must catch. -1 on a device error. */
+ * variant 1 is the uncorrected product a * rcp(b), which the probe must catch; variant 2 is div_f32_normal (the unmodulated
+ * rows' division). -1 on a device error. */
 HOOK long long sauAmd_kat_div_device(uint32_t wave, int variant, uint32_t *first_bad) {
 	unsigned long long m = 0;
 	uint32_t fb = 0xffffffffu;
@@ -71,6 +74,12 @@ HOOK long long sauAmd_kat_rint64_device(int scattered, uint32_t *first_bad) {
 	if (!kat_rint64(scattered, &m, &fb)) return -1;
 	if (first_bad) *first_bad = fb;
 	return (long long)m;
+}
+/* the 32-bit rounding forms (kat_kernels.hip: kat_round32_kernel, `fn` 0..5) over every 32-bit pattern: counts[3] = mismatches where
+ * the form must hold, in the positive and in the negative control range; 0 on a device error */
+HOOK int sauAmd_kat_round32_device(int fn, int scattered, unsigned long long *counts, uint32_t *first_bad) {
+	if (fn < 0 || fn > 5) return 0;
+	return kat_round32(fn, scattered, counts, first_bad) ? 1 : 0;
 }
 HOOK int sauAmd_kat_scan64_device(const unsigned long long *in, unsigned long long *scan, unsigned long long *sum, uint32_t n_waves) {
 	return kat_scan64(in, scan, sum, n_waves) ? 1 : 0;

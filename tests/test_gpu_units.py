@@ -164,6 +164,8 @@ def test_differentiator_division_exhaustive(sa, hooks):
         first = C.c_uint32()
         assert fn(wave, 0, C.byref(first)) == 0, (wave, hex(first.value))
         assert fn(wave, 1, C.byref(first)) > 0
+        # div_f32_normal: the unmodulated rows' one division per group (k_fast_group.h), by (float)(int32_t)inc
+        assert fn(wave, 2, C.byref(first)) == 0, (wave, hex(first.value))
 
 
 def test_a_batch_on_a_named_device(sa, oracle):
@@ -196,6 +198,31 @@ def test_rint64_and_the_gauss_noise_conversions_on_every_bit_pattern(hooks, scat
     fb = C.c_uint32(0)
     bad = hooks.sauAmd_kat_rint64_device(scattered, C.byref(fb))
     assert bad == 0, (bad, hex(fb.value))
+
+
+ROUND32 = ["rint32w", "rint32w_p31", "rint32w_p31_small", "rint32w_small", "f2i_x86", "floor_i32_ref"]
+
+
+@pytest.mark.parametrize("scattered", [0, 1])
+@pytest.mark.parametrize("fn", range(len(ROUND32)), ids=ROUND32)
+def test_32_bit_rounding_forms_on_every_bit_pattern(hooks, fn, scattered):
+    """The kernels' 32-bit roundings of phase offsets, increments and cycle counts (sau_dev_math.h, k_common.h) against independent
+    f64 forms of the host's llrintf / cvttss2si / the reference build's floorf, for all 2^32 bit patterns in both lane orders: the
+    general forms everywhere (NaN and the infinities included), the short forms inside the range their guards allow. Each short
+    form is also shown wrong just past it -- offsets in [2^20, 2^21) cycles of either sign, increments in [2^51, 2^52) -- so that
+    the probe can fail and the guards are needed."""
+    import ctypes as C
+    f = hooks.sauAmd_kat_round32_device
+    f.restype = C.c_int
+    f.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    n = (C.c_ulonglong * 3)()
+    fb = C.c_uint32(0)
+    assert f(fn, scattered, n, C.byref(fb)) == 1
+    assert n[0] == 0, (ROUND32[fn], n[0], hex(fb.value))
+    if ROUND32[fn] == "rint32w_p31_small":
+        assert n[1] > 0 and n[2] > 0, list(n)
+    elif ROUND32[fn] == "rint32w_small":
+        assert n[1] > 0, list(n)
 
 
 def test_wave_scan_of_64_bit_values_counts_its_carries(hooks):

@@ -299,3 +299,23 @@ def test_config4_all_seeds_fixture(oracle, sa, index):
         pcm = oracle.oracle_render(prg.ptr, 44100, False)
         assert len(pcm) == int(fx["frames"][k])
         assert hashlib.sha256(pcm.tobytes()).hexdigest() == str(fx["sha256"][k]), k
+
+
+@pytest.mark.parametrize("rate", [44100, 1000])
+def test_range_guard_programs_vs_reference(oracle, rate):
+    """The programs of tests/test_gpu_range_guards.py -- PM offsets across 2^20 cycles, increments across 2^50 and 2^51, W feedback
+    across chain_batch's switches, R feedback past 2^31 cycles -- render identically in the oracle and in the compiled reference,
+    mono and stereo: the oracle is a valid checker at the values where the kernels' short rounding forms end."""
+    if not oracle.have_ref():
+        pytest.skip("compiled reference not present")
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from saugns_amd import voicebank as vb
+    from test_gpu_range_guards import guard_programs
+    oracle.oracle().ora_set_fastmath_forms(2)
+    for name, voices in sorted(guard_programs().items()):
+        prg = vb.build_program(voices)
+        for stereo in (False, True):
+            a = oracle.oracle_render(prg.ptr, rate, stereo)
+            b = oracle.ref_render(prg.ptr, rate, stereo)
+            assert len(a) == len(b) > 0 and max_diff(a, b) == 0, (name, stereo)
