@@ -1,0 +1,362 @@
+/* k_fast_group_lm.h -- part of hip_backend.hip: the evaluation of one row group in fast_voice (k_fast_voice.h) in the lane-major
+ * form (SPLIT 3: the INNER build's groups between, closed-form phases, no segment edge in the group). The group's 64 T frames are
+ * the same as k_fast_group.h's, [cg GF - H, cg GF - H + 64 T); relative frame j = l T + k lies in lane l, register k, where the
+ * row-major form has j = 64 k + l. A frame's neighbour before is then register k - 1 of the same lane, and only register 0 reads
+ * lane l - 1's register T - 1: one DPP move per dword of a differentiator per group, where the row-major form's later rows take two
+ * per register (prev_of there) -- 5.3 of the build's 31.7 vector instructions per operator-sample (profiles/census/).
+ * The block buffers keep their layout (element (k, l) at off + 64 k + l): producer and consumer are both this form.
+ * The arithmetic and its order are k_fast_group.h's with EDGE false, SCAN 0, REPAIR false, CUB false; only what reaches a frame's
+ * neighbour differs. In scope: everything fast_voice has defined up to its row-group loop, plus cg. */
+		const int j0 = l * T;                              /* this lane's first frame of the group, relative */
+		const int t0 = (int)(cg * GF) - (int)H + j0;       /* ... and in the segment: register k holds frame t0 + k */
+		/* which registers hold frames of the group's own (lead-in: j < H -- the first lanes' first registers): bit k */
+		const uint32_t om = ((1u << T) - 1u) & ~((1u << min(max((int)H - j0, 0), T)) - 1u);
+		/* the frame before: the register before; for register 0 lane l - 1's last (lane 0: zero; frame 0 is lead-in) */
+		auto prev32 = [&](const uint32_t *x, int k) -> uint32_t { return k > 0 ? x[k - 1] : lane_prev(x[T - 1]); };
+		auto prev64 = [&](const double *x, int k) -> double { return k > 0 ? x[k - 1] : lane_prev(x[T - 1]); };
+		/* a voice row's frames of this lane: T consecutive floats. 16-byte stores where the group starts on a multiple of four frames
+		 * (then so does every lane's run, T being one), for the quads the lane owns whole; dword stores elsewhere */
+		const bool quads = ((cg * GF - H) & 3u) == 0;
+		/* (the tests on the mask at the stores, not hoisted out of the step loop: as lane masks they took two scalar registers each) */
+		auto store_row = [&](float *row, const float *x, const bool nt) {
+			uint32_t o = om;
+			asm volatile("" : "+v"(o));
+			if (quads) {
+#pragma unroll
+				for (int q = 0; q < T / 4; ++q) {
+					const uint32_t oq = (o >> (4 * q)) & 15u;
+					if (oq == 15u) {
+						const fk_f32x4 v4 = {x[4 * q], x[4 * q + 1], x[4 * q + 2], x[4 * q + 3]};
+						fk_f32x4 *p = (fk_f32x4 *)(row + t0 + 4 * q);
+						if (nt) FK_VSTORE(p, v4); else *p = v4;
+					} else if (oq != 0u) {
+#pragma unroll
+						for (int u = 0; u < 4; ++u)
+							if ((oq >> u) & 1u) { if (nt) FK_VSTORE(&row[t0 + 4 * q + u], x[4 * q + u]); else row[t0 + 4 * q + u] = x[4 * q + u]; }
+					}
+				}
+			} else {
+#pragma unroll
+				for (int k = 0; k < T; ++k)
+					if ((o >> k) & 1u) { if (nt) FK_VSTORE(&row[t0 + k], x[k]); else row[t0 + k] = x[k]; }
+			}
+		};
+		uint32_t held_rows = 0; /* which of the group's first owned frames unresolved holds spoil (bit j: owned frame j, as k_fast_group.h) */
+		bool held_far = false;  /* ... or something the repair pass cannot put right */
+		for (uint32_t si = 0; si < n_fsteps; ++si) {
+			const FastStep f = load_step_uniform(fsteps + si);
+			const uint32_t kind = f.kind & 0xff;
+			const uint32_t flags = (f.kind >> 8) & 0xff;
+			if (kind == ST_OSC) {
+				const uint32_t type = f.type & 0xff;
+				const bool wave_env = (flags & SF_WAVE_ENV) != 0;
+				const bool layer = (flags & SF_LAYER) != 0;
+				const bool to_voice = ((f.kind >> 16) & OX_VOICE) != 0;
+				float s[T];
+				if (type == OT_WAVE) {
+					const bool has_pm = f.pm_off != ~0u, has_fpm = f.fpm_off != ~0u;
+					/* this operator's values are defined from relative frame p_min on */
+					const int p_min = (int)H - (int)(f.kind >> 24) + 1;
+					/* which of this lane's registers hold frames the operator defines (j >= p_min): bit k -- per-lane masks, where
+					 * arrays of flags took a lane-mask register pair each */
+					const int nd = min(max(p_min - j0, 0), T);
+					const uint32_t dm = ((1u << T) - 1u) & ~((1u << nd) - 1u);
+					bool done = false;
+					if (FK_COMMON && f.tab >= 0 && !has_fpm && !(f.ramp & 2)) {
+						/* the common case, straight-line: table in LDS, plain PM or none */
+						uint32_t ph[T];
+						{
+							uint32_t acc = f.phase0 + f.inc * (uint32_t)(t0 + 1);
+#pragma unroll
+							for (int k = 0; k < T; ++k) { ph[k] = acc; acc += f.inc; }
+						}
+						bool ok = true;
+						if (has_pm) {
+							float pm[T];
+							bool big = false;
+#pragma unroll
+							for (int k = 0; k < T; ++k) {
+								pm[k] = slots[f.pm_off + k * 64];
+								big |= !(fabsf(pm[k]) < 0x1p20f);
+							}
+							ok = !__any(big);
+#pragma unroll
+							for (int k = 0; k < T; ++k) ph[k] += rint32w_p31_small(pm[k]);
+						}
+						if (ok) {
+							const uint32_t ltab = tabs + (uint32_t)f.tab * FkTab<WIDE>::BYTES;
+							double Is[T];
+#pragma unroll
+							for (int k = 0; k < T; ++k) Is[k] = fk_poly(fk_entry<WIDE>(ltab, ph[k]), ph[k]);
+							if (FK_CONSTD && !has_pm && f.inc != 0) {
+								/* unmodulated: every phase step is inc, one division serves all */
+								const double x = (double)div_f32_normal(f.diff_scale, (float)(int32_t)f.inc);
+#pragma unroll
+								for (int k = 0; k < T; ++k)
+									s[k] = (float)((Is[k] - prev64(Is, k)) * x + (double)f.diff_offset);
+								done = true;
+							} else {
+								/* a phase step of zero anywhere: the unsigned minimum of the steps (v_min_u32, k_fast_group.h), then
+								 * -- rarely -- which of the zeros fall on defined frames (lead-in frames may have any) */
+								uint32_t dmin = 0xffffffffu;
+#pragma unroll
+								for (int k = 0; k < T; ++k) {
+									uint32_t pp = prev32(ph, k);
+									if (k == 0) asm("" : "+v"(pp)); /* (keeps the DPP move a move: k_fast_group.h) */
+									const int32_t d = (int32_t)(ph[k] - pp);
+									dmin = min(dmin, (uint32_t)d);
+									s[k] = wosc_diff(Is[k], prev64(Is, k), d, f.diff_scale, f.diff_offset);
+								}
+								done = true;
+								if (__any(dmin == 0u)) {
+									uint32_t hz = 0;
+#pragma unroll
+									for (int k = 0; k < T; ++k) hz |= ph[k] == prev32(ph, k) ? 1u << k : 0u;
+									done = !__any((hz & dm) != 0u);
+								}
+							}
+						}
+					}
+					if (!done) {
+						uint32_t ph[T];
+						double Is[T];
+						float fv[T]; /* frequency per frame (freq-scaled PM reads it) */
+						{
+							uint32_t acc = f.phase0 + f.inc * (uint32_t)(t0 + 1);
+#pragma unroll
+							for (int k = 0; k < T; ++k) { ph[k] = acc; acc += f.inc; fv[k] = f.fc; }
+						}
+						if (has_pm && !has_fpm) {
+							float pm[T];
+							bool big = false;
+#pragma unroll
+							for (int k = 0; k < T; ++k) {
+								pm[k] = slots[f.pm_off + k * 64];
+								big |= !(fabsf(pm[k]) < 0x1p20f);
+							}
+							if (!__any(big)) {
+#pragma unroll
+								for (int k = 0; k < T; ++k) ph[k] += rint32w_p31_small(pm[k]);
+							} else {
+#pragma unroll
+								for (int k = 0; k < T; ++k) ph[k] += rint32w_p31(pm[k]);
+							}
+						} else if (has_pm || has_fpm) {
+							float pm[T], fpm[T];
+#pragma unroll
+							for (int k = 0; k < T; ++k) { pm[k] = 0.f; fpm[k] = 0.f; }
+							if (has_pm) {
+#pragma unroll
+								for (int k = 0; k < T; ++k) pm[k] = slots[f.pm_off + k * 64];
+							}
+							if (has_fpm) {
+#pragma unroll
+								for (int k = 0; k < T; ++k) fpm[k] = slots[f.fpm_off + k * 64];
+							}
+							if (has_pm) {
+#pragma unroll
+								for (int k = 0; k < T; ++k) ph[k] += pm_offset32(true, true, pm[k], fpm[k], fv[k]);
+							} else {
+#pragma unroll
+								for (int k = 0; k < T; ++k) ph[k] += pm_offset32(false, true, 0.f, fpm[k], fv[k]);
+							}
+						}
+						if (f.tab >= 0) {
+							const uint32_t ltab = tabs + (uint32_t)f.tab * FkTab<WIDE>::BYTES;
+#pragma unroll
+							for (int k = 0; k < T; ++k) Is[k] = fk_poly(fk_entry<WIDE>(ltab, ph[k]), ph[k]);
+						} else {
+							const uint32_t wave = (f.type >> 8) & 0xff;
+							const HerpC23 *g23 = P.g_c23 + (size_t)wave * WAVE_LEN;
+							const HerpC01 *g01 = P.g_c01 + (size_t)wave * WAVE_LEN;
+#pragma unroll
+							for (int k = 0; k < T; ++k) {
+								const uint32_t ind = ph[k] >> SLEN_BITS;
+								Is[k] = herp_poly(g23[ind], g01[ind], ph[k]);
+							}
+						}
+						uint32_t hz = 0; /* registers with a phase step of zero: bit k */
+						if (FK_CONSTD && !has_pm && !has_fpm && f.inc != 0) {
+							/* unmodulated: every phase step is inc, one division serves all */
+							const double x = (double)div_f32_normal(f.diff_scale, (float)(int32_t)f.inc);
+#pragma unroll
+							for (int k = 0; k < T; ++k) {
+								const double pIs = prev64(Is, k);
+								s[k] = (float)((Is[k] - pIs) * x + (double)f.diff_offset);
+							}
+						} else {
+#pragma unroll
+							for (int k = 0; k < T; ++k) {
+								const uint32_t pph = prev32(ph, k);
+								const double pIs = prev64(Is, k);
+								const int32_t d = (int32_t)(ph[k] - pph);
+								hz |= d == 0 ? 1u << k : 0u;
+								s[k] = wosc_diff(Is[k], pIs, d, f.diff_scale, f.diff_offset);
+							}
+						}
+						uint32_t held = hz & dm;
+						if (__any(held != 0u)) {
+							/* dphase == 0: the differentiator holds its previous output (wosc.h:251-252). In frame order: a pass
+							 * over the lane's registers, then -- for runs that cross from one lane into the next -- lane l - 1's
+							 * last register, and again the pass, until nothing changes. A run that reaches back to the operator's
+							 * first defined frame stays: the repair pass's (below). */
+							uint32_t src = dm & ~held; /* holds a defined output to copy from */
+							auto in_lane = [&]() {
+#pragma unroll
+								for (int k = 1; k < T; ++k)
+									if (((held >> k) & 1u) && ((src >> (k - 1)) & 1u)) { s[k] = s[k - 1]; held &= ~(1u << k); src |= 1u << k; }
+							};
+							in_lane();
+							for (int it = 0; it < 64; ++it) {
+								const float sp = __shfl_up(s[T - 1], 1);
+								const uint32_t okp = ((uint32_t)__shfl_up((int)src, 1) >> (T - 1)) & 1u;
+								bool changed = false;
+								if ((held & 1u) && okp && l > 0) { s[0] = sp; held &= ~1u; src |= 1u; changed = true; in_lane(); }
+								if (!__any(changed)) break;
+							}
+							/* What is left is a run of repeats that begins on the operator's first defined frame, p_min; the hold at
+							 * p_min + j spoils the carrier's owned frame j (k_fast_group.h). The repair pass stores the first jm such
+							 * frames; a hold further on is not a case for it. */
+							const int jm = min(32, 64 - (int)FAST_REPAIR_SHIFT - (int)H);
+							if (held) {
+								const int j = j0 + (int)__builtin_ctz(held);
+								rep[1] = ((uint32_t)(j % 64 - p_min) << 24) | ((uint32_t)(j / 64) << 20) | (si << 12) | (cg & 0xfff); /* debug */
+							}
+							const int nf = jm + p_min - j0; /* this lane's first register beyond the frames the repair pass stores */
+							const bool far = nf <= 0 ? held != 0u : nf < T ? (held >> nf) != 0u : false;
+							if (__any(far)) held_far = true;
+							if (jm > 0) {
+								/* the frames p_min .. p_min + jm - 1 as bits: the first lanes' held registers side by side */
+								unsigned long long run = 0;
+#pragma unroll
+								for (int L = 0; L * T < 64; ++L)
+									run |= (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)held, L) << (L * T);
+								held_rows |= (uint32_t)((run >> p_min) & ((1ull << jm) - 1ull));
+							}
+						}
+					}
+				} else if (type == OT_RASEG) {
+					/* rasg.h:165-222 + 692-743: frame t reads the counter cp0 + inc * t (+ PM) */
+					const bool rate2x = (f.type >> 17) & 1;
+					const float phase_scale = rate2x ? 0x1p31f * 2 : 0x1p31f;
+					const RasParams rp = ras_params((uint32_t)f.tab & 0xff, ((uint32_t)f.tab >> 8) & 0xffff,
+							f_bits(f.diff_scale), f_bits(f.diff_offset), ((uint32_t)f.tab >> 24) & 0x7f);
+					const unsigned long long inc64 = ((unsigned long long)f.prev_phase << 32) | f.inc;
+					const unsigned long long cp0 = (unsigned long long)__double_as_longlong(f.prev_Is);
+					const bool has_pm = f.pm_off != ~0u, has_fpm = f.fpm_off != ~0u;
+#pragma unroll
+					for (int k = 0; k < T; ++k) {
+						unsigned long long cp = cp0 + inc64 * (unsigned long long)(long long)(t0 + k);
+						if (has_pm || has_fpm)
+							cp += (unsigned long long)pm_offset(has_pm, has_fpm,
+									has_pm ? slots[f.pm_off + k * 64] : 0.f,
+									has_fpm ? slots[f.fpm_off + k * 64] : 0.f, f.fc, phase_scale);
+						uint32_t cyc;
+						float phf;
+						ras_split(cp, cyc, phf);
+						s[k] = ras_sample(rp, cyc, phf, true, false);
+					}
+				} else if (type == OT_NOISE) {
+					const uint32_t nz = (f.type >> 8) & 0xff;
+					const uint32_t n0 = f.phase0;
+#pragma unroll
+					for (int k = 0; k < T; ++k) {
+						const uint32_t n = n0 + (uint32_t)(t0 + k);
+						if (nz == NZ_vi) {
+							uint32_t s1 = ranfast32(n);
+							uint32_t s0 = ranfast32(n - 1);
+							s[k] = fscalei((s1 / 2) - (s0 / 2), 0x1p-31f);
+						} else if (nz == NZ_bv) {
+							int32_t s1 = noise_bv_term(n);
+							int32_t s0 = noise_bv_term(n - 1);
+							s[k] = (float)(s1 - s0);
+						} else {
+							s[k] = noise_stateless(nz, n);
+						}
+					}
+				} else { /* OT_AMP (generator.c:517-518: 1), or an oscillator whose output stands still */
+#pragma unroll
+					for (int k = 0; k < T; ++k) s[k] = f.fc;
+				}
+				/* amplitude and combine: generator.c:384-440 */
+				float r[T];
+				if (f.amp_off != ~0u) {
+#pragma unroll
+					for (int k = 0; k < T; ++k) r[k] = slots[f.amp_off + k * 64];
+				} else if (f.ramp & 1) { /* amplitude ramp in progress, sau/line.c:65-281 */
+					const FastLine fl = load_line_uniform(flines + si);
+#pragma unroll
+					for (int k = 0; k < T; ++k) r[k] = fast_line_value(fl, t0 + k);
+				} else {
+#pragma unroll
+					for (int k = 0; k < T; ++k) r[k] = f.ac;
+				}
+				if (layer) {
+#pragma unroll
+					for (int k = 0; k < T; ++k)
+						r[k] = mix_combine(slots[f.out_off + k * 64], s[k], r[k], wave_env, true);
+				} else if (wave_env) {
+#pragma unroll
+					for (int k = 0; k < T; ++k) r[k] = mix_combine(0.f, s[k], r[k], true, false);
+				} else {
+#pragma unroll
+					for (int k = 0; k < T; ++k) r[k] = s[k] * r[k];
+				}
+				if (to_voice) {
+					store_row(vrow, r, true);
+				} else {
+#pragma unroll
+					for (int k = 0; k < T; ++k) slots[f.out_off + k * 64] = r[k];
+				}
+			} else if (kind == ST_LINE) {
+				/* held line: v0 (sau/line.c:435-442) */
+				if (f.ramp) {
+					FastLine fl;
+					fl.goal_len = 0; fl.hold = f.ac; fl.pad = 0;
+					fl.sw = sweep_setup(LN_sah, 0.f, 0.f, 0, 1);
+					if (f.ramp & 1) fl = load_line_uniform(flines + si);
+#pragma unroll
+					for (int k = 0; k < T; ++k) slots[f.out_off + k * 64] = fast_line_value(fl, t0 + k);
+				} else {
+#pragma unroll
+					for (int k = 0; k < T; ++k) slots[f.out_off + k * 64] = f.ac;
+				}
+			} else if (kind == ST_LERP) { /* generator.c:466-467 */
+				const bool end_const = f.aux_off == ~0u;
+#pragma unroll
+				for (int k = 0; k < T; ++k) {
+					float pv = slots[f.out_off + k * 64];
+					pv += ((end_const ? f.fc : slots[f.aux_off + k * 64]) - pv) * slots[f.pm_off + k * 64];
+					slots[f.out_off + k * 64] = pv;
+				}
+			} else if (kind == ST_VOICE) { /* generator.c:749-788 with pan modulators */
+				float x[T];
+#pragma unroll
+				for (int k = 0; k < T; ++k) x[k] = slots[f.out_off + k * 64];
+				store_row(vrow, x, true);
+				if (prow) {
+#pragma unroll
+					for (int k = 0; k < T; ++k) x[k] = f.pm_off != ~0u ? slots[f.pm_off + k * 64] : f.pan;
+					store_row(prow, x, false);
+				}
+			}
+		}
+		if (held_rows || held_far) {
+			/* to the repair pass (k_fast_group.h) */
+			bool noted = false;
+			if (P.repair_on && !held_far && (int)(cg * GF) - (int)H >= (int)FAST_REPAIR_SHIFT) {
+				uint32_t at = 0;
+				if (l == 0) at = atomicAdd(&rep[0], 1u);
+				at = uni(at);
+				if (at < FAST_MAX_REPAIR) {
+					if (l == 0) {
+						rep[2 + 2 * at] = cg;
+						rep[3 + 2 * at] = held_rows;
+						atomicOr(&P.pass_flags[FAST_MAX_LEVELS], 1u);
+						atomicOr(&P.work_count[1], 2u); /* (frames the mixer may have taken early -- k_finish.h: premix_kernel -- change in the repair pass) */
+					}
+					noted = true;
+				}
+			}
+			if (!noted) zero_acc = 1;
+		}

@@ -35,6 +35,7 @@ __device__ __forceinline__ double lane_prev(double x) {
 /* The Hermite value from a table block in LDS (FAST_TAB_BYTES: see k_fast_types.h). `tab`: the block's LDS address. */
 typedef double __attribute__((ext_vector_type(2))) fk_f64x2;
 typedef float __attribute__((ext_vector_type(2))) fk_f32x2;
+typedef float __attribute__((ext_vector_type(4))) fk_f32x4;
 typedef const fk_f64x2 __attribute__((address_space(3))) *fk_lds_f64x2;
 typedef const fk_f32x2 __attribute__((address_space(3))) *fk_lds_f32x2;
 struct FkHerp { double c3, c2, c1, c0; };
@@ -112,7 +113,7 @@ __device__ __forceinline__ FastStep load_step_uniform(const FastStep *p) {
  * (frequency ramps, FM); the plain build stays as lean as closed-form voices
  * need it (the same code with the running-sum branches compiled in was 27 %
  * slower on them), and a kernel that may meet both kinds holds both copies. */
-template <int T, int SCAN, bool REPAIR = false, bool CUB = false, bool WIDE = false, int SPLIT = 0 /* 1: three loops, 2: the groups between only */, bool TAIL = false>
+template <int T, int SCAN, bool REPAIR = false, bool CUB = false, bool WIDE = false, int SPLIT = 0 /* 1: three loops, 2: the groups between only, 3: the same in the lane-major form */, bool TAIL = false>
 __device__ __forceinline__ void fast_voice(const FastParams &P, const uint32_t v, const FastInfo &fi,
 		float *slots, unsigned long long *carry, const uint32_t tabs /* LDS address of the launch's table blocks */, const int l,
 		const uint32_t wpv, const uint32_t cstart, unsigned long long *lring = nullptr,
@@ -217,7 +218,14 @@ __device__ __forceinline__ void fast_voice(const FastParams &P, const uint32_t v
 	 * and not one loop with both forms in it, which kept the edge form's hoisted values alive across the other's iterations
 	 * (178 spilled vector registers in the look-back build). */
 #define FKG_ADVANCE() (it += gstride, cgm = cgm + wpv >= lk_ring ? cgm + wpv - lk_ring : cgm + wpv)
-	if constexpr (SPLIT == 2 && !REPAIR) {
+	if constexpr (SPLIT == 3 && SCAN == 0 && !REPAIR && !CUB && !TAIL) {
+		/* (the same groups in the lane-major form, k_fast_group_lm.h; fast_kernel's other builds never reach it) */
+		for (uint32_t it = it_lo + cstart; it < n_iter; FKG_ADVANCE()) {
+			if (it == 0 || it == last_group) continue;
+			const uint32_t cg = it;
+#include "k_fast_group_lm.h"
+		}
+	} else if constexpr (SPLIT == 2 && !REPAIR) {
 		/* (FK_INNER builds, fast_kernel: the groups between only -- the first and the last are another launch's, FastParams.edge_only) */
 		for (uint32_t it = it_lo + cstart; it < n_iter; FKG_ADVANCE()) {
 			if (it == 0 || it == last_group) continue;
@@ -476,16 +484,18 @@ __device__ __forceinline__ void inmix_after(const InmixArgs &A, const uint32_t k
  * segment, in the form without in-segment masks (fast_voice: EDGE false), one loop; the first and the last group of every voice are
  * rendered by a launch of the plain build ahead of this one (FastParams.edge_only). The three-loop form of fast_voice, which holds
  * both forms in one kernel, spilled 175 vector registers at 12 rows. */
-template <int T, int SCAN, bool CUB = false, bool WIDE = false, bool TAIL = false, bool INNER = false>
+/* LM (round 7): the INNER build's groups in the lane-major form (k_fast_group_lm.h); the row-major one stays for A/B (SAU_AMD_NO_LANEMAJOR) */
+template <int T, int SCAN, bool CUB = false, bool WIDE = false, bool TAIL = false, bool INNER = false, bool LM = false>
 __global__ void FK_ATTR fast_kernel(FastParams P) {
 	static_assert(!INNER || (SCAN == 0 && WIDE && T == 12 && !CUB && !TAIL), "the inner-groups-only form exists for the 12-row wide closed-form build");
+	static_assert(!LM || INNER, "the lane-major form exists for the inner-groups-only build");
 	static_assert(!WIDE || ((SCAN == 0 || SCAN == 2) && !CUB), "only the closed-form and the look-back builds have a wide-table form");
 	static_assert(!TAIL || (SCAN == 2 && !CUB && T == 8), "the stream-mixing form exists for the 8-row look-back build");
 	constexpr int NP = 64 * T;
 	constexpr int W = 16;
 	/* the builds whose groups away from the segment's ends take a copy of their own (fast_voice: SPLIT) -- the ones BASELINE's
 	 * configurations and the FM bank run in; each costs its compile time and code size twice */
-	constexpr int SPLIT = INNER ? 2 : (!CUB && ((SCAN == 0 && T == 8 && (FK_SPLIT_MASK & 1)) || (SCAN == 0 && T == 10 && (FK_SPLIT_MASK & 2)) ||
+	constexpr int SPLIT = INNER ? (LM ? 3 : 2) : (!CUB && ((SCAN == 0 && T == 8 && (FK_SPLIT_MASK & 1)) || (SCAN == 0 && T == 10 && (FK_SPLIT_MASK & 2)) ||
 	                                (SCAN == 0 && T == 12 && (FK_SPLIT_MASK & 4)) || (SCAN == 2 && T == 8 && (FK_SPLIT_MASK & 8)))) ? 1 : 0;
 	extern __shared__ __align__(16) unsigned char lds[];
 	const int tid = threadIdx.x;
