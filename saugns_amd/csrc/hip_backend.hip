@@ -1235,6 +1235,8 @@ public:
 						HIP_OK(hipLaunchKernel(ik, dim3(fgrid), dim3(1024), iargs, lds, stream_));
 						if (inner_report_) fprintf(stderr, "[sau-amd] inner: %s, %u voices\n", lanemajor_ ? "lane-major" : "row-major", seg.n_voices);
 					} else {
+						/* (a closed-form segment that did not take the two launches, and what kept it from them) */
+						if (inner_report_) fprintf(stderr, "[sau-amd] inner: none (rows %u, wide %d, chunks %u), %u voices\n", FT, wide_cf ? 1 : 0, fp.dyn_chunks, seg.n_voices);
 						launch_fast(0);
 					}
 					fp.dyn_chunks = 0; fp.inmix_flags = 0; fp.dyn_small = 0;

@@ -319,3 +319,25 @@ def test_range_guard_programs_vs_reference(oracle, rate):
             a = oracle.oracle_render(prg.ptr, rate, stereo)
             b = oracle.ref_render(prg.ptr, rate, stereo)
             assert len(a) == len(b) > 0 and max_diff(a, b) == 0, (name, stereo)
+
+
+@pytest.mark.parametrize("rate", [44100, 8000])
+def test_lanemajor_programs_vs_reference(oracle, rate):
+    """The programs of tests/test_gpu_lanemajor_ops.py -- banks of PM across 2^20 cycles, frequency-scaled PM, N, A and R operators,
+    amplitude lists and ramps, the discontinuous waves, later events, long hold runs, and the banks that must not take the inner
+    launch -- render identically in the oracle and in the compiled reference (mono at 44.1 kHz, stereo at 8 kHz): the GPU tests'
+    comparison with the oracle is a comparison with the reference. (Some 25 banks of 80 to 96 voices for 3 to 4 s, rendered twice
+    each: half a minute at 44.1 kHz, five seconds at 8 kHz.)"""
+    if not oracle.have_ref():
+        pytest.skip("compiled reference not present")
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from saugns_amd import voicebank as vb
+    from test_gpu_lanemajor_ops import lanemajor_programs
+    oracle.oracle().ora_set_fastmath_forms(2)
+    stereo = rate != 44100
+    for name, (voices, ups) in sorted(lanemajor_programs().items()):
+        prg = vb.build_program(voices, updates=ups)
+        a = oracle.oracle_render(prg.ptr, rate, stereo)
+        b = oracle.ref_render(prg.ptr, rate, stereo)
+        assert len(a) == len(b) > 0 and max_diff(a, b) == 0, (name, rate)
