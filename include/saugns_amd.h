@@ -74,8 +74,23 @@ SAU_AMD_API bool sauAmd_Batch_run(sauAmdBatch *b, int16_t *const *bufs, size_t b
  * that many frames each (rendering far ahead of a host that asks for 11289 frames at a time). */
 SAU_AMD_API void sauAmd_Batch_set_call_len(sauAmdBatch *b, size_t frames);
 
-/* Device address of stream i's PCM row of the last run (hipMalloc memory). */
+/* Device address of stream i's PCM row of the last run (hipMalloc memory); NULL when that run was a float32 run. */
 SAU_AMD_API const int16_t *sauAmd_Batch_device_pcm(sauAmdBatch *b, size_t stream);
+
+/* Float32 sample output. sauAmd_Batch_run_f32 is sauAmd_Batch_run, sample for sample in time (buf_len, the block lattice and
+ * sauAmd_Batch_set_call_len mean what they mean there), with the mixer's f32 accumulator stored as it stands: the reference's
+ * ordered voice sum (generator.c:749-788), L, R interleaved when stereo, else (L + R) * 0.5f -- not clamped to +-1, not
+ * rounded to 15 bits, a NaN left a NaN; frames of [0, out_len) in which nothing sounds are +0.0f. The int16 sample of
+ * sauAmd_Batch_run is this one clamped and rounded. The format belongs to the call: run and run_f32 calls may alternate on
+ * one batch in any order, each continues where the last one stopped. False (sauAmd_last_error) on a backend without float
+ * output: nothing is rendered then and the batch stands where it stood. */
+SAU_AMD_API bool sauAmd_Batch_run_f32(sauAmdBatch *b, float *const *bufs, size_t buf_len,
+		bool stereo, bool *more, size_t *out_len);
+/* Device address of stream i's float32 row of the last run; NULL when that run was an int16 run. */
+SAU_AMD_API const float *sauAmd_Batch_device_pcm_f32(sauAmdBatch *b, size_t stream);
+/* Bytes between the rows of consecutive streams in the last run's format: all streams' rows are one strided array
+ * (0 on a backend that keeps no device PCM). Rows may move when a run is longer than any before it or changes the format. */
+SAU_AMD_API size_t sauAmd_Batch_device_pcm_pitch(sauAmdBatch *b);
 
 /* Wait for all queued device work of the batch. */
 SAU_AMD_API bool sauAmd_Batch_sync(sauAmdBatch *b);
@@ -166,7 +181,9 @@ SAU_AMD_API void sauAmd_free_bank(sauProgram *prg);
  * format as SGS_SNDFILE_* (player/sndfile.h:21-26); channels 1 or 2. The file
  * is byte-identical to what the reference writer produces from the same PCM.
  * *frames_out (may be NULL) = frames written. False on failure. */
-enum { SAU_AMD_SNDFILE_RAW = 0, SAU_AMD_SNDFILE_AU = 1, SAU_AMD_SNDFILE_WAV = 2 };
+/* SAU_AMD_SNDFILE_WAV_F32 (an extension: the reference writes int16 only): the float32 samples of sauAmd_Batch_run_f32 as
+ * WAVE_FORMAT_IEEE_FLOAT -- `fmt ` chunk of 18 bytes (tag 3, 32 bits, cbSize 0), `fact` chunk with the frame count, `data`. */
+enum { SAU_AMD_SNDFILE_RAW = 0, SAU_AMD_SNDFILE_AU = 1, SAU_AMD_SNDFILE_WAV = 2, SAU_AMD_SNDFILE_WAV_F32 = 3 };
 SAU_AMD_API bool sauAmd_render_file(const sauProgram *prg, uint32_t srate, const char *path,
 		int format, int channels, uint64_t *frames_out);
 

@@ -125,6 +125,16 @@ def _declare(L):
         L.sauAmd_Batch_order_after.argtypes = [C.c_void_p, C.c_void_p]
     L.sauAmd_Batch_stream.restype = C.c_void_p
     L.sauAmd_Batch_stream.argtypes = [C.c_void_p]
+    if hasattr(L, "sauAmd_Batch_run_f32"):  # float32 sample output (SAU_AMD_LIB may name an older build)
+        L.sauAmd_Batch_run_f32.restype = C.c_bool
+        L.sauAmd_Batch_run_f32.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t, C.c_bool,
+                                           C.POINTER(C.c_bool), C.POINTER(C.c_size_t)]
+    if hasattr(L, "sauAmd_Batch_device_pcm_f32"):
+        L.sauAmd_Batch_device_pcm_f32.restype = C.c_void_p
+        L.sauAmd_Batch_device_pcm_f32.argtypes = [C.c_void_p, C.c_size_t]
+    if hasattr(L, "sauAmd_Batch_device_pcm_pitch"):
+        L.sauAmd_Batch_device_pcm_pitch.restype = C.c_size_t
+        L.sauAmd_Batch_device_pcm_pitch.argtypes = [C.c_void_p]
     L.sauAmd_set_piluts.argtypes = [C.c_void_p]
     L.sauAmd_get_piluts.restype = C.POINTER(C.c_float)
     L.sauAmd_last_error.restype = C.c_char_p
@@ -217,10 +227,11 @@ def set_piluts(tables):
 
 
 SNDFILE_RAW, SNDFILE_AU, SNDFILE_WAV = 0, 1, 2
+SNDFILE_WAV_F32 = 3  # WAVE_FORMAT_IEEE_FLOAT: the mixers' f32 samples, unclamped
 
 
 def render_file(program, srate, path, fmt=SNDFILE_WAV, channels=1, backend=None):
-    """sauAmd_render_file: render a whole program into a raw/AU/WAV file -> frames written.
+    """sauAmd_render_file: render a whole program into a raw/AU/WAV (int16) or float32 WAV file -> frames written.
     ``backend`` (tests): a sauengine::Backend* to run the same output stage without a GPU."""
     n = C.c_uint64()
     if backend is None:
@@ -352,6 +363,22 @@ class Batch:
             raise RuntimeError("sauAmd_Batch_run failed: " + last_error(self._L))
         return pcm, [bool(m) for m in more], [int(x) for x in lens]
 
+    def run_f32(self, buf_len, stereo=False, fetch=True):
+        """sauAmd_Batch_run_f32: the same run with the mixers' float32 samples, neither clamped nor rounded
+        -> (float32 pcm [n, buf_len*ch] or None, more[n], out_len[n]). May alternate with run() on one batch."""
+        ch = 2 if stereo else 1
+        more = (C.c_bool * self.n)()
+        lens = (C.c_size_t * self.n)()
+        if fetch:
+            pcm = np.zeros((self.n, buf_len * ch), np.float32)
+            ptrs = (C.c_void_p * self.n)(*[pcm[i].ctypes.data for i in range(self.n)])
+        else:
+            pcm, ptrs = None, None
+        ok = _used(self._L).sauAmd_Batch_run_f32(self._b, ptrs, buf_len, stereo, more, lens)
+        if not ok:
+            raise RuntimeError("sauAmd_Batch_run_f32 failed: " + last_error(self._L))
+        return pcm, [bool(m) for m in more], [int(x) for x in lens]
+
     def render(self, stereo=False, chunk=11289, max_frames=0):
         """Render every stream to its end -> list of int16 arrays."""
         ch = 2 if stereo else 1
@@ -402,7 +429,42 @@ class Batch:
                 "segments": n.value}
 
     def device_pcm(self, stream):
+        """Device address of the stream's int16 row of the last run; None after a float32 run."""
         return self._L.sauAmd_Batch_device_pcm(self._b, stream)
+
+    def device_pcm_f32(self, stream):
+        """Device address of the stream's float32 row of the last run; None after an int16 run."""
+        return self._L.sauAmd_Batch_device_pcm_f32(self._b, stream)
+
+    def device_pcm_pitch(self):
+        """Bytes between the rows of consecutive streams, in the last run's format."""
+        return int(self._L.sauAmd_Batch_device_pcm_pitch(self._b))
+
+    def device_tensor(self, frames, stereo=False):
+        """The last run's PCM rows as a torch tensor [n, frames, ch] on the batch's device -- int16 after run(), float32 after
+        run_f32() -- that ALIASES the device rows: no copy. Call sync() first (the run is asynchronous). The tensor is valid
+        until the batch's next run or close(); `frames` and `stereo` are those of the last run (or fewer frames).
+        A process has room for one HIP runtime, and torch's wheels bring their own: import torch before the first saugns_amd
+        call (as bench.py does), so that the library binds to the runtime torch has loaded."""
+        import torch  # (only here: the binding itself does not need torch)
+        if not torch.cuda.is_available():
+            raise RuntimeError("torch sees no GPU in this process: import torch before the first saugns_amd call "
+                               "(torch loads a HIP runtime of its own, and the one loaded first has the device)")
+        f32 = self.device_pcm_f32(0)
+        ptr = f32 or self.device_pcm(0)
+        if not ptr:
+            raise RuntimeError("no device PCM: nothing has run yet, or the backend keeps none")
+        size = 4 if f32 else 2
+        ch = 2 if stereo else 1
+        pitch = self.device_pcm_pitch()
+        if frames * ch * size > pitch:
+            raise ValueError("frames beyond the rows of the last run")
+
+        class _Rows:  # the rows as one strided array, the way any CUDA-array consumer reads it
+            __cuda_array_interface__ = {"shape": (self.n, int(frames), ch), "typestr": "<f4" if f32 else "<i2",
+                                        "data": (int(ptr), False), "strides": (pitch, ch * size, size), "version": 3}
+
+        return torch.as_tensor(_Rows(), device="cuda")
 
     def close(self):
         if getattr(self, "_b", None):

@@ -363,12 +363,35 @@ extern "C" bool sauAmd_Batch_run(sauAmdBatch *b, int16_t *const *bufs, size_t bu
 	return true;
 }
 
+extern "C" bool sauAmd_Batch_run_f32(sauAmdBatch *b, float *const *bufs, size_t buf_len,
+		bool stereo, bool *more, size_t *out_len) {
+	std::string err;
+	try {
+		if (!b->engine->run_f32(bufs, buf_len, stereo, more, out_len, err)) {
+			report("batch", err);
+			return false;
+		}
+	} catch (const std::exception &ex) { /* (nothing C++ crosses the C ABI) */
+		report("batch", std::string("internal error: ") + ex.what());
+		return false;
+	}
+	return true;
+}
+
 extern "C" void sauAmd_Batch_set_call_len(sauAmdBatch *b, size_t frames) {
 	b->engine->set_call_len(frames);
 }
 
 extern "C" const int16_t *sauAmd_Batch_device_pcm(sauAmdBatch *b, size_t stream) {
 	return b->engine->backend()->device_pcm((uint32_t)stream);
+}
+
+extern "C" const float *sauAmd_Batch_device_pcm_f32(sauAmdBatch *b, size_t stream) {
+	return b->engine->backend()->device_pcm_f32((uint32_t)stream);
+}
+
+extern "C" size_t sauAmd_Batch_device_pcm_pitch(sauAmdBatch *b) {
+	return b->engine->backend()->device_pcm_pitch();
 }
 
 extern "C" bool sauAmd_Batch_sync(sauAmdBatch *b) {

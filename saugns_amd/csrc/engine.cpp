@@ -547,7 +547,7 @@ bool Engine::render_segment(uint32_t len, uint32_t offset, bool stereo, std::str
 		}
 	}
 	SegmentDesc seg;
-	seg.len = len; seg.pcm_offset = offset; seg.stereo = stereo; seg.swap_bytes = pcm_swap_;
+	seg.len = len; seg.pcm_offset = offset; seg.stereo = stereo; seg.swap_bytes = pcm_swap_; seg.format = format_;
 	seg.voices = descs.data(); seg.n_voices = (uint32_t)descs.size();
 	seg.streams = sdescs.data(); seg.n_streams = (uint32_t)sdescs.size();
 	seg.n_slots = n_main + n_fpool; seg.n_main = n_main; seg.n_fast = n_fast; seg.n_fast_full = n_fast_full; seg.max_ops = max_ops; seg.n_pan_rows = n_pan;
@@ -618,9 +618,12 @@ bool Engine::restore(const Snapshot &s, int slot, std::string &err) {
 }
 
 /* generator.c:905-973, for all streams in lock step. */
-bool Engine::run(int16_t *const *host_bufs, size_t buf_len, bool stereo,
+bool Engine::run(void *const *host_bufs, SampleFormat format, size_t buf_len, bool stereo,
 		bool *more, size_t *out_len, std::string &err) {
 	if (buf_len > UINT32_MAX) { err = "buffer too long"; return false; }
+	if (format == SF_F32 && pcm_swap_) { err = "float32 samples are not byte-swapped"; return false; }
+	/* the run's format, ahead of anything that moves: a backend without float output refuses here */
+	if (!set_format(format, err)) return false;
 	const uint32_t total = (uint32_t)buf_len;
 	if (total > reserved_frames_ || (stereo && !reserved_stereo_)) {
 		uint32_t want = std::max(total, reserved_frames_);
@@ -733,7 +736,8 @@ bool Engine::run(int16_t *const *host_bufs, size_t buf_len, bool stereo,
 		if (more) more[s] = !ended;
 		if (out_len) out_len[s] = ended ? st.call_gen : buf_len;
 		if (host_bufs && host_bufs[s]) {
-			if (!backend_->fetch_pcm((uint32_t)s, host_bufs[s], total, stereo, err))
+			if (format == SF_F32 ? !backend_->fetch_pcm_f32((uint32_t)s, (float *)host_bufs[s], total, stereo, err)
+			                     : !backend_->fetch_pcm((uint32_t)s, (int16_t *)host_bufs[s], total, stereo, err))
 				return false;
 		}
 	}

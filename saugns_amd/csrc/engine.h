@@ -25,12 +25,17 @@ namespace sauengine {
 
 using namespace saudev;
 
+/* What a run stores per sample: the reference's int16 (clamped to +-1, rounded to 15 bits: pcm16 in sau_dev_math.h), or the
+ * mixer's f32 sum as it stands (include/saugns_amd.h: sauAmd_Batch_run_f32). The format belongs to the run, not to the engine. */
+enum SampleFormat : uint8_t { SF_S16 = 0, SF_F32 = 1 };
+
 /* Everything the backend needs to render one segment (no events inside). */
 struct SegmentDesc {
 	uint32_t len;             /* frames */
 	uint32_t pcm_offset;      /* frame offset into each stream's PCM row */
 	bool stereo;
 	bool swap_bytes;          /* store PCM big-endian (AU files, player/sndfile.c:160-168) */
+	SampleFormat format = SF_S16; /* of the run the segment belongs to (Backend::set_format has announced it) */
 	/* active voices of all streams, ascending (stream, voice id) */
 	const VoiceDesc *voices;
 	uint32_t n_voices;
@@ -139,6 +144,25 @@ public:
 	/* bytes this backend has for the feedback chains' rows of one segment (engine.h: chain_rows_budget; the engine cuts segments
 	 * with such voices accordingly) */
 	virtual size_t chain_rows_budget() { return sauengine::chain_rows_budget(0, 0); }
+	/* Float32 sample output. A run of another format than the last one is announced here, ahead of everything else of the
+	 * run (reserve_frames, poison_run, zero_pcm, render and the fetches then go by it); a backend without float output
+	 * refuses -- these defaults -- and the engine then renders nothing and stands where it stood. */
+	virtual bool set_format(SampleFormat fmt, std::string &err) {
+		if (fmt == SF_S16) return true;
+		err = "this backend has no float32 sample output";
+		return false;
+	}
+	/* fetch_pcm / fetch_pcm_async after a float run */
+	virtual bool fetch_pcm_f32(uint32_t stream, float *dst, uint32_t frames, bool stereo, std::string &err) {
+		(void)stream; (void)dst; (void)frames; (void)stereo; err = "this backend has no float32 sample output"; return false;
+	}
+	virtual bool fetch_pcm_f32_async(uint32_t stream, float *dst, uint32_t frames, bool stereo, int slot, std::string &err) {
+		(void)stream; (void)dst; (void)frames; (void)stereo; (void)slot; err = "this backend has no float32 sample output"; return false;
+	}
+	/* device address of stream s float row when the last run was a float run, else NULL (device_pcm: NULL after a float run) */
+	virtual const float *device_pcm_f32(uint32_t stream) { (void)stream; return nullptr; }
+	/* bytes between the rows of consecutive streams in the last run's format (0: no device PCM) */
+	virtual size_t device_pcm_pitch() { return 0; }
 };
 
 /* ---- plan compiler (plan.cpp) -------------------------------------------- */
@@ -212,7 +236,23 @@ public:
 	/* Advance every stream by buf_len frames. host_bufs[s] may be NULL (PCM
 	 * stays on the device). more[s]/out_len[s] as sauGenerator_run. */
 	bool run(int16_t *const *host_bufs, size_t buf_len, bool stereo,
+			bool *more, size_t *out_len, std::string &err) {
+		return run((void *const *)host_bufs, SF_S16, buf_len, stereo, more, out_len, err);
+	}
+	/* The same run with float32 samples (SampleFormat). int16 and float runs may alternate; each continues where the last one
+	 * stopped. False, with nothing rendered and no position moved, on a backend without float output. */
+	bool run_f32(float *const *host_bufs, size_t buf_len, bool stereo,
+			bool *more, size_t *out_len, std::string &err) {
+		return run((void *const *)host_bufs, SF_F32, buf_len, stereo, more, out_len, err);
+	}
+	bool run(void *const *host_bufs, SampleFormat format, size_t buf_len, bool stereo,
 			bool *more, size_t *out_len, std::string &err);
+	/* Announce the next run's format to the backend now (run() does it itself; the file writer asks before it opens a file). */
+	bool set_format(SampleFormat format, std::string &err) {
+		if (format != format_ && !backend_->set_format(format, err)) return false;
+		format_ = format;
+		return true;
+	}
 
 	/* Size the device buffers for runs of up to `frames` frames now (run() grows them on demand, which waits for the
 	 * stream: a host that knows its longest run says so once). */
@@ -303,6 +343,7 @@ private:
 	uint32_t reserved_frames_ = 0;
 	bool reserved_stereo_ = false;
 	bool pcm_swap_ = false;
+	SampleFormat format_ = SF_S16;   /* of the run being rendered */
 	bool plans_dirty_ = true;
 	/* concatenated plans as uploaded; per (stream,voice) offsets */
 	std::vector<Step> all_steps_;

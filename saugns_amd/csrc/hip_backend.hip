@@ -8,7 +8,7 @@
  *   k_decode.h      FastStep / FastLine / FastAux / ChainDesc, scan_kernel, decode_kernel
  *   k_fast_voice.h  fast_voice, fast_kernel<T,SCAN>, repair_kernel<T>
  *   k_chain.h       chain_kernel
- *   k_finish.h      finalize_kernel, mix_kernel, event_kernel
+ *   k_finish.h      finalize_kernel, mix_kernel, mix_few_kernel (int16 and float32 forms), event_kernel
  *   (this file)     buffer and stream pools, table sets, HipBackendImpl: what is launched when
  *
  * Work decomposition (DESIGN.md "Kernels"):
@@ -26,7 +26,8 @@
  *       Each voice's carrier block goes to HBM once (f32 [voice][frame]).
  *   mix_kernel  one thread per output frame sums the voices of its stream in
  *       ascending voice order (the reference's f32 accumulation order,
- *       generator.c:749-788) and writes int16 PCM (795-825).
+ *       generator.c:749-788) and writes int16 PCM (795-825) -- or, on a float32
+ *       run (engine.h: SampleFormat), the sum as it stands.
  *   event_kernel  applies operator updates to the state in HBM.
  *
  * Arithmetic: sau_dev_math.h, compiled with -ffp-contract=off.
@@ -442,11 +443,28 @@ public:
 		pcm_row_ = (size_t)row_stride_ * 2; /* room for stereo */
 		(void)stereo;
 		{
-			if (!pcm_.ensure(pcm_row_ * cfg_.n_streams, err)) return false;
+			if (!pcm_.ensure(pcm_row_ * cfg_.n_streams * pcm_units(), err)) return false;
 			/* (not cleared: every frame of a run is written by a mixer or cleared by zero_pcm, and no frame behind a run's
 			 * length is ever handed out -- until round 6 a memset here, 32 us for a config-4 batch's 677 MB) */
 		}
 		set_.vout_rows = 0; /* re-sized on the next render */
+		return true;
+	}
+
+	/* The PCM block holds a row of pcm_row_ samples per stream in the format of the run at hand: int16, or float32 (engine.h:
+	 * SampleFormat) at twice the bytes. A run of the other format than the last one says so first; the block grows (and may
+	 * move) when the float rows do not fit it -- every MixStream record is then sent again, its row pointer has changed. */
+	size_t pcm_units() const { return pcm_f32_ ? 2 : 1; } /* int16 units per sample */
+	size_t pcm_pitch() const { return pcm_row_ * pcm_units() * sizeof(int16_t); } /* bytes from a stream's row to the next one's */
+	char *pcm_at(uint32_t stream) const { return (char *)pcm_.p + pcm_pitch() * stream; }
+	bool set_format(sauengine::SampleFormat fmt, std::string &err) override {
+		use_device();
+		const bool f32 = fmt == sauengine::SF_F32;
+		if (f32 == pcm_f32_) return true;
+		/* (no wait: the last run's copies out of the rows and this run's stores are in order on the one stream, and a block
+		 * that moves is freed only once the device has drained -- DevBuf::ensure) */
+		pcm_f32_ = f32;
+		if (pcm_row_ && !pcm_.ensure(pcm_row_ * cfg_.n_streams * pcm_units(), err)) { pcm_f32_ = !f32; return false; }
 		return true;
 	}
 
@@ -504,7 +522,8 @@ public:
 	bool poison_run(uint32_t frames, bool stereo, std::string &err) override {
 		(void)frames; (void)stereo;
 		use_device();
-		if (pcm_.p) HIP_OK(hipMemsetD16Async((hipDeviceptr_t)pcm_.p, 0x5a5a, pcm_row_ * cfg_.n_streams, stream_));
+		/* (a float row then reads 0x5a5a5a5a = 1.5e16 per sample: no mix of voices comes near it) */
+		if (pcm_.p) HIP_OK(hipMemsetD16Async((hipDeviceptr_t)pcm_.p, 0x5a5a, pcm_row_ * cfg_.n_streams * pcm_units(), stream_));
 		return true;
 	}
 
@@ -512,10 +531,10 @@ public:
 			std::string &err) override {
 		use_device();
 		if (!pcm_.p || !n_streams || !n_frames) return true;
-		const size_t ch = stereo ? 2 : 1;
-		int16_t *at = pcm_.p + pcm_row_ * first_stream + (size_t)first_frame * ch;
-		if (n_streams == 1) HIP_OK(hipMemsetAsync(at, 0, (size_t)n_frames * ch * sizeof(int16_t), stream_));
-		else HIP_OK(hipMemset2DAsync(at, pcm_row_ * sizeof(int16_t), 0, (size_t)n_frames * ch * sizeof(int16_t), n_streams, stream_));
+		const size_t fb = (stereo ? 2 : 1) * pcm_units() * sizeof(int16_t); /* bytes per frame (zero bytes are +0.0f too) */
+		char *at = pcm_at(first_stream) + (size_t)first_frame * fb;
+		if (n_streams == 1) HIP_OK(hipMemsetAsync(at, 0, (size_t)n_frames * fb, stream_));
+		else HIP_OK(hipMemset2DAsync(at, pcm_pitch(), 0, (size_t)n_frames * fb, n_streams, stream_));
 		return true;
 	}
 
@@ -534,6 +553,9 @@ public:
 		++acc_launches_; /* segments rendered */
 		early_mixed_blocks_ = 0;
 		inmix_live_ = false;
+		const bool f32 = seg.format == sauengine::SF_F32; /* (a float run: set_format has sized the rows) */
+		if (f32 != pcm_f32_) { err = "a segment of another sample format than the run announced"; return false; }
+		if (f32 && seg.swap_bytes) { err = "float32 samples are not byte-swapped"; return false; }
 		const size_t tab_bytes = (size_t)WAVE_LEN * (sizeof(HerpC23) + sizeof(HerpC01));
 		/* (the time-parallel kernels keep their LDS copy of a table in another form: FAST_TAB_BYTES, k_fast_types.h) */
 		const size_t ftab_bytes = FAST_TAB_BYTES;
@@ -618,7 +640,7 @@ public:
 			m.n_rows = seg.streams[s].n_voices;
 			m.amp_scale = seg.streams[s].amp_scale;
 			m.write_len = seg.streams[s].write_len;
-			m.pcm = pcm_.p + pcm_row_ * s;
+			m.pcm = (int16_t *)pcm_at(s); /* (a row of floats on a float run: the mixers' float forms read it so) */
 			if (m.write_len > max_write) max_write = m.write_len;
 			if (m.n_rows > max_rows) max_rows = m.n_rows;
 		}
@@ -978,7 +1000,7 @@ public:
 				};
 				FastParams cfp; /* the closed-form launch of a split segment (also what repair_kernel runs with) */
 				tail_live_ = false;
-				if (main_build == 2 && fp.look && FT == 8 && tailmix_enabled_ && max_write && !fp.cub_ok && seg.len < (1u << 30) &&
+				if (main_build == 2 && fp.look && FT == 8 && tailmix_enabled_ && !f32 && max_write && !fp.cub_ok && seg.len < (1u << 30) &&
 				    mix_few_enabled_ && max_rows <= 8 && seg.n_streams >= 8 && (seg.pcm_offset & 3u) == 0 && (pcm_row_ & 3u) == 0) {
 					/* many streams of a few voices (a batch of small scripts): where a stream's last row is a look-back voice's and the
 					 * others are closed-form voices', the look-back launch mixes the stream as it stores that row (k_fast_types.h:
@@ -1167,7 +1189,7 @@ public:
 										mp.blk_lo = mixed_blocks; mp.blk_hi = hi;
 										TimedPair *tm = timing_on_ ? new_pair(1) : nullptr;
 										if (tm) (void)hipEventRecord(tm->a, stream_);
-										hipLaunchKernelGGL(mix_kernel, dim3(hi - mixed_blocks, seg.n_streams), dim3(256), 0, stream_, mp);
+										hipLaunchKernelGGL((f32 ? mix_kernel_f32 : mix_kernel), dim3(hi - mixed_blocks, seg.n_streams), dim3(256), 0, stream_, mp);
 										if (tm) (void)hipEventRecord(tm->b, stream_);
 										mixed_blocks = hi;
 									}
@@ -1208,7 +1230,9 @@ public:
 						/* ... and a bank of voices mixed into one stream: the launch mixes its own rows, chunk by chunk behind the rendering;
 						 * premix_kernel has the last word. Config 3: 2.056 -> 1.995 ms per step (the launch 1.74 -> 1.87 ms, the mixer
 						 * 0.26 -> 0.07 ms) */
-						if (inmix_enabled_ && seg.n_streams == 1 && max_write && seg.n_voices >= inmix_min_voices_ && seg.max_steps >= inmix_min_steps_ &&
+						/* (not on a float run: the launch's tiles store int16 -- the 12-row build has no register to spare for another
+						 * store form -- so mix_kernel_f32 writes every frame, as under SAU_AMD_NO_INMIX) */
+						if (inmix_enabled_ && !f32 && seg.n_streams == 1 && max_write && seg.n_voices >= inmix_min_voices_ && seg.max_steps >= inmix_min_steps_ &&
 						    row_stride_ < (1u << 24)) {
 							fp.inmix_stream = S.mstreams.p;
 							fp.inmix_flags = 64u | 32u | (seg.stereo ? 1u : 0u) | (seg.swap_bytes ? 2u : 0u) | (tune_env("SAU_AMD_INMIX_DRY") ? 4u : 0u) | ((inmix_at_ & 15u) << 8);
@@ -1354,7 +1378,16 @@ public:
 			hipStream_t ms = stream_;
 			TimedPair *tm = timing_on_ ? new_pair(1) : nullptr;
 			if (tm) (void)hipEventRecord(tm->a, ms);
-			if (mix_few_enabled_ && max_rows <= 8 && seg.n_streams >= 8 && (seg.pcm_offset & 3u) == 0 && (pcm_row_ & 3u) == 0)
+			/* mix_few_kernel_f32's 16-byte stores, derived for 4-byte samples: a thread's four frames begin at byte
+			 * pcm_pitch() * stream + (pcm_offset + i0) * 4 * channels of a 256-byte-aligned block, i0 a multiple of 4 -- aligned
+			 * when the pitch is a multiple of 16 bytes and pcm_offset a multiple of 4 (mono), of 2 (stereo: a frame is 8 bytes).
+			 * (Its 16-byte row loads are at i0 of the voice rows, whatever pcm_offset is.) */
+			const bool few_f32_aligned = (pcm_pitch() & 15u) == 0 && (seg.pcm_offset & (seg.stereo ? 1u : 3u)) == 0;
+			if (f32 && mix_few_enabled_ && max_rows <= 8 && seg.n_streams >= 8 && few_f32_aligned)
+				hipLaunchKernelGGL(mix_few_kernel_f32, dim3((max_write + 1023) / 1024, seg.n_streams), dim3(256), 0, ms, mp);
+			else if (f32) /* (mp.inmix is NULL on a float run: no launch has mixed anything) */
+				hipLaunchKernelGGL(mix_kernel_f32, dim3((max_write + 255) / 256, seg.n_streams), dim3(256), 0, ms, mp);
+			else if (mix_few_enabled_ && max_rows <= 8 && seg.n_streams >= 8 && (seg.pcm_offset & 3u) == 0 && (pcm_row_ & 3u) == 0)
 				/* many streams of a few voices each: four frames per thread, no tile staging (k_finish.h) */
 				hipLaunchKernelGGL(mix_few_kernel, dim3((max_write + 1023) / 1024, seg.n_streams), dim3(256), 0, ms, mp);
 			else if (mp.inmix && !mp.early_blocks && mix64_enabled_)
@@ -1400,13 +1433,21 @@ public:
 	}
 
 	bool fetch_pcm(uint32_t stream, int16_t *dst, uint32_t frames, bool stereo, std::string &err) override {
+		if (pcm_f32_) { err = "the last run's samples are float32"; return false; }
+		return fetch_units(stream, dst, (size_t)frames * (stereo ? 2 : 1), err);
+	}
+	bool fetch_pcm_f32(uint32_t stream, float *dst, uint32_t frames, bool stereo, std::string &err) override {
+		if (!pcm_f32_) { err = "the last run's samples are int16"; return false; }
+		return fetch_units(stream, (int16_t *)dst, (size_t)frames * (stereo ? 2 : 1) * 2, err);
+	}
+	/* n int16 units (a float sample is two) from the start of the stream's row */
+	bool fetch_units(uint32_t stream, int16_t *dst, const size_t n, std::string &err) {
 		use_device();
-		const size_t n = (size_t)frames * (stereo ? 2 : 1);
 		/* the caller's memory is pageable: a device copy straight into it costs milliseconds of
 		 * pinning per call, so the PCM goes through a page-locked block (unless dst is one) */
 		const bool pinned = host_blocks_.count(dst) != 0;
 		if (!pinned && !h_pcm_.ensure(n, err)) return false;
-		HIP_OK(hipMemcpyAsync(pinned ? dst : h_pcm_.p, pcm_.p + pcm_row_ * stream, n * sizeof(int16_t),
+		HIP_OK(hipMemcpyAsync(pinned ? dst : h_pcm_.p, pcm_at(stream), n * sizeof(int16_t),
 				hipMemcpyDeviceToHost, stream_));
 		HIP_OK(hipStreamSynchronize(stream_));
 		if (!pinned) memcpy(dst, h_pcm_.p, n * sizeof(int16_t));
@@ -1417,12 +1458,20 @@ public:
 	 * ahead of the next run's kernels on the one stream */
 	bool fetch_pcm_async(uint32_t stream, int16_t *dst, uint32_t frames, bool stereo, int slot,
 			std::string &err) override {
+		if (pcm_f32_) { err = "the last run's samples are float32"; return false; }
+		return fetch_bytes_async(stream, dst, (size_t)frames * (stereo ? 2 : 1) * sizeof(int16_t), slot, err);
+	}
+	bool fetch_pcm_f32_async(uint32_t stream, float *dst, uint32_t frames, bool stereo, int slot,
+			std::string &err) override {
+		if (!pcm_f32_) { err = "the last run's samples are int16"; return false; }
+		return fetch_bytes_async(stream, dst, (size_t)frames * (stereo ? 2 : 1) * sizeof(float), slot, err);
+	}
+	bool fetch_bytes_async(uint32_t stream, void *dst, size_t bytes, int slot, std::string &err) {
 		slot &= 3;
 		use_device();
 		if (!fetch_ev_[slot]) HIP_OK(hipEventCreateWithFlags(&fetch_ev_[slot], hipEventDisableTiming));
 		hipStream_t cs = stream_;
-		HIP_OK(hipMemcpyAsync(dst, pcm_.p + pcm_row_ * stream,
-				(size_t)frames * (stereo ? 2 : 1) * sizeof(int16_t), hipMemcpyDeviceToHost, cs));
+		HIP_OK(hipMemcpyAsync(dst, pcm_at(stream), bytes, hipMemcpyDeviceToHost, cs));
 		HIP_OK(hipEventRecord(fetch_ev_[slot], cs));
 		return true;
 	}
@@ -1447,7 +1496,9 @@ public:
 		host_blocks_.erase(it);
 	}
 
-	const int16_t *device_pcm(uint32_t stream) override { return pcm_.p ? pcm_.p + pcm_row_ * stream : nullptr; }
+	const int16_t *device_pcm(uint32_t stream) override { return pcm_.p && !pcm_f32_ ? (const int16_t *)pcm_at(stream) : nullptr; }
+	const float *device_pcm_f32(uint32_t stream) override { return pcm_.p && pcm_f32_ ? (const float *)pcm_at(stream) : nullptr; }
+	size_t device_pcm_pitch() override { return pcm_.p ? pcm_pitch() : 0; }
 
 	bool sync(std::string &err) override {
 		use_device();
@@ -1600,7 +1651,8 @@ private:
 	int geo_ = 0;
 	bool debug_ = false;
 	uint32_t row_stride_ = 0;
-	size_t pcm_row_ = 0;
+	size_t pcm_row_ = 0;   /* samples per stream's row (room for stereo) */
+	bool pcm_f32_ = false; /* the rows hold float32 samples: the run at hand, or the last one, is a float run (set_format) */
 	WaveConst wconst_[12];
 	DevBuf<DevOp> ops_;
 	DevBuf<DevOp> ops_snap_[4]; /* save_state() */

@@ -1,5 +1,5 @@
 /* k_finish.h -- part of hip_backend.hip (included there, inside namespace sauhip; not a header of its own).
- * finalize_kernel, premix_kernel, mix_kernel, mix_few_kernel, event_kernel. */
+ * finalize_kernel, premix_kernel, mix_kernel, mix_few_kernel and their float32 forms, event_kernel. */
 /* Apply the closed forms to the operator state, or hand the whole segment
  * to the block loop when a chunk had to bail out. */
 __global__ void __launch_bounds__(64) finalize_kernel(FastParams P) {
@@ -231,7 +231,9 @@ struct MixParams {
 #endif
 constexpr int MIX_TILE = 256; /* voices whose constants are staged at a time */
 constexpr int MIX_AHEAD = 32; /* loads per batch and thread */
-template <int BLK = 256>
+/* OutT: int16_t -- the reference's PCM, pcm16() of the sum -- or float: the sum as it stands, neither clamped nor rounded, a NaN
+ * left a NaN (float32 runs, engine.h: SampleFormat; the stream's row is then a row of floats, and nothing swaps bytes) */
+template <int BLK = 256, typename OutT = int16_t>
 __device__ __forceinline__ void mix_body(const MixParams &P, const MixStream &ms, const uint32_t bx,
 		float *s_pan, uint32_t *s_valid, uint32_t *s_prow, uint32_t &s_special, const bool covered = false) {
 	const uint32_t tl = threadIdx.x; /* within the BLK frames of bx */
@@ -317,6 +319,17 @@ __device__ __forceinline__ void mix_body(const MixParams &P, const MixStream &ms
 		}
 	}
 	if (!act) return;
+	if constexpr (std::is_same<OutT, float>::value) {
+		float *row = (float *)ms.pcm;
+		if (P.stereo) {
+			typedef float __attribute__((ext_vector_type(2))) f32x2;
+			f32x2 lr; lr.x = L; lr.y = R;
+			*(f32x2 *)(row + 2 * (size_t)(P.pcm_offset + i)) = lr; /* (8-byte aligned: rows start on 256 bytes) */
+		} else {
+			row[P.pcm_offset + i] = (L + R) * 0.5f;
+		}
+		return;
+	}
 	if (P.stereo) {
 		int16_t *d = ms.pcm + 2 * (size_t)(P.pcm_offset + i);
 		const int16_t l16 = pcm16(L), r16 = pcm16(R);
@@ -328,7 +341,7 @@ __device__ __forceinline__ void mix_body(const MixParams &P, const MixStream &ms
 	}
 }
 
-template <int BLK>
+template <int BLK, typename OutT = int16_t>
 __device__ __forceinline__ void mix_kernel_body(const MixParams &P) {
 	__shared__ float s_pan[MIX_TILE];
 	__shared__ uint32_t s_valid[MIX_TILE];
@@ -350,9 +363,13 @@ __device__ __forceinline__ void mix_kernel_body(const MixParams &P) {
 		covered = k < P.inmix[INMIX_NCH] && ((P.inmix[INMIX_CHUNK + INMIX_LINE * k + INMIX_BITS + (j >> 5)] >> (j & 31u)) & 1u) != 0;
 		if (__syncthreads_and(covered)) return;
 	}
-	mix_body<BLK>(P, ms, bx, s_pan, s_valid, s_prow, s_special, covered);
+	mix_body<BLK, OutT>(P, ms, bx, s_pan, s_valid, s_prow, s_special, covered);
 }
 __global__ void __launch_bounds__(256) mix_kernel(MixParams P) { mix_kernel_body<256>(P); }
+/* ... with float32 samples. A float run's every frame is this kernel's or mix_few_kernel_f32's: the launches that mix tiles or
+ * stream tails themselves (k_fast_types.h) store int16 only and are not asked to on such a run (hip_backend.hip), so P.inmix
+ * is NULL here and the 64-frame form has no float build */
+__global__ void __launch_bounds__(256) mix_kernel_f32(MixParams P) { mix_kernel_body<256, float>(P); }
 /* ... in blocks of 64 frames, a wave each: what follows a closed-form launch that has mixed most of the tiles itself (round 6). What
  * is left then is a few hundred tiles in a row -- each XCD's last chunk -- and as workgroups of 256 frames x 1024 rows (1 MB of
  * loads each) they were one or two per CU, by chance: 87 us for 0.36 GB. A quarter the size they spread evenly */
@@ -362,7 +379,8 @@ __global__ void __launch_bounds__(64) mix_kernel64(MixParams P) { mix_kernel_bod
  * consecutive frames per thread, 16-byte row loads, per-row records read straight from memory -- mix_kernel's tile
  * staging (three barriers per workgroup for a tile of two rows) and one workgroup per 256 frames left the 64-stream
  * batch's mixer at 1 TB/s. Same sums in the same order. pcm_offset is a multiple of 4 (the host checks). */
-__global__ void __launch_bounds__(256) mix_few_kernel(MixParams P) {
+template <typename OutT>
+__device__ __forceinline__ void mix_few_body(const MixParams &P) {
 	const MixStream ms = P.streams[blockIdx.y];
 	const uint32_t i0 = (blockIdx.x * 256 + threadIdx.x) * 4;
 	if (i0 >= ms.write_len) return;
@@ -404,6 +422,37 @@ __global__ void __launch_bounds__(256) mix_few_kernel(MixParams P) {
 			}
 		}
 	}
+	if constexpr (std::is_same<OutT, float>::value) {
+		/* float32 samples: the four frames are 16 bytes mono, 32 bytes stereo. The host launches this form only where those
+		 * stores are aligned: rows start on 256 bytes, a mono frame is 4 bytes (pcm_offset a multiple of 4, as for int16),
+		 * a stereo frame 8 (pcm_offset even); i0 is a multiple of 4. A partial last group takes the scalar tail */
+		typedef float __attribute__((ext_vector_type(4))) f32x4;
+		float *row = (float *)ms.pcm;
+		if (P.stereo) {
+			float *d = row + 2 * (size_t)(P.pcm_offset + i0);
+			if (full) {
+				f32x4 a, b;
+				a.x = L[0]; a.y = R[0]; a.z = L[1]; a.w = R[1];
+				b.x = L[2]; b.y = R[2]; b.z = L[3]; b.w = R[3];
+				((f32x4 *)d)[0] = a;
+				((f32x4 *)d)[1] = b;
+			} else {
+#pragma unroll
+				for (int k = 0; k < 4; ++k) if (i0 + k < ms.write_len) { d[2 * k] = L[k]; d[2 * k + 1] = R[k]; }
+			}
+		} else {
+			float *d = row + (size_t)(P.pcm_offset + i0);
+			if (full) {
+				f32x4 m;
+				m.x = (L[0] + R[0]) * 0.5f; m.y = (L[1] + R[1]) * 0.5f; m.z = (L[2] + R[2]) * 0.5f; m.w = (L[3] + R[3]) * 0.5f;
+				*(f32x4 *)d = m;
+			} else {
+#pragma unroll
+				for (int k = 0; k < 4; ++k) if (i0 + k < ms.write_len) d[k] = (L[k] + R[k]) * 0.5f;
+			}
+		}
+		return;
+	}
 	int16_t o[8];
 #pragma unroll
 	for (int k = 0; k < 4; ++k) {
@@ -426,6 +475,8 @@ __global__ void __launch_bounds__(256) mix_few_kernel(MixParams P) {
 		else for (uint32_t k = 0; i0 + k < ms.write_len; ++k) d[k] = o[k];
 	}
 }
+__global__ void __launch_bounds__(256) mix_few_kernel(MixParams P) { mix_few_body<int16_t>(P); }
+__global__ void __launch_bounds__(256) mix_few_kernel_f32(MixParams P) { mix_few_body<float>(P); }
 
 /* (launched with 64 threads per workgroup: told so, the kernel keeps a DevOp in registers instead of spilling 84 of them) */
 __global__ void __launch_bounds__(64) event_kernel(DevOp *ops, const OpUpdate *recs, uint32_t n, const WaveConst *wc) {

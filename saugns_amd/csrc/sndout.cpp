@@ -8,6 +8,8 @@
  * page-locked memory and to the file while the next chunk renders.
  * Files are byte-identical to the reference writer's for the same PCM,
  * including its AU quirk of storing the frame count in the size field.
+ * SAU_AMD_SNDFILE_WAV_F32 has no counterpart there: the mixers' float32 samples
+ * (Engine::run_f32) as a WAVE_FORMAT_IEEE_FLOAT file, through the same stage.
  */
 #include "../../include/saugns_amd.h"
 #include "engine.h"
@@ -60,11 +62,31 @@ struct SndOut {
 			put_le16(f, 16);
 			fputs("data", f);
 			put_le32(f, 0);
+		} else if (fmt == SAU_AMD_SNDFILE_WAV_F32) {
+			/* a non-PCM format: the `fmt ` chunk carries cbSize, and a `fact` chunk the frame count */
+			fputs("RIFF", f);
+			put_le32(f, 50);
+			fputs("WAVE", f);
+			fputs("fmt ", f);
+			put_le32(f, 18);
+			put_le16(f, 3); /* WAVE_FORMAT_IEEE_FLOAT */
+			put_le16(f, ch);
+			put_le32(f, srate);
+			put_le32(f, (uint32_t)ch * srate * 4);
+			put_le16(f, (uint16_t)(ch * 4));
+			put_le16(f, 32);
+			put_le16(f, 0); /* cbSize */
+			fputs("fact", f);
+			put_le32(f, 4);
+			put_le32(f, 0);
+			fputs("data", f);
+			put_le32(f, 0);
 		}
 		return true;
 	}
-	bool write(const int16_t *buf, size_t n_frames) {
-		size_t w = fwrite(buf, (size_t)channels * 2, n_frames, f);
+	size_t sample_bytes() const { return format == SAU_AMD_SNDFILE_WAV_F32 ? 4 : 2; }
+	bool write(const void *buf, size_t n_frames) {
+		size_t w = fwrite(buf, (size_t)channels * sample_bytes(), n_frames, f);
 		frames += w;
 		return w == n_frames;
 	}
@@ -78,6 +100,14 @@ struct SndOut {
 			put_le32(f, 36 + bytes);
 			fseek(f, 32, SEEK_CUR);
 			put_le32(f, bytes);
+		} else if (format == SAU_AMD_SNDFILE_WAV_F32) {
+			uint32_t bytes = (uint32_t)(channels * frames * 4);
+			fseek(f, 4, SEEK_SET);
+			put_le32(f, 50 + bytes);
+			fseek(f, 46, SEEK_SET);
+			put_le32(f, (uint32_t)frames);
+			fseek(f, 54, SEEK_SET);
+			put_le32(f, bytes);
 		}
 		int err = ferror(f);
 		fclose(f);
@@ -90,7 +120,7 @@ thread_local std::string g_file_error;
 
 bool render_file_over(const sauProgram *prg, uint32_t srate, const char *path, int format,
 		int channels, Backend *backend /* owned */, uint64_t *frames_out, std::string &err) {
-	if (!prg || !path || (channels != 1 && channels != 2) || format < 0 || format > SAU_AMD_SNDFILE_WAV) {
+	if (!prg || !path || (channels != 1 && channels != 2) || format < 0 || format > SAU_AMD_SNDFILE_WAV_F32) {
 		err = "bad argument";
 		delete backend;
 		return false;
@@ -98,15 +128,18 @@ bool render_file_over(const sauProgram *prg, uint32_t srate, const char *path, i
 	Engine *engine = Engine::create(&prg, 1, srate, backend, err);
 	if (!engine) return false;
 	const bool stereo = channels == 2;
+	const bool f32 = format == SAU_AMD_SNDFILE_WAV_F32;
 	engine->set_pcm_byteswap(format == SAU_AMD_SNDFILE_AU);
+	/* (a backend without float output says so before there is a file) */
+	if (f32 && !engine->set_format(sauengine::SF_F32, err)) { delete engine; return false; }
 	/* Player_run asks the generator for 256 ms at a time (saugns.c:471,526: ch_len); the
 	 * reference's block lattice restarts at each of those calls, so a device run covers whole ones */
 	size_t call = (size_t)((uint64_t)256 * srate / 1000);
 	if (call == 0) call = 1;
 	engine->set_call_len(call);
 	const size_t chunk = call >= 176400 ? call : 176400 / call * call; /* frames per device run */
-	const size_t bytes = chunk * (size_t)channels * sizeof(int16_t);
-	int16_t *host[2] = {(int16_t *)backend->alloc_host(bytes), (int16_t *)backend->alloc_host(bytes)};
+	const size_t bytes = chunk * (size_t)channels * (f32 ? sizeof(float) : sizeof(int16_t));
+	void *host[2] = {backend->alloc_host(bytes), backend->alloc_host(bytes)};
 	SndOut out;
 	bool ok = host[0] && host[1];
 	if (!ok) err = "out of page-locked memory";
@@ -120,10 +153,11 @@ bool render_file_over(const sauProgram *prg, uint32_t srate, const char *path, i
 	while (ok && more) {
 		size_t len = 0;
 		/* PCM stays on the device; the copy below queues behind the mixer */
-		ok = engine->run(nullptr, chunk, stereo, &more, &len, err);
+		ok = f32 ? engine->run_f32(nullptr, chunk, stereo, &more, &len, err) : engine->run(nullptr, chunk, stereo, &more, &len, err);
 		if (!ok) break;
 		if (len) {
-			ok = backend->fetch_pcm_async(0, host[slot], (uint32_t)len, stereo, slot, err);
+			ok = f32 ? backend->fetch_pcm_f32_async(0, (float *)host[slot], (uint32_t)len, stereo, slot, err)
+			         : backend->fetch_pcm_async(0, (int16_t *)host[slot], (uint32_t)len, stereo, slot, err);
 			pending[slot] = len;
 		}
 		/* while this chunk renders and copies, the previous one goes to the file */
