@@ -15,16 +15,10 @@
  * all; and it stores the previous batch of samples to the chain's first row, where the final pass takes them
  * (amplitude, mixing into the parent, voice output). One barrier per batch. 4096 chains are 64 workgroups on
  * 64 CUs, and the render takes frames x chain latency. */
-#ifndef SAU_CHAIN_BATCH_FRAMES
-#define SAU_CHAIN_BATCH_FRAMES 32
-#endif
 /* frames per lane and batch: what a batch costs beside the recurrence itself (its LDS reads and writes, the bound check
  * of the short rounding form, the barrier) is spread over that many sample steps -- 16: 117 ns per step, 32: see DESIGN.md 4.3 */
-constexpr uint32_t CHAIN_BATCH = SAU_CHAIN_BATCH_FRAMES;
+/* (CHAIN_BATCH and the sizes that follow from it -- CHAIN_IO_WORDS, CHAIN_IO_BYTES, CHAIN_TAB_BYTES -- are in launch_plan.h) */
 constexpr uint32_t CHAIN_NQ = CHAIN_BATCH / 4;     /* 16-byte quads of a batch */
-constexpr uint32_t CHAIN_IO_WORDS = CHAIN_BATCH * 64; /* one array of one batch */
-constexpr uint32_t CHAIN_TAB_BYTES = 65536, CHAIN_TAB_C01 = 32768; /* a wave table in chain_kernel's LDS: [c3, c2] x 2048, then [c1, c0] x 2048 as f64 */
-constexpr size_t CHAIN_IO_BYTES = (size_t)(2 * 2 + 2) * CHAIN_IO_WORDS * 4; /* in[2][2] + out[2] */
 
 /* LDS layout of a batch array: frame 4q + r of lane l at word (q * 64 + l) * 4 + r -- a lane's four 16-byte
  * accesses are conflict-free */

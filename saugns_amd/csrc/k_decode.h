@@ -72,9 +72,6 @@ static_assert(sizeof(FastAux) == 80, "FastAux is 20 dwords");
 
 
 typedef const uint32_t __attribute__((address_space(4))) *const_u32_ptr;
-#ifndef FK_GRID
-#define FK_GRID 256 /* workgroups at most: one per CU (LDS allows no more at T = 4) */
-#endif
 #ifndef FK_COMMON
 #define FK_COMMON 1
 #endif

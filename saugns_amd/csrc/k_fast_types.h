@@ -52,17 +52,14 @@ template <bool WIDE> struct FkTab {
 	static constexpr uint32_t BYTES = WIDE ? 65536u : (uint32_t)(WAVE_LEN * (sizeof(HerpC23) + sizeof(HerpC01)));
 	static constexpr uint32_t C01 = (uint32_t)(WAVE_LEN * sizeof(HerpC23)); /* where a block's [c1, c0] entries begin */
 };
-constexpr uint32_t FAST_TAB_BYTES = FkTab<false>::BYTES, FAST_TAB_BYTES_WIDE = FkTab<true>::BYTES;
+static_assert(FAST_TAB_BYTES == FkTab<false>::BYTES && FAST_TAB_BYTES_WIDE == FkTab<true>::BYTES, "launch_plan.h plans with these sizes");
 
 struct FastStep;
 struct FastLine;
 struct FastAux;
 struct ChainDesc;
 constexpr uint32_t CHAIN_DESC_WORDS = 32;
-constexpr uint32_t FAST_MAX_SCAN = 8;   /* oscillators with running-sum phases per multi-pass voice */
-constexpr uint32_t LOOK_LDS_BYTES = FAST_MAX_SCAN * 2 * 64 * sizeof(unsigned long long); /* the look-back rings of a workgroup */
-constexpr uint32_t FAST_MAX_LEVELS = 3; /* running sums that depend on running sums: at most that many sum passes
-                                         * (FastParams.sum_levels of them are launched for a segment) */
+/* (FAST_MAX_SCAN, LOOK_LDS_BYTES, FAST_MAX_LEVELS, FAST_CUB_ROWS, FAST_LISTS, INMIX_NSMALL: launch_plan.h -- the host's planner needs them too) */
 /* A repeated phase (the output holds, wosc.h:251-252) on the first lane an operator's values are
  * defined in cannot take the held output from the lane before. What that spoils is exactly the
  * first owned frame of the row (one lane per nesting level upwards). fast_kernel notes such row
@@ -76,14 +73,10 @@ constexpr uint32_t FAST_REPAIR_WORDS = 2 + 2 * FAST_MAX_REPAIR; /* count, pad, t
 constexpr uint32_t FAST_FLAGS = FAST_MAX_LEVELS + 9; /* pass_flags words */
 constexpr uint32_t FAST_EARLY_FLAG = FAST_MAX_LEVELS + 8; /* some voice has early chains (FastInfo.early) */
 constexpr uint32_t FAST_CUB_FLAG = FAST_MAX_LEVELS + 7; /* some voice has FastInfo.cub set */
-constexpr uint32_t FAST_CUB_ROWS = 4;                  /* rows per pass of that build */
 constexpr uint32_t FAST_CF_COUNT = FAST_MAX_LEVELS + 5; /* voices in FastParams.vlists[0]: closed-form ones of a segment that also has look-back voices */
 constexpr uint32_t FAST_LK_COUNT = FAST_MAX_LEVELS + 6; /* ... in vlists[1]: the look-back voices */
 constexpr uint32_t FAST_LEAN_FLAG = FAST_MAX_LEVELS + 4; /* ... some voice has feedback chains and no running sum to scan (fast_kernel<T, 3>) */
 constexpr uint32_t FAST_DYN_CTR = FAST_MAX_LEVELS + 3; /* ... the one that deals out fast_kernel<T, 0>'s tasks (dyn_chunks) */
-/* Decoded steps are kept once per pass that runs them ([list][voice][step]): a pass walks its own list and never
- * loads a step only to find that another pass needs it (the per-step cost of the interpreter is most of a pass). */
-constexpr uint32_t FAST_LISTS = 5; /* 0: only / final pass, 1..3: sum passes, 4: chain-input pass */
 __device__ __forceinline__ uint32_t fast_list_of(uint32_t mode, uint32_t sum_levels) {
 	return (mode == 0 || mode == sum_levels + 1) ? 0u : (mode == sum_levels + 2 ? 4u : mode);
 }
@@ -99,7 +92,6 @@ constexpr uint32_t CHAIN_MARK = 0xC4A10001u; /* DevOp.ras_level of a W operator:
  * them `small` groups long, the others sharing what is in front (and numbered first). Used alike by fast_voice (a task's groups),
  * premix_kernel (the chunks' frames) and, through its control words, the tiles and mix_kernel. -> regular chunks there are, the
  * group the short ones begin at (ngroups: none), groups per regular chunk */
-constexpr uint32_t INMIX_NSMALL = 8; /* short chunks at the end of the closed-form launch's queues: one per XCD (see INMIX_NCH1 below) */
 struct FkChunks { uint32_t nch1, body, per; };
 __device__ __forceinline__ FkChunks fk_chunk_groups(const uint32_t ngroups, const uint32_t K, const uint32_t small, const uint32_t c,
 		uint32_t &lo, uint32_t &hi) {

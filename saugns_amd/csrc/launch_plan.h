@@ -1,0 +1,703 @@
+/* launch_plan.h -- what the HIP backend launches for a segment, decided on the host.
+ *
+ * Plain C++: no HIP, no device, no allocation. Everything here is arithmetic on a SegmentDesc, the tuning switches and four
+ * device limits -- rows per pass and LDS budgets, which build of the time-parallel kernels a segment takes, wide or narrow
+ * tables, split / duo / inner launches, in-launch mixing, chain chunk boundaries, task sizes, every grid. hip_backend.hip
+ * asks for a plan per segment and carries it out (buffers, parameter blocks, launches, events); tests/test_launch_plan.py
+ * asks for the same plans without a GPU (tests/hooks/test_hooks.cpp: sauAmd_launch_plan).
+ *
+ * The measurement comments are the project's memory of why a rule is what it is: they stay with their rule.
+ */
+#ifndef SAU_LAUNCH_PLAN_H
+#define SAU_LAUNCH_PLAN_H
+
+#include "engine.h"
+#include "sau_dev_math.h"
+#include <string.h>
+
+namespace sauplan {
+
+using namespace saudev;
+using sauengine::SegmentDesc;
+
+/* ---- constants both sides see (the kernel parts of hip_backend.hip take them from here; where a value follows a
+ * device-only type, a static_assert there ties the two together) ---- */
+#ifndef FK_GRID
+#define FK_GRID 256 /* workgroups of a time-parallel launch at most: one per CU (LDS allows no more at T = 4) */
+#endif
+/* a wave table in the time-parallel kernels' LDS, narrow and wide form (k_fast_types.h: FkTab) */
+constexpr uint32_t FAST_TAB_BYTES = (uint32_t)(WAVE_LEN * (sizeof(HerpC23) + sizeof(HerpC01))), FAST_TAB_BYTES_WIDE = 65536u;
+constexpr uint32_t FAST_MAX_SCAN = 8;   /* oscillators with running-sum phases per multi-pass voice */
+constexpr uint32_t LOOK_LDS_BYTES = FAST_MAX_SCAN * 2 * 64 * sizeof(unsigned long long); /* the look-back rings of a workgroup */
+constexpr uint32_t FAST_MAX_LEVELS = 3; /* running sums that depend on running sums: at most that many sum passes
+                                         * (FastParams.sum_levels of them are launched for a segment) */
+constexpr uint32_t FAST_CUB_ROWS = 4;   /* rows per pass of the builds with the loop tails of `cub` R segments */
+/* Decoded steps are kept once per pass that runs them ([list][voice][step]): a pass walks its own list and never
+ * loads a step only to find that another pass needs it (the per-step cost of the interpreter is most of a pass). */
+constexpr uint32_t FAST_LISTS = 5; /* 0: only / final pass, 1..3: sum passes, 4: chain-input pass */
+constexpr uint32_t INMIX_NSMALL = 8; /* short chunks at the end of the closed-form launch's queues: one per XCD (k_fast_types.h: INMIX_NCH1) */
+#ifndef SAU_CHAIN_BATCH_FRAMES
+#define SAU_CHAIN_BATCH_FRAMES 32
+#endif
+/* chain_kernel (k_chain.h): frames per lane and batch: what a batch costs beside the recurrence itself (its LDS reads and writes, the bound check
+ * of the short rounding form, the barrier) is spread over that many sample steps -- 16: 117 ns per step, 32: see DESIGN.md 4.3 */
+constexpr uint32_t CHAIN_BATCH = SAU_CHAIN_BATCH_FRAMES;
+constexpr uint32_t CHAIN_IO_WORDS = CHAIN_BATCH * 64; /* one array of one batch */
+constexpr uint32_t CHAIN_TAB_BYTES = 65536, CHAIN_TAB_C01 = 32768; /* a wave table in chain_kernel's LDS: [c3, c2] x 2048, then [c1, c0] x 2048 as f64 */
+constexpr size_t CHAIN_IO_BYTES = (size_t)(2 * 2 + 2) * CHAIN_IO_WORDS * 4; /* in[2][2] + out[2] */
+constexpr size_t MISC_BYTES = 1488;      /* sizeof(Misc), the block loop's per-team record (k_common.h) */
+/* a wave table as the block loop stages it: the Hermite coefficients as they are in HBM */
+constexpr size_t BLOCK_TAB_BYTES = (size_t)WAVE_LEN * (sizeof(HerpC23) + sizeof(HerpC01));
+
+/* ---- the tuning switches (SAU_AMD_*, looked at only under SAU_AMD_TUNE: engine.h) ---- */
+struct Tuning {
+	/* block loop */
+	int geo = 1;                 /* SAU_AMD_GEOMETRY: "4x4" (1, default: 4 waves x 4 samples per lane) or "8x2" (0) */
+	/* voices per segment from which feedback voices get sixteen one-wave teams per workgroup
+	 * (0: never; 1: always, also without feedback -- tests) */
+	uint32_t multi_min = 256;    /* SAU_AMD_MULTI_MIN */
+	uint32_t multi_teams = 16;   /* SAU_AMD_MULTI_TEAMS: 8 or 16 single-wave teams per workgroup */
+	/* device limits as set by hand */
+	uint32_t fk_grid = 0;        /* SAU_AMD_FK_GRID: 1..FK_GRID (0: what the device has) */
+	bool lds_limit_set = false;  /* SAU_AMD_LDS_LIMIT */
+	size_t lds_limit = 0;
+	/* time-parallel path */
+	bool fast = true;            /* SAU_AMD_NO_FAST */
+	bool seq = true;             /* SAU_AMD_NO_SEQ: running-sum phases in the time-parallel kernel */
+	bool two_pass = true;        /* SAU_AMD_NO_TWO_PASS: ... in two passes where possible */
+	bool lookback = true;        /* SAU_AMD_NO_LOOKBACK: single-pass running sums */
+	bool inc_rows = true;        /* SAU_AMD_NO_INC_ROWS */
+	uint32_t fast_rows = 8;      /* SAU_AMD_FAST_ROWS: 8 (default), 6, 5, 4 or 2 */
+	uint32_t look_rows = 8;      /* rows per pass of the single-pass build (SAU_AMD_LOOK_ROWS; 0: no such build, the full one takes every voice) */
+	uint32_t look_min_voices = 1;/* SAU_AMD_LOOK_MIN_VOICES: segments with fewer voices keep the several-pass form */
+	bool look_no_lds = false, look_withhold = false, look_spread = false; /* SAU_AMD_LOOK_NO_LDS / _WITHHOLD / _SPREAD (FastParams.look_wpv_flags) */
+	bool wide_tabs = true;       /* SAU_AMD_NO_WIDE_TABS: closed-form launches with f64 [c1, c0] table entries in LDS */
+	bool wide_look = true;       /* SAU_AMD_NO_WIDE_LOOK: ... and the look-back launch */
+	uint32_t more_rows = 12;     /* SAU_AMD_MORE_ROWS: 0, 10 or 12 */
+	bool repair = true;          /* SAU_AMD_NO_REPAIR */
+	bool analyze_lds = true;     /* SAU_AMD_ANALYZE_NO_LDS: analyze_kernel on the records in HBM */
+	/* feedback chains */
+	bool chain = true;           /* SAU_AMD_NO_CHAIN: feedback recurrences with lanes = voices */
+	bool chain_inline = true;    /* SAU_AMD_NO_CHAIN_INLINE: chains fed from their own lines: chain_kernel's feeder waves evaluate them */
+	bool chain_early = true;     /* SAU_AMD_NO_EARLY_CHAINS */
+	uint32_t chain_chunks = 0;   /* SAU_AMD_CHAIN_CHUNKS: a fixed number of chunks per segment, 1..32 (1: no pipeline; 0: by frames) */
+	uint32_t chain_chunk_frames = 16384; /* SAU_AMD_CHAIN_CHUNK_FRAMES, at least 4096 */
+	bool short_last_chunk = true;/* SAU_AMD_NO_SHORT_LAST_CHUNK */
+	bool chain_alone = false;    /* SAU_AMD_CHAIN_ALONE (hip_backend.hip: chain_alone_lds) */
+	bool lean = true;            /* SAU_AMD_NO_LEAN: chains' passes in a build without the several-pass sums */
+	uint32_t lean_rows = 6;      /* SAU_AMD_LEAN_ROWS: rows per pass of fast_kernel<T, 3> at most (6, 5 or 4) */
+	/* closed-form launches: tasks, queues, mixing */
+	bool dyn = true;             /* SAU_AMD_NO_DYN: closed-form launches deal tasks out through a counter */
+	uint32_t dyn_groups = 12;    /* row groups per task of a closed-form launch, at least (SAU_AMD_DYN_GROUPS) */
+	/* ... and steps x row groups per task, at least (SAU_AMD_DYN_FLOOR), and the tasks per wave from which the queues deal them out
+	 * (fewer: a fixed share per wave; SAU_AMD_DYN_MIN_TASKS). Round 6: 48 -> 24 and 4 -> 2, which takes BASELINE config 2 (256 voices of
+	 * one step: 20 tasks a voice were 1.25 a wave, so every wave got a sixteenth of a voice, fixed) to the queues: its launch 0.192 ->
+	 * 0.163-0.166 ms, the step 0.287 -> 0.259 (floors 4-12 the same, 16: 0.272; profiles/r06_ab.txt [17]) */
+	uint32_t dyn_floor = 24;
+	uint32_t dyn_min_tasks = 2;
+	bool xcd_queues = true;      /* a closed-form launch's tasks come from one queue per XCD, chunk-major (SAU_AMD_NO_XCD_QUEUES: the one counter, voice-major) */
+	bool inmix = true;           /* a many-voice stream's closed-form launch mixes its own rows (SAU_AMD_NO_INMIX: the mixer alone) */
+	uint32_t inmix_min_voices = 64; /* ... from that many voices on (SAU_AMD_INMIX_MIN_VOICES) */
+	uint32_t inmix_min_steps = 2;/* ... of two steps or more (SAU_AMD_INMIX_MIN_STEPS): behind one-step voices (config 2) the launch's mixing
+	                              * costs it more than the mixer saves -- step 0.269-0.272 ms with it, 0.258-0.261 without */
+	bool inmix_taper = false;    /* SAU_AMD_INMIX_TAPER: the queues' last eight chunks are short ones, so that less is left to mix_kernel. Measured
+	                              * slower on config 3 (2.04 -> 2.08 ms per step, the launch 1.91 -> 1.94: profiles/r06_ab.txt): off */
+	uint32_t inmix_at = 13;      /* which of a chunk's tasks mix the chunk before: from this many sixteenths into it (SAU_AMD_INMIX_AT) */
+	bool inmix_dry = false;      /* SAU_AMD_INMIX_DRY: timing aid (FastParams.inmix_flags bit 4) */
+	bool inner = true;           /* the 12-row wide closed-form build as two launches, edges and inner groups (SAU_AMD_NO_INNER: one) */
+	bool lanemajor = true;       /* ... its groups between in the lane-major form (SAU_AMD_NO_LANEMAJOR: row-major) */
+	bool duo = true;             /* closed-form and look-back voices of a segment in one launch where there are plenty of both (SAU_AMD_NO_DUO: two launches) */
+	uint32_t duo_lw = 0, duo_prio = 0; /* SAU_AMD_DUO_LW (4 bits), SAU_AMD_DUO_PRIO (1: none, 2: 1, 3: 2 (default), 4: 3): FastParams.look_wpv_flags */
+	bool tailmix = false;        /* SAU_AMD_TAILMIX: the look-back launch mixes few-voice streams itself. Exact (357 GPU tests with it on), and
+	                              * measured slower: BASELINE config 4 4.19 -> 4.26 ms per step -- the launch is issue-bound and pays 0.32 ms for
+	                              * the six flops, the clamp and the conversion per frame (and 42 spilled registers), the mixer gives back 0.25
+	                              * (profiles/r06_ab.txt). Off; kept for the record */
+	/* mixers */
+	bool mix_few = true;         /* SAU_AMD_NO_MIX_FEW */
+	bool early_mix = true;       /* SAU_AMD_NO_EARLY_MIX: segments with chains in chunks: the mixer follows the final passes chunk by chunk */
+	bool mix64 = true;           /* behind a launch that has mixed most tiles itself: the mixer in blocks of 64 frames (SAU_AMD_NO_MIX64: 256) */
+	bool poison = false;         /* SAU_AMD_POISON: voice and pan rows filled with 0x3ea5a5a5 ahead of every segment (tests) */
+};
+
+/* The switches as the environment has them, with their clamps. `env`: sauengine::tune_env (a name -> its value or NULL). */
+inline Tuning tuning_from_env(const char *(*env)(const char *)) {
+	Tuning t;
+	auto off = [&](const char *name) { return env(name) == nullptr; }; /* a SAU_AMD_NO_* switch: true while it is not set */
+	auto num = [&](const char *name, uint32_t &v) { if (const char *s = env(name)) v = (uint32_t)atoi(s); };
+	auto at_least_1 = [&](const char *name, uint32_t &v) { if (const char *s = env(name)) { const int n = atoi(s); v = n >= 1 ? (uint32_t)n : 1u; } };
+	const char *wt = env("SAU_AMD_GEOMETRY");
+	t.geo = (wt && !strcmp(wt, "8x2")) ? 0 : 1;
+	if (const char *mm = env("SAU_AMD_MULTI_MIN")) t.multi_min = (uint32_t)atol(mm);
+	if (const char *mt = env("SAU_AMD_MULTI_TEAMS")) t.multi_teams = atoi(mt) == 8 ? 8u : 16u;
+	if (const char *fg = env("SAU_AMD_FK_GRID")) { const int n = atoi(fg); if (n >= 1 && n <= (int)FK_GRID) t.fk_grid = (uint32_t)n; }
+	if (const char *ll = env("SAU_AMD_LDS_LIMIT")) { t.lds_limit_set = true; t.lds_limit = (size_t)atol(ll); }
+	t.fast = off("SAU_AMD_NO_FAST");
+	t.seq = off("SAU_AMD_NO_SEQ");
+	t.two_pass = off("SAU_AMD_NO_TWO_PASS");
+	t.lookback = off("SAU_AMD_NO_LOOKBACK");
+	t.inc_rows = off("SAU_AMD_NO_INC_ROWS");
+	if (const char *fr = env("SAU_AMD_FAST_ROWS")) {
+		const int r = atoi(fr);
+		t.fast_rows = r >= 8 ? 8 : r >= 6 ? 6 : r >= 5 ? 5 : r >= 4 ? 4 : 2;
+	}
+	num("SAU_AMD_LOOK_ROWS", t.look_rows);
+	num("SAU_AMD_LOOK_MIN_VOICES", t.look_min_voices);
+	t.look_no_lds = !off("SAU_AMD_LOOK_NO_LDS");
+	t.look_withhold = !off("SAU_AMD_LOOK_WITHHOLD");
+	t.look_spread = !off("SAU_AMD_LOOK_SPREAD");
+	t.wide_tabs = off("SAU_AMD_NO_WIDE_TABS");
+	t.wide_look = off("SAU_AMD_NO_WIDE_LOOK");
+	num("SAU_AMD_MORE_ROWS", t.more_rows);
+	t.repair = off("SAU_AMD_NO_REPAIR");
+	t.analyze_lds = off("SAU_AMD_ANALYZE_NO_LDS");
+	t.chain = off("SAU_AMD_NO_CHAIN");
+	t.chain_inline = off("SAU_AMD_NO_CHAIN_INLINE");
+	t.chain_early = off("SAU_AMD_NO_EARLY_CHAINS");
+	if (const char *cc = env("SAU_AMD_CHAIN_CHUNKS")) { /* pipeline depth of a segment with chains (1: off; default: by frames) */
+		const int n = atoi(cc);
+		t.chain_chunks = n >= 32 ? 32 : n >= 1 ? (uint32_t)n : 1;
+	}
+	if (const char *cf = env("SAU_AMD_CHAIN_CHUNK_FRAMES")) { const int n = atoi(cf); if (n >= 4096) t.chain_chunk_frames = (uint32_t)n; }
+	t.short_last_chunk = off("SAU_AMD_NO_SHORT_LAST_CHUNK");
+	if (const char *ca = env("SAU_AMD_CHAIN_ALONE")) t.chain_alone = atoi(ca) != 0;
+	t.lean = off("SAU_AMD_NO_LEAN");
+	num("SAU_AMD_LEAN_ROWS", t.lean_rows);
+	t.dyn = off("SAU_AMD_NO_DYN");
+	at_least_1("SAU_AMD_DYN_GROUPS", t.dyn_groups);
+	at_least_1("SAU_AMD_DYN_FLOOR", t.dyn_floor);
+	at_least_1("SAU_AMD_DYN_MIN_TASKS", t.dyn_min_tasks);
+	t.xcd_queues = off("SAU_AMD_NO_XCD_QUEUES");
+	t.inmix = off("SAU_AMD_NO_INMIX");
+	num("SAU_AMD_INMIX_MIN_VOICES", t.inmix_min_voices);
+	num("SAU_AMD_INMIX_MIN_STEPS", t.inmix_min_steps);
+	t.inmix_taper = !off("SAU_AMD_INMIX_TAPER");
+	if (const char *ia = env("SAU_AMD_INMIX_AT")) t.inmix_at = (uint32_t)atoi(ia) & 15u;
+	t.inmix_dry = !off("SAU_AMD_INMIX_DRY");
+	t.inner = off("SAU_AMD_NO_INNER");
+	t.lanemajor = off("SAU_AMD_NO_LANEMAJOR");
+	t.duo = off("SAU_AMD_NO_DUO");
+	if (const char *lw = env("SAU_AMD_DUO_LW")) t.duo_lw = (uint32_t)atoi(lw) & 15u;
+	if (const char *pr = env("SAU_AMD_DUO_PRIO")) t.duo_prio = (uint32_t)atoi(pr) & 7u;
+	t.tailmix = !off("SAU_AMD_TAILMIX");
+	t.mix_few = off("SAU_AMD_NO_MIX_FEW");
+	t.early_mix = off("SAU_AMD_NO_EARLY_MIX");
+	t.mix64 = off("SAU_AMD_NO_MIX64");
+	t.poison = !off("SAU_AMD_POISON");
+	return t;
+}
+
+/* ---- what the rules need to know of the device ---- */
+struct DeviceLimits {
+	size_t lds_limit = 160 * 1024; /* bytes of LDS a workgroup may ask for */
+	uint32_t fk_grid = FK_GRID;    /* workgroups of a time-parallel launch at most */
+	uint32_t cus = 256;
+	bool eight_xcds = true;        /* the device is a whole MI355X */
+};
+/* From a device's LDS per CU and its CU count. The time-parallel kernels' grids are one 1024-thread workgroup per CU at most:
+ * waves that wait for other workgroups' sums (spread look-back launches) need the whole grid resident, so the grid follows the
+ * CUs this device really has (a partitioned or CU-masked device has fewer than 256). The per-XCD task queues and the launch's
+ * own mixing take chunk k mod 8 for XCD k mod 8 and hand rows from wave to wave through ONE XCD's L2 (k_fast_types.h): only on
+ * a device that is the whole MI355X -- 256 CUs = 8 XCDs x 32. A partition (CPX: 32 CUs, one XCD) or a masked device keeps the
+ * single counter and mix_kernel */
+inline DeviceLimits device_limits(size_t lds_per_cu, uint32_t cus, const Tuning &t) {
+	DeviceLimits d;
+	d.cus = cus;
+	d.eight_xcds = cus == 256;
+	d.fk_grid = t.fk_grid ? t.fk_grid : cus < FK_GRID ? cus : FK_GRID;
+	d.lds_limit = t.lds_limit_set ? t.lds_limit : lds_per_cu > 160 * 1024 ? (size_t)160 * 1024 : lds_per_cu;
+	return d;
+}
+
+/* what else of the backend the rules read */
+struct PlanInputs {
+	uint32_t row_stride = 0;   /* floats per voice row */
+	size_t pcm_row = 0;        /* samples per stream's PCM row */
+	size_t chain_budget = 0;   /* Backend::chain_rows_budget() */
+	bool f32 = false;          /* a float32 run */
+	uint32_t max_write = 0;    /* the longest write_len of the segment's streams */
+	uint32_t max_rows = 0;     /* the most voices any of them has */
+};
+
+/* ---- helpers ---- */
+/* which wave tables a launch stages in LDS: the first `max_tabs` of those the segment uses */
+struct TableMap {
+	uint32_t n = 0;
+	int8_t tab_of_wave[12];  /* LDS table index per wave id, or -1 */
+	uint8_t wave_of_tab[12];
+};
+inline TableMap map_tables(uint64_t wave_mask, size_t max_tabs) {
+	TableMap m;
+	memset(m.wave_of_tab, 0, sizeof m.wave_of_tab);
+	for (int wv = 0; wv < 12; ++wv) {
+		m.tab_of_wave[wv] = -1;
+		if (((wave_mask >> wv) & 1) && m.n < max_tabs) {
+			m.tab_of_wave[wv] = (int8_t)m.n;
+			m.wave_of_tab[m.n] = (uint8_t)wv;
+			++m.n;
+		}
+	}
+	return m;
+}
+inline size_t tabs_that_fit(size_t limit, size_t fixed, size_t tab_bytes) { return fixed > limit ? 0 : (limit - fixed) / tab_bytes; }
+inline uint32_t n_waves_used(uint64_t wave_mask) { return (uint32_t)__builtin_popcountll(wave_mask & 0xffffffffull); }
+
+/* a wave's block buffers in a time-parallel launch: `n_bufs` rows-of-64 x `rows` floats, and a word per step */
+inline size_t buf_area(uint32_t n_bufs, uint32_t rows, uint32_t fmax_steps) {
+	return (size_t)n_bufs * 64 * rows * sizeof(float) + (size_t)fmax_steps * sizeof(unsigned long long);
+}
+/* THE fit test of a time-parallel launch: its tables, sixteen waves' buffers, what else the build keeps in LDS (the look-back
+ * rings), and 1 KiB for the rest */
+inline bool fits_lds(const DeviceLimits &d, size_t n_tabs, size_t tab_bytes, size_t area, size_t extra = 0) {
+	return n_tabs * tab_bytes + 16 * area + extra + 1024 <= d.lds_limit;
+}
+inline uint32_t row_groups(uint32_t len, uint32_t rows) { return (len + (60 * rows) - 1) / (60 * rows); }
+/* THE grid of a time-parallel launch: sixteen waves per workgroup, `max_grid` workgroups at most, one at least */
+inline uint32_t wave_grid(unsigned long long waves, uint32_t max_grid) {
+	const unsigned long long g = (waves + 15) / 16;
+	return g > max_grid ? max_grid : g < 1 ? 1u : (uint32_t)g;
+}
+/* ... with as many waves per voice as it has row groups (up to 64) when voices are few */
+inline uint32_t group_grid(uint32_t n_voices, uint32_t groups, uint32_t max_grid) {
+	return wave_grid((unsigned long long)n_voices * (groups < 64 ? groups : 64), max_grid);
+}
+/* 8, 6, 5, 4 or 2 rows per pass */
+inline uint32_t fewer_rows(uint32_t t) { return t > 6 ? 6u : t > 5 ? 5u : t > 4 ? 4u : 2u; }
+inline uint32_t rows_at_most(uint32_t r) { return r >= 8 ? 8u : r >= 6 ? 6u : r >= 5 ? 5u : r >= 4 ? 4u : 2u; }
+
+/* ---- the block loop ---- */
+struct BlockLoopPlan {
+	bool ok = true;          /* false: the voice does not fit a workgroup's LDS */
+	uint32_t W = 4, T = 4, V = 1;
+	bool HB = false;         /* block buffers in HBM (render_kernel<1, 1, 1, true>) */
+	size_t team_bytes = 0, lds = 0;
+	TableMap tabs;
+	/* persistent over the device-built work list. When the host knows of nothing that needs it (no sweeps, FM, feedback or
+	 * expiring operators), a token grid still serves the rare dphase == 0 bail-out. */
+	uint32_t grid(const SegmentDesc &seg, bool use_fast) const {
+		const bool all = seg.maybe_block || !use_fast;
+		if (V > 1) {
+			const uint32_t full = (seg.n_voices + V - 1) / V;
+			return all ? (full < 512 ? full : 512) : 2;
+		}
+		return all ? (seg.n_voices < 1024 ? seg.n_voices : 1024) : 16;
+	}
+};
+/* Block-loop geometry. Few voices: W waves share one voice (4x4 or 8x2 frames per lane). Many voices: sixteen single-wave
+ * teams per workgroup, each with its own voice, so that every CU has 16 voices in flight. */
+inline BlockLoopPlan plan_block_loop(const SegmentDesc &seg, const Tuning &tun, const DeviceLimits &dev) {
+	BlockLoopPlan p;
+	p.W = tun.geo ? 4 : 8; p.T = tun.geo ? 4 : 2;
+	auto team_size = [&](uint32_t w, uint32_t t) {
+		size_t b = p.HB ? MISC_BYTES + 64 /* (buffers, operator records and steps in HBM) */
+			: (size_t)w * 64 * t * sizeof(float) * seg.n_slots + (size_t)seg.max_ops * sizeof(DevOp) +
+			MISC_BYTES + (size_t)seg.max_steps * sizeof(Step) + 64;
+		return (b + 15) & ~(size_t)15;
+	};
+	if (tun.multi_min && seg.n_voices >= tun.multi_min && (seg.serial || tun.multi_min == 1)) {
+		const size_t need_tab = seg.wave_mask ? BLOCK_TAB_BYTES : 0;
+		/* longer blocks amortise the per-step bookkeeping: 255 samples per block measured
+		 * 14 % faster than 127 on BASELINE config 5 */
+		const uint32_t mt = tun.multi_teams; /* single-wave teams per workgroup: 8 (512 threads: 256 VGPRs each, no scratch) or 16 */
+		for (uint32_t t : {4u, 3u, 2u, 1u})
+			if (mt * team_size(1, t) + need_tab <= dev.lds_limit) { p.W = 1; p.T = t; p.V = mt; break; }
+	}
+	/* a voice with very many block buffers: one wave, one frame per lane (256 B per buffer) */
+	if (p.V == 1 && team_size(p.W, p.T) > dev.lds_limit) { p.W = 1; p.T = 1; }
+	/* more of them than LDS holds (wide plans: graphs nested hundreds of levels deep): the buffers go to HBM */
+	if (p.V == 1 && p.W == 1 && team_size(1, 1) > dev.lds_limit) p.HB = true;
+	/* LDS budget: slots + operator cache + misc per team, rest for tables */
+	p.team_bytes = team_size(p.W, p.T);
+	const size_t fixed = p.team_bytes * p.V;
+	if (fixed > dev.lds_limit) { p.ok = false; return p; }
+	/* keep two workgroups per CU when possible: cap at half the LDS */
+	size_t budget = dev.lds_limit / 2 > fixed ? dev.lds_limit / 2 - fixed : 0;
+	if (p.V > 1) budget = dev.lds_limit - fixed;
+	if (budget < BLOCK_TAB_BYTES && dev.lds_limit - fixed >= BLOCK_TAB_BYTES) budget = BLOCK_TAB_BYTES;
+	p.tabs = map_tables(seg.wave_mask, budget / BLOCK_TAB_BYTES);
+	p.lds = p.tabs.n * BLOCK_TAB_BYTES + fixed;
+	return p;
+}
+
+/* ---- feedback chains in chunks ---- */
+/* Chunks of about chain_chunk_frames frames (what the first chunk's inputs and the last chunk's final pass take is not
+ * overlapped with the chains), 32 at most. Boundaries: multiples of the chain kernel's batch. What follows the last chunk's
+ * chains is not overlapped with anything -- its final pass, finalize_kernel, its share of the mixer (which follows the other
+ * chunks since round 5) -- so the last chunk is a short one (4096 frames: 0.4 ms of chains, 0.15 ms of final pass behind them
+ * instead of 0.5-0.7) */
+struct ChainChunks {
+	uint32_t n = 1;        /* chunks (more than one: the chains run on a stream of their own) */
+	uint32_t cb[34];       /* chunk c is frames [cb[c], cb[c + 1]) */
+	bool short_last = false;
+};
+inline ChainChunks chain_chunk_bounds(uint32_t len, const Tuning &tun) {
+	ChainChunks k;
+	uint32_t n = tun.chain_chunks ? tun.chain_chunks : (len + tun.chain_chunk_frames - 1) / tun.chain_chunk_frames;
+	if (n > 32) n = 32;
+	while (n > 1 && len / n < 4096) --n;
+	if (n < 1) n = 1;
+	k.short_last = !tun.chain_chunks && tun.short_last_chunk && n >= 4 && n < 32 && len > 8 * 4096u;
+	const uint32_t tail = k.short_last ? 4096u : 0u;
+	const uint32_t body = tail ? (len - tail) & ~255u : len;
+	const uint32_t clen0 = ((body + n - 1) / n + 255) & ~255u;
+	for (uint32_t c = 0; c <= n; ++c) k.cb[c] = (unsigned long long)c * clen0 < body ? c * clen0 : body;
+	if (tail) { ++n; k.cb[n] = len; }
+	/* (with the rounded-up chunk length the last body chunks can come out empty -- len 81930 in 20
+	 * chunks: cb[19] == cb[20] -- and each would still cost a chain launch, two pass launches and two events) */
+	uint32_t m = 0;
+	for (uint32_t c = 0; c < n; ++c)
+		if (k.cb[c + 1] > k.cb[c]) { k.cb[m] = k.cb[c]; ++m; k.cb[m] = k.cb[c + 1]; }
+	if (m) n = m;
+	k.n = n;
+	return k;
+}
+
+/* ---- closed-form tasks ---- */
+struct Tasks { uint32_t dyn_chunks = 0, dyn_static = 0, dyn_small = 0; };
+/* row groups per task: dyn_groups, or what makes steps x groups reach dyn_floor */
+inline uint32_t task_groups(const SegmentDesc &seg, const Tuning &tun) {
+	const uint32_t S = seg.max_steps ? seg.max_steps : 1;
+	uint32_t G = tun.dyn_groups;
+	if (G * S < tun.dyn_floor) G = (tun.dyn_floor + S - 1) / S;
+	return G;
+}
+/* Tasks of a closed-form launch: G row groups each. The counter takes about one add per 12 ns chip-wide (r03: config 3 with
+ * tasks of 3 or 4 groups x 4 steps, one add per 8 ns, ran 1.3-1.6x slower), and a task of G groups x S steps keeps a wave for
+ * about G x S x 2.2 us, so G x S >= 48 leaves a factor of two; and dealing tasks out only pays when there are several per
+ * wave -- a short segment's few tasks go out in fixed strides, one contiguous run of groups per wave (1024 one-operator
+ * voices x 44100 frames: 0.15 ms in strides, 0.31 ms through the counter). */
+inline Tasks plan_tasks(const SegmentDesc &seg, const Tuning &tun, uint32_t n_groups, uint32_t grid) {
+	Tasks q;
+	const uint32_t waves = grid * 16;
+	const uint32_t G = task_groups(seg, tun);
+	const uint32_t k_dyn = (n_groups + G - 1) / G;
+	if (tun.dyn && (unsigned long long)seg.n_voices * k_dyn >= (unsigned long long)tun.dyn_min_tasks * waves) {
+		q.dyn_chunks = k_dyn ? k_dyn : 1;
+		q.dyn_static = 0;
+	} else {
+		uint32_t k = waves / seg.n_voices;
+		if (k > n_groups) k = n_groups;
+		q.dyn_chunks = k ? k : 1;
+		q.dyn_static = 1;
+	}
+	return q;
+}
+/* fixed strides: what `grid` workgroups' waves make per voice, one task per row group at most */
+inline Tasks static_tasks(const SegmentDesc &seg, uint32_t n_groups, uint32_t grid) {
+	Tasks q;
+	uint32_t k = grid * 16 / seg.n_voices;
+	if (k > n_groups) k = n_groups;
+	q.dyn_chunks = k ? k : 1; q.dyn_static = 1;
+	return q;
+}
+/* d as a divisor for the kernels' udiv_magic (k_fast_voice.h): s = ceil(log2 d), m = floor(2^(32 + s) / d) + 1 - 2^32 */
+struct MagicDiv { uint32_t m = 0, s = 0; };
+inline MagicDiv magic_div(uint32_t d) {
+	MagicDiv q;
+	while ((1ull << q.s) < d) ++q.s;
+	q.m = (uint32_t)(((1ull << (32 + q.s)) / d) + 1ull - (1ull << 32));
+	return q;
+}
+/* (the host's copy of udiv_magic: tests) */
+inline uint32_t magic_quotient(uint32_t q, MagicDiv d) {
+	if (d.s == 0) return q;
+	const uint32_t t = (uint32_t)(((unsigned long long)q * d.m) >> 32);
+	return (t + ((q - t) >> 1)) >> (d.s - 1);
+}
+
+/* ---- the time-parallel path ---- */
+enum Inner : uint32_t { INNER_NONE = 0, INNER_ROW_MAJOR = 1, INNER_LANE_MAJOR = 2 };
+enum Mixer : uint32_t { MIX_NONE = 0, MIX_FEW_F32, MIX_F32, MIX_FEW, MIX_64, MIX_256 };
+
+struct FastPlan {
+	/* rows per pass and what sits in LDS */
+	bool use_fast = false;
+	bool seq_ok = false;       /* block buffers with frequency blocks: some voice may need the sequential scan */
+	bool look_split = false;   /* the single-pass (look-back) build takes the running-sum voices it serves */
+	/* build 0: closed-form phases only; 1: every kind of running-sum voice; 2: single-pass voices and closed-form ones */
+	int main_build = 0;
+	uint32_t fmax_steps = 0, n_fast = 0, n_fast_cf = 0;
+	uint32_t rows = 2;         /* rows per pass of the main build */
+	uint32_t rows_multi = 2;   /* ... of the full build */
+	uint32_t rows_cf = 2;      /* ... of a split segment's closed-form launch */
+	uint32_t rows_lean = 4;    /* ... of the build for voices with chains and nothing to scan */
+	bool lean_on = false;
+	TableMap tabs;
+	uint32_t n_want = 0;       /* tables the segment uses */
+	bool wide_cf = false;      /* the closed-form launch (and repair_kernel) take wide table blocks */
+	bool wide_look = false;    /* ... and so does the look-back launch */
+	bool cub_ok = false;
+	uint32_t sum_levels = 2;
+	/* running sums */
+	uint32_t scan_groups = 0;
+	bool scan = false;         /* the several-pass form's sums are wanted */
+	bool look = false;         /* the look-back launch runs */
+	size_t look_words = 0;
+	bool look_words_real = false; /* this segment's look-back words in HBM are usable (not the token block) */
+	uint32_t look_wpv = 1;     /* the single-pass launch: waves per voice, and whether every voice sits */
+	bool look_inside = true;   /* inside one workgroup (LDS rings, no waits across workgroups) */
+	uint32_t look_wpv_flags = 0;
+	bool inc_rows = false;     /* saved phase increments between the sum pass and the final pass */
+	uint32_t inc_stride = 0;
+	/* feedback chains */
+	bool chains = false;
+	uint32_t chain_stride = 0, chain_grid = 0;
+	TableMap ctabs;
+	ChainChunks chunks;
+	uint32_t pass_grid = 0;    /* the time-parallel passes leave the chains' CUs alone while both run */
+	bool early_mix = false;
+	/* launches */
+	bool split_cf = false, duo = false, tailmix = false;
+	bool queues = false;       /* the closed-form launch's tasks come from the XCDs' queues */
+	bool inmix = false;        /* ... and it mixes its own rows */
+	uint32_t inmix_flags = 0;
+	MagicDiv div;
+	Inner inner = INNER_NONE;
+	Tasks tasks, tasks_cf, tasks_cub;
+	uint32_t groups = 0, groups_cf = 0;
+	uint32_t grid = 1, grid_cf = 1, grid_look = 1, grid_edge = 1, grid_cub = 1, grid_repair = 1;
+	uint32_t rows_repair = 2;
+
+	/* If allocating the chain rows fails, the segment's feedback voices take the block loop, and the lean build goes with them. */
+	void drop_chains() { chains = false; lean_on = false; }
+	/* LDS bytes of a launch of `build` at `rows` rows per pass (cf: over the closed-form voices' buffers only) */
+	size_t launch_lds(int build, uint32_t r, bool wide, bool cf = false) const {
+		return tabs.n * (size_t)(wide ? FAST_TAB_BYTES_WIDE : FAST_TAB_BYTES) + 16 * buf_area(cf ? n_fast_cf : n_fast, r, fmax_steps) +
+			(build == 2 ? LOOK_LDS_BYTES : 0);
+	}
+};
+
+/* Rows per wave and pass: as many as LDS holds beside one wave table (more rows amortise the per-step work: 8 rows measured
+ * 8 % faster than 4, 4 rows 28 % faster than 2) -- and which tables. */
+inline void plan_rows(FastPlan &p, const SegmentDesc &seg, const Tuning &tun, const DeviceLimits &dev) {
+	p.fmax_steps = seg.max_steps < 64 ? seg.max_steps : 64;
+	uint32_t FT = tun.fast_rows;
+	/* The build with all the running-sum code needs more registers: 8 rows per pass would spill. Where the
+	 * single-pass (look-back) build serves, it takes those voices and the closed-form ones at the full rows
+	 * per pass, and the full build's launches only see what is left (voices with feedback chains, voices
+	 * one wave walks in order). */
+	p.look_split = tun.seq && seg.may_scan && tun.two_pass && tun.lookback && tun.look_rows != 0 && seg.n_voices >= tun.look_min_voices;
+	if (tun.seq && seg.may_scan && FT > 4 && !p.look_split) FT = 4;
+	if (p.look_split && FT > tun.look_rows) FT = rows_at_most(tun.look_rows);
+	/* block buffers: without frequency blocks, or with them when some voice may need
+	 * the sequential scan (ramped or modulated frequencies) */
+	p.seq_ok = tun.seq && seg.may_scan;
+	p.n_fast = p.seq_ok && seg.n_fast_full > seg.n_fast ? seg.n_fast_full : seg.n_fast;
+	p.n_fast_cf = seg.n_fast;
+	p.n_want = n_waves_used(seg.wave_mask);
+	auto area_of = [&](uint32_t t) { return buf_area(p.n_fast, t, p.fmax_steps); };
+	const size_t look_lds = p.look_split ? LOOK_LDS_BYTES : 0;
+	while (FT > 2 && !fits_lds(dev, seg.wave_mask ? 1 : 0, FAST_TAB_BYTES, area_of(FT), look_lds)) FT = fewer_rows(FT);
+	{ /* every wave table the segment uses in LDS is worth more than rows per pass (an oscillator whose table
+	   * is left out reads it from L2 per sample): fewer rows where that makes them all fit */
+		uint32_t t = FT;
+		while (t > 4 && !fits_lds(dev, p.n_want, FAST_TAB_BYTES, area_of(t), look_lds)) t = fewer_rows(t); /* (but not below 4 rows: that costs more) */
+		if (fits_lds(dev, p.n_want, FAST_TAB_BYTES, area_of(t), look_lds)) FT = t;
+	}
+	p.use_fast = tun.fast && fits_lds(dev, 0, 0, area_of(FT), look_lds);
+	p.rows = FT;
+	p.rows_multi = FT > 4 && p.seq_ok ? 4 : FT; /* rows per pass of the full build */
+	p.tabs = map_tables(seg.wave_mask, p.use_fast ? tabs_that_fit(dev.lds_limit, 16 * area_of(FT) + look_lds + 1024, FAST_TAB_BYTES) : 0);
+	const uint32_t ft = p.tabs.n;
+	const bool all_wide_ok = tun.wide_tabs && tun.more_rows && ft > 0 && ft == p.n_want && seg.max_steps >= 2;
+	/* Closed-form segments whose tables all sit in LDS in the wide form: more rows per pass where LDS holds them (round 4:
+	 * a group's rows are contiguous in time since then, which took the 8-row build from 128 to 114 VGPRs) */
+	if (p.use_fast && !p.seq_ok && all_wide_ok && FT == 8)
+		for (uint32_t t : {12u, 10u}) /* (14 and 16 rows: hipcc's "requires even aligned vector registers" error on their spills) */
+			if (t <= tun.more_rows && fits_lds(dev, ft, FAST_TAB_BYTES_WIDE, area_of(t))) { p.rows = p.rows_multi = t; break; }
+	/* the closed-form voices of a segment that may also have look-back voices: a launch of their own (FastParams.vlists) */
+	p.split_cf = p.use_fast && p.seq_ok && p.look_split;
+	auto area_cf = [&](uint32_t t) { return buf_area(p.n_fast_cf, t, p.fmax_steps); };
+	p.rows_cf = 2;
+	if (p.split_cf) {
+		for (uint32_t t : {8u, 6u, 5u, 4u})
+			if (t <= tun.fast_rows && fits_lds(dev, ft, FAST_TAB_BYTES, area_cf(t))) { p.rows_cf = t; break; }
+		/* (10 or 12 rows exist in the wide-table form only: where that fits -- the same test as wide_fits below) */
+		if (p.rows_cf == 8 && all_wide_ok)
+			for (uint32_t t : {12u, 10u})
+				if (t <= tun.more_rows && fits_lds(dev, ft, FAST_TAB_BYTES_WIDE, area_cf(t))) { p.rows_cf = t; break; }
+	}
+	p.cub_ok = p.use_fast && seg.maybe_cub && fits_lds(dev, ft, FAST_TAB_BYTES, area_cf(FAST_CUB_ROWS)) &&
+		(!p.look_split || fits_lds(dev, ft, FAST_TAB_BYTES, area_of(FAST_CUB_ROWS), LOOK_LDS_BYTES));
+	/* the build for voices with chains and nothing to scan: as many rows per pass as fit beside the tables */
+	p.rows_lean = 4;
+	for (uint32_t t : {6u, 5u}) /* (decode_kernel lays the slots out for exactly the rows the build has: 4, 5 or 6) */
+		if (t <= tun.fast_rows && t <= tun.lean_rows && fits_lds(dev, ft, FAST_TAB_BYTES, area_of(t))) { p.rows_lean = t; break; }
+	p.main_build = !p.seq_ok ? 0 : p.look_split ? 2 : 1;
+	/* the closed-form build with wide table blocks in LDS (k_fast_types.h: FkTab), at 6, 8, 10 and 12 rows per pass: taken when
+	 * every table the segment wants is in LDS and still fits in that form at the launch's rows */
+	auto wide_fits = [&](uint32_t rows, size_t area) {
+		/* (voices of one step -- flat banks, BASELINE config 2 -- have no modulation to evaluate: fewer VALU
+		 * instructions per sample to begin with, and the wider gather costs them 3-4 %) */
+		return tun.wide_tabs && (rows == 8 || rows == 6 || rows == 10 || rows == 12) && ft > 0 && ft == p.n_want && seg.max_steps >= 2 &&
+			fits_lds(dev, ft, FAST_TAB_BYTES_WIDE, area);
+	};
+	/* (which form the closed-form launch of this segment takes -- repair_kernel runs in the same layout) */
+	p.wide_cf = p.main_build == 2 ? wide_fits(p.rows_cf, area_cf(p.rows_cf)) : p.main_build == 0 && wide_fits(p.rows, area_of(p.rows));
+	/* (wide table blocks for the look-back voices too, where they fit beside the buffers at 8 rows: the carrier-FM bank) */
+	p.wide_look = tun.wide_tabs && tun.wide_look && p.rows == 8 && ft > 0 && ft == p.n_want &&
+		fits_lds(dev, ft, FAST_TAB_BYTES_WIDE, area_of(p.rows), LOOK_LDS_BYTES);
+	p.sum_levels = seg.sum_levels >= FAST_MAX_LEVELS ? FAST_MAX_LEVELS : 2u;
+}
+
+/* The running sums: the several-pass form's scan words, the single-pass build's look-back words and waves per voice, the saved
+ * phase increments. */
+inline void plan_sums(FastPlan &p, const SegmentDesc &seg, const Tuning &tun, const DeviceLimits &dev) {
+	if (p.seq_ok && tun.two_pass) {
+		/* row groups per voice at most: rows hold at least 32 new frames (H <= 32) */
+		p.scan_groups = seg.len / (32 * p.rows_multi) + 2;
+		/* (the several-pass form's sums: with look-back only voices that have, or may get, feedback chains take it) */
+		p.scan = !p.look_split || seg.n_chain_rows;
+		p.look = p.look_split && seg.n_look_rows;
+	}
+	if (p.look) {
+		/* Waves per voice of the single-pass build's launch (as many as the voice has row groups, up to 64,
+		 * when voices are few). Voices whose waves sit in one workgroup (1, 2, 4, 8 or 16 of them) look back
+		 * through rings in LDS and need no words in HBM; only a launch that spreads voices over
+		 * neighbouring workgroups does. Those words (8 B x 2 x row groups per running-sum oscillator) are
+		 * capped at 1 GiB: beyond that the launch keeps every voice inside a workgroup instead. */
+		const uint32_t groups = row_groups(seg.len, p.rows);
+		unsigned long long wpv = ((unsigned long long)dev.fk_grid * 16) / seg.n_voices;
+		if (wpv > 64) wpv = 64;
+		if (wpv > groups) wpv = groups;
+		if (wpv < 1) wpv = 1;
+		auto is_inside = [&](unsigned long long w) { return w <= 16 && (16 % w) == 0 && !tun.look_no_lds; };
+		p.look_words = (size_t)seg.n_look_rows * 2 * p.scan_groups;
+		/* the words exist whenever they fit 1 GiB: the kernel then picks the waves per voice from the number of
+		 * look-back voices analyze_kernel finds (the host only knows how many there may be) */
+		p.look_words_real = p.look_words * sizeof(unsigned long long) <= ((size_t)1 << 30);
+		if (!p.look_words_real && !is_inside(wpv) && !tun.look_no_lds)
+			wpv = wpv > 16 ? 16 : wpv > 8 ? 8 : wpv > 4 ? 4 : 2;
+		p.look_wpv = (uint32_t)wpv;
+		p.look_inside = !p.look_words_real && is_inside(wpv);
+	}
+	/* saved phase increments of running-sum oscillators (sum pass -> final pass), one segment long */
+	/* (only voices that take several passes use them -- with look-back those with feedback chains -- and a
+	 * bank of thousands of those would ask for gigabytes: beyond 1 GiB the final pass recomputes instead) */
+	p.inc_stride = (seg.len + 63) & ~63u;
+	p.inc_rows = tun.inc_rows && p.use_fast && p.scan && seg.n_inc_rows && seg.len <= sauengine::CHAIN_SEG &&
+		(size_t)seg.n_inc_rows * 2 * p.inc_stride * sizeof(uint32_t) <= ((size_t)1 << 30);
+}
+
+/* Feedback chains: a pair of rows per chain in HBM, one segment long (the engine keeps segments with such voices within
+ * CHAIN_SEG frames); without them those voices take the block loop. `grid`: the main launches'. */
+inline void plan_chains(FastPlan &p, const SegmentDesc &seg, const Tuning &tun, const DeviceLimits &dev, const PlanInputs &in) {
+	p.chains = tun.chain && p.use_fast && p.scan && seg.serial && seg.n_chain_rows &&
+		seg.len <= sauengine::chain_seg_frames(seg.n_chain_rows, in.chain_budget);
+	p.chain_stride = (seg.len + 63) & ~63u;
+	p.ctabs = map_tables(seg.wave_mask, tabs_that_fit(dev.lds_limit, CHAIN_IO_BYTES + 1024, CHAIN_TAB_BYTES));
+	p.lean_on = p.chains && tun.lean &&
+		fits_lds(dev, p.tabs.n, FAST_TAB_BYTES, buf_area(p.n_fast, p.rows_lean, p.fmax_steps)); /* (a tight LDS budget: the full build's rows) */
+	p.chain_grid = (seg.n_chain_slots + 63) / 64;
+	if (p.chains) p.chunks = chain_chunk_bounds(seg.len, tun);
+	p.pass_grid = p.chunks.n > 1 && p.grid + p.chain_grid > dev.fk_grid ? (dev.fk_grid > p.chain_grid + 32 ? dev.fk_grid - p.chain_grid : 32) : p.grid;
+	/* the mixer follows the final passes chunk by chunk (k_finish.h: premix_kernel): after the pass over the
+	 * row groups that end in chunk c, every frame below the chunk's end less one group's span is written
+	 * (a group has at most 64 x 6 frames in the builds that run here) */
+	/* (not where a launch BEHIND the chunks still writes voice rows: the closed-form build with the loop tails of
+	 * `cub` R segments -- found by round 5's drop-in sweep, 2 programs of 3000; rows that repair_kernel
+	 * touches afterwards make the last launch mix everything again: fast_voice notes it in work_count[1]) */
+	p.early_mix = tun.early_mix && in.max_write && !p.cub_ok && !(tun.mix_few && in.max_rows <= 8 && seg.n_streams >= 8);
+}
+
+/* A split segment (main build 2): the closed-form launch and the look-back launch, or both in one (duo_kernel). */
+inline void plan_split(FastPlan &p, const SegmentDesc &seg, const Tuning &tun, const DeviceLimits &dev, const PlanInputs &in) {
+	const uint32_t ft = p.tabs.n;
+	/* many streams of a few voices (a batch of small scripts): where a stream's last row is a look-back voice's and the
+	 * others are closed-form voices', the look-back launch mixes the stream as it stores that row (k_fast_types.h:
+	 * FastParams.tail_ok) and mix_few_kernel has nothing left to do (SAU_AMD_TAILMIX; off by default: see Tuning.tailmix) */
+	p.tailmix = p.look && p.rows == 8 && tun.tailmix && !in.f32 && in.max_write && !p.cub_ok && seg.len < (1u << 30) &&
+		tun.mix_few && in.max_rows <= 8 && seg.n_streams >= 8 && (seg.pcm_offset & 3u) == 0 && (in.pcm_row & 3u) == 0;
+	p.groups_cf = row_groups(seg.len, p.rows_cf);
+	p.grid_cf = group_grid(seg.n_voices, p.groups_cf, dev.fk_grid);
+	/* Both kinds of voice in ONE launch (duo_kernel, k_fast_voice.h; round 6) where both launches would run 8 rows per pass
+	 * on narrow tables and the look-back voices' words in HBM exist (a voice then takes as many waves as there are). How
+	 * many voices are of which kind only analyze_kernel knows: the kernel splits its waves by the lists' lengths */
+	/* (wide_look: the look-back launch would take wide tables: better apart) */
+	p.duo = tun.duo && p.look && p.look_words_real && p.rows == 8 && p.rows_cf == 8 && !p.cub_ok && !p.tailmix &&
+		!p.wide_look && !p.wide_cf && fits_lds(dev, ft, FAST_TAB_BYTES, buf_area(p.n_fast, p.rows, p.fmax_steps), LOOK_LDS_BYTES);
+	p.tasks_cf = plan_tasks(seg, tun, p.groups_cf, p.duo ? (dev.fk_grid + 1) / 2 : p.grid_cf); /* (duo: half a workgroup's waves take closed-form tasks) */
+	p.look_wpv_flags = (tun.look_no_lds ? 1u : 0u) | (tun.look_withhold ? 2u : 0u) | (tun.look_spread ? 4u : 0u);
+	if (p.duo) p.look_wpv_flags |= (tun.duo_lw << 8) | (tun.duo_prio << 12);
+	p.grid_look = wave_grid((unsigned long long)seg.n_voices * (p.look_words_real ? (p.groups < 64 ? p.groups : 64) : p.look_wpv), dev.fk_grid);
+}
+
+/* A closed-form segment (nothing to scan): tasks of about eight row groups dealt out by a counter, the XCDs' queues, the
+ * launch's own mixing, the inner two-launch form. */
+inline void plan_closed_form(FastPlan &p, const SegmentDesc &seg, const Tuning &tun, const DeviceLimits &dev, const PlanInputs &in) {
+	if (p.main_build == 0) p.tasks = plan_tasks(seg, tun, p.groups, p.grid);
+	/* tasks dealt out by the counter: one queue per XCD, chunk-major (k_fast_types.h) -- 1.80 -> 1.76 ms per config-3
+	 * launch against the one counter in voice order */
+	p.queues = tun.xcd_queues && dev.eight_xcds && p.main_build == 0 && !p.tasks.dyn_static && p.tasks.dyn_chunks >= 16 && !p.cub_ok;
+	if (p.queues) {
+		p.inmix_flags = 64u; /* (analyze_kernel has cleared the queues) */
+		/* ... whose last eight chunks are short ones (k_fast_types.h: INMIX_NCH1): a quarter of a task's row groups, where the
+		 * segment has at least four regular chunks per XCD besides */
+		if (tun.inmix_taper) {
+			const uint32_t G = task_groups(seg, tun);
+			const uint32_t small = G / 4 ? G / 4 : 1;
+			if (p.groups >= 32 * G + INMIX_NSMALL * small) {
+				p.tasks.dyn_small = small;
+				p.tasks.dyn_chunks = (p.groups - INMIX_NSMALL * small + G - 1) / G + INMIX_NSMALL;
+			}
+		}
+		p.div = magic_div(seg.n_voices); /* the voice count as a divisor (k_fast_voice.h: udiv_magic) */
+		/* ... and a bank of voices mixed into one stream: the launch mixes its own rows, chunk by chunk behind the rendering;
+		 * premix_kernel has the last word. Config 3: 2.056 -> 1.995 ms per step (the launch 1.74 -> 1.87 ms, the mixer
+		 * 0.26 -> 0.07 ms) */
+		/* (not on a float run: the launch's tiles store int16 -- the 12-row build has no register to spare for another
+		 * store form -- so mix_kernel_f32 writes every frame, as under SAU_AMD_NO_INMIX) */
+		p.inmix = tun.inmix && !in.f32 && seg.n_streams == 1 && in.max_write && seg.n_voices >= tun.inmix_min_voices &&
+			seg.max_steps >= tun.inmix_min_steps && in.row_stride < (1u << 24);
+		if (p.inmix)
+			p.inmix_flags = 64u | 32u | (seg.stereo ? 1u : 0u) | (seg.swap_bytes ? 2u : 0u) | (tun.inmix_dry ? 4u : 0u) | ((tun.inmix_at & 15u) << 8);
+	}
+	/* BASELINE config 3's build in two launches (k_fast_voice.h: INNER): every voice's first and last row group by the plain
+	 * build, a wave per group; then the groups between by the build that holds only the form without in-segment masks */
+	/* (the groups in the lane-major form, k_fast_group_lm.h; SAU_AMD_NO_LANEMAJOR: the row-major one) */
+	if (tun.inner && p.main_build == 0 && p.wide_cf && p.rows == 12 && p.tasks.dyn_chunks >= 3)
+		p.inner = tun.lanemajor ? INNER_LANE_MAJOR : INNER_ROW_MAJOR;
+	p.grid_edge = wave_grid(2ull * seg.n_voices, dev.fk_grid); /* (two tasks a voice: its first group, its last) */
+}
+
+/* Everything the time-parallel path of a segment launches. */
+inline FastPlan plan_fast(const SegmentDesc &seg, const Tuning &tun, const DeviceLimits &dev, const PlanInputs &in) {
+	FastPlan p;
+	plan_rows(p, seg, tun, dev);
+	plan_sums(p, seg, tun, dev);
+	/* as many waves per voice as it has row groups (up to 64) when voices are few, one CU-filling grid at most */
+	p.groups = row_groups(seg.len, p.rows);
+	p.grid = group_grid(seg.n_voices, p.groups, dev.fk_grid);
+	plan_chains(p, seg, tun, dev, in);
+	if (p.use_fast && p.main_build == 2) plan_split(p, seg, tun, dev, in);
+	if (p.use_fast && !p.scan) plan_closed_form(p, seg, tun, dev, in);
+	/* closed-form voices with the loop tails of `cub` R segments (FastInfo.cub): FAST_CUB_ROWS rows per pass, fixed strides
+	 * over the same voices as the closed-form launch */
+	const uint32_t g4 = row_groups(seg.len, FAST_CUB_ROWS);
+	p.grid_cub = group_grid(seg.n_voices, g4, dev.fk_grid);
+	p.tasks_cub = static_tasks(seg, g4, p.grid_cub);
+	/* row groups noted for a second evaluation */
+	/* (only closed-form voices note any: with split launches they run at rows_cf rows per pass, in the closed-form launch's layout) */
+	p.rows_repair = p.main_build == 2 ? p.rows_cf : p.rows;
+	p.grid_repair = wave_grid(seg.n_voices, 64);
+	return p;
+}
+
+/* The mixer behind the segment's kernels. `early_blocks`: 256-frame blocks that launches between the chain chunks have mixed. */
+inline Mixer plan_mixer(const SegmentDesc &seg, const Tuning &tun, const PlanInputs &in, size_t pcm_pitch, bool inmix_live,
+		uint32_t early_blocks) {
+	if (!in.max_write) return MIX_NONE;
+	const bool few = tun.mix_few && in.max_rows <= 8 && seg.n_streams >= 8;
+	/* mix_few_kernel_f32's 16-byte stores, derived for 4-byte samples: a thread's four frames begin at byte
+	 * pcm_pitch * stream + (pcm_offset + i0) * 4 * channels of a 256-byte-aligned block, i0 a multiple of 4 -- aligned
+	 * when the pitch is a multiple of 16 bytes and pcm_offset a multiple of 4 (mono), of 2 (stereo: a frame is 8 bytes).
+	 * (Its 16-byte row loads are at i0 of the voice rows, whatever pcm_offset is.) */
+	const bool few_f32_aligned = (pcm_pitch & 15u) == 0 && (seg.pcm_offset & (seg.stereo ? 1u : 3u)) == 0;
+	if (in.f32) return few && few_f32_aligned ? MIX_FEW_F32 : MIX_F32; /* (no launch has mixed anything on a float run) */
+	/* many streams of a few voices each: four frames per thread, no tile staging (k_finish.h) */
+	if (few && (seg.pcm_offset & 3u) == 0 && (in.pcm_row & 3u) == 0) return MIX_FEW;
+	if (inmix_live && !early_blocks && tun.mix64) return MIX_64;
+	return MIX_256;
+}
+
+} /* namespace sauplan */
+#endif

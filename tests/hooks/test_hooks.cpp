@@ -5,11 +5,13 @@
  *     the host control plane, the drop-in generator and the output stage over a caller-supplied sauengine::Backend
  *     (tests/seqexec: the sequential plan executor) -- host logic without a GPU
  *   sauAmd_Generator_rewinds: how often a changed call size / channel layout took a generator's read-ahead back
+ *   sauAmd_launch_plan: what saugns_amd/csrc/launch_plan.h decides for a segment given as scalars (no GPU, no pointers)
  *   sauAmd_kat_line_device / _host, sauAmd_kat_div_device: the shared arithmetic as compiled for the device and the host
  *   sauAmd_kat_scan64_device: the kernels' 64-bit wave scan and sum (k_wave_scan.h) over caller-supplied values
  *   sauAmd_kat_round32_device: the 32-bit rounding forms of phases (sau_dev_math.h, k_common.h) on every bit pattern */
 #include "../../saugns_amd/csrc/capi_internal.h"
 #include "../../saugns_amd/csrc/sau_dev_ops.h"
+#include "../../saugns_amd/csrc/launch_plan.h"
 #include <stdio.h>
 #include <string.h>
 
@@ -38,6 +40,64 @@ HOOK bool sauAmd_render_file_with_backend(const sauProgram *prg, uint32_t srate,
 	return ok;
 }
 HOOK unsigned sauAmd_Generator_rewinds(const sauGenerator *g) { return sauamd_internal::generator_rewinds(g); }
+
+/* The HIP backend's launch planner on its own. The switches come from the environment as the backend reads them (plain
+ * getenv here: no SAU_AMD_TUNE needed). -> values written to `out`, or -1.
+ *   what 0: in = a segment's 24 scalars in the order of tests/seqexec's seq_backend_last_segment, then lds per CU, CUs,
+ *           row_stride, pcm_row, f32, max_write, max_rows; out = the plans' scalars (tests/test_launch_plan.py names them)
+ *   what 1: in = {len}; out = {chunks, short last chunk, cb[0..chunks]} (chain_chunk_bounds)
+ *   what 2: in = {d, q...}; out = {q / d by the kernels' udiv_magic with the host's divisor words...} */
+HOOK int sauAmd_launch_plan(int what, const uint32_t *in, uint32_t n_in, uint32_t *out, uint32_t n_out) {
+	using namespace sauplan;
+	const Tuning tun = tuning_from_env([](const char *name) -> const char * { return getenv(name); });
+	if (what == 1 && n_in >= 1 && n_out >= 36) {
+		const ChainChunks k = chain_chunk_bounds(in[0], tun);
+		out[0] = k.n; out[1] = k.short_last;
+		for (uint32_t c = 0; c <= k.n; ++c) out[2 + c] = k.cb[c];
+		return (int)(3 + k.n);
+	}
+	if (what == 2 && n_in >= 1 && n_out + 1 >= n_in) {
+		const MagicDiv d = magic_div(in[0]);
+		for (uint32_t i = 1; i < n_in; ++i) out[i - 1] = magic_quotient(in[i], d);
+		return (int)(n_in - 1);
+	}
+	if (what != 0 || n_in < 31 || n_out < 52) return -1;
+	sauengine::SegmentDesc seg;
+	memset((void *)&seg, 0, sizeof seg);
+	seg.n_main = in[0]; seg.n_fast = in[1]; seg.n_fast_full = in[2]; seg.may_scan = in[3]; seg.serial = in[4];
+	seg.len = in[5]; seg.n_voices = in[6]; seg.n_streams = in[7]; seg.n_slots = in[8]; seg.sum_levels = in[9]; seg.max_ops = in[10];
+	seg.max_steps = in[11]; seg.n_pan_rows = in[12]; seg.wave_mask = in[13]; seg.maybe_block = in[14]; seg.maybe_cub = in[15];
+	seg.n_chain_rows = in[16]; seg.n_inc_rows = in[17]; seg.n_look_rows = in[18]; seg.n_may_scan = in[19]; seg.n_chain_slots = in[20];
+	seg.chain_rows_padded = in[21]; seg.stereo = in[22]; seg.pcm_offset = in[23];
+	const DeviceLimits dev = device_limits(in[24], in[25], tun);
+	PlanInputs pi;
+	pi.row_stride = in[26]; pi.pcm_row = in[27]; pi.f32 = in[28]; pi.max_write = in[29]; pi.max_rows = in[30];
+	pi.chain_budget = sauengine::chain_rows_budget(0, 0);
+	seg.format = pi.f32 ? sauengine::SF_F32 : sauengine::SF_S16;
+	const BlockLoopPlan b = plan_block_loop(seg, tun, dev);
+	const FastPlan k = plan_fast(seg, tun, dev, pi);
+	/* the most LDS any launch of the plan asks for */
+	size_t lds = 0;
+	auto ask = [&](bool on, size_t bytes) { if (on && bytes > lds) lds = bytes; };
+	if (k.use_fast) {
+		ask(k.main_build != 2, k.launch_lds(k.main_build, k.rows, k.wide_cf));
+		ask(k.main_build == 2, k.launch_lds(0, k.rows_cf, k.wide_cf, true));
+		ask(k.main_build == 2, k.launch_lds(2, k.rows, k.wide_look));
+		ask(k.main_build == 2, k.launch_lds(1, k.rows_multi > 4 ? 4 : k.rows_multi, false));
+		ask(k.lean_on, k.launch_lds(3, k.rows_lean, false));
+		ask(k.cub_ok, k.launch_lds(k.main_build == 2 ? 2 : 0, FAST_CUB_ROWS, false));
+		ask(true, k.launch_lds(0, k.rows_repair, k.wide_cf, k.main_build == 2));
+	}
+	const uint32_t vals[52] = {b.ok, b.W, b.T, b.V, b.HB, (uint32_t)b.lds, b.tabs.n, b.ok ? b.grid(seg, k.use_fast) : 0u,
+		k.use_fast, (uint32_t)k.main_build, k.rows, k.rows_multi, k.rows_cf, k.rows_lean, k.lean_on, k.tabs.n, k.wide_cf, k.wide_look,
+		k.cub_ok, k.look_split, k.scan, k.look, k.look_wpv, k.look_inside, k.look_words_real, k.chains, k.chunks.n, k.chunks.short_last,
+		k.duo, k.tailmix, k.queues, k.inmix, (uint32_t)k.inner, k.tasks.dyn_chunks, k.tasks.dyn_static, k.tasks.dyn_small, k.div.m, k.div.s,
+		k.grid, k.grid_cf, k.grid_look, k.pass_grid, (uint32_t)lds, (uint32_t)dev.lds_limit,
+		(uint32_t)plan_mixer(seg, tun, pi, (pi.pcm_row * (pi.f32 ? 4 : 2)), k.inmix, 0), k.tasks_cf.dyn_chunks, k.tasks_cf.dyn_static,
+		k.groups, task_groups(seg, tun), tun.dyn_min_tasks, k.n_want, dev.fk_grid};
+	memcpy(out, vals, sizeof vals);
+	return 52;
+}
 
 /* state = {v0, vt, pos, end, type, flags} as 6 dwords, updated in place */
 HOOK int sauAmd_kat_line_host(uint32_t *state, uint32_t len, const float *mul, float *out) {

@@ -16,7 +16,10 @@ using namespace sauengine;
 namespace {
 
 /* what the host control plane asked of the most recent segment (host-logic tests) */
-static uint32_t g_last_counts[5];
+/* [0..4] n_main, n_fast, n_fast_full, may_scan, serial; then len, n_voices, n_streams, n_slots, sum_levels, max_ops, max_steps,
+ * n_pan_rows, wave_mask, maybe_block, maybe_cub, n_chain_rows, n_inc_rows, n_look_rows, n_may_scan, n_chain_slots,
+ * chain_rows_padded, stereo, pcm_offset (tests/hooks/test_hooks.cpp: sauAmd_launch_plan takes a segment in this order) */
+static uint32_t g_last_counts[24];
 
 struct SeqBackend : public Backend {
 	BackendConfig cfg;
@@ -319,6 +322,10 @@ struct SeqBackend : public Backend {
 		++segments; if (seg.len > longest) longest = seg.len;
 		g_last_counts[0] = seg.n_main; g_last_counts[1] = seg.n_fast; g_last_counts[2] = seg.n_fast_full;
 		g_last_counts[3] = seg.may_scan ? 1u : 0u; g_last_counts[4] = seg.serial ? 1u : 0u;
+		const uint32_t more[19] = {seg.len, seg.n_voices, seg.n_streams, seg.n_slots, seg.sum_levels, seg.max_ops, seg.max_steps,
+			seg.n_pan_rows, (uint32_t)seg.wave_mask, seg.maybe_block, seg.maybe_cub, seg.n_chain_rows, seg.n_inc_rows, seg.n_look_rows,
+			seg.n_may_scan, seg.n_chain_slots, seg.chain_rows_padded, seg.stereo, seg.pcm_offset};
+		for (int i = 0; i < 19; ++i) g_last_counts[5 + i] = more[i];
 		std::vector<std::vector<float>> vout(seg.n_voices), pan(seg.n_voices);
 		std::vector<float> pan_const(seg.n_voices, 0.f);
 		for (uint32_t v = 0; v < seg.n_voices; ++v) {
@@ -367,6 +374,10 @@ struct SeqBackend : public Backend {
 
 extern "C" __attribute__((visibility("default"))) void seq_backend_last_counts(uint32_t *out5) {
 	for (int i = 0; i < 5; ++i) out5[i] = g_last_counts[i];
+}
+/* ... and every scalar of that segment (the order: g_last_counts) */
+extern "C" __attribute__((visibility("default"))) void seq_backend_last_segment(uint32_t *out24) {
+	for (int i = 0; i < 24; ++i) out24[i] = g_last_counts[i];
 }
 
 extern "C" __attribute__((visibility("default"))) void *seq_backend_create(uint32_t block_len) {

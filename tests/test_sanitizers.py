@@ -3,7 +3,8 @@
 tests/seqexec/Makefile `asan` compiles the seven host sources of libsaugns_amd.so exactly as they ship -- engine.cpp, plan.cpp,
 capi.cpp, program_io.cpp, bank_builder.cpp, sndout.cpp, tables.cpp; none of them touches HIP -- together with the sequential
 executor into one g++ library with -fsanitize=address,undefined, every finding fatal. A child process with the ASan runtime
-preloaded then (i) runs the host tests (tests/test_host.py, tests/test_output.py) on that library and (ii) feeds 10000 mutated
+preloaded then (i) runs the host tests (tests/test_host.py, tests/test_output.py) and the launch planner's
+(tests/test_launch_plan.py: saugns_amd/csrc/launch_plan.h is plain C++, in the library through the test hooks) on that library and (ii) feeds 10000 mutated
 program images to sauAmd_program_load and 2500 mutated operator descriptions to sauAmd_build_bank, rendering what is accepted
 (tests/tools/fuzz_host_inputs.py). GPU sanitizers are not available on this pool; the device code is out of this test's reach.
 Round 4's first runs found: a shift by an R level beyond 31 from a mutated image (sar32), and image counts of 2^31 operators
@@ -41,7 +42,8 @@ def san_env():
 
 def test_host_tests_under_asan_ubsan(san_env):
     out = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_host.py"),
-                          os.path.join(ROOT, "tests", "test_output.py"), "-x", "-q", "-m", "not gpu", "-p", "no:cacheprovider"],
+                          os.path.join(ROOT, "tests", "test_output.py"), os.path.join(ROOT, "tests", "test_launch_plan.py"),
+                          "-x", "-q", "-m", "not gpu", "-p", "no:cacheprovider"],
                          capture_output=True, text=True, env=san_env, cwd=ROOT, timeout=1500)
     tail = (out.stdout + out.stderr)[-3000:]
     assert out.returncode == 0, tail
