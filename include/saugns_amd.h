@@ -187,6 +187,56 @@ enum { SAU_AMD_SNDFILE_RAW = 0, SAU_AMD_SNDFILE_AU = 1, SAU_AMD_SNDFILE_WAV = 2,
 SAU_AMD_API bool sauAmd_render_file(const sauProgram *prg, uint32_t srate, const char *path,
 		int format, int channels, uint64_t *frames_out);
 
+/* ---- Level metering ---------------------------------------------------------
+ * Is this render clipping, and by how much should it be scaled? -- answered where the samples are, without fetching them.
+ * One record per stream (or row). What a sample x is: a float row's sample as it stands; an int16 row's sample s measured
+ * in integers (max |s|, the sum of s * s in 64 bits) and converted once on the host: peak = (float)max|s| / 32767.0f,
+ * sum_sq = (double)sum / (32767.0 * 32767.0), full_scale counts |s| >= 32767, over counts s == -32768, nonfinite is 0 -- a
+ * single int16 measurement is exact. Float rows: x * x is formed in f64 (exact) and summed in f64; full_scale counts what an
+ * int16 run of the same frames would put on the rail (the kernels' own rounding, a NaN included: it becomes -32767).
+ * The sums are reproducible: no atomics, a fixed share of the row per workgroup and a fixed order of every addition, so
+ * the same rows give the same bits on any MI355X partition. */
+typedef struct sauAmdLevels {
+	uint64_t frames;        /* frames measured */
+	float    peak[2];       /* max |x| over finite samples; [0] L or mono, [1] R (0 on mono) */
+	double   sum_sq[2];     /* sum of x*x over finite samples, in f64 */
+	uint64_t over[2];       /* samples the int16 clamp alters: |x| > 1, or not finite */
+	uint64_t full_scale[2]; /* samples whose pcm16() is +-32767 */
+	uint64_t nonfinite[2];  /* NaN or +-inf (left out of peak and sum_sq) */
+} sauAmdLevels;
+#ifdef __cplusplus
+static_assert(sizeof(sauAmdLevels) == 80, "sauAmdLevels is 80 bytes");
+#else
+_Static_assert(sizeof(sauAmdLevels) == 80, "sauAmdLevels is 80 bytes");
+#endif
+
+/* Metering is off by default, and while it is off a run does nothing for it. On: every sauAmd_Batch_run / _run_f32 ends with
+ * the device measuring stream i over the frames [0, out_len[i]) of that run -- in the run's format, on the batch's stream,
+ * before any copy to the host; frames behind a stream's end are not measured and a stream that has ended adds nothing -- and
+ * adding the result to stream i's record on the device. int16 and float runs may alternate. False (sauAmd_last_error), with
+ * nothing changed, on a backend without metering; switching it off always succeeds and keeps the records. */
+SAU_AMD_API bool sauAmd_Batch_set_metering(sauAmdBatch *b, int on);
+/* Wait for the batch's stream and copy the records out, one per stream; reset != 0 clears them afterwards. All zero while
+ * metering has never been on. */
+SAU_AMD_API bool sauAmd_Batch_levels(sauAmdBatch *b, sauAmdLevels *out /* [streams] */, int reset);
+/* The same measurement of n_rows rows the caller holds on the batch's device (say, the rows of sauAmd_Batch_device_pcm_f32
+ * after the caller's own processing): row r begins pitch_bytes * r bytes behind `rows` and holds `frames` frames of
+ * `channels` (1, or 2 interleaved) samples, float32 when f32 != 0, else int16 in host byte order. `rows` and pitch_bytes must
+ * be multiples of 16 and channels 1 or 2 -- anything else is refused as a bad argument, as are rows that are not wholly inside
+ * one allocation of that device. Synchronous: what the caller has queued for the rows on other streams must have finished;
+ * the call returns with out[0 .. n_rows) written. The batch's own records are untouched. frames == 0 gives zeroed records. */
+SAU_AMD_API bool sauAmd_Batch_measure_rows(sauAmdBatch *b, const void *rows, size_t pitch_bytes, size_t n_rows,
+		int f32, size_t frames, int channels, sauAmdLevels *out /* [n_rows] */);
+/* sauAmd_render_file to a target peak: the file holds x * gain, gain = target_peak / max(peak[0], peak[1]) (one f32 division;
+ * 1 for a silent program), and the int16 formats round once, after the gain: pcm16(x * gain). The render is made TWICE: a
+ * script's length is unbounded, so the whole render cannot be kept in device memory until its peak is known, and renders are
+ * deterministic -- the first pass renders float runs with metering on and fetches nothing, the second renders the same runs
+ * again and writes them scaled. format and channels as for sauAmd_render_file (SAU_AMD_SNDFILE_WAV_F32 writes x * gain as
+ * floats); target_peak must be finite and > 0. *levels_out (may be NULL) = the first pass's record, before the gain. False
+ * (sauAmd_last_error), before any file is created, on a bad argument or a backend without metering. */
+SAU_AMD_API bool sauAmd_render_file_normalized(const sauProgram *prg, uint32_t srate, const char *path, int format,
+		int channels, float target_peak, uint64_t *frames_out, sauAmdLevels *levels_out);
+
 #ifdef __cplusplus
 }
 #endif

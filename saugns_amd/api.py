@@ -91,6 +91,22 @@ class OpDesc(C.Structure):
                 ("freq2", LineDesc), ("pm_a", LineDesc)]
 
 
+class Levels(C.Structure):
+    """sauAmdLevels (include/saugns_amd.h): what the level meter reports of one stream or row. [0] is L or mono, [1] R."""
+    _fields_ = [("frames", C.c_uint64), ("peak", C.c_float * 2), ("sum_sq", C.c_double * 2), ("over", C.c_uint64 * 2),
+                ("full_scale", C.c_uint64 * 2), ("nonfinite", C.c_uint64 * 2)]
+
+    def as_dict(self):
+        return {"frames": int(self.frames), "peak": list(self.peak), "sum_sq": list(self.sum_sq), "over": list(self.over),
+                "full_scale": list(self.full_scale), "nonfinite": list(self.nonfinite)}
+
+    def __repr__(self):
+        return "Levels(%r)" % (self.as_dict(),)
+
+
+assert C.sizeof(Levels) == 80
+
+
 def _declare(L):
     """The C ABI of include/saugns_amd.h on a loaded library."""
     L.sau_create_Generator.restype = C.c_void_p
@@ -135,6 +151,17 @@ def _declare(L):
     if hasattr(L, "sauAmd_Batch_device_pcm_pitch"):
         L.sauAmd_Batch_device_pcm_pitch.restype = C.c_size_t
         L.sauAmd_Batch_device_pcm_pitch.argtypes = [C.c_void_p]
+    if hasattr(L, "sauAmd_Batch_set_metering"):  # level metering (SAU_AMD_LIB may name an older build)
+        L.sauAmd_Batch_set_metering.restype = C.c_bool
+        L.sauAmd_Batch_set_metering.argtypes = [C.c_void_p, C.c_int]
+        L.sauAmd_Batch_levels.restype = C.c_bool
+        L.sauAmd_Batch_levels.argtypes = [C.c_void_p, C.POINTER(Levels), C.c_int]
+        L.sauAmd_Batch_measure_rows.restype = C.c_bool
+        L.sauAmd_Batch_measure_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_size_t, C.c_int,
+                                                C.POINTER(Levels)]
+        L.sauAmd_render_file_normalized.restype = C.c_bool
+        L.sauAmd_render_file_normalized.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_int, C.c_int, C.c_float,
+                                                    C.POINTER(C.c_uint64), C.POINTER(Levels)]
     L.sauAmd_set_piluts.argtypes = [C.c_void_p]
     L.sauAmd_get_piluts.restype = C.POINTER(C.c_float)
     L.sauAmd_last_error.restype = C.c_char_p
@@ -242,6 +269,42 @@ def render_file(program, srate, path, fmt=SNDFILE_WAV, channels=1, backend=None)
     if not ok:
         raise RuntimeError("sauAmd_render_file failed: " + last_error(None if backend is None else hooks()))
     return n.value
+
+
+_file_hooks = None
+
+
+def use_file_hooks(path):
+    """tests/ only: load the library that runs the normalised file writer over an injected backend
+    (tests/hooks_levels: the product's object files + sauAmd_render_file_normalized_with_backend)."""
+    global _file_hooks
+    if _file_hooks is None:
+        L = _declare(C.CDLL(path))
+        L.sauAmd_render_file_normalized_with_backend.restype = C.c_bool
+        L.sauAmd_render_file_normalized_with_backend.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_int, C.c_int, C.c_float,
+                                                                 C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(Levels)]
+        _file_hooks = L
+    return _file_hooks
+
+
+def render_file_normalized(program, srate, path, fmt=SNDFILE_WAV, channels=1, target_peak=1.0, backend=None):
+    """sauAmd_render_file_normalized: render a whole program into a file scaled to `target_peak` -> (frames written, Levels of
+    the render before the gain). Two passes over the program: one that measures, one that writes x * gain (the int16 formats
+    round once, after the gain). ``backend`` (tests): a sauengine::Backend* for the first pass, without a GPU."""
+    n, lv = C.c_uint64(), Levels()
+    if backend is None:
+        L = _used(lib())
+        ok = L.sauAmd_render_file_normalized(program.ptr, srate, os.fsencode(path), fmt, channels, target_peak,
+                                             C.byref(n), C.byref(lv))
+    else:
+        if _file_hooks is None:
+            raise RuntimeError("the file-hook library is not loaded (use_file_hooks)")
+        L = _used(_file_hooks)
+        ok = L.sauAmd_render_file_normalized_with_backend(program.ptr, srate, os.fsencode(path), fmt, channels, target_peak,
+                                                          backend, C.byref(n), C.byref(lv))
+    if not ok:
+        raise RuntimeError("sauAmd_render_file_normalized failed: " + last_error(L))
+    return n.value, lv
 
 
 def get_piluts():
@@ -427,6 +490,27 @@ class Batch:
         self._L.sauAmd_Batch_timing_ex(self._b, out, C.byref(n), int(reset))
         return {"fast_ms": out[0], "block_ms": out[1], "mix_ms": out[2], "aux_ms": out[3],
                 "segments": n.value}
+
+    def set_metering(self, on):
+        """sauAmd_Batch_set_metering: from the next run on, every run ends with the device measuring each stream's frames of
+        that run into the stream's Levels record (off by default; off costs nothing)."""
+        if not _used(self._L).sauAmd_Batch_set_metering(self._b, 1 if on else 0):
+            raise RuntimeError("sauAmd_Batch_set_metering failed: " + last_error(self._L))
+
+    def levels(self, reset=False):
+        """sauAmd_Batch_levels: wait for the batch's stream -> the streams' accumulated records, a list of Levels."""
+        out = (Levels * self.n)()
+        if not _used(self._L).sauAmd_Batch_levels(self._b, out, 1 if reset else 0):
+            raise RuntimeError("sauAmd_Batch_levels failed: " + last_error(self._L))
+        return list(out)
+
+    def measure_rows(self, ptr, pitch, n_rows, f32, frames, channels):
+        """sauAmd_Batch_measure_rows: measure n_rows rows of device memory at `ptr`, `pitch` bytes apart, of `frames` frames of
+        `channels` float32 (f32) or int16 samples -> a list of Levels. ptr and pitch must be multiples of 16."""
+        out = (Levels * max(int(n_rows), 1))()
+        if not _used(self._L).sauAmd_Batch_measure_rows(self._b, ptr, pitch, n_rows, 1 if f32 else 0, frames, channels, out):
+            raise RuntimeError("sauAmd_Batch_measure_rows failed: " + last_error(self._L))
+        return list(out)[:int(n_rows)]
 
     def device_pcm(self, stream):
         """Device address of the stream's int16 row of the last run; None after a float32 run."""

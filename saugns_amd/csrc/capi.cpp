@@ -5,6 +5,7 @@
 #include "capi_internal.h"
 #include <stdio.h>
 #include <string.h>
+#include <stddef.h>
 #include <stdlib.h>
 #include <chrono>
 #include <exception>
@@ -392,6 +393,44 @@ extern "C" const float *sauAmd_Batch_device_pcm_f32(sauAmdBatch *b, size_t strea
 
 extern "C" size_t sauAmd_Batch_device_pcm_pitch(sauAmdBatch *b) {
 	return b->engine->backend()->device_pcm_pitch();
+}
+
+static_assert(sizeof(sauAmdLevels) == sizeof(sauengine::Levels) && offsetof(sauAmdLevels, sum_sq) == offsetof(sauengine::Levels, sum_sq) &&
+	offsetof(sauAmdLevels, nonfinite) == offsetof(sauengine::Levels, nonfinite), "sauengine::Levels is sauAmdLevels");
+void sauamd_internal::set_last_error(const char *where, const std::string &err) { report(where, err); }
+
+extern "C" bool sauAmd_Batch_set_metering(sauAmdBatch *b, int on) {
+	std::string err;
+	if (!b->engine->set_metering(on != 0, err)) { report("batch", err); return false; }
+	return true;
+}
+
+extern "C" bool sauAmd_Batch_levels(sauAmdBatch *b, sauAmdLevels *out, int reset) {
+	std::string err;
+	try {
+		if (!out) err = "bad argument";
+		else if (b->engine->levels((sauengine::Levels *)out, reset != 0, err)) return true;
+	} catch (const std::exception &ex) { /* (nothing C++ crosses the C ABI) */
+		err = std::string("internal error: ") + ex.what();
+	}
+	report("batch", err);
+	return false;
+}
+
+extern "C" bool sauAmd_Batch_measure_rows(sauAmdBatch *b, const void *rows, size_t pitch_bytes, size_t n_rows,
+		int f32, size_t frames, int channels, sauAmdLevels *out) {
+	std::string err;
+	try {
+		if (!rows || !out || ((uintptr_t)rows & 15u) || (pitch_bytes & 15u) || (channels != 1 && channels != 2))
+			err = "bad argument";
+		else if (b->engine->backend()->measure_rows(rows, pitch_bytes, n_rows, f32 ? sauengine::SF_F32 : sauengine::SF_S16, frames,
+				channels == 2, (sauengine::Levels *)out, err))
+			return true;
+	} catch (const std::exception &ex) {
+		err = std::string("internal error: ") + ex.what();
+	}
+	report("batch", err);
+	return false;
 }
 
 extern "C" bool sauAmd_Batch_sync(sauAmdBatch *b) {

@@ -7,6 +7,8 @@
 #define SAU_CAPI_INTERNAL_H
 #include "../../include/saugns_amd.h"
 #include "engine.h"
+#include <functional>
+#include <string>
 
 namespace sauamd_internal {
 /* sau_create_Generator / sauAmd_create_Batch over a caller-supplied backend (owned by the object made; NULL: the HIP one) */
@@ -17,5 +19,12 @@ unsigned generator_rewinds(const sauGenerator *g);
 /* sauAmd_render_file's body (sndout.cpp) */
 bool render_file(const sauProgram *prg, uint32_t srate, const char *path, int format, int channels,
 		sauengine::Backend *injected, uint64_t *frames_out, std::string &err);
+/* sauAmd_render_file_normalized's body (sndout.cpp). The two passes run on two engines, each over a backend of its own:
+ * make_backend is asked once per pass (NULL with err: that pass cannot run) and the engine made over it owns what it returns. */
+bool render_file_normalized(const sauProgram *prg, uint32_t srate, const char *path, int format, int channels, float target_peak,
+		const std::function<sauengine::Backend *(std::string &)> &make_backend, uint64_t *frames_out, sauAmdLevels *levels_out,
+		std::string &err);
+/* the thread's sauAmd_last_error text (capi.cpp), with the line on stderr */
+void set_last_error(const char *where, const std::string &err);
 } /* namespace sauamd_internal */
 #endif

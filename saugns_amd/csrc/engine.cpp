@@ -622,6 +622,7 @@ bool Engine::run(void *const *host_bufs, SampleFormat format, size_t buf_len, bo
 		bool *more, size_t *out_len, std::string &err) {
 	if (buf_len > UINT32_MAX) { err = "buffer too long"; return false; }
 	if (format == SF_F32 && pcm_swap_) { err = "float32 samples are not byte-swapped"; return false; }
+	if (metering_ && pcm_swap_) { err = "level metering reads samples in host byte order, not byte-swapped ones"; return false; }
 	/* the run's format, ahead of anything that moves: a backend without float output refuses here */
 	if (!set_format(format, err)) return false;
 	const uint32_t total = (uint32_t)buf_len;
@@ -720,6 +721,7 @@ bool Engine::run(void *const *host_bufs, SampleFormat format, size_t buf_len, bo
 	}
 	frames_done_ += total;
 	call_phase_ = (uint32_t)(((uint64_t)call_phase_ + total) % lat_call_);
+	if (metering_) meter_frames_.assign(streams_.size(), 0);
 	for (size_t s = 0; s < streams_.size(); ++s) {
 		Stream &st = streams_[s];
 		st.call_gen += st.part_gen;
@@ -735,6 +737,11 @@ bool Engine::run(void *const *host_bufs, SampleFormat format, size_t buf_len, bo
 		}
 		if (more) more[s] = !ended;
 		if (out_len) out_len[s] = ended ? st.call_gen : buf_len;
+		if (metering_) meter_frames_[s] = (uint32_t)(ended ? st.call_gen : buf_len);
+	}
+	/* the meter reads what the mixers wrote, where it is: behind them on the backend's stream, ahead of any fetch */
+	if (metering_ && !backend_->measure_streams(meter_frames_.data(), stereo, format, err)) return false;
+	for (size_t s = 0; s < streams_.size(); ++s) {
 		if (host_bufs && host_bufs[s]) {
 			if (format == SF_F32 ? !backend_->fetch_pcm_f32((uint32_t)s, (float *)host_bufs[s], total, stereo, err)
 			                     : !backend_->fetch_pcm((uint32_t)s, (int16_t *)host_bufs[s], total, stereo, err))
@@ -742,6 +749,14 @@ bool Engine::run(void *const *host_bufs, SampleFormat format, size_t buf_len, bo
 		}
 	}
 	return true;
+}
+
+bool Engine::levels(Levels *out, bool reset, std::string &err) {
+	if (!metered_) { /* (no backend has records yet) */
+		memset((void *)out, 0, sizeof(Levels) * streams_.size());
+		return true;
+	}
+	return backend_->read_levels(out, reset, err);
 }
 
 } /* namespace sauengine */

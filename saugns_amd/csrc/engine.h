@@ -29,6 +29,15 @@ using namespace saudev;
  * mixer's f32 sum as it stands (include/saugns_amd.h: sauAmd_Batch_run_f32). The format belongs to the run, not to the engine. */
 enum SampleFormat : uint8_t { SF_S16 = 0, SF_F32 = 1 };
 
+/* What a level meter reports of one stream or row (include/saugns_amd.h: sauAmdLevels, the same 80 bytes). */
+struct Levels {
+	uint64_t frames;
+	float peak[2];
+	double sum_sq[2];
+	uint64_t over[2], full_scale[2], nonfinite[2];
+};
+static_assert(sizeof(Levels) == 80, "sauAmdLevels");
+
 /* Everything the backend needs to render one segment (no events inside). */
 struct SegmentDesc {
 	uint32_t len;             /* frames */
@@ -163,6 +172,34 @@ public:
 	virtual const float *device_pcm_f32(uint32_t stream) { (void)stream; return nullptr; }
 	/* bytes between the rows of consecutive streams in the last run's format (0: no device PCM) */
 	virtual size_t device_pcm_pitch() { return 0; }
+	/* Level metering (include/saugns_amd.h: sauAmdLevels), where the samples are. A backend without it refuses -- these
+	 * defaults, as with float output -- and nothing changes. begin_metering: make the streams' records (zeroed) if they are
+	 * not there yet. */
+	virtual bool begin_metering(std::string &err) { err = "this backend has no level metering"; return false; }
+	/* measure frames [0, frames[s]) of every stream's row of the run just rendered (its format, its channels) and add the
+	 * result to the stream's record: device work on the backend's stream, behind the run's mixers and ahead of any fetch */
+	virtual bool measure_streams(const uint32_t *frames, bool stereo, SampleFormat format, std::string &err) {
+		(void)frames; (void)stereo; (void)format; err = "this backend has no level metering"; return false;
+	}
+	/* wait for the stream and copy the records out; `reset`: clear them */
+	virtual bool read_levels(Levels *out, bool reset, std::string &err) {
+		(void)out; (void)reset; err = "this backend has no level metering"; return false;
+	}
+	/* the same measurement of rows the caller holds on the backend's device (synchronous; the streams' records are untouched) */
+	virtual bool measure_rows(const void *rows, size_t pitch_bytes, size_t n_rows, SampleFormat format, size_t frames,
+			bool stereo, Levels *out, std::string &err) {
+		(void)rows; (void)pitch_bytes; (void)n_rows; (void)format; (void)frames; (void)stereo; (void)out;
+		err = "this backend has no level metering"; return false;
+	}
+	/* The normalised file writer's second pass: frames [0, frames) of stream s's float row of the run just rendered, times
+	 * `gain`, into a device buffer of the backend's own -- as int16 (pcm16 of the product; `swap_bytes`: big-endian) or as
+	 * float32 -- and fetch_requant_async queues the copy of that buffer out, like fetch_pcm_async (`slot`, wait_fetch). */
+	virtual bool requantize(uint32_t stream, uint32_t frames, bool stereo, float gain, SampleFormat out, bool swap_bytes, std::string &err) {
+		(void)stream; (void)frames; (void)stereo; (void)gain; (void)out; (void)swap_bytes; err = "this backend has no level metering"; return false;
+	}
+	virtual bool fetch_requant_async(void *dst, size_t bytes, int slot, std::string &err) {
+		(void)dst; (void)bytes; (void)slot; err = "this backend has no level metering"; return false;
+	}
 };
 
 /* ---- plan compiler (plan.cpp) -------------------------------------------- */
@@ -254,6 +291,19 @@ public:
 		return true;
 	}
 
+	/* Level metering (include/saugns_amd.h: sauAmd_Batch_set_metering). On: every run ends with the backend measuring each
+	 * stream's frames [0, out_len) of that run, in the run's format, into the stream's record. Off (the default): run() makes
+	 * no call for it. False, with the switch where it was, on a backend without metering. */
+	bool set_metering(bool on, std::string &err) {
+		if (on && !metering_ && !backend_->begin_metering(err)) return false;
+		if (on) metered_ = true;
+		metering_ = on;
+		return true;
+	}
+	bool metering() const { return metering_; }
+	/* the streams' records, out[n_streams()]; all zero while metering has never been on */
+	bool levels(Levels *out, bool reset, std::string &err);
+
 	/* Size the device buffers for runs of up to `frames` frames now (run() grows them on demand, which waits for the
 	 * stream: a host that knows its longest run says so once). */
 	bool reserve(size_t frames, bool stereo, std::string &err);
@@ -344,6 +394,9 @@ private:
 	bool reserved_stereo_ = false;
 	bool pcm_swap_ = false;
 	SampleFormat format_ = SF_S16;   /* of the run being rendered */
+	bool metering_ = false;          /* set_metering() */
+	bool metered_ = false;           /* ... has ever been on: the backend has records */
+	std::vector<uint32_t> meter_frames_; /* per stream: out_len of the run at hand */
 	bool plans_dirty_ = true;
 	/* concatenated plans as uploaded; per (stream,voice) offsets */
 	std::vector<Step> all_steps_;

@@ -9,6 +9,7 @@
  *   k_fast_voice.h  fast_voice, fast_kernel<T,SCAN>, repair_kernel<T>
  *   k_chain.h       chain_kernel
  *   k_finish.h      finalize_kernel, mix_kernel, mix_few_kernel (int16 and float32 forms), event_kernel
+ *   k_levels.h      levels_kernel, levels_finish_kernel (level metering), requant_kernel (the normalised file writer)
  *   launch_plan.h   (plain C++, no HIP) the tuning switches and every decision about a segment's launches: rows per pass, LDS
  *                   budgets, builds, grids, tasks, chain chunks, the mixer -- a plan per segment, testable without a GPU
  *   (this file)     buffer and stream pools, table sets, the kernel lookup, HipBackendImpl: render() carries a plan out,
@@ -68,6 +69,7 @@ using namespace sauplan;
 #include "k_fast_voice.h"
 #include "k_chain.h"
 #include "k_finish.h"
+#include "k_levels.h"
 static_assert(MISC_BYTES == sizeof(Misc), "launch_plan.h plans the block loop's LDS with this size");
 
 /* ------------------------------------------------------------------------ */
@@ -1247,6 +1249,135 @@ public:
 		host_blocks_.erase(it);
 	}
 
+	/* ---- level metering (k_levels.h; the geometry is launch_plan.h's plan_levels) ---- */
+	bool begin_metering(std::string &err) override {
+		use_device();
+		if (lev_acc_.p) return true;
+		if (!lev_acc_.ensure(cfg_.n_streams, err)) return false;
+		HIP_OK(hipMemsetAsync(lev_acc_.p, 0, (size_t)cfg_.n_streams * sizeof(LevelsAcc), stream_));
+		return true;
+	}
+	/* the two launches of one measurement, on the backend's stream */
+	bool launch_levels(LevelsParams lp, const LevelsPlan &plan, std::string &err) {
+		if (!plan.blocks) lp.parts = nullptr; /* (rows without a sample: the records are all there is to write) */
+		else {
+			if (!lev_parts_.ensure(plan.parts, err)) return false;
+			lp.parts = lev_parts_.p;
+			lp.blocks = plan.blocks;
+			if (lp.f32) hipLaunchKernelGGL(levels_kernel<float>, dim3(plan.blocks, plan.rows), dim3(LEVELS_THREADS), 0, stream_, lp);
+			else hipLaunchKernelGGL(levels_kernel<int16_t>, dim3(plan.blocks, plan.rows), dim3(LEVELS_THREADS), 0, stream_, lp);
+			HIP_OK(hipGetLastError());
+		}
+		hipLaunchKernelGGL(levels_finish_kernel, dim3(plan.finish_grid), dim3(64), 0, stream_, lp);
+		HIP_OK(hipGetLastError());
+		return true;
+	}
+	bool measure_streams(const uint32_t *frames, bool stereo, sauengine::SampleFormat format, std::string &err) override {
+		use_device();
+		const bool f32 = format == sauengine::SF_F32;
+		if (!lev_acc_.p) { err = "level metering has not begun"; return false; }
+		if (f32 != pcm_f32_ || !pcm_.p) { err = "no rows of that sample format to measure"; return false; }
+		uint32_t longest = 0;
+		for (uint32_t s = 0; s < cfg_.n_streams; ++s) {
+			if (frames[s] > row_stride_) { err = "frames beyond the streams' rows"; return false; }
+			if (frames[s] > longest) longest = frames[s];
+		}
+		if (!longest) return true; /* every stream has ended: nothing to add */
+		const LevelsPlan plan = plan_levels(longest, stereo ? 2 : 1, cfg_.n_streams);
+		if (!plan.ok) { err = "too many streams for one level measurement"; return false; }
+		if (!lev_frames_.ensure(cfg_.n_streams, err) || !send(lev_frames_.p, frames, (size_t)cfg_.n_streams * sizeof(uint32_t), err)) return false;
+		LevelsParams lp;
+		memset((void *)&lp, 0, sizeof lp);
+		lp.rows = pcm_.p; lp.pitch = pcm_pitch(); /* (rows start on 256 bytes: reserve_frames) */
+		lp.row_frames = lev_frames_.p;
+		lp.channels = stereo ? 2 : 1;
+		lp.acc = lev_acc_.p; lp.n_rows = cfg_.n_streams; lp.f32 = f32 ? 1 : 0; lp.accumulate = 1;
+		return launch_levels(lp, plan, err);
+	}
+	static void levels_out(const LevelsAcc &a, sauengine::Levels &o) {
+		o.frames = a.frames;
+		for (int c = 0; c < 2; ++c) {
+			/* int16 runs: one conversion, here (a batch of int16 runs alone has fpeak and fsum +0: max and sum leave the int16 part as it is) */
+			const float ip = (float)a.ipeak[c] / 32767.0f;
+			o.peak[c] = a.fpeak[c] > ip ? a.fpeak[c] : ip;
+			o.sum_sq[c] = a.fsum[c] + (double)a.isum[c] / (32767.0 * 32767.0);
+			o.over[c] = a.over[c]; o.full_scale[c] = a.full[c]; o.nonfinite[c] = a.nonf[c];
+		}
+	}
+	bool read_records(const LevelsAcc *dev, size_t n, sauengine::Levels *out, std::string &err) {
+		std::vector<LevelsAcc> h(n);
+		HIP_OK(hipMemcpyAsync(h.data(), dev, n * sizeof(LevelsAcc), hipMemcpyDeviceToHost, stream_));
+		HIP_OK(hipStreamSynchronize(stream_));
+		for (size_t i = 0; i < n; ++i) levels_out(h[i], out[i]);
+		return true;
+	}
+	bool read_levels(sauengine::Levels *out, bool reset, std::string &err) override {
+		use_device();
+		if (!lev_acc_.p) { memset((void *)out, 0, sizeof(sauengine::Levels) * cfg_.n_streams); return true; }
+		if (!read_records(lev_acc_.p, cfg_.n_streams, out, err)) return false;
+		if (reset) HIP_OK(hipMemsetAsync(lev_acc_.p, 0, (size_t)cfg_.n_streams * sizeof(LevelsAcc), stream_));
+		return true;
+	}
+	bool measure_rows(const void *rows, size_t pitch, size_t n_rows, sauengine::SampleFormat format, size_t frames, bool stereo,
+			sauengine::Levels *out, std::string &err) override {
+		use_device();
+		const bool f32 = format == sauengine::SF_F32;
+		const size_t ch = stereo ? 2 : 1, size = f32 ? sizeof(float) : sizeof(int16_t);
+		if (!n_rows) return true;
+		if (!rows || ((uintptr_t)rows & 15u) || (pitch & 15u) || !out) { err = "bad argument: rows and pitch_bytes must be multiples of 16"; return false; }
+		if (frames > SIZE_MAX / 8 || (n_rows > 1 && frames * ch * size > pitch)) { err = "bad argument: rows longer than their pitch"; return false; }
+		if (frames) { /* the rows are read by a kernel: they have to lie inside one allocation of this device */
+			hipPointerAttribute_t at;
+			memset((void *)&at, 0, sizeof at);
+			if (hipPointerGetAttributes(&at, rows) != hipSuccess) { (void)hipGetLastError(); err = "bad argument: rows is not device memory"; return false; }
+			if (at.type != hipMemoryTypeDevice || at.device != dev_) { err = "bad argument: rows must be memory of the batch's device"; return false; }
+			hipDeviceptr_t base = nullptr;
+			size_t span = 0;
+			if (hipMemGetAddressRange(&base, &span, (hipDeviceptr_t)rows) != hipSuccess) { (void)hipGetLastError(); err = "bad argument: rows is not device memory"; return false; }
+			size_t need = 0;
+			const bool wraps = __builtin_mul_overflow(pitch, n_rows - 1, &need) || __builtin_add_overflow(need, frames * ch * size, &need);
+			const size_t ofs = (size_t)((const char *)rows - (const char *)base);
+			if (wraps || ofs > span || need > span - ofs) { err = "bad argument: the rows reach beyond their allocation"; return false; }
+		}
+		const LevelsPlan plan = plan_levels(frames, (uint32_t)ch, n_rows);
+		if (!plan.ok) { err = "bad argument: too many rows (65535 at most) or frames for one level measurement"; return false; }
+		if (!lev_out_.ensure(n_rows, err)) return false;
+		LevelsParams lp;
+		memset((void *)&lp, 0, sizeof lp);
+		lp.rows = rows; lp.pitch = pitch; lp.row_frames = nullptr; lp.frames = frames;
+		lp.channels = (uint32_t)ch;
+		lp.acc = lev_out_.p; lp.n_rows = (uint32_t)n_rows; lp.f32 = f32 ? 1 : 0; lp.accumulate = 0;
+		return launch_levels(lp, plan, err) && read_records(lev_out_.p, n_rows, out, err);
+	}
+	bool requantize(uint32_t stream, uint32_t frames, bool stereo, float gain, sauengine::SampleFormat out, bool swap_bytes,
+			std::string &err) override {
+		use_device();
+		if (!pcm_f32_ || !pcm_.p) { err = "the last run's samples are not float32"; return false; }
+		if (stream >= cfg_.n_streams || frames > row_stride_) { err = "frames beyond the stream's row"; return false; }
+		const bool f32 = out == sauengine::SF_F32;
+		if (f32 && swap_bytes) { err = "float32 samples are not byte-swapped"; return false; }
+		const size_t n = (size_t)frames * (stereo ? 2 : 1);
+		if (!n) return true;
+		if (!requant_.ensure(n * (f32 ? sizeof(float) : sizeof(int16_t)), err)) return false;
+		RequantParams rq;
+		rq.src = (const float *)pcm_at(stream); rq.dst = requant_.p; rq.n = n; rq.gain = gain; rq.swap_bytes = swap_bytes ? 1 : 0;
+		const dim3 grid((unsigned)((n + 1023) / 1024));
+		if (f32) hipLaunchKernelGGL(requant_kernel<float>, grid, dim3(256), 0, stream_, rq);
+		else hipLaunchKernelGGL(requant_kernel<int16_t>, grid, dim3(256), 0, stream_, rq);
+		HIP_OK(hipGetLastError());
+		return true;
+	}
+	/* (the next run's requant_kernel is ordered behind this copy on the one stream: one buffer serves both host slots) */
+	bool fetch_requant_async(void *dst, size_t bytes, int slot, std::string &err) override {
+		slot &= 3;
+		use_device();
+		if (bytes > requant_.bytes) { err = "more bytes than were requantised"; return false; }
+		if (!fetch_ev_[slot]) HIP_OK(hipEventCreateWithFlags(&fetch_ev_[slot], hipEventDisableTiming));
+		HIP_OK(hipMemcpyAsync(dst, requant_.p, bytes, hipMemcpyDeviceToHost, stream_));
+		HIP_OK(hipEventRecord(fetch_ev_[slot], stream_));
+		return true;
+	}
+
 	const int16_t *device_pcm(uint32_t stream) override { return pcm_.p && !pcm_f32_ ? (const int16_t *)pcm_at(stream) : nullptr; }
 	const float *device_pcm_f32(uint32_t stream) override { return pcm_.p && pcm_f32_ ? (const float *)pcm_at(stream) : nullptr; }
 	size_t device_pcm_pitch() override { return pcm_.p ? pcm_pitch() : 0; }
@@ -1462,6 +1593,12 @@ private:
 	bool after_pending_ = false;
 	DevBuf<uint32_t> inmix_ctl_;
 	DevBuf<uint32_t> tail_ok_;        /* [stream]: the look-back launch mixes this stream itself (k_fast_types.h: FastParams.tail_ok) */
+	/* level metering: the streams' running records, one measurement's partial records and frame counts, the records of
+	 * foreign rows (measure_rows), and the normalised writer's requantised row -- all from the pool, none there until asked for */
+	DevBuf<LevelsAcc> lev_acc_, lev_out_;
+	DevBuf<LevelsPart> lev_parts_;
+	DevBuf<uint32_t> lev_frames_;
+	DevBuf<unsigned char> requant_;
 	DevBuf<uint32_t> vlists_;   /* [2][n_voices]: analyze_kernel's lists of closed-form and look-back voices (split launches) */
 	/* A chain kernel's workgroup is three waves on a latency-bound recurrence. SAU_AMD_CHAIN_ALONE=1 (a tuning switch): while a
 	 * launch has no more workgroups than the device has CUs, each asks for more than half a CU's LDS and so gets a CU of its own.

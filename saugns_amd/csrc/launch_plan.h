@@ -699,5 +699,38 @@ inline Mixer plan_mixer(const SegmentDesc &seg, const Tuning &tun, const PlanInp
 	return MIX_256;
 }
 
+/* ---- level metering (k_levels.h) ----
+ * A workgroup of levels_kernel owns LEVELS_WG_SAMPLES consecutive samples of one row -- samples, not frames: the two channels
+ * of a stereo row interleave, and an even block start keeps every block's channel parity the same. The number is a constant,
+ * never a function of the device: which samples meet in which partial sum, and in which order, is part of the result's bits,
+ * and the same rows must give the same bits on any partition of an MI355X. One sweep is the 256 lanes' one 16-byte load each:
+ * LEVELS_SWEEP_F32 float or LEVELS_SWEEP_S16 int16 samples; a block is 16 (8) sweeps, four of them in flight per lane.
+ * 16384 samples: a 10 s stereo float render of 64 streams is 3456 workgroups of 64 KiB each, thirteen per CU -- enough to hide
+ * the tail, and 54 partial records per row for the one thread that folds them. */
+constexpr uint32_t LEVELS_THREADS = 256;
+constexpr uint32_t LEVELS_SWEEP_F32 = LEVELS_THREADS * 4, LEVELS_SWEEP_S16 = LEVELS_THREADS * 8;
+constexpr uint32_t LEVELS_WG_SAMPLES = 16384;
+static_assert(LEVELS_WG_SAMPLES % LEVELS_SWEEP_S16 == 0 && LEVELS_WG_SAMPLES % LEVELS_SWEEP_F32 == 0, "a block is whole sweeps (and begins on an even sample, on 16 bytes)");
+constexpr uint32_t LEVELS_MAX_ROWS = 65535; /* grid.y */
+struct LevelsPlan {
+	bool ok = false;      /* false: more rows or blocks than a grid has */
+	uint32_t blocks = 0;  /* grid.x of levels_kernel: blocks of the longest row (0: nothing to measure, no launch) */
+	uint32_t rows = 0;    /* grid.y */
+	uint32_t finish_grid = 0; /* levels_finish_kernel: 64 rows per workgroup */
+	size_t parts = 0;     /* partial records: rows * blocks */
+};
+inline LevelsPlan plan_levels(uint64_t max_frames, uint32_t channels, size_t n_rows) {
+	LevelsPlan p;
+	const uint64_t samples = max_frames * channels;
+	const uint64_t blocks = (samples + LEVELS_WG_SAMPLES - 1) / LEVELS_WG_SAMPLES;
+	if (n_rows > LEVELS_MAX_ROWS || blocks > 0x7fffffffull || max_frames > (~(uint64_t)0 >> 2)) return p;
+	p.ok = true;
+	p.blocks = (uint32_t)blocks;
+	p.rows = (uint32_t)n_rows;
+	p.finish_grid = (uint32_t)((n_rows + 63) / 64);
+	p.parts = (size_t)n_rows * (size_t)blocks;
+	return p;
+}
+
 } /* namespace sauplan */
 #endif

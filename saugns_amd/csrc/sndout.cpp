@@ -15,8 +15,10 @@
 #include "engine.h"
 #include "hip_backend.h"
 #include "capi_internal.h"
+#include <float.h>
 #include <stdio.h>
 #include <string.h>
+#include <exception>
 #include <string>
 
 using sauengine::Backend;
@@ -186,7 +188,130 @@ bool render_file_over(const sauProgram *prg, uint32_t srate, const char *path, i
 	return ok;
 }
 
+/* Player_run's call size and the frames per device run that sauAmd_render_file uses (above): both passes of the normalised
+ * writer render on the same lattice, so they -- and sauAmd_render_file -- compute the same samples */
+void file_lattice(uint32_t srate, size_t &call, size_t &chunk) {
+	call = (size_t)((uint64_t)256 * srate / 1000);
+	if (call == 0) call = 1;
+	chunk = call >= 176400 ? call : 176400 / call * call;
+}
+
+/* Pass 1 of the normalised writer: the whole program in float runs with metering on, nothing fetched -> its record.
+ * Every refusal of a backend without float output or metering happens here, before there is a file. */
+bool measure_program(const sauProgram *prg, uint32_t srate, bool stereo, Backend *backend /* owned */, sauengine::Levels &lv,
+		std::string &err) {
+	Engine *engine = Engine::create(&prg, 1, srate, backend, err);
+	if (!engine) return false;
+	size_t call, chunk;
+	file_lattice(srate, call, chunk);
+	engine->set_call_len(call);
+	bool ok = engine->set_format(sauengine::SF_F32, err) && engine->set_metering(true, err);
+	bool more = ok;
+	while (ok && more) {
+		size_t len = 0;
+		ok = engine->run_f32(nullptr, chunk, stereo, &more, &len, err);
+	}
+	ok = ok && engine->levels(&lv, false, err);
+	delete engine; /* owns the backend */
+	return ok;
+}
+
+/* Pass 2: the same runs on a fresh engine, each through requant_kernel into a device buffer of its own and from there
+ * through the two page-locked slots to the file, as render_file_over's chunks go. */
+bool write_scaled(const sauProgram *prg, uint32_t srate, const char *path, int format, int channels, float gain,
+		Backend *backend /* owned */, uint64_t *frames_out, std::string &err) {
+	Engine *engine = Engine::create(&prg, 1, srate, backend, err);
+	if (!engine) return false;
+	const bool stereo = channels == 2;
+	const bool f32 = format == SAU_AMD_SNDFILE_WAV_F32;
+	const sauengine::SampleFormat out_fmt = f32 ? sauengine::SF_F32 : sauengine::SF_S16;
+	size_t call, chunk;
+	file_lattice(srate, call, chunk);
+	engine->set_call_len(call);
+	if (!engine->set_format(sauengine::SF_F32, err)) { delete engine; return false; }
+	const size_t frame_bytes = (size_t)channels * (f32 ? sizeof(float) : sizeof(int16_t));
+	void *host[2] = {backend->alloc_host(chunk * frame_bytes), backend->alloc_host(chunk * frame_bytes)};
+	SndOut out;
+	bool ok = host[0] && host[1];
+	if (!ok) err = "out of page-locked memory";
+	if (ok && !out.open(path, format, (uint16_t)channels, srate)) {
+		err = std::string("couldn't open \"") + path + "\" for writing";
+		ok = false;
+	}
+	size_t pending[2] = {0, 0};
+	int slot = 0;
+	bool more = ok;
+	while (ok && more) {
+		size_t len = 0;
+		ok = engine->run_f32(nullptr, chunk, stereo, &more, &len, err);
+		if (!ok) break;
+		if (len) {
+			/* (the rounding happens here, once, after the gain; AU files get their byte order here too) */
+			ok = backend->requantize(0, (uint32_t)len, stereo, gain, out_fmt, format == SAU_AMD_SNDFILE_AU, err) &&
+			     backend->fetch_requant_async(host[slot], len * frame_bytes, slot, err);
+			pending[slot] = len;
+		}
+		const int other = slot ^ 1;
+		if (ok && pending[other]) {
+			ok = backend->wait_fetch(other, err);
+			if (ok && !out.write(host[other], pending[other])) { err = "write failed"; ok = false; }
+			pending[other] = 0;
+		}
+		slot = other;
+	}
+	for (int s = 0; ok && s < 2; ++s) { /* oldest first */
+		const int k = slot ^ s;
+		if (pending[k]) {
+			ok = backend->wait_fetch(k, err);
+			if (ok && !out.write(host[k], pending[k])) { err = "write failed"; ok = false; }
+			pending[k] = 0;
+		}
+	}
+	{ std::string e2; (void)backend->sync(e2); }
+	if (out.f && out.close() != 0 && ok) { err = "write failed"; ok = false; }
+	if (frames_out) *frames_out = out.frames;
+	backend->free_host(host[0]);
+	backend->free_host(host[1]);
+	delete engine;
+	return ok;
+}
+
 } /* namespace */
+
+bool sauamd_internal::render_file_normalized(const sauProgram *prg, uint32_t srate, const char *path, int format, int channels,
+		float target_peak, const std::function<Backend *(std::string &)> &make_backend, uint64_t *frames_out,
+		sauAmdLevels *levels_out, std::string &err) {
+	if (frames_out) *frames_out = 0;
+	if (!prg || !path || (channels != 1 && channels != 2) || format < 0 || format > SAU_AMD_SNDFILE_WAV_F32 ||
+	    !(target_peak > 0.f) || !(target_peak <= FLT_MAX)) { /* (a NaN fails both comparisons) */
+		err = "bad argument";
+		return false;
+	}
+	Backend *first = make_backend(err);
+	if (!first) return false;
+	sauengine::Levels lv;
+	if (!measure_program(prg, srate, channels == 2, first, lv, err)) return false;
+	if (levels_out) memcpy(levels_out, &lv, sizeof lv);
+	const float peak = lv.peak[0] > lv.peak[1] ? lv.peak[0] : lv.peak[1];
+	const float gain = peak == 0.f ? 1.0f : target_peak / peak;
+	Backend *second = make_backend(err);
+	if (!second) return false;
+	return write_scaled(prg, srate, path, format, channels, gain, second, frames_out, err);
+}
+
+extern "C" bool sauAmd_render_file_normalized(const sauProgram *prg, uint32_t srate, const char *path, int format,
+		int channels, float target_peak, uint64_t *frames_out, sauAmdLevels *levels_out) {
+	std::string err;
+	bool ok = false;
+	try {
+		ok = sauamd_internal::render_file_normalized(prg, srate, path, format, channels, target_peak,
+				[](std::string &e) -> Backend * { return sauhip::create_hip_backend(e); }, frames_out, levels_out, err);
+	} catch (const std::exception &ex) { /* (nothing C++ crosses the C ABI) */
+		err = std::string("internal error: ") + ex.what();
+	}
+	if (!ok) sauamd_internal::set_last_error("output", err);
+	return ok;
+}
 
 extern "C" bool sauAmd_render_file(const sauProgram *prg, uint32_t srate, const char *path,
 		int format, int channels, uint64_t *frames_out) {
