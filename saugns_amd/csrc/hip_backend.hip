@@ -1006,7 +1006,7 @@ public:
 		if (k.inner != INNER_NONE) {
 			const bool lm = k.inner == INNER_LANE_MAJOR;
 			const void *ik = fast_kernel_fn(0, 12, FK_WIDE | FK_INNER | (lm ? FK_LANEMAJOR : 0u));
-			const size_t lds = k.launch_lds(0, k.rows, true);
+			const size_t lds = k.inner_lds();
 			FastParams ep = fp;
 			ep.mode = 0; ep.edge_only = 1; ep.dyn_static = 1; ep.dyn_chunks = 2; ep.dyn_small = 0; ep.inmix_flags = 0; /* (two tasks a voice: its first group, its last) */
 			if (!launch_build(j, err, 0, k.rows, k.grid_edge, &ep, false, true)) j.launched = false;

@@ -4,7 +4,9 @@
  * row-major form has j = 64 k + l. A frame's neighbour before is then register k - 1 of the same lane, and only register 0 reads
  * lane l - 1's register T - 1: one DPP move per dword of a differentiator per group, where the row-major form's later rows take two
  * per register (prev_of there) -- 5.3 of the build's 31.7 vector instructions per operator-sample (profiles/census/).
- * The block buffers keep their layout (element (k, l) at off + 64 k + l): producer and consumer are both this form.
+ * The block buffer is T registers of the lane (blk): where the row-major form keeps element (k, l) at off + 64 k + l in LDS, here
+ * lane l both writes and reads it, and the launch only takes segments whose voices share ONE buffer (launch_plan.h:
+ * plan_closed_form), so every *_off that is not ~0u names that block. The launch's LDS holds the tables and nothing else.
  * The arithmetic and its order are k_fast_group.h's with EDGE false, SCAN 0, REPAIR false, CUB false; only what reaches a frame's
  * neighbour differs. In scope: everything fast_voice has defined up to its row-group loop, plus cg. */
 		const int j0 = l * T;                              /* this lane's first frame of the group, relative */
@@ -43,13 +45,32 @@
 		};
 		uint32_t held_rows = 0; /* which of the group's first owned frames unresolved holds spoil (bit j: owned frame j, as k_fast_group.h) */
 		bool held_far = false;  /* ... or something the repair pass cannot put right */
+		/* the block buffer: this lane's T values, written by one step and read by a later one of the same group (nothing is carried
+		 * from group to group: a group evaluates all its steps from scratch) */
+		float blk[T];
 		for (uint32_t si = 0; si < n_fsteps; ++si) {
 			const FastStep f = load_step_uniform(fsteps + si);
 			const uint32_t kind = f.kind & 0xff;
 			const uint32_t flags = (f.kind >> 8) & 0xff;
+			/* (the step's own copy of t0: t0 + 1 ... t0 + T - 1, which only the ramps, N and R read, were computed ahead of the step
+			 * loop and held in T - 1 registers across it -- registers the block now needs) */
+			int t0s = t0;
+			asm volatile("" : "+v"(t0s));
+			{
+				/* A step that needs a second block -- a buffer beyond the first, PM beside FPM, a range list's blend or envelope, a pan
+				 * block -- is not this form's. The host does not send such a segment here (launch_plan.h: plan_closed_form); should a
+				 * step say so all the same, the voice goes to the block loop, as with holds the repair pass cannot put right. */
+				/* (off + 1: 0 none, 1 the first buffer, more another one -- in integers: as booleans these tests became vector code) */
+				const uint32_t o1 = f.out_off + 1u, p1 = f.pm_off + 1u, q1 = f.fpm_off + 1u, a1 = f.amp_off + 1u;
+				uint32_t two = 0;
+				if (kind == ST_OSC) two = o1 | a1 | (p1 + q1) | (flags & SF_WAVE_ENV);
+				else if (kind == ST_LINE) two = o1;
+				else if (kind == ST_VOICE) two = o1 | (p1 << 1);
+				else if (kind == ST_LERP) two = 2u;
+				if (two > 1u) { zero_acc = 1; continue; }
+			}
 			if (kind == ST_OSC) {
 				const uint32_t type = f.type & 0xff;
-				const bool wave_env = (flags & SF_WAVE_ENV) != 0;
 				const bool layer = (flags & SF_LAYER) != 0;
 				const bool to_voice = ((f.kind >> 16) & OX_VOICE) != 0;
 				float s[T];
@@ -76,7 +97,7 @@
 							bool big = false;
 #pragma unroll
 							for (int k = 0; k < T; ++k) {
-								pm[k] = slots[f.pm_off + k * 64];
+								pm[k] = blk[k];
 								big |= !(fabsf(pm[k]) < 0x1p20f);
 							}
 							ok = !__any(big);
@@ -131,7 +152,7 @@
 							bool big = false;
 #pragma unroll
 							for (int k = 0; k < T; ++k) {
-								pm[k] = slots[f.pm_off + k * 64];
+								pm[k] = blk[k];
 								big |= !(fabsf(pm[k]) < 0x1p20f);
 							}
 							if (!__any(big)) {
@@ -141,25 +162,9 @@
 #pragma unroll
 								for (int k = 0; k < T; ++k) ph[k] += rint32w_p31(pm[k]);
 							}
-						} else if (has_pm || has_fpm) {
-							float pm[T], fpm[T];
+						} else if (has_fpm) {
 #pragma unroll
-							for (int k = 0; k < T; ++k) { pm[k] = 0.f; fpm[k] = 0.f; }
-							if (has_pm) {
-#pragma unroll
-								for (int k = 0; k < T; ++k) pm[k] = slots[f.pm_off + k * 64];
-							}
-							if (has_fpm) {
-#pragma unroll
-								for (int k = 0; k < T; ++k) fpm[k] = slots[f.fpm_off + k * 64];
-							}
-							if (has_pm) {
-#pragma unroll
-								for (int k = 0; k < T; ++k) ph[k] += pm_offset32(true, true, pm[k], fpm[k], fv[k]);
-							} else {
-#pragma unroll
-								for (int k = 0; k < T; ++k) ph[k] += pm_offset32(false, true, 0.f, fpm[k], fv[k]);
-							}
+							for (int k = 0; k < T; ++k) ph[k] += pm_offset32(false, true, 0.f, blk[k], fv[k]);
 						}
 						if (f.tab >= 0) {
 							const uint32_t ltab = tabs + (uint32_t)f.tab * FkTab<WIDE>::BYTES;
@@ -246,11 +251,11 @@
 					const bool has_pm = f.pm_off != ~0u, has_fpm = f.fpm_off != ~0u;
 #pragma unroll
 					for (int k = 0; k < T; ++k) {
-						unsigned long long cp = cp0 + inc64 * (unsigned long long)(long long)(t0 + k);
+						unsigned long long cp = cp0 + inc64 * (unsigned long long)(long long)(t0s + k);
 						if (has_pm || has_fpm)
 							cp += (unsigned long long)pm_offset(has_pm, has_fpm,
-									has_pm ? slots[f.pm_off + k * 64] : 0.f,
-									has_fpm ? slots[f.fpm_off + k * 64] : 0.f, f.fc, phase_scale);
+									has_pm ? blk[k] : 0.f,
+									has_fpm ? blk[k] : 0.f, f.fc, phase_scale);
 						uint32_t cyc;
 						float phf;
 						ras_split(cp, cyc, phf);
@@ -261,7 +266,7 @@
 					const uint32_t n0 = f.phase0;
 #pragma unroll
 					for (int k = 0; k < T; ++k) {
-						const uint32_t n = n0 + (uint32_t)(t0 + k);
+						const uint32_t n = n0 + (uint32_t)(t0s + k);
 						if (nz == NZ_vi) {
 							uint32_t s1 = ranfast32(n);
 							uint32_t s0 = ranfast32(n - 1);
@@ -282,22 +287,18 @@
 				float r[T];
 				if (f.amp_off != ~0u) {
 #pragma unroll
-					for (int k = 0; k < T; ++k) r[k] = slots[f.amp_off + k * 64];
+					for (int k = 0; k < T; ++k) r[k] = blk[k];
 				} else if (f.ramp & 1) { /* amplitude ramp in progress, sau/line.c:65-281 */
 					const FastLine fl = load_line_uniform(flines + si);
 #pragma unroll
-					for (int k = 0; k < T; ++k) r[k] = fast_line_value(fl, t0 + k);
+					for (int k = 0; k < T; ++k) r[k] = fast_line_value(fl, t0s + k);
 				} else {
 #pragma unroll
 					for (int k = 0; k < T; ++k) r[k] = f.ac;
 				}
 				if (layer) {
 #pragma unroll
-					for (int k = 0; k < T; ++k)
-						r[k] = mix_combine(slots[f.out_off + k * 64], s[k], r[k], wave_env, true);
-				} else if (wave_env) {
-#pragma unroll
-					for (int k = 0; k < T; ++k) r[k] = mix_combine(0.f, s[k], r[k], true, false);
+					for (int k = 0; k < T; ++k) r[k] = mix_combine(blk[k], s[k], r[k], false, true);
 				} else {
 #pragma unroll
 					for (int k = 0; k < T; ++k) r[k] = s[k] * r[k];
@@ -306,7 +307,7 @@
 					store_row(vrow, r, true);
 				} else {
 #pragma unroll
-					for (int k = 0; k < T; ++k) slots[f.out_off + k * 64] = r[k];
+					for (int k = 0; k < T; ++k) blk[k] = r[k];
 				}
 			} else if (kind == ST_LINE) {
 				/* held line: v0 (sau/line.c:435-442) */
@@ -316,27 +317,17 @@
 					fl.sw = sweep_setup(LN_sah, 0.f, 0.f, 0, 1);
 					if (f.ramp & 1) fl = load_line_uniform(flines + si);
 #pragma unroll
-					for (int k = 0; k < T; ++k) slots[f.out_off + k * 64] = fast_line_value(fl, t0 + k);
+					for (int k = 0; k < T; ++k) blk[k] = fast_line_value(fl, t0s + k);
 				} else {
 #pragma unroll
-					for (int k = 0; k < T; ++k) slots[f.out_off + k * 64] = f.ac;
+					for (int k = 0; k < T; ++k) blk[k] = f.ac;
 				}
-			} else if (kind == ST_LERP) { /* generator.c:466-467 */
-				const bool end_const = f.aux_off == ~0u;
-#pragma unroll
-				for (int k = 0; k < T; ++k) {
-					float pv = slots[f.out_off + k * 64];
-					pv += ((end_const ? f.fc : slots[f.aux_off + k * 64]) - pv) * slots[f.pm_off + k * 64];
-					slots[f.out_off + k * 64] = pv;
-				}
-			} else if (kind == ST_VOICE) { /* generator.c:749-788 with pan modulators */
-				float x[T];
-#pragma unroll
-				for (int k = 0; k < T; ++k) x[k] = slots[f.out_off + k * 64];
-				store_row(vrow, x, true);
+			} else if (kind == ST_VOICE) { /* generator.c:749-788, the pan one value */
+				store_row(vrow, blk, true);
 				if (prow) {
+					float x[T];
 #pragma unroll
-					for (int k = 0; k < T; ++k) x[k] = f.pm_off != ~0u ? slots[f.pm_off + k * 64] : f.pan;
+					for (int k = 0; k < T; ++k) x[k] = f.pan;
 					store_row(prow, x, false);
 				}
 			}

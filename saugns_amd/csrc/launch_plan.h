@@ -464,6 +464,11 @@ struct FastPlan {
 		return tabs.n * (size_t)(wide ? FAST_TAB_BYTES_WIDE : FAST_TAB_BYTES) + 16 * buf_area(cf ? n_fast_cf : n_fast, r, fmax_steps) +
 			(build == 2 ? LOOK_LDS_BYTES : 0);
 	}
+	/* LDS bytes of the inner launch. Row-major: the 12-row wide build's. Lane-major: the table blocks and nothing else -- its block
+	 * buffer is registers (k_fast_group_lm.h), and fast_kernel's task loop and mixing tail keep nothing in LDS */
+	size_t inner_lds() const {
+		return inner == INNER_LANE_MAJOR ? tabs.n * (size_t)FAST_TAB_BYTES_WIDE : launch_lds(0, rows, true);
+	}
 };
 
 /* Rows per wave and pass: as many as LDS holds beside one wave table (more rows amortise the per-step work: 8 rows measured
@@ -654,8 +659,11 @@ inline void plan_closed_form(FastPlan &p, const SegmentDesc &seg, const Tuning &
 	/* BASELINE config 3's build in two launches (k_fast_voice.h: INNER): every voice's first and last row group by the plain
 	 * build, a wave per group; then the groups between by the build that holds only the form without in-segment masks */
 	/* (the groups in the lane-major form, k_fast_group_lm.h; SAU_AMD_NO_LANEMAJOR: the row-major one) */
+	/* (... which keeps the block buffer in registers: only where the launch's voices share exactly ONE buffer. 12 rows of buffers
+	 * fit beside a 64 KiB table only at one buffer on a 160 KiB LDS, so the rule costs no segment the form; it is what the
+	 * kernel relies on, said here and not left to the sizes) */
 	if (tun.inner && p.main_build == 0 && p.wide_cf && p.rows == 12 && p.tasks.dyn_chunks >= 3)
-		p.inner = tun.lanemajor ? INNER_LANE_MAJOR : INNER_ROW_MAJOR;
+		p.inner = tun.lanemajor && p.n_fast == 1 ? INNER_LANE_MAJOR : INNER_ROW_MAJOR;
 	p.grid_edge = wave_grid(2ull * seg.n_voices, dev.fk_grid); /* (two tasks a voice: its first group, its last) */
 }
 
