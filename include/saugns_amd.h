@@ -237,6 +237,54 @@ SAU_AMD_API bool sauAmd_Batch_measure_rows(sauAmdBatch *b, const void *rows, siz
 SAU_AMD_API bool sauAmd_render_file_normalized(const sauProgram *prg, uint32_t srate, const char *path, int format,
 		int channels, float target_peak, uint64_t *frames_out, sauAmdLevels *levels_out);
 
+/* ---- Oversampled rendering ---------------------------------------------------
+ * The reference's oscillators are not band-limited: PM chains, `sqr`/`saw` tables, FM and noise put energy above the
+ * Nyquist frequency, and a render folds it back into the audible band. The cure is to render at `factor` times the wanted
+ * rate and low-pass down to it -- here on the device, on the float rows of sauAmd_Batch_run_f32, without fetching them.
+ *
+ * The filter, for factor K in {2, 4, 8}: half-length H = 32 output frames, L = 2 * H * K + 1 taps (129, 257, 513), centre
+ * C = H * K; g[n] = sinc((n - C) / K) * I0(beta * sqrt(1 - ((n - C) / C)^2)) / I0(beta) for n = 0 .. C, beta = 10.06,
+ * sinc(t) = sin(pi t) / (pi t), I0 by its power series; g[L - 1 - n] = g[n] mirrored; h = g / sum(g). In f64, on the host.
+ * Passband to 0.45 of the output rate within 2e-4 dB, -6.02 dB at half of it, stopband from 0.55 of it below -98 dB.
+ *
+ * The arithmetic is reproducible bit for bit. With x[i] the float sample of high-rate frame i of a stream and channel,
+ * counted from the start of the decimated sequence, +0.0f for i < 0 and for every frame at or behind the stream's end:
+ *   acc = +0.0 (f64); for j = 0 .. L-1 ascending: acc = acc + h[j] * (double)x[m * K - j]; y[m] = (float)acc
+ * -- one accumulator per output sample, a multiply and then an add, no sum split or reordered. The filter is causal: the
+ * output lags the input by exactly H output frames. */
+
+/* sauAmd_decimator_taps: L, and the L taps h in out[] when cap >= L (nothing is written when cap < L; out may then be
+ * NULL); 0 for a factor other than 2, 4, 8. sauAmd_decimator_latency: H = 32 output frames; 0 for such a factor. */
+SAU_AMD_API size_t sauAmd_decimator_taps(int factor, double *out, size_t cap);
+SAU_AMD_API size_t sauAmd_decimator_latency(int factor);
+/* A float run of buf_len * factor frames, decimated on the device to buf_len frames per stream. The batch was created at
+ * srate_out * factor: a run advances every stream by buf_len * factor frames of the batch's rate, and
+ * sauAmd_Batch_set_call_len stays in those high-rate frames. more[i] is the float run's; out_len[i] =
+ * ceil(out_len_hi[i] / factor) of the float run's out_len_hi. Every stream's decimated row -- and bufs[i] when given (bufs
+ * may be NULL) -- holds buf_len valid frames, the input zero-extended behind the stream's end: a stream's tail therefore
+ * appears in later runs, and a run after every stream has ended renders nothing and still delivers buf_len frames of it.
+ * The history belongs to a sequence of decimated runs with the same (factor, stereo): a decimated run that follows a
+ * sauAmd_Batch_run, a sauAmd_Batch_run_f32, or a decimated run with another (factor, stereo) starts from zero history.
+ * False (sauAmd_last_error) with "bad argument" on a factor other than 2, 4, 8 or buf_len * factor beyond 32 bits, and on a
+ * backend without a decimator or float output; nothing is rendered then and the batch stands where it stood. A batch that
+ * never makes a decimated run does nothing for it. */
+SAU_AMD_API bool sauAmd_Batch_run_decimated_f32(sauAmdBatch *b, int factor, float *const *bufs, size_t buf_len,
+		bool stereo, bool *more, size_t *out_len);
+/* Device address of stream i's decimated float row of the last decimated run (NULL before one), and the bytes between the
+ * rows of consecutive streams. The rows are 16-byte aligned and the pitch is a multiple of 256, so
+ * sauAmd_Batch_measure_rows measures them as they are. Valid until the batch's next decimated run (call sauAmd_Batch_sync
+ * first: the run is asynchronous). */
+SAU_AMD_API const float *sauAmd_Batch_device_decimated_f32(sauAmdBatch *b, size_t stream);
+SAU_AMD_API size_t sauAmd_Batch_device_decimated_pitch(sauAmdBatch *b);
+/* sauAmd_render_file, rendered at srate * factor and decimated on the device: the high-rate signal is exactly what
+ * sauAmd_render_file(prg, srate * factor, ..) writes (the same call lattice), the filter's delay of H frames is dropped and
+ * its tail kept, so the file holds exactly ceil(N / factor) frames for N high-rate frames, time-aligned with them, and its
+ * header carries srate. format and channels as for sauAmd_render_file; the int16 formats are pcm16 of the f64 sum rounded
+ * to float, formed (and for AU byte-swapped) on the device. False (sauAmd_last_error), before any file is created, on a
+ * bad argument -- another factor, srate * factor beyond 32 bits -- or a backend without float output or a decimator. */
+SAU_AMD_API bool sauAmd_render_file_oversampled(const sauProgram *prg, uint32_t srate, int factor, const char *path,
+		int format, int channels, uint64_t *frames_out);
+
 #ifdef __cplusplus
 }
 #endif

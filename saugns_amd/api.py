@@ -162,6 +162,21 @@ def _declare(L):
         L.sauAmd_render_file_normalized.restype = C.c_bool
         L.sauAmd_render_file_normalized.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_int, C.c_int, C.c_float,
                                                     C.POINTER(C.c_uint64), C.POINTER(Levels)]
+    if hasattr(L, "sauAmd_Batch_run_decimated_f32"):  # oversampled rendering (SAU_AMD_LIB may name an older build)
+        L.sauAmd_Batch_run_decimated_f32.restype = C.c_bool
+        L.sauAmd_Batch_run_decimated_f32.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_size_t, C.c_bool,
+                                                     C.POINTER(C.c_bool), C.POINTER(C.c_size_t)]
+        L.sauAmd_Batch_device_decimated_f32.restype = C.c_void_p
+        L.sauAmd_Batch_device_decimated_f32.argtypes = [C.c_void_p, C.c_size_t]
+        L.sauAmd_Batch_device_decimated_pitch.restype = C.c_size_t
+        L.sauAmd_Batch_device_decimated_pitch.argtypes = [C.c_void_p]
+        L.sauAmd_decimator_taps.restype = C.c_size_t
+        L.sauAmd_decimator_taps.argtypes = [C.c_int, C.POINTER(C.c_double), C.c_size_t]
+        L.sauAmd_decimator_latency.restype = C.c_size_t
+        L.sauAmd_decimator_latency.argtypes = [C.c_int]
+        L.sauAmd_render_file_oversampled.restype = C.c_bool
+        L.sauAmd_render_file_oversampled.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_char_p, C.c_int, C.c_int,
+                                                     C.POINTER(C.c_uint64)]
     L.sauAmd_set_piluts.argtypes = [C.c_void_p]
     L.sauAmd_get_piluts.restype = C.POINTER(C.c_float)
     L.sauAmd_last_error.restype = C.c_char_p
@@ -307,6 +322,57 @@ def render_file_normalized(program, srate, path, fmt=SNDFILE_WAV, channels=1, ta
     return n.value, lv
 
 
+_oversample_hooks = None
+
+
+def use_oversample_hooks(path):
+    """tests/ only: load the library that runs the oversampled file writer over an injected backend
+    (tests/hooks_oversample: the product's object files + sauAmd_render_file_oversampled_with_backend)."""
+    global _oversample_hooks
+    if _oversample_hooks is None:
+        L = _declare(C.CDLL(path))
+        L.sauAmd_render_file_oversampled_with_backend.restype = C.c_bool
+        L.sauAmd_render_file_oversampled_with_backend.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_char_p, C.c_int, C.c_int,
+                                                                  C.c_void_p, C.POINTER(C.c_uint64)]
+        _oversample_hooks = L
+    return _oversample_hooks
+
+
+def render_file_oversampled(program, srate, factor, path, fmt=SNDFILE_WAV, channels=1, backend=None):
+    """sauAmd_render_file_oversampled: render a whole program at ``srate * factor`` (factor 2, 4 or 8), decimate it on the
+    device and write it at ``srate`` -> frames written: ceil(N / factor) for N high-rate frames, time-aligned with them.
+    ``backend`` (tests): a sauengine::Backend* to run the writer over, without a GPU."""
+    n = C.c_uint64()
+    if backend is None:
+        L = _used(lib())
+        ok = L.sauAmd_render_file_oversampled(program.ptr, srate, factor, os.fsencode(path), fmt, channels, C.byref(n))
+    else:
+        if _oversample_hooks is None:
+            raise RuntimeError("the oversample-hook library is not loaded (use_oversample_hooks)")
+        L = _used(_oversample_hooks)
+        ok = L.sauAmd_render_file_oversampled_with_backend(program.ptr, srate, factor, os.fsencode(path), fmt, channels,
+                                                           backend, C.byref(n))
+    if not ok:
+        raise RuntimeError("sauAmd_render_file_oversampled failed: " + last_error(L))
+    return n.value
+
+
+def decimator_taps(factor):
+    """sauAmd_decimator_taps: the decimating filter's L = 64 * factor + 1 taps as a float64 array (empty for a factor
+    other than 2, 4, 8) -- the one definition the device, the file writer and the tests share."""
+    L = lib()
+    n = int(L.sauAmd_decimator_taps(int(factor), None, 0))
+    out = np.zeros(n, np.float64)
+    if n:
+        L.sauAmd_decimator_taps(int(factor), out.ctypes.data_as(C.POINTER(C.c_double)), n)
+    return out
+
+
+def decimator_latency(factor):
+    """sauAmd_decimator_latency: the filter's delay in output frames (32), 0 for a factor other than 2, 4, 8."""
+    return int(lib().sauAmd_decimator_latency(int(factor)))
+
+
 def get_piluts():
     p = lib().sauAmd_get_piluts()
     return np.ctypeslib.as_array(p, shape=(12 * 2048,)).reshape(12, 2048).copy()
@@ -441,6 +507,32 @@ class Batch:
         if not ok:
             raise RuntimeError("sauAmd_Batch_run_f32 failed: " + last_error(self._L))
         return pcm, [bool(m) for m in more], [int(x) for x in lens]
+
+    def run_decimated(self, factor, buf_len, stereo=False, fetch=True):
+        """sauAmd_Batch_run_decimated_f32: a float run of buf_len * factor frames (the batch was created at the output rate
+        times `factor`), decimated on the device to buf_len frames per stream
+        -> (float32 [n, buf_len*ch] or None, more[n], out_len[n]); out_len = ceil(the float run's / factor). Every row holds
+        buf_len valid frames, a stream's filter tail included; the rows stay on the device (device_decimated_f32)."""
+        ch = 2 if stereo else 1
+        more = (C.c_bool * self.n)()
+        lens = (C.c_size_t * self.n)()
+        if fetch:
+            pcm = np.zeros((self.n, buf_len * ch), np.float32)
+            ptrs = (C.c_void_p * self.n)(*[pcm[i].ctypes.data for i in range(self.n)])
+        else:
+            pcm, ptrs = None, None
+        ok = _used(self._L).sauAmd_Batch_run_decimated_f32(self._b, int(factor), ptrs, buf_len, stereo, more, lens)
+        if not ok:
+            raise RuntimeError("sauAmd_Batch_run_decimated_f32 failed: " + last_error(self._L))
+        return pcm, [bool(m) for m in more], [int(x) for x in lens]
+
+    def device_decimated_f32(self, stream):
+        """Device address of the stream's decimated float32 row of the last decimated run; None before one."""
+        return self._L.sauAmd_Batch_device_decimated_f32(self._b, stream)
+
+    def device_decimated_pitch(self):
+        """Bytes between the decimated rows of consecutive streams (a multiple of 256)."""
+        return int(self._L.sauAmd_Batch_device_decimated_pitch(self._b))
 
     def render(self, stereo=False, chunk=11289, max_frames=0):
         """Render every stream to its end -> list of int16 arrays."""

@@ -433,6 +433,29 @@ extern "C" bool sauAmd_Batch_measure_rows(sauAmdBatch *b, const void *rows, size
 	return false;
 }
 
+extern "C" bool sauAmd_Batch_run_decimated_f32(sauAmdBatch *b, int factor, float *const *bufs, size_t buf_len,
+		bool stereo, bool *more, size_t *out_len) {
+	std::string err;
+	try {
+		if (b->engine->run_decimated((void *const *)bufs, sauengine::SF_F32, false, factor, buf_len, stereo, more, out_len, err)) return true;
+	} catch (const std::exception &ex) { /* (nothing C++ crosses the C ABI) */
+		err = std::string("internal error: ") + ex.what();
+	}
+	report("batch", err);
+	return false;
+}
+
+extern "C" const float *sauAmd_Batch_device_decimated_f32(sauAmdBatch *b, size_t stream) {
+	return b->engine->backend()->device_decimated_f32((uint32_t)stream);
+}
+
+extern "C" size_t sauAmd_Batch_device_decimated_pitch(sauAmdBatch *b) {
+	return b->engine->backend()->device_decimated_pitch();
+}
+
+extern "C" size_t sauAmd_decimator_taps(int factor, double *out, size_t cap) { return sauengine::decimator_taps(factor, out, cap); }
+extern "C" size_t sauAmd_decimator_latency(int factor) { return sauengine::decimator_latency(factor); }
+
 extern "C" bool sauAmd_Batch_sync(sauAmdBatch *b) {
 	std::string err;
 	if (!b->engine->backend()->sync(err)) { report("batch", err); return false; }

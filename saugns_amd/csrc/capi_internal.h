@@ -24,6 +24,10 @@ bool render_file(const sauProgram *prg, uint32_t srate, const char *path, int fo
 bool render_file_normalized(const sauProgram *prg, uint32_t srate, const char *path, int format, int channels, float target_peak,
 		const std::function<sauengine::Backend *(std::string &)> &make_backend, uint64_t *frames_out, sauAmdLevels *levels_out,
 		std::string &err);
+/* sauAmd_render_file_oversampled's body (sndout.cpp). make_backend is asked once, after the arguments have been looked at
+ * (NULL with err: the render cannot run); the engine made over what it returns owns it. */
+bool render_file_oversampled(const sauProgram *prg, uint32_t srate, int factor, const char *path, int format, int channels,
+		const std::function<sauengine::Backend *(std::string &)> &make_backend, uint64_t *frames_out, std::string &err);
 /* the thread's sauAmd_last_error text (capi.cpp), with the line on stderr */
 void set_last_error(const char *where, const std::string &err);
 } /* namespace sauamd_internal */

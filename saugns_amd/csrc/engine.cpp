@@ -614,6 +614,8 @@ bool Engine::restore(const Snapshot &s, int slot, std::string &err) {
 	plans_dirty_ = true;
 	frames_done_ = s.frames_done;
 	call_len_ = s.call_len; lat_call_ = s.lat_call; call_phase_ = s.call_phase;
+	all_ended_ = false;
+	decim_factor_ = 0; /* (the history is not part of a snapshot) */
 	return backend_->load_state(slot, err);
 }
 
@@ -625,6 +627,7 @@ bool Engine::run(void *const *host_bufs, SampleFormat format, size_t buf_len, bo
 	if (metering_ && pcm_swap_) { err = "level metering reads samples in host byte order, not byte-swapped ones"; return false; }
 	/* the run's format, ahead of anything that moves: a backend without float output refuses here */
 	if (!set_format(format, err)) return false;
+	if (!in_decimated_) decim_factor_ = 0; /* (a run of any other kind ends a sequence of decimated runs) */
 	const uint32_t total = (uint32_t)buf_len;
 	if (total > reserved_frames_ || (stereo && !reserved_stereo_)) {
 		uint32_t want = std::max(total, reserved_frames_);
@@ -722,6 +725,7 @@ bool Engine::run(void *const *host_bufs, SampleFormat format, size_t buf_len, bo
 	frames_done_ += total;
 	call_phase_ = (uint32_t)(((uint64_t)call_phase_ + total) % lat_call_);
 	if (metering_) meter_frames_.assign(streams_.size(), 0);
+	all_ended_ = true;
 	for (size_t s = 0; s < streams_.size(); ++s) {
 		Stream &st = streams_[s];
 		st.call_gen += st.part_gen;
@@ -737,6 +741,7 @@ bool Engine::run(void *const *host_bufs, SampleFormat format, size_t buf_len, bo
 		}
 		if (more) more[s] = !ended;
 		if (out_len) out_len[s] = ended ? st.call_gen : buf_len;
+		if (!ended) all_ended_ = false;
 		if (metering_) meter_frames_[s] = (uint32_t)(ended ? st.call_gen : buf_len);
 	}
 	/* the meter reads what the mixers wrote, where it is: behind them on the backend's stream, ahead of any fetch */
@@ -747,6 +752,50 @@ bool Engine::run(void *const *host_bufs, SampleFormat format, size_t buf_len, bo
 			                     : !backend_->fetch_pcm((uint32_t)s, (int16_t *)host_bufs[s], total, stereo, err))
 				return false;
 		}
+	}
+	return true;
+}
+
+bool Engine::begin_decimated(int factor, bool stereo, std::string &err) {
+	if (!decimator_latency(factor)) { err = "bad argument"; return false; }
+	if (!backend_->begin_decimation(factor, stereo, err)) return false;
+	decim_factor_ = factor;
+	decim_stereo_ = stereo;
+	return true;
+}
+
+bool Engine::run_decimated(void *const *host_bufs, SampleFormat out_fmt, bool swap_bytes, int factor, size_t buf_len, bool stereo,
+		bool *more, size_t *out_len, std::string &err) {
+	if (!decimator_latency(factor) || buf_len > UINT32_MAX / (size_t)factor || (out_fmt == SF_F32 && swap_bytes)) {
+		err = "bad argument";
+		return false;
+	}
+	/* the decimator first: a backend without one refuses here, ahead of anything that moves */
+	if ((decim_factor_ != factor || decim_stereo_ != stereo) && !begin_decimated(factor, stereo, err)) return false;
+	const size_t n = streams_.size();
+	decim_frames_.assign(n, 0);
+	if (all_ended_) { /* nothing left to render: the rows are not read, the history gives the tail */
+		for (size_t s = 0; s < n; ++s) {
+			if (more) more[s] = false;
+			if (out_len) out_len[s] = 0;
+		}
+	} else {
+		std::vector<size_t> len_hi(n, 0);
+		in_decimated_ = true;
+		const bool ok = run(nullptr, SF_F32, buf_len * (size_t)factor, stereo, more, len_hi.data(), err);
+		in_decimated_ = false;
+		if (!ok) { decim_factor_ = 0; return false; }
+		for (size_t s = 0; s < n; ++s) {
+			decim_frames_[s] = (uint32_t)len_hi[s];
+			if (out_len) out_len[s] = (len_hi[s] + (size_t)factor - 1) / (size_t)factor;
+		}
+	}
+	if (!backend_->decimate(decim_frames_.data(), (uint32_t)buf_len, factor, stereo, out_fmt, swap_bytes, err)) { decim_factor_ = 0; return false; }
+	if (host_bufs) {
+		const size_t bytes = buf_len * (stereo ? 2 : 1) * (out_fmt == SF_F32 ? sizeof(float) : sizeof(int16_t));
+		for (size_t s = 0; s < n; ++s)
+			if (host_bufs[s] && bytes && !(backend_->fetch_decimated_async((uint32_t)s, host_bufs[s], bytes, 0, err) && backend_->wait_fetch(0, err)))
+				return false;
 	}
 	return true;
 }

@@ -38,6 +38,13 @@ struct Levels {
 };
 static_assert(sizeof(Levels) == 80, "sauAmdLevels");
 
+/* The decimator's filter (tables.cpp; include/saugns_amd.h: sauAmd_decimator_taps). Factors 2, 4 and 8; half-length
+ * DECIM_HALF output frames, which is also the filter's latency; L = 2 * DECIM_HALF * factor + 1 taps in f64.
+ * decimator_taps returns L and writes the taps when cap >= L (nothing otherwise); both return 0 for another factor. */
+constexpr size_t DECIM_HALF = 32;
+size_t decimator_taps(int factor, double *out, size_t cap);
+size_t decimator_latency(int factor);
+
 /* Everything the backend needs to render one segment (no events inside). */
 struct SegmentDesc {
 	uint32_t len;             /* frames */
@@ -200,6 +207,30 @@ public:
 	virtual bool fetch_requant_async(void *dst, size_t bytes, int slot, std::string &err) {
 		(void)dst; (void)bytes; (void)slot; err = "this backend has no level metering"; return false;
 	}
+	/* Decimation of float runs rendered at `factor` times the wanted rate (include/saugns_amd.h: sauAmd_Batch_run_decimated_f32),
+	 * where the samples are. A backend without it refuses -- these defaults -- and nothing changes. begin_decimation: a
+	 * sequence of decimated runs with this factor and channel layout starts: every stream's history is zero. */
+	virtual bool begin_decimation(int factor, bool stereo, std::string &err) {
+		(void)factor; (void)stereo; err = "this backend has no decimator"; return false;
+	}
+	/* buf_len output frames of every stream from the float run just rendered (buf_len * factor frames, of which the first
+	 * frames_hi[s] are stream s's; the rest, whatever the rows hold there, count as +0) and the stream's history, into device
+	 * rows of the backend's own -- float32, or int16 (pcm16 of the sum; `swap_bytes`: big-endian) -- and the history moves on:
+	 * device work on the backend's stream, behind the run's mixers. frames_hi all 0: the rows are not read. */
+	virtual bool decimate(const uint32_t *frames_hi, uint32_t buf_len, int factor, bool stereo, SampleFormat out_fmt, bool swap_bytes,
+			std::string &err) {
+		(void)frames_hi; (void)buf_len; (void)factor; (void)stereo; (void)out_fmt; (void)swap_bytes;
+		err = "this backend has no decimator"; return false;
+	}
+	/* queue the copy of the first `bytes` bytes of stream s's decimated row out, like fetch_pcm_async (`slot`, wait_fetch);
+	 * into memory that is not from alloc_host() the copy has finished on return */
+	virtual bool fetch_decimated_async(uint32_t stream, void *dst, size_t bytes, int slot, std::string &err) {
+		(void)stream; (void)dst; (void)bytes; (void)slot; err = "this backend has no decimator"; return false;
+	}
+	/* device address of stream s's decimated float row of the last decimated run (NULL: none, or int16 rows), and the bytes
+	 * between the rows of consecutive streams (a multiple of 256; 0: none) */
+	virtual const float *device_decimated_f32(uint32_t stream) { (void)stream; return nullptr; }
+	virtual size_t device_decimated_pitch() { return 0; }
 };
 
 /* ---- plan compiler (plan.cpp) -------------------------------------------- */
@@ -290,6 +321,20 @@ public:
 		format_ = format;
 		return true;
 	}
+
+	/* A float run of buf_len * factor frames, decimated on the device to buf_len frames per stream (include/saugns_amd.h:
+	 * sauAmd_Batch_run_decimated_f32; the engine was created at the output rate times `factor`). The decimated rows stay on
+	 * the device (Backend::device_decimated_f32, fetch_decimated_async) -- float32, or with out_fmt SF_S16 the kernels' own
+	 * pcm16, byte-swapped on request (the file writer) -- and host_bufs[s], when given, gets stream s's buf_len frames.
+	 * more[s] is the float run's; out_len[s] = ceil(the float run's / factor). The history belongs to a sequence of decimated
+	 * runs with one (factor, stereo): any other run in between, or another pair, starts it from zero. False with "bad
+	 * argument" on another factor or buf_len * factor beyond 32 bits, and with the backend's text on one without a decimator
+	 * or float output; nothing is rendered then and the batch stands where it stood. Once every stream has ended nothing is
+	 * rendered; the rows then hold the filter's tail. */
+	bool run_decimated(void *const *host_bufs, SampleFormat out_fmt, bool swap_bytes, int factor, size_t buf_len, bool stereo,
+			bool *more, size_t *out_len, std::string &err);
+	/* start such a sequence now (run_decimated does it itself; the file writer asks before it opens a file) */
+	bool begin_decimated(int factor, bool stereo, std::string &err);
 
 	/* Level metering (include/saugns_amd.h: sauAmd_Batch_set_metering). On: every run ends with the backend measuring each
 	 * stream's frames [0, out_len) of that run, in the run's format, into the stream's record. Off (the default): run() makes
@@ -397,6 +442,11 @@ private:
 	bool metering_ = false;          /* set_metering() */
 	bool metered_ = false;           /* ... has ever been on: the backend has records */
 	std::vector<uint32_t> meter_frames_; /* per stream: out_len of the run at hand */
+	int decim_factor_ = 0;           /* run_decimated(): the sequence at hand (0: none -- any other run ends it) */
+	bool decim_stereo_ = false;
+	bool in_decimated_ = false;      /* run() is run_decimated()'s own */
+	bool all_ended_ = false;         /* the last run left no stream with anything to render */
+	std::vector<uint32_t> decim_frames_; /* per stream: the float run's out_len */
 	bool plans_dirty_ = true;
 	/* concatenated plans as uploaded; per (stream,voice) offsets */
 	std::vector<Step> all_steps_;

@@ -10,6 +10,7 @@
  *   k_chain.h       chain_kernel
  *   k_finish.h      finalize_kernel, mix_kernel, mix_few_kernel (int16 and float32 forms), event_kernel
  *   k_levels.h      levels_kernel, levels_finish_kernel (level metering), requant_kernel (the normalised file writer)
+ *   k_decimate.h    decimate_kernel, decimate_carry_kernel (oversampled rendering: the decimating FIR and its history)
  *   launch_plan.h   (plain C++, no HIP) the tuning switches and every decision about a segment's launches: rows per pass, LDS
  *                   budgets, builds, grids, tasks, chain chunks, the mixer -- a plan per segment, testable without a GPU
  *   (this file)     buffer and stream pools, table sets, the kernel lookup, HipBackendImpl: render() carries a plan out,
@@ -70,6 +71,7 @@ using namespace sauplan;
 #include "k_chain.h"
 #include "k_finish.h"
 #include "k_levels.h"
+#include "k_decimate.h"
 static_assert(MISC_BYTES == sizeof(Misc), "launch_plan.h plans the block loop's LDS with this size");
 
 /* ------------------------------------------------------------------------ */
@@ -1378,6 +1380,89 @@ public:
 		return true;
 	}
 
+	/* ---- the decimator (k_decimate.h; the geometry is launch_plan.h's plan_decimate) ---- */
+	bool begin_decimation(int factor, bool stereo, std::string &err) override {
+		use_device();
+		const DecimPlan plan = plan_decimate(0, factor, stereo ? 2 : 1, cfg_.n_streams, sizeof(float));
+		if (!plan.ok) { err = "bad argument"; return false; }
+		const size_t hist = (size_t)cfg_.n_streams * plan.hist_floats;
+		if (!decim_hist_.ensure(hist, err) || !decim_taps_.ensure(plan.taps, err) || !decim_frames_.ensure(cfg_.n_streams, err)) return false;
+		HIP_OK(hipMemsetAsync(decim_hist_.p, 0, hist * sizeof(float), stream_)); /* (behind the last sequence's kernels on the one stream) */
+		std::vector<double> h(plan.taps);
+		if (sauengine::decimator_taps(factor, h.data(), h.size()) != plan.taps) { err = "bad argument"; return false; }
+		if (!send(decim_taps_.p, h.data(), h.size() * sizeof(double), err)) return false;
+		decim_factor_ = factor; decim_stereo_ = stereo;
+		return true;
+	}
+	template <int K, typename OutT> void launch_decimate(const DecimPlan &plan, const DecimParams &dp, bool stereo) {
+		const dim3 grid(plan.tiles, plan.streams), block(DECIM_THREADS);
+		if (stereo) hipLaunchKernelGGL((decimate_kernel<K, OutT, 2>), grid, block, 0, stream_, dp, (const double *)decim_taps_.p);
+		else hipLaunchKernelGGL((decimate_kernel<K, OutT, 1>), grid, block, 0, stream_, dp, (const double *)decim_taps_.p);
+	}
+	bool decimate(const uint32_t *frames_hi, uint32_t buf_len, int factor, bool stereo, sauengine::SampleFormat out_fmt, bool swap_bytes,
+			std::string &err) override {
+		use_device();
+		if (!decim_hist_.p || factor != decim_factor_ || stereo != decim_stereo_) { err = "decimation has not begun"; return false; }
+		const bool f32 = out_fmt == sauengine::SF_F32;
+		if (f32 && swap_bytes) { err = "float32 samples are not byte-swapped"; return false; }
+		const uint32_t ch = stereo ? 2 : 1;
+		const DecimPlan plan = plan_decimate(buf_len, factor, ch, cfg_.n_streams, f32 ? sizeof(float) : sizeof(int16_t));
+		if (!plan.ok) { err = "bad argument"; return false; }
+		const unsigned long long n_hi = (unsigned long long)buf_len * (unsigned)factor;
+		bool any = false;
+		for (uint32_t s = 0; s < cfg_.n_streams; ++s) {
+			if (frames_hi[s] > n_hi || frames_hi[s] > row_stride_) { err = "frames beyond the streams' rows"; return false; }
+			any = any || frames_hi[s] != 0;
+		}
+		if (any && (!pcm_f32_ || !pcm_.p)) { err = "the last run's samples are not float32"; return false; }
+		decim_out_f32_ = f32; decim_out_pitch_ = plan.out_pitch; decim_out_bytes_ = (size_t)buf_len * ch * (f32 ? sizeof(float) : sizeof(int16_t));
+		if (!plan.tiles) return true; /* no output frame: nothing to launch, and the history stands */
+		if (!decim_out_.ensure(plan.out_pitch * cfg_.n_streams, err)) return false;
+		if (!send(decim_frames_.p, frames_hi, (size_t)cfg_.n_streams * sizeof(uint32_t), err)) return false;
+		DecimParams dp;
+		memset((void *)&dp, 0, sizeof dp);
+		dp.rows = (const float *)pcm_.p; dp.row_pitch = pcm_f32_ ? pcm_pitch() : 0; /* (rows start on 256 bytes: reserve_frames) */
+		dp.frames = decim_frames_.p; dp.hist = decim_hist_.p;
+		dp.out = decim_out_.p; dp.out_pitch = plan.out_pitch;
+		dp.buf_len = buf_len; dp.swap_bytes = swap_bytes ? 1 : 0;
+		switch (factor * 2 + (f32 ? 1 : 0)) {
+		case 5: launch_decimate<2, float>(plan, dp, stereo); break;
+		case 4: launch_decimate<2, int16_t>(plan, dp, stereo); break;
+		case 9: launch_decimate<4, float>(plan, dp, stereo); break;
+		case 8: launch_decimate<4, int16_t>(plan, dp, stereo); break;
+		case 17: launch_decimate<8, float>(plan, dp, stereo); break;
+		default: launch_decimate<8, int16_t>(plan, dp, stereo); break;
+		}
+		HIP_OK(hipGetLastError());
+		/* behind decimate_kernel on the one stream: every read of the old history has finished */
+		hipLaunchKernelGGL(decimate_carry_kernel, dim3(plan.streams), dim3(DECIM_CARRY_THREADS), 0, stream_, dp, plan.hist_floats, ch, n_hi);
+		HIP_OK(hipGetLastError());
+		return true;
+	}
+	/* (the next run's decimate_kernel is ordered behind this copy on the one stream) */
+	bool fetch_decimated_async(uint32_t stream, void *dst, size_t bytes, int slot, std::string &err) override {
+		slot &= 3;
+		use_device();
+		if (stream >= cfg_.n_streams || bytes > decim_out_bytes_ || (bytes && !decim_out_.p)) { err = "more bytes than were decimated"; return false; }
+		if (!fetch_ev_[slot]) HIP_OK(hipEventCreateWithFlags(&fetch_ev_[slot], hipEventDisableTiming));
+		if (bytes) {
+			const char *src = (const char *)decim_out_.p + decim_out_pitch_ * stream;
+			if (host_blocks_.count(dst)) HIP_OK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream_));
+			else { /* pageable memory: through the page-locked block, as fetch_pcm goes */
+				if (!h_pcm_.ensure((bytes + 1) / 2, err)) return false;
+				HIP_OK(hipMemcpyAsync(h_pcm_.p, src, bytes, hipMemcpyDeviceToHost, stream_));
+				HIP_OK(hipStreamSynchronize(stream_));
+				memcpy(dst, h_pcm_.p, bytes);
+			}
+		}
+		HIP_OK(hipEventRecord(fetch_ev_[slot], stream_));
+		return true;
+	}
+	const float *device_decimated_f32(uint32_t stream) override {
+		return decim_out_.p && decim_out_f32_ && decim_out_bytes_ && stream < cfg_.n_streams ? (const float *)((const char *)decim_out_.p + decim_out_pitch_ * stream) : nullptr;
+	}
+	size_t device_decimated_pitch() override { return decim_out_.p && decim_out_bytes_ ? decim_out_pitch_ : 0; }
+
 	const int16_t *device_pcm(uint32_t stream) override { return pcm_.p && !pcm_f32_ ? (const int16_t *)pcm_at(stream) : nullptr; }
 	const float *device_pcm_f32(uint32_t stream) override { return pcm_.p && pcm_f32_ ? (const float *)pcm_at(stream) : nullptr; }
 	size_t device_pcm_pitch() override { return pcm_.p ? pcm_pitch() : 0; }
@@ -1599,6 +1684,15 @@ private:
 	DevBuf<LevelsPart> lev_parts_;
 	DevBuf<uint32_t> lev_frames_;
 	DevBuf<unsigned char> requant_;
+	/* the decimator: the streams' histories, the taps of the sequence at hand, a run's frame counts and its output rows -- all
+	 * from the pool, none there until a decimated run asks for them */
+	DevBuf<float> decim_hist_;
+	DevBuf<double> decim_taps_;
+	DevBuf<uint32_t> decim_frames_;
+	DevBuf<unsigned char> decim_out_;
+	int decim_factor_ = 0;
+	bool decim_stereo_ = false, decim_out_f32_ = false;
+	size_t decim_out_pitch_ = 0, decim_out_bytes_ = 0; /* of the last decimated run: between the rows, and of a row's frames */
 	DevBuf<uint32_t> vlists_;   /* [2][n_voices]: analyze_kernel's lists of closed-form and look-back voices (split launches) */
 	/* A chain kernel's workgroup is three waves on a latency-bound recurrence. SAU_AMD_CHAIN_ALONE=1 (a tuning switch): while a
 	 * launch has no more workgroups than the device has CUs, each asks for more than half a CU's LDS and so gets a CU of its own.

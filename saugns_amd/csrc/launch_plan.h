@@ -740,5 +740,44 @@ inline LevelsPlan plan_levels(uint64_t max_frames, uint32_t channels, size_t n_r
 	return p;
 }
 
+/* ---- the decimator (k_decimate.h) ----
+ * A workgroup of decimate_kernel -- one wave -- owns DECIM_TILE consecutive output frames of one stream, both channels of a
+ * stereo row: lane l computes the DECIM_PER_LANE frames l, l + 64, ... of the tile, each channel of each in an f64 chain of
+ * its own (four chains on a mono row, eight on a stereo one). The tile is a constant, as LEVELS_WG_SAMPLES is and never a
+ * function of the device; unlike there no sum is shared between lanes, so it decides speed only, not bits. The tile's input
+ * span in LDS is (DECIM_TILE + 2 * DECIM_HALF) * K frames: 320 * K * channels floats, 20 KiB at K = 8 stereo.
+ * 256 frames: a 10 s render at 44.1 kHz is 1723 workgroups per stream, seven one-wave workgroups per CU. */
+constexpr uint32_t DECIM_THREADS = 64, DECIM_PER_LANE = 4;
+constexpr uint32_t DECIM_TILE = 256;
+static_assert(DECIM_TILE == DECIM_THREADS * DECIM_PER_LANE, "a lane's frames are DECIM_THREADS apart");
+constexpr uint32_t DECIM_HALF = (uint32_t)sauengine::DECIM_HALF; /* H: the filter's half-length, and its latency, in output frames */
+constexpr uint32_t DECIM_SPAN_Q = DECIM_TILE + 2 * DECIM_HALF; /* input frames of one phase in a tile's span */
+constexpr uint32_t DECIM_CARRY_THREADS = 256; /* decimate_carry_kernel: one workgroup per stream, four floats per thread */
+constexpr uint32_t DECIM_MAX_STREAMS = 65535; /* grid.y */
+struct DecimPlan {
+	bool ok = false;       /* false: a factor that is not 2, 4 or 8, channels not 1 or 2, more streams or tiles than a grid has */
+	uint32_t tiles = 0;    /* grid.x of decimate_kernel (0: no output frame, no launch) */
+	uint32_t streams = 0;  /* grid.y, and decimate_carry_kernel's grid.x */
+	uint32_t taps = 0;     /* L = 2 * H * K + 1 */
+	uint32_t hist_floats = 0; /* a stream's history: (L - 1) * channels */
+	uint32_t lds_bytes = 0;   /* the span of one tile */
+	size_t out_pitch = 0;  /* bytes between the output rows: buf_len * channels samples, rounded up to 256 */
+};
+inline DecimPlan plan_decimate(uint64_t buf_len, int factor, uint32_t channels, size_t n_streams, size_t sample_bytes) {
+	DecimPlan p;
+	if ((factor != 2 && factor != 4 && factor != 8) || (channels != 1 && channels != 2) || n_streams > DECIM_MAX_STREAMS) return p;
+	const uint64_t tiles = (buf_len + DECIM_TILE - 1) / DECIM_TILE;
+	if (tiles > 0x7fffffffull || buf_len * (uint64_t)factor > 0xffffffffull) return p;
+	p.ok = true;
+	p.tiles = (uint32_t)tiles;
+	p.streams = (uint32_t)n_streams;
+	p.taps = 2 * DECIM_HALF * (uint32_t)factor + 1;
+	p.hist_floats = (p.taps - 1) * channels;
+	p.lds_bytes = DECIM_SPAN_Q * (uint32_t)factor * channels * (uint32_t)sizeof(float);
+	p.out_pitch = ((size_t)buf_len * channels * sample_bytes + 255) & ~(size_t)255;
+	return p;
+}
+static_assert(2 * DECIM_HALF * 8 * 2 <= DECIM_CARRY_THREADS * 4, "decimate_carry_kernel: a stream's longest history, four floats per thread");
+
 } /* namespace sauplan */
 #endif

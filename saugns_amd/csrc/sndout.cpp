@@ -276,6 +276,80 @@ bool write_scaled(const sauProgram *prg, uint32_t srate, const char *path, int f
 	return ok;
 }
 
+/* The oversampled writer: float runs at srate * factor on render_file_over's lattice for that rate, each decimated on the
+ * device (Engine::run_decimated) into rows of the file's format, and those through the two page-locked slots to the file, as
+ * write_scaled's chunks go. The filter delays by H = decimator_latency output frames: with y the decimated runs end to end
+ * and N the high-rate frames rendered, the file is y[H .. H + ceil(N / factor)) -- time-aligned with the input -- and one
+ * last decimated run of H frames behind the program's end delivers what of it the runs so far have not. */
+bool write_oversampled(const sauProgram *prg, uint32_t srate, int factor, const char *path, int format, int channels,
+		Backend *backend /* owned */, uint64_t *frames_out, std::string &err) {
+	const uint32_t srate_hi = srate * (uint32_t)factor;
+	Engine *engine = Engine::create(&prg, 1, srate_hi, backend, err);
+	if (!engine) return false;
+	const bool stereo = channels == 2;
+	const bool f32 = format == SAU_AMD_SNDFILE_WAV_F32;
+	const sauengine::SampleFormat out_fmt = f32 ? sauengine::SF_F32 : sauengine::SF_S16;
+	const bool swap = format == SAU_AMD_SNDFILE_AU;
+	const size_t H = sauengine::decimator_latency(factor);
+	size_t call, chunk;
+	file_lattice(srate_hi, call, chunk); /* a device run is chunk * factor high-rate frames: whole calls, and `chunk` output frames */
+	engine->set_call_len(call);
+	/* a backend without float output or without a decimator says so here, before there is a file */
+	if (!engine->set_format(sauengine::SF_F32, err) || !engine->begin_decimated(factor, stereo, err)) { delete engine; return false; }
+	const size_t frame_bytes = (size_t)channels * (f32 ? sizeof(float) : sizeof(int16_t));
+	const size_t slot_frames = chunk > H ? chunk : H;
+	void *host[2] = {backend->alloc_host(slot_frames * frame_bytes), backend->alloc_host(slot_frames * frame_bytes)};
+	SndOut out;
+	bool ok = host[0] && host[1];
+	if (!ok) err = "out of page-locked memory";
+	if (ok && !out.open(path, format, (uint16_t)channels, srate)) {
+		err = std::string("couldn't open \"") + path + "\" for writing";
+		ok = false;
+	}
+	size_t pending[2] = {0, 0}, first[2] = {0, 0}; /* frames of the slot to write, and where they begin in it */
+	int slot = 0;
+	bool more = ok, tail = false;
+	uint64_t y_pos = 0, wanted = 0; /* decimated frames made so far; ceil(N / factor) of the N high-rate frames rendered so far */
+	while (ok && !tail) {
+		tail = !more; /* behind the program's end: the one run for the filter's tail */
+		const size_t n = tail ? H : chunk;
+		size_t len = 0;
+		ok = engine->run_decimated(nullptr, out_fmt, swap, factor, n, stereo, &more, &len, err);
+		if (!ok) break;
+		wanted += len; /* (every run but the program's last is whole: the ceilings add up to the ceiling of the sum) */
+		/* the file is y[H, H + wanted): while the program runs that covers every frame of a run but the first H */
+		const uint64_t lo = y_pos > H ? y_pos : H, end = y_pos + n, hi = H + wanted < end ? H + wanted : end;
+		if (hi > lo) {
+			ok = backend->fetch_decimated_async(0, host[slot], (size_t)(hi - y_pos) * frame_bytes, slot, err);
+			first[slot] = (size_t)(lo - y_pos);
+			pending[slot] = (size_t)(hi - lo);
+		}
+		y_pos = end;
+		const int other = slot ^ 1;
+		if (ok && pending[other]) {
+			ok = backend->wait_fetch(other, err);
+			if (ok && !out.write((const char *)host[other] + first[other] * frame_bytes, pending[other])) { err = "write failed"; ok = false; }
+			pending[other] = 0;
+		}
+		slot = other;
+	}
+	for (int s = 0; ok && s < 2; ++s) { /* oldest first */
+		const int k = slot ^ s;
+		if (pending[k]) {
+			ok = backend->wait_fetch(k, err);
+			if (ok && !out.write((const char *)host[k] + first[k] * frame_bytes, pending[k])) { err = "write failed"; ok = false; }
+			pending[k] = 0;
+		}
+	}
+	{ std::string e2; (void)backend->sync(e2); }
+	if (out.f && out.close() != 0 && ok) { err = "write failed"; ok = false; }
+	if (frames_out) *frames_out = out.frames;
+	backend->free_host(host[0]);
+	backend->free_host(host[1]);
+	delete engine;
+	return ok;
+}
+
 } /* namespace */
 
 bool sauamd_internal::render_file_normalized(const sauProgram *prg, uint32_t srate, const char *path, int format, int channels,
@@ -306,6 +380,33 @@ extern "C" bool sauAmd_render_file_normalized(const sauProgram *prg, uint32_t sr
 	try {
 		ok = sauamd_internal::render_file_normalized(prg, srate, path, format, channels, target_peak,
 				[](std::string &e) -> Backend * { return sauhip::create_hip_backend(e); }, frames_out, levels_out, err);
+	} catch (const std::exception &ex) { /* (nothing C++ crosses the C ABI) */
+		err = std::string("internal error: ") + ex.what();
+	}
+	if (!ok) sauamd_internal::set_last_error("output", err);
+	return ok;
+}
+
+bool sauamd_internal::render_file_oversampled(const sauProgram *prg, uint32_t srate, int factor, const char *path, int format,
+		int channels, const std::function<Backend *(std::string &)> &make_backend, uint64_t *frames_out, std::string &err) {
+	if (frames_out) *frames_out = 0;
+	if (!prg || !path || (channels != 1 && channels != 2) || format < 0 || format > SAU_AMD_SNDFILE_WAV_F32 ||
+	    !sauengine::decimator_latency(factor) || !srate || srate > UINT32_MAX / (uint32_t)factor) {
+		err = "bad argument";
+		return false;
+	}
+	Backend *backend = make_backend(err);
+	if (!backend) return false;
+	return write_oversampled(prg, srate, factor, path, format, channels, backend, frames_out, err);
+}
+
+extern "C" bool sauAmd_render_file_oversampled(const sauProgram *prg, uint32_t srate, int factor, const char *path, int format,
+		int channels, uint64_t *frames_out) {
+	std::string err;
+	bool ok = false;
+	try {
+		ok = sauamd_internal::render_file_oversampled(prg, srate, factor, path, format, channels,
+				[](std::string &e) -> Backend * { return sauhip::create_hip_backend(e); }, frames_out, err);
 	} catch (const std::exception &ex) { /* (nothing C++ crosses the C ABI) */
 		err = std::string("internal error: ") + ex.what();
 	}

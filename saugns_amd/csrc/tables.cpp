@@ -168,4 +168,47 @@ const WaveConst *wave_consts() {
 	return g_wconst;
 }
 
+/* ---- the decimator's filter (engine.h: decimator_taps; the one definition every layer and the tests use) ----
+ * A Kaiser-windowed sinc with its cutoff at the output rate's Nyquist frequency: for n = 0 .. C,
+ *   g[n] = sinc((n - C) / K) * I0(beta * sqrt(1 - ((n - C) / C)^2)) / I0(beta),  sinc(t) = sin(pi t) / (pi t),  beta = 10.06,
+ * the upper half mirrored from the lower (not computed again: the symmetry is exact), and h = g / S with S the sum of g in
+ * ascending n. All in f64, on the host. */
+namespace {
+
+/* the modified Bessel function of order 0 by its power series, until a term no longer changes the sum */
+double bessel_i0(double x) {
+	const double q = x * x * 0.25;
+	double sum = 1.0, term = 1.0;
+	for (int k = 1; k < 1000; ++k) {
+		term *= q / ((double)k * (double)k);
+		const double next = sum + term;
+		if (next == sum) break;
+		sum = next;
+	}
+	return sum;
+}
+
+} /* namespace */
+
+size_t decimator_latency(int factor) { return factor == 2 || factor == 4 || factor == 8 ? DECIM_HALF : 0; }
+
+size_t decimator_taps(int factor, double *out, size_t cap) {
+	if (!decimator_latency(factor)) return 0;
+	const size_t K = (size_t)factor, C = DECIM_HALF * K, L = 2 * C + 1;
+	if (!out || cap < L) return L;
+	const double beta = 10.06, pi = 3.14159265358979323846, i0b = bessel_i0(beta);
+	for (size_t n = 0; n <= C; ++n) {
+		const double d = (double)n - (double)C; /* n - C */
+		const double t = d / (double)K, r = d / (double)C;
+		const double sinc = n == C ? 1.0 : sin(pi * t) / (pi * t);
+		const double w = 1.0 - r * r;
+		out[n] = sinc * bessel_i0(beta * sqrt(w > 0.0 ? w : 0.0)) / i0b;
+	}
+	for (size_t n = 0; n < C; ++n) out[L - 1 - n] = out[n];
+	double S = 0.0;
+	for (size_t n = 0; n < L; ++n) S += out[n];
+	for (size_t n = 0; n < L; ++n) out[n] /= S;
+	return L;
+}
+
 } /* namespace sauengine */
