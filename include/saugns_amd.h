@@ -285,6 +285,110 @@ SAU_AMD_API size_t sauAmd_Batch_device_decimated_pitch(sauAmdBatch *b);
 SAU_AMD_API bool sauAmd_render_file_oversampled(const sauProgram *prg, uint32_t srate, int factor, const char *path,
 		int format, int channels, uint64_t *frames_out);
 
+/* ---- Loudness and true peak ---------------------------------------------------
+ * sauAmdLevels answers "is it clipping"; a delivery target is programme loudness (ITU-R BS.1770-4 / EBU R 128, in LUFS) under a
+ * true-peak ceiling (dBTP: the peaks between the samples included). Both are measured where the samples are, on the float rows
+ * of sauAmd_Batch_run_f32; the gating runs on the host over 16 bytes per 100 ms.
+ *
+ * The arithmetic is a fixed order of IEEE operations (the build is -ffp-contract=off: a product is rounded, then the sum): the
+ * same rows in the same sequence of run lengths give the same bits on any MI355X partition -- no atomics, no sum whose order
+ * depends on scheduling. A sample x is the float sample as a double; a NaN or +-inf counts as +0.0 throughout
+ * (sauAmdLevels.nonfinite counts those).
+ *
+ * K-weighting, for the rate fs, in f64 on the host (the bilinear-transform forms that give BS.1770's table at 48 kHz):
+ *   stage 1, high shelf: f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196;
+ *     K = tan(pi f0 / fs), Vh = 10^(G / 20), Vb = Vh^0.4996667741545416, a0 = 1 + K / Q + K K;
+ *     b = [(Vh + Vb K / Q + K K) / a0, 2 (K K - Vh) / a0, (Vh - Vb K / Q + K K) / a0], a1 = 2 (K K - 1) / a0, a2 = (1 - K / Q + K K) / a0
+ *   stage 2, high-pass: f0 = 38.13547087602444, Q = 0.5003270373238773, K and a0 as above;
+ *     b' = [1, -2, 1], a1' = 2 (K K - 1) / a0, a2' = (1 - K / Q + K K) / a0
+ * One frame updates the state (s1, s2, t1, t2), transposed direct form II, every product rounded and then every sum:
+ *   u = b0 x + s1;    s1 = (b1 x - a1 u) + s2;     s2 = b2 x - a2 u
+ *   y = b0' u + t1;   t1 = (b1' u - a1' y) + t2;   t2 = b2' u - a2' y
+ * Chunks make the recurrence parallel. A chunk is 256 frames -- a constant, never a function of the device: chunk c of a run
+ * is the stream's frames [256 c, 256 c + 256) of that run, cut at the stream's frame count for the run. M is the 4x4 map of
+ * the state over 256 frames of zero input (column k: the frame update run 256 times from the k-th unit state), z_c the state
+ * after chunk c evaluated from zero state, S_0 the state the stream's previous metered run left (zero at the start and after
+ * a reset). Behind a FULL chunk c
+ *   S_{c+1}[r] = ((((0.0 + M[r][0] S_c[0]) + M[r][1] S_c[1]) + M[r][2] S_c[2]) + M[r][3] S_c[3]) + z_c[r]
+ * and chunk c is then evaluated frame by frame from S_c; the state after the run's last chunk, full or partial, evaluated that
+ * way is what the stream carries on. A stream with no frames in a run changes nothing.
+ * Hop energies. hop = fs / 10 frames (integer division; fs >= 2560, so a chunk never touches more than two hops). A stream
+ * counts its metered frames from 0, and the frame at position p belongs to hop p / hop. Evaluating chunk c gives one sum per
+ * hop it touches: acc = +0.0, then for its frames of that hop ascending acc = acc + y y. E[h][ch], the running f64 sum of
+ * hop h (+0.0 before anything is added), takes those sums in ascending chunk order, within a chunk the earlier hop first.
+ * True peak. 4x interpolation with the decimator's formula for K = 4, half-length H = 16 input frames, beta = 5.0: g[n],
+ * n = 0 .. 128, is that section's Kaiser-windowed sinc, NOT normalised (passband to 0.45 of the rate within 0.02 dB, stopband
+ * from 0.55 of it below -53 dB). For a stream's frame m and phase p = 1, 2, 3:
+ *   acc = +0.0; for q = 0 .. 31 ascending: acc = acc + g[4 q + p] x[m - q]; w = (float)acc
+ * with x = +0.0 before the stream's first metered frame (31 frames are carried from run to run). true_peak[ch] is the largest
+ * of |x[m]| as a float and every finite |w|, compared as bit patterns. The positions that lag behind a stream's last frame
+ * -- m = N .. N + 30 with zeros for x[N ..] -- are covered when the record is read: on the host, into the copy that is
+ * returned; the device state is untouched and later runs continue exactly.
+ * Gating, in f64 on the host over the complete hops. Block j covers hops j .. j + 3:
+ *   z_j = 0.0, then for ch ascending z_j = z_j + (((E[j][ch] + E[j+1][ch]) + E[j+2][ch]) + E[j+3][ch]) / (4.0 hop)
+ * (every channel has weight 1: BS.1770 for mono and for L/R); l_j = -0.691 + 10 log10(z_j), or -inf for 0; momentary_max =
+ * max l_j; the absolute gate keeps blocks with l_j > -70, the relative gate those of them with l_j > (-0.691 + 10 log10(mean
+ * z of the absolute-gated blocks)) - 10; integrated = -0.691 + 10 log10(mean z of the blocks passing both). A mean is the
+ * sum in ascending j divided by the count. With no block, or none passing, the result is -HUGE_VAL.
+ *
+ * Limits: float runs only (decimated rows are not metered yet -- fetch the hops of a float run at the low rate instead);
+ * fs >= 2560; one channel layout per record; no loudness range or short-term measure yet (sauAmd_Batch_loudness_hops gives a
+ * caller what those need). */
+typedef struct sauAmdLoudness {
+	uint64_t frames;        /* frames measured */
+	uint64_t blocks;        /* 400 ms blocks: complete hops - 3, or 0 */
+	uint64_t gated_blocks;  /* those passing both gates */
+	double   integrated;    /* LUFS; -HUGE_VAL when no block passes */
+	double   momentary_max; /* LUFS; -HUGE_VAL without a block */
+	float    true_peak[2];  /* [0] L or mono, [1] R (0 on mono) */
+} sauAmdLoudness;
+#ifdef __cplusplus
+static_assert(sizeof(sauAmdLoudness) == 48, "sauAmdLoudness is 48 bytes");
+#else
+_Static_assert(sizeof(sauAmdLoudness) == 48, "sauAmdLoudness is 48 bytes");
+#endif
+
+/* The ten coefficients b0 b1 b2 a1 a2, b0' b1' b2' a1' a2' for a rate; false (nothing written) below 2560 Hz. */
+SAU_AMD_API bool sauAmd_loudness_filter(uint32_t srate, double out[10]);
+/* 129, and the taps g in out[] when cap >= 129 (nothing is written when cap < 129; out may then be NULL). */
+SAU_AMD_API size_t sauAmd_truepeak_taps(double *out, size_t cap);
+/* The gating above over n_hops complete hops, hops[h][2] ([h][1] is not read for channels == 1), of hop_frames frames each:
+ * blocks, gated_blocks, integrated and momentary_max; frames = n_hops * hop_frames and true_peak = 0. Public so that a caller
+ * can gate windows of its own. False on channels other than 1 or 2, hop_frames == 0 or a NULL pointer. */
+SAU_AMD_API bool sauAmd_loudness_gate(const double *hops /* [n_hops][2] */, size_t n_hops, uint32_t hop_frames, int channels,
+		sauAmdLoudness *out);
+/* Loudness metering is off by default, and while it is off a run does nothing for it. On: every sauAmd_Batch_run_f32 ends with
+ * the device measuring stream i over the frames [0, out_len[i]) of that run -- on the batch's stream, before any copy to the
+ * host -- into stream i's record on the device: hop energies (16 bytes per 100 ms, growing with the stream), filter state,
+ * true peak, the 31-frame history, the frame count. Independent of sauAmd_Batch_set_metering; both may be on. While on,
+ * sauAmd_Batch_run, sauAmd_Batch_run_decimated_f32 and a float run of the other channel layout than the record's are refused
+ * as a bad argument: nothing is rendered and the batch stands where it stood. False (sauAmd_last_error), with nothing
+ * changed, on a backend without it or a batch rate below 2560 Hz; switching it off always succeeds and keeps the records. */
+SAU_AMD_API bool sauAmd_Batch_set_loudness(sauAmdBatch *b, int on);
+/* Wait for the batch's stream, fetch hops, peaks and histories, gate, and cover the true-peak tail in the copy: one record per
+ * stream. reset != 0 then clears hops, filter state, history, peaks and frame count. Empty records (-HUGE_VAL, zeros) while
+ * loudness metering has never been on. */
+SAU_AMD_API bool sauAmd_Batch_loudness(sauAmdBatch *b, sauAmdLoudness *out /* [streams] */, int reset);
+/* The number of complete hops of a stream, and their energies out[h][2] when cap (in hops) suffices (nothing is written when
+ * it does not; out may then be NULL). Waits for the batch's stream. */
+SAU_AMD_API size_t sauAmd_Batch_loudness_hops(sauAmdBatch *b, size_t stream, double *out, size_t cap);
+/* The same measurement, from zero state, of n_rows float32 rows the caller holds on the batch's device, at the rate srate
+ * (>= 2560): the argument rules are sauAmd_Batch_measure_rows' (and frames must fit 32 bits). Synchronous; the batch's own
+ * records are untouched. hops_out (may be NULL): the rows' frames / (srate / 10) complete hops each, [n_rows][hops][2], when
+ * hops_cap (in doubles) suffices. frames == 0 gives empty records. */
+SAU_AMD_API bool sauAmd_Batch_measure_loudness_rows(sauAmdBatch *b, const void *rows, size_t pitch_bytes, size_t n_rows,
+		size_t frames, int channels, uint32_t srate, sauAmdLoudness *out /* [n_rows] */, double *hops_out, size_t hops_cap);
+/* sauAmd_render_file to a target loudness under a true-peak ceiling. Rendered twice, as sauAmd_render_file_normalized is and on
+ * the same call lattice: pass 1 makes float runs with loudness metering on and fetches nothing;
+ *   gain = (float)pow(10.0, (target_lufs - integrated) / 20.0);
+ *   if max(true_peak) * gain > max_true_peak (f32): gain = max_true_peak / max(true_peak), one f32 division;
+ * gain = 1 when integrated is -HUGE_VAL; pass 2 writes x * gain through the same requantiser (the int16 formats round once,
+ * after the gain). *loud_out (may be NULL) = pass 1's record, before the gain; *gain_out (may be NULL) = the gain. False
+ * (sauAmd_last_error), before any file is created, on a bad argument -- a target that is not finite, max_true_peak not finite
+ * or <= 0, srate < 2560 -- or a backend without float output or loudness metering. */
+SAU_AMD_API bool sauAmd_render_file_loudness(const sauProgram *prg, uint32_t srate, const char *path, int format, int channels,
+		double target_lufs, float max_true_peak, uint64_t *frames_out, sauAmdLoudness *loud_out, float *gain_out);
+
 #ifdef __cplusplus
 }
 #endif

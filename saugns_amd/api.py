@@ -107,6 +107,23 @@ class Levels(C.Structure):
 assert C.sizeof(Levels) == 80
 
 
+class Loudness(C.Structure):
+    """sauAmdLoudness (include/saugns_amd.h): BS.1770 loudness and true peak of one stream or row. [0] is L or mono, [1] R."""
+    _fields_ = [("frames", C.c_uint64), ("blocks", C.c_uint64), ("gated_blocks", C.c_uint64), ("integrated", C.c_double),
+                ("momentary_max", C.c_double), ("true_peak", C.c_float * 2)]
+
+    def as_dict(self):
+        return {"frames": int(self.frames), "blocks": int(self.blocks), "gated_blocks": int(self.gated_blocks),
+                "integrated": float(self.integrated), "momentary_max": float(self.momentary_max),
+                "true_peak": list(self.true_peak)}
+
+    def __repr__(self):
+        return "Loudness(%r)" % (self.as_dict(),)
+
+
+assert C.sizeof(Loudness) == 48
+
+
 def _declare(L):
     """The C ABI of include/saugns_amd.h on a loaded library."""
     L.sau_create_Generator.restype = C.c_void_p
@@ -177,6 +194,25 @@ def _declare(L):
         L.sauAmd_render_file_oversampled.restype = C.c_bool
         L.sauAmd_render_file_oversampled.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_char_p, C.c_int, C.c_int,
                                                      C.POINTER(C.c_uint64)]
+    if hasattr(L, "sauAmd_Batch_set_loudness"):  # loudness and true peak (SAU_AMD_LIB may name an older build)
+        L.sauAmd_loudness_filter.restype = C.c_bool
+        L.sauAmd_loudness_filter.argtypes = [C.c_uint32, C.POINTER(C.c_double)]
+        L.sauAmd_truepeak_taps.restype = C.c_size_t
+        L.sauAmd_truepeak_taps.argtypes = [C.POINTER(C.c_double), C.c_size_t]
+        L.sauAmd_loudness_gate.restype = C.c_bool
+        L.sauAmd_loudness_gate.argtypes = [C.POINTER(C.c_double), C.c_size_t, C.c_uint32, C.c_int, C.POINTER(Loudness)]
+        L.sauAmd_Batch_set_loudness.restype = C.c_bool
+        L.sauAmd_Batch_set_loudness.argtypes = [C.c_void_p, C.c_int]
+        L.sauAmd_Batch_loudness.restype = C.c_bool
+        L.sauAmd_Batch_loudness.argtypes = [C.c_void_p, C.POINTER(Loudness), C.c_int]
+        L.sauAmd_Batch_loudness_hops.restype = C.c_size_t
+        L.sauAmd_Batch_loudness_hops.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_double), C.c_size_t]
+        L.sauAmd_Batch_measure_loudness_rows.restype = C.c_bool
+        L.sauAmd_Batch_measure_loudness_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int,
+                                                         C.c_uint32, C.POINTER(Loudness), C.POINTER(C.c_double), C.c_size_t]
+        L.sauAmd_render_file_loudness.restype = C.c_bool
+        L.sauAmd_render_file_loudness.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_int, C.c_int, C.c_double, C.c_float,
+                                                  C.POINTER(C.c_uint64), C.POINTER(Loudness), C.POINTER(C.c_float)]
     L.sauAmd_set_piluts.argtypes = [C.c_void_p]
     L.sauAmd_get_piluts.restype = C.POINTER(C.c_float)
     L.sauAmd_last_error.restype = C.c_char_p
@@ -371,6 +407,71 @@ def decimator_taps(factor):
 def decimator_latency(factor):
     """sauAmd_decimator_latency: the filter's delay in output frames (32), 0 for a factor other than 2, 4, 8."""
     return int(lib().sauAmd_decimator_latency(int(factor)))
+
+
+_loudness_hooks = None
+
+
+def use_loudness_hooks(path):
+    """tests/ only: load the library that runs the loudness-normalised file writer over an injected backend
+    (tests/hooks_loudness: the product's object files + sauAmd_render_file_loudness_with_backend)."""
+    global _loudness_hooks
+    if _loudness_hooks is None:
+        L = _declare(C.CDLL(path))
+        L.sauAmd_render_file_loudness_with_backend.restype = C.c_bool
+        L.sauAmd_render_file_loudness_with_backend.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_int, C.c_int, C.c_double,
+                                                               C.c_float, C.c_void_p, C.POINTER(C.c_uint64),
+                                                               C.POINTER(Loudness), C.POINTER(C.c_float)]
+        _loudness_hooks = L
+    return _loudness_hooks
+
+
+def render_file_loudness(program, srate, path, fmt=SNDFILE_WAV, channels=1, target_lufs=-23.0, max_true_peak=1.0, backend=None):
+    """sauAmd_render_file_loudness: render a whole program into a file at `target_lufs` integrated loudness (BS.1770) with its
+    true peak held at or under `max_true_peak` -> (frames written, Loudness of the render before the gain, the gain). Two
+    passes over the program: one that measures, one that writes x * gain. ``backend`` (tests): a sauengine::Backend* for the
+    first pass, without a GPU."""
+    n, ld, gain = C.c_uint64(), Loudness(), C.c_float()
+    if backend is None:
+        L = _used(lib())
+        ok = L.sauAmd_render_file_loudness(program.ptr, srate, os.fsencode(path), fmt, channels, target_lufs, max_true_peak,
+                                           C.byref(n), C.byref(ld), C.byref(gain))
+    else:
+        if _loudness_hooks is None:
+            raise RuntimeError("the loudness-hook library is not loaded (use_loudness_hooks)")
+        L = _used(_loudness_hooks)
+        ok = L.sauAmd_render_file_loudness_with_backend(program.ptr, srate, os.fsencode(path), fmt, channels, target_lufs,
+                                                        max_true_peak, backend, C.byref(n), C.byref(ld), C.byref(gain))
+    if not ok:
+        raise RuntimeError("sauAmd_render_file_loudness failed: " + last_error(L))
+    return n.value, ld, gain.value
+
+
+def loudness_filter(srate):
+    """sauAmd_loudness_filter: the K-weighting coefficients b0 b1 b2 a1 a2, b0' b1' b2' a1' a2' for a rate as a float64 array
+    of ten -- the one definition the device, the writer and the tests share; None below 2560 Hz."""
+    out = np.zeros(10, np.float64)
+    ok = lib().sauAmd_loudness_filter(int(srate), out.ctypes.data_as(C.POINTER(C.c_double)))
+    return out if ok else None
+
+
+def truepeak_taps():
+    """sauAmd_truepeak_taps: the 4x true-peak interpolator's 129 taps g (not normalised) as a float64 array."""
+    L = lib()
+    n = int(L.sauAmd_truepeak_taps(None, 0))
+    out = np.zeros(n, np.float64)
+    L.sauAmd_truepeak_taps(out.ctypes.data_as(C.POINTER(C.c_double)), n)
+    return out
+
+
+def loudness_gate(hops, hop_frames, channels):
+    """sauAmd_loudness_gate: BS.1770 gating of complete hop energies [n][2] (float64) -> Loudness (frames = n * hop_frames)."""
+    h = np.ascontiguousarray(hops, dtype=np.float64).reshape(-1, 2)
+    out = Loudness()
+    if not _used(lib()).sauAmd_loudness_gate(h.ctypes.data_as(C.POINTER(C.c_double)), len(h), int(hop_frames), int(channels),
+                                             C.byref(out)):
+        raise RuntimeError("sauAmd_loudness_gate failed: " + last_error(lib()))
+    return out
 
 
 def get_piluts():
@@ -603,6 +704,41 @@ class Batch:
         if not _used(self._L).sauAmd_Batch_measure_rows(self._b, ptr, pitch, n_rows, 1 if f32 else 0, frames, channels, out):
             raise RuntimeError("sauAmd_Batch_measure_rows failed: " + last_error(self._L))
         return list(out)[:int(n_rows)]
+
+    def set_loudness(self, on):
+        """sauAmd_Batch_set_loudness: from the next run on, every float32 run ends with the device taking each stream's frames
+        of that run into the stream's loudness record; int16 and decimated runs are refused while on (off by default)."""
+        if not _used(self._L).sauAmd_Batch_set_loudness(self._b, 1 if on else 0):
+            raise RuntimeError("sauAmd_Batch_set_loudness failed: " + last_error(self._L))
+
+    def loudness(self, reset=False):
+        """sauAmd_Batch_loudness: wait for the batch's stream -> the streams' records, a list of Loudness."""
+        out = (Loudness * self.n)()
+        if not _used(self._L).sauAmd_Batch_loudness(self._b, out, 1 if reset else 0):
+            raise RuntimeError("sauAmd_Batch_loudness failed: " + last_error(self._L))
+        return list(out)
+
+    def loudness_hops(self, stream):
+        """sauAmd_Batch_loudness_hops: the stream's complete 100 ms hop energies, float64 [hops, 2]."""
+        L = _used(self._L)
+        n = int(L.sauAmd_Batch_loudness_hops(self._b, stream, None, 0))
+        out = np.zeros((n, 2), np.float64)
+        if n and int(L.sauAmd_Batch_loudness_hops(self._b, stream, out.ctypes.data_as(C.POINTER(C.c_double)), n)) != n:
+            raise RuntimeError("sauAmd_Batch_loudness_hops failed: " + last_error(self._L))
+        return out
+
+    def measure_loudness_rows(self, ptr, pitch, n_rows, frames, channels, srate):
+        """sauAmd_Batch_measure_loudness_rows: measure n_rows float32 rows of device memory at `ptr`, `pitch` bytes apart, of
+        `frames` frames of `channels` samples at the rate `srate`, from zero state -> (a list of Loudness, the rows' complete
+        hop energies as float64 [n_rows, hops, 2]). ptr and pitch must be multiples of 16."""
+        n_rows, frames, srate = int(n_rows), int(frames), int(srate)
+        nh = frames // (srate // 10) if srate >= 10 else 0
+        out = (Loudness * max(n_rows, 1))()
+        hops = np.zeros((n_rows, nh, 2), np.float64)
+        if not _used(self._L).sauAmd_Batch_measure_loudness_rows(self._b, ptr, pitch, n_rows, frames, channels, srate, out,
+                                                                 hops.ctypes.data_as(C.POINTER(C.c_double)), hops.size):
+            raise RuntimeError("sauAmd_Batch_measure_loudness_rows failed: " + last_error(self._L))
+        return list(out)[:n_rows], hops
 
     def device_pcm(self, stream):
         """Device address of the stream's int16 row of the last run; None after a float32 run."""

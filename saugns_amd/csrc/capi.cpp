@@ -456,6 +456,68 @@ extern "C" size_t sauAmd_Batch_device_decimated_pitch(sauAmdBatch *b) {
 extern "C" size_t sauAmd_decimator_taps(int factor, double *out, size_t cap) { return sauengine::decimator_taps(factor, out, cap); }
 extern "C" size_t sauAmd_decimator_latency(int factor) { return sauengine::decimator_latency(factor); }
 
+static_assert(sizeof(sauAmdLoudness) == sizeof(sauengine::Loudness) && offsetof(sauAmdLoudness, integrated) == offsetof(sauengine::Loudness, integrated) &&
+	offsetof(sauAmdLoudness, true_peak) == offsetof(sauengine::Loudness, true_peak), "sauengine::Loudness is sauAmdLoudness");
+
+extern "C" bool sauAmd_loudness_filter(uint32_t srate, double out[10]) { return sauengine::loudness_filter(srate, out); }
+extern "C" size_t sauAmd_truepeak_taps(double *out, size_t cap) { return sauengine::truepeak_taps(out, cap); }
+extern "C" bool sauAmd_loudness_gate(const double *hops, size_t n_hops, uint32_t hop_frames, int channels, sauAmdLoudness *out) {
+	if (sauengine::loudness_gate(hops, n_hops, hop_frames, channels, (sauengine::Loudness *)out)) return true;
+	report("loudness", "bad argument");
+	return false;
+}
+
+extern "C" bool sauAmd_Batch_set_loudness(sauAmdBatch *b, int on) {
+	std::string err;
+	try {
+		if (b->engine->set_loudness(on != 0, err)) return true;
+	} catch (const std::exception &ex) { /* (nothing C++ crosses the C ABI) */
+		err = std::string("internal error: ") + ex.what();
+	}
+	report("batch", err);
+	return false;
+}
+
+extern "C" bool sauAmd_Batch_loudness(sauAmdBatch *b, sauAmdLoudness *out, int reset) {
+	std::string err;
+	try {
+		if (!out) err = "bad argument";
+		else if (b->engine->loudness((sauengine::Loudness *)out, reset != 0, err)) return true;
+	} catch (const std::exception &ex) {
+		err = std::string("internal error: ") + ex.what();
+	}
+	report("batch", err);
+	return false;
+}
+
+extern "C" size_t sauAmd_Batch_loudness_hops(sauAmdBatch *b, size_t stream, double *out, size_t cap) {
+	std::string err;
+	size_t n = 0;
+	try {
+		if (b->engine->loudness_hops(stream, out, cap, &n, err)) return n;
+	} catch (const std::exception &ex) {
+		err = std::string("internal error: ") + ex.what();
+	}
+	report("batch", err);
+	return 0;
+}
+
+extern "C" bool sauAmd_Batch_measure_loudness_rows(sauAmdBatch *b, const void *rows, size_t pitch_bytes, size_t n_rows, size_t frames,
+		int channels, uint32_t srate, sauAmdLoudness *out, double *hops_out, size_t hops_cap) {
+	std::string err;
+	try {
+		if (!rows || !out || ((uintptr_t)rows & 15u) || (pitch_bytes & 15u) || (channels != 1 && channels != 2) || srate < sauengine::LOUD_MIN_RATE)
+			err = "bad argument";
+		else if (b->engine->backend()->measure_loudness_rows(rows, pitch_bytes, n_rows, frames, channels == 2, srate, (sauengine::Loudness *)out,
+				hops_out, hops_cap, err))
+			return true;
+	} catch (const std::exception &ex) {
+		err = std::string("internal error: ") + ex.what();
+	}
+	report("batch", err);
+	return false;
+}
+
 extern "C" bool sauAmd_Batch_sync(sauAmdBatch *b) {
 	std::string err;
 	if (!b->engine->backend()->sync(err)) { report("batch", err); return false; }

@@ -625,6 +625,12 @@ bool Engine::run(void *const *host_bufs, SampleFormat format, size_t buf_len, bo
 	if (buf_len > UINT32_MAX) { err = "buffer too long"; return false; }
 	if (format == SF_F32 && pcm_swap_) { err = "float32 samples are not byte-swapped"; return false; }
 	if (metering_ && pcm_swap_) { err = "level metering reads samples in host byte order, not byte-swapped ones"; return false; }
+	/* loudness is measured on float runs, of one channel layout: anything else is refused ahead of anything that moves */
+	if (loudness_ && (format != SF_F32 || in_decimated_)) { err = "bad argument: while loudness metering is on only float32 runs are made"; return false; }
+	if (loudness_ && loud_channels_ && loud_channels_ != (stereo ? 2 : 1)) {
+		err = "bad argument: the loudness records belong to the other channel layout (reset them first)";
+		return false;
+	}
 	/* the run's format, ahead of anything that moves: a backend without float output refuses here */
 	if (!set_format(format, err)) return false;
 	if (!in_decimated_) decim_factor_ = 0; /* (a run of any other kind ends a sequence of decimated runs) */
@@ -724,7 +730,7 @@ bool Engine::run(void *const *host_bufs, SampleFormat format, size_t buf_len, bo
 	}
 	frames_done_ += total;
 	call_phase_ = (uint32_t)(((uint64_t)call_phase_ + total) % lat_call_);
-	if (metering_) meter_frames_.assign(streams_.size(), 0);
+	if (metering_ || loudness_) meter_frames_.assign(streams_.size(), 0);
 	all_ended_ = true;
 	for (size_t s = 0; s < streams_.size(); ++s) {
 		Stream &st = streams_[s];
@@ -742,10 +748,14 @@ bool Engine::run(void *const *host_bufs, SampleFormat format, size_t buf_len, bo
 		if (more) more[s] = !ended;
 		if (out_len) out_len[s] = ended ? st.call_gen : buf_len;
 		if (!ended) all_ended_ = false;
-		if (metering_) meter_frames_[s] = (uint32_t)(ended ? st.call_gen : buf_len);
+		if (metering_ || loudness_) meter_frames_[s] = (uint32_t)(ended ? st.call_gen : buf_len);
 	}
 	/* the meter reads what the mixers wrote, where it is: behind them on the backend's stream, ahead of any fetch */
 	if (metering_ && !backend_->measure_streams(meter_frames_.data(), stereo, format, err)) return false;
+	if (loudness_) {
+		if (!backend_->measure_loudness(meter_frames_.data(), stereo, err)) return false;
+		loud_channels_ = stereo ? 2 : 1;
+	}
 	for (size_t s = 0; s < streams_.size(); ++s) {
 		if (host_bufs && host_bufs[s]) {
 			if (format == SF_F32 ? !backend_->fetch_pcm_f32((uint32_t)s, (float *)host_bufs[s], total, stereo, err)
@@ -770,6 +780,7 @@ bool Engine::run_decimated(void *const *host_bufs, SampleFormat out_fmt, bool sw
 		err = "bad argument";
 		return false;
 	}
+	if (loudness_) { err = "bad argument: while loudness metering is on only float32 runs are made (decimated rows are not metered)"; return false; }
 	/* the decimator first: a backend without one refuses here, ahead of anything that moves */
 	if ((decim_factor_ != factor || decim_stereo_ != stereo) && !begin_decimated(factor, stereo, err)) return false;
 	const size_t n = streams_.size();
@@ -806,6 +817,22 @@ bool Engine::levels(Levels *out, bool reset, std::string &err) {
 		return true;
 	}
 	return backend_->read_levels(out, reset, err);
+}
+
+bool Engine::loudness(Loudness *out, bool reset, std::string &err) {
+	if (!loud_begun_) { /* (no backend has records yet: what an empty record reads as) */
+		for (size_t s = 0; s < streams_.size(); ++s) (void)loudness_gate(nullptr, 0, srate_ / 10 ? srate_ / 10 : 1, 1, &out[s]);
+		return true;
+	}
+	if (!backend_->read_loudness(out, reset, err)) return false;
+	if (reset) loud_channels_ = 0;
+	return true;
+}
+
+bool Engine::loudness_hops(size_t stream, double *out, size_t cap, size_t *n_hops, std::string &err) {
+	if (stream >= streams_.size() || !n_hops) { err = "bad argument"; return false; }
+	if (!loud_begun_) { *n_hops = 0; return true; }
+	return backend_->read_loudness_hops((uint32_t)stream, out, cap, n_hops, err);
 }
 
 } /* namespace sauengine */

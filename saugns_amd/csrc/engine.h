@@ -38,6 +38,28 @@ struct Levels {
 };
 static_assert(sizeof(Levels) == 80, "sauAmdLevels");
 
+/* What the loudness meter reports of one stream or row (include/saugns_amd.h: sauAmdLoudness, the same 48 bytes). */
+struct Loudness {
+	uint64_t frames, blocks, gated_blocks;
+	double integrated, momentary_max;
+	float true_peak[2];
+};
+static_assert(sizeof(Loudness) == 48, "sauAmdLoudness");
+/* Loudness on the host (tables.cpp; include/saugns_amd.h states the arithmetic). loudness_filter: the ten K-weighting
+ * coefficients for a rate (false below LOUD_MIN_RATE); loudness_chunk_map: the state's 4x4 map M over `chunk` frames of zero
+ * input, row-major; loudness_step: one frame of the recurrence on st[4] -> y; truepeak_taps: as decimator_taps, 129 taps g;
+ * loudness_gate: BS.1770 gating of complete hops [n][2] into out (frames = n_hops * hop_frames, true_peak 0);
+ * truepeak_tail: the positions that lag behind a row's last frame -- hist holds the row's last TP_HIST + 1 = 32 frames
+ * (cleaned, interleaved) and is followed by 31 zero frames -- folded into peak_bits[channels]. */
+constexpr uint32_t LOUD_MIN_RATE = 2560;
+constexpr size_t TP_TAPS = 129, TP_LEAD = 32;
+bool loudness_filter(uint32_t srate, double out[10]);
+void loudness_chunk_map(const double f[10], uint32_t chunk, double m[16]);
+double loudness_step(double st[4], const double f[10], double x);
+size_t truepeak_taps(double *out, size_t cap);
+bool loudness_gate(const double *hops, size_t n_hops, uint32_t hop_frames, int channels, Loudness *out);
+void truepeak_tail(const float *hist, int channels, const double *taps, uint32_t *peak_bits);
+
 /* The decimator's filter (tables.cpp; include/saugns_amd.h: sauAmd_decimator_taps). Factors 2, 4 and 8; half-length
  * DECIM_HALF output frames, which is also the filter's latency; L = 2 * DECIM_HALF * factor + 1 taps in f64.
  * decimator_taps returns L and writes the taps when cap >= L (nothing otherwise); both return 0 for another factor. */
@@ -231,6 +253,31 @@ public:
 	 * between the rows of consecutive streams (a multiple of 256; 0: none) */
 	virtual const float *device_decimated_f32(uint32_t stream) { (void)stream; return nullptr; }
 	virtual size_t device_decimated_pitch() { return 0; }
+	/* BS.1770 loudness and true peak of float runs (include/saugns_amd.h: sauAmdLoudness), where the samples are. A backend
+	 * without it refuses -- these defaults -- and nothing changes. begin_loudness: make the streams' records (empty) for the
+	 * backend's rate if they are not there yet. */
+	virtual bool begin_loudness(std::string &err) { err = "this backend has no loudness metering"; return false; }
+	/* measure frames [0, frames[s]) of every stream's float row of the run just rendered and take them into the stream's
+	 * record -- hop energies, filter state, true peak, history, frame count: device work on the backend's stream, behind the
+	 * run's mixers and ahead of any fetch */
+	virtual bool measure_loudness(const uint32_t *frames, bool stereo, std::string &err) {
+		(void)frames; (void)stereo; err = "this backend has no loudness metering"; return false;
+	}
+	/* wait for the stream, fetch hops, peaks and histories, gate, cover the true-peak tail in the copy; `reset`: empty records */
+	virtual bool read_loudness(Loudness *out, bool reset, std::string &err) {
+		(void)out; (void)reset; err = "this backend has no loudness metering"; return false;
+	}
+	/* *n_hops = the stream's complete hops; their energies [h][2] into out when cap (in hops) suffices */
+	virtual bool read_loudness_hops(uint32_t stream, double *out, size_t cap, size_t *n_hops, std::string &err) {
+		(void)stream; (void)out; (void)cap; (void)n_hops; err = "this backend has no loudness metering"; return false;
+	}
+	/* the same measurement, from zero state, of float rows the caller holds on the backend's device (synchronous; the streams'
+	 * records are untouched). hops_out, when given and hops_cap (in doubles) suffices: [n_rows][frames / hop][2] */
+	virtual bool measure_loudness_rows(const void *rows, size_t pitch_bytes, size_t n_rows, size_t frames, bool stereo, uint32_t srate,
+			Loudness *out, double *hops_out, size_t hops_cap, std::string &err) {
+		(void)rows; (void)pitch_bytes; (void)n_rows; (void)frames; (void)stereo; (void)srate; (void)out; (void)hops_out; (void)hops_cap;
+		err = "this backend has no loudness metering"; return false;
+	}
 };
 
 /* ---- plan compiler (plan.cpp) -------------------------------------------- */
@@ -349,6 +396,21 @@ public:
 	/* the streams' records, out[n_streams()]; all zero while metering has never been on */
 	bool levels(Levels *out, bool reset, std::string &err);
 
+	/* Loudness metering (include/saugns_amd.h: sauAmd_Batch_set_loudness). On: every float run ends with the backend taking
+	 * each stream's frames [0, out_len) into the stream's loudness record, and int16 and decimated runs are refused. Off (the
+	 * default): run() makes no call for it. False, with the switch where it was, on a backend without it or a rate below
+	 * LOUD_MIN_RATE. The records belong to one channel layout: a float run of the other one while on is refused until a reset. */
+	bool set_loudness(bool on, std::string &err) {
+		if (on && srate_ < LOUD_MIN_RATE) { err = "bad argument: loudness metering needs a rate of 2560 Hz or more"; return false; }
+		if (on && !loud_begun_ && !backend_->begin_loudness(err)) return false;
+		if (on) loud_begun_ = true;
+		loudness_ = on;
+		return true;
+	}
+	/* the streams' records, out[n_streams()]; empty ones while loudness has never been on */
+	bool loudness(Loudness *out, bool reset, std::string &err);
+	bool loudness_hops(size_t stream, double *out, size_t cap, size_t *n_hops, std::string &err);
+
 	/* Size the device buffers for runs of up to `frames` frames now (run() grows them on demand, which waits for the
 	 * stream: a host that knows its longest run says so once). */
 	bool reserve(size_t frames, bool stereo, std::string &err);
@@ -442,6 +504,9 @@ private:
 	bool metering_ = false;          /* set_metering() */
 	bool metered_ = false;           /* ... has ever been on: the backend has records */
 	std::vector<uint32_t> meter_frames_; /* per stream: out_len of the run at hand */
+	bool loudness_ = false;          /* set_loudness() */
+	bool loud_begun_ = false;        /* ... has ever been on: the backend has records */
+	int loud_channels_ = 0;          /* the channel layout the records belong to (0: none yet, or reset) */
 	int decim_factor_ = 0;           /* run_decimated(): the sequence at hand (0: none -- any other run ends it) */
 	bool decim_stereo_ = false;
 	bool in_decimated_ = false;      /* run() is run_decimated()'s own */

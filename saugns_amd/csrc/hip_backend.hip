@@ -11,6 +11,7 @@
  *   k_finish.h      finalize_kernel, mix_kernel, mix_few_kernel (int16 and float32 forms), event_kernel
  *   k_levels.h      levels_kernel, levels_finish_kernel (level metering), requant_kernel (the normalised file writer)
  *   k_decimate.h    decimate_kernel, decimate_carry_kernel (oversampled rendering: the decimating FIR and its history)
+ *   k_loudness.h    loud_chunk_kernel, loud_scan_kernel, truepeak_kernel, loud_finish_kernel, loud_carry_kernel (BS.1770 loudness, true peak)
  *   launch_plan.h   (plain C++, no HIP) the tuning switches and every decision about a segment's launches: rows per pass, LDS
  *                   budgets, builds, grids, tasks, chain chunks, the mixer -- a plan per segment, testable without a GPU
  *   (this file)     buffer and stream pools, table sets, the kernel lookup, HipBackendImpl: render() carries a plan out,
@@ -72,6 +73,7 @@ using namespace sauplan;
 #include "k_finish.h"
 #include "k_levels.h"
 #include "k_decimate.h"
+#include "k_loudness.h"
 static_assert(MISC_BYTES == sizeof(Misc), "launch_plan.h plans the block loop's LDS with this size");
 
 /* ------------------------------------------------------------------------ */
@@ -1463,6 +1465,211 @@ public:
 	}
 	size_t device_decimated_pitch() override { return decim_out_.p && decim_out_bytes_ ? decim_out_pitch_ : 0; }
 
+	/* ---- loudness and true peak (k_loudness.h; the geometry is launch_plan.h's plan_loudness) ---- */
+	/* the records of a set of rows: the batch's streams, or the foreign rows of one measure_loudness_rows call */
+	struct LoudSet {
+		DevBuf<LoudState> state;
+		DevBuf<unsigned long long> pos;
+		DevBuf<double> E;
+		DevBuf<uint32_t> peak;
+		DevBuf<float> hist;
+		std::vector<uint64_t> pos_h; /* the host's copy of pos: what E has to hold is known without asking the device */
+		size_t e_cap = 0;            /* hops E holds per row */
+		uint32_t rows = 0, channels = 0;
+	};
+	bool loud_setup(uint32_t srate, std::string &err) {
+		if (loud_rate_ == srate) return true;
+		double f[10], m[16];
+		if (!sauengine::loudness_filter(srate, f)) { err = "bad argument: loudness metering needs a rate of 2560 Hz or more"; return false; }
+		sauengine::loudness_chunk_map(f, LOUD_CHUNK, m);
+		loud_f_ = LoudFilter{f[0], f[1], f[2], f[3], f[4], f[5], f[6], f[7], f[8], f[9]};
+		for (int r = 0; r < 4; ++r) for (int k = 0; k < 4; ++k) loud_m_.m[r][k] = m[4 * r + k];
+		if (!loud_taps_.p) {
+			double g[TP_TAPS];
+			if (sauengine::truepeak_taps(g, TP_TAPS) != TP_TAPS || !loud_taps_.ensure(TP_TAPS, err) || !send(loud_taps_.p, g, sizeof g, err)) return false;
+		}
+		loud_rate_ = srate;
+		return true;
+	}
+	bool loud_clear(LoudSet &L, std::string &err) {
+		HIP_OK(hipMemsetAsync(L.state.p, 0, (size_t)L.rows * 2 * sizeof(LoudState), stream_));
+		HIP_OK(hipMemsetAsync(L.pos.p, 0, (size_t)L.rows * sizeof(unsigned long long), stream_));
+		HIP_OK(hipMemsetAsync(L.peak.p, 0, (size_t)L.rows * 2 * sizeof(uint32_t), stream_));
+		HIP_OK(hipMemsetAsync(L.hist.p, 0, (size_t)L.rows * TP_LEAD * 2 * sizeof(float), stream_));
+		if (L.e_cap) HIP_OK(hipMemsetAsync(L.E.p, 0, L.e_cap * L.rows * 2 * sizeof(double), stream_));
+		L.pos_h.assign(L.rows, 0);
+		L.channels = 0;
+		return true;
+	}
+	bool loud_make(LoudSet &L, size_t rows, std::string &err) {
+		if (L.rows != rows && L.E.p) { /* (E is [hop][row][2]: another number of rows is another block) */
+			HIP_OK(hipStreamSynchronize(stream_));
+			L.E.release();
+			L.e_cap = 0;
+		}
+		L.rows = (uint32_t)rows;
+		if (!L.state.ensure(rows * 2, err) || !L.pos.ensure(rows, err) || !L.peak.ensure(rows * 2, err) || !L.hist.ensure(rows * TP_LEAD * 2, err)) return false;
+		return loud_clear(L, err);
+	}
+	/* E grows by reallocation on the backend's stream: the hops so far are copied, the rest is cleared, and the old block goes
+	 * back to the pool once the stream has drained. [hop][row][2]: the rows' hops so far are a prefix of the block. */
+	bool loud_grow(LoudSet &L, size_t need, std::string &err) {
+		if (need <= L.e_cap) return true;
+		const size_t want = need + need / 2 + 32, per = (size_t)L.rows * 2;
+		DevBuf<double> nb;
+		if (!nb.ensure(want * per, err)) return false;
+		if (L.e_cap) HIP_OK(hipMemcpyAsync(nb.p, L.E.p, L.e_cap * per * sizeof(double), hipMemcpyDeviceToDevice, stream_));
+		HIP_OK(hipMemsetAsync(nb.p + L.e_cap * per, 0, (want - L.e_cap) * per * sizeof(double), stream_));
+		if (L.E.p) { HIP_OK(hipStreamSynchronize(stream_)); L.E.release(); }
+		L.E.p = nb.p; L.E.cap = nb.cap; L.E.bytes = nb.bytes;
+		nb.p = nullptr; nb.cap = 0; nb.bytes = 0;
+		L.e_cap = want;
+		return true;
+	}
+	/* the launches of one measurement, on the backend's stream: frames[r] frames of row r */
+	bool loud_measure(LoudSet &L, const void *rows, size_t pitch, const uint32_t *frames, uint32_t ch, std::string &err) {
+		uint32_t longest = 0;
+		for (uint32_t r = 0; r < L.rows; ++r) if (frames[r] > longest) longest = frames[r];
+		if (!longest) return true; /* no row has a frame: nothing changes */
+		const LoudPlan plan = plan_loudness(longest, ch, L.rows, loud_rate_);
+		if (!plan.ok) { err = "bad argument: too many rows (65535 at most) for one loudness measurement"; return false; }
+		size_t need = 0;
+		for (uint32_t r = 0; r < L.rows; ++r) {
+			const size_t h = (size_t)((L.pos_h[r] + frames[r]) / plan.hop) + 1; /* (the hop the row's end lies in: loud_finish_kernel loads it) */
+			if (h > need) need = h;
+		}
+		if (!loud_grow(L, need, err)) return false;
+		const size_t lanes = (size_t)L.rows * 2 * plan.chunks;
+		if (!loud_z_.ensure(lanes, err) || !loud_s_.ensure(lanes, err) || !loud_parts_.ensure(lanes * 2, err) ||
+		    !loud_tp_parts_.ensure((size_t)L.rows * plan.tiles * 2, err) || !loud_frames_.ensure(L.rows, err) ||
+		    !send(loud_frames_.p, frames, (size_t)L.rows * sizeof(uint32_t), err))
+			return false;
+		LoudParams lp;
+		memset((void *)&lp, 0, sizeof lp);
+		lp.rows = (const float *)rows; lp.row_pitch = pitch; lp.frames = loud_frames_.p;
+		lp.channels = ch; lp.n_rows = L.rows; lp.hop = plan.hop; lp.chunk_cap = plan.chunks; lp.tile_cap = plan.tiles;
+		lp.state = L.state.p; lp.pos = L.pos.p; lp.zstate = loud_z_.p; lp.sstate = loud_s_.p; lp.parts = loud_parts_.p;
+		lp.E = L.E.p; lp.e_cap = (uint32_t)(L.e_cap > 0xffffffffull ? 0xffffffffull : L.e_cap);
+		lp.tp_parts = loud_tp_parts_.p; lp.peak = L.peak.p; lp.hist = L.hist.p;
+		const dim3 cgrid(plan.chunk_grid, plan.rows), tgrid(plan.tiles, plan.rows);
+		if (ch == 2) hipLaunchKernelGGL((loud_chunk_kernel<2, 0>), cgrid, dim3(LOUD_THREADS), 0, stream_, lp, loud_f_);
+		else hipLaunchKernelGGL((loud_chunk_kernel<1, 0>), cgrid, dim3(LOUD_THREADS), 0, stream_, lp, loud_f_);
+		HIP_OK(hipGetLastError());
+		hipLaunchKernelGGL(loud_scan_kernel, dim3(plan.lane_grid), dim3(64), 0, stream_, lp, loud_m_);
+		HIP_OK(hipGetLastError());
+		if (ch == 2) hipLaunchKernelGGL((loud_chunk_kernel<2, 1>), cgrid, dim3(LOUD_THREADS), 0, stream_, lp, loud_f_);
+		else hipLaunchKernelGGL((loud_chunk_kernel<1, 1>), cgrid, dim3(LOUD_THREADS), 0, stream_, lp, loud_f_);
+		HIP_OK(hipGetLastError());
+		if (ch == 2) hipLaunchKernelGGL(truepeak_kernel<2>, tgrid, dim3(TP_THREADS), 0, stream_, lp, (const double *)loud_taps_.p);
+		else hipLaunchKernelGGL(truepeak_kernel<1>, tgrid, dim3(TP_THREADS), 0, stream_, lp, (const double *)loud_taps_.p);
+		HIP_OK(hipGetLastError());
+		/* behind both on the one stream: every partial record is written, every read of the old history has finished */
+		hipLaunchKernelGGL(loud_finish_kernel, dim3((plan.rows + 63) / 64), dim3(64), 0, stream_, lp);
+		HIP_OK(hipGetLastError());
+		hipLaunchKernelGGL(loud_carry_kernel, dim3(plan.rows), dim3(64), 0, stream_, lp);
+		HIP_OK(hipGetLastError());
+		for (uint32_t r = 0; r < L.rows; ++r) L.pos_h[r] += frames[r];
+		L.channels = ch;
+		return true;
+	}
+	/* wait for the stream; the rows' records -- gated hops, peaks with the tail covered in the copy -- and, where asked for,
+	 * the complete hops of every row, [row][hops][2] with `hops_stride` hops per row */
+	bool loud_read(LoudSet &L, sauengine::Loudness *out, std::vector<double> *hops_out, size_t *hops_stride, std::string &err) {
+		const size_t per = (size_t)L.rows * 2;
+		const uint32_t hop = loud_rate_ / 10, ch = L.channels ? L.channels : 1;
+		size_t max_hops = 0;
+		for (uint32_t r = 0; r < L.rows; ++r) { const size_t h = (size_t)(L.pos_h[r] / hop); if (h > max_hops) max_hops = h; }
+		std::vector<double> E(max_hops * per);
+		std::vector<uint32_t> peak(per);
+		std::vector<float> hist((size_t)L.rows * TP_LEAD * 2);
+		if (max_hops) HIP_OK(hipMemcpyAsync(E.data(), L.E.p, E.size() * sizeof(double), hipMemcpyDeviceToHost, stream_));
+		HIP_OK(hipMemcpyAsync(peak.data(), L.peak.p, per * sizeof(uint32_t), hipMemcpyDeviceToHost, stream_));
+		HIP_OK(hipMemcpyAsync(hist.data(), L.hist.p, hist.size() * sizeof(float), hipMemcpyDeviceToHost, stream_));
+		HIP_OK(hipStreamSynchronize(stream_));
+		double g[TP_TAPS];
+		(void)sauengine::truepeak_taps(g, TP_TAPS);
+		if (hops_out) { hops_out->assign((size_t)L.rows * max_hops * 2, 0.0); *hops_stride = max_hops; }
+		std::vector<double> mine;
+		for (uint32_t r = 0; r < L.rows; ++r) {
+			const size_t nh = (size_t)(L.pos_h[r] / hop);
+			mine.assign(nh * 2, 0.0);
+			for (size_t h = 0; h < nh; ++h) { mine[2 * h] = E[h * per + (size_t)r * 2]; mine[2 * h + 1] = E[h * per + (size_t)r * 2 + 1]; }
+			if (!sauengine::loudness_gate(mine.data(), nh, hop, (int)ch, &out[r])) { err = "bad argument"; return false; }
+			out[r].frames = L.pos_h[r];
+			uint32_t pk[2] = {peak[(size_t)r * 2], peak[(size_t)r * 2 + 1]};
+			if (L.pos_h[r]) sauengine::truepeak_tail(hist.data() + (size_t)r * TP_LEAD * 2, (int)ch, g, pk);
+			memcpy(out[r].true_peak, pk, sizeof pk);
+			if (hops_out && nh) memcpy(hops_out->data() + (size_t)r * max_hops * 2, mine.data(), nh * 2 * sizeof(double));
+		}
+		return true;
+	}
+	bool begin_loudness(std::string &err) override {
+		use_device();
+		if (loud_own_.state.p) return true;
+		return loud_setup(cfg_.srate, err) && loud_make(loud_own_, cfg_.n_streams, err);
+	}
+	bool measure_loudness(const uint32_t *frames, bool stereo, std::string &err) override {
+		use_device();
+		if (!loud_own_.state.p) { err = "loudness metering has not begun"; return false; }
+		if (!pcm_f32_ || !pcm_.p) { err = "the last run's samples are not float32"; return false; }
+		for (uint32_t s = 0; s < cfg_.n_streams; ++s)
+			if (frames[s] > row_stride_) { err = "frames beyond the streams' rows"; return false; }
+		if (!loud_setup(cfg_.srate, err)) return false; /* (a measure_loudness_rows call at another rate has been in between) */
+		return loud_measure(loud_own_, pcm_.p, pcm_pitch(), frames, stereo ? 2 : 1, err); /* (rows start on 256 bytes: reserve_frames) */
+	}
+	bool read_loudness(sauengine::Loudness *out, bool reset, std::string &err) override {
+		use_device();
+		if (!loud_own_.state.p) { err = "loudness metering has not begun"; return false; }
+		if (!loud_setup(cfg_.srate, err) || !loud_read(loud_own_, out, nullptr, nullptr, err)) return false;
+		return !reset || loud_clear(loud_own_, err);
+	}
+	bool read_loudness_hops(uint32_t stream, double *out, size_t cap, size_t *n_hops, std::string &err) override {
+		use_device();
+		if (!loud_own_.state.p || stream >= cfg_.n_streams) { err = "loudness metering has not begun"; return false; }
+		const uint32_t hop = cfg_.srate / 10;
+		const size_t nh = (size_t)(loud_own_.pos_h[stream] / hop), per = (size_t)loud_own_.rows * 2;
+		*n_hops = nh;
+		if (!out || cap < nh || !nh) return true;
+		/* (the stream's two doubles of every hop: a strided copy, in order behind the measurements on the one stream) */
+		HIP_OK(hipMemcpy2DAsync(out, 2 * sizeof(double), loud_own_.E.p + (size_t)stream * 2, per * sizeof(double), 2 * sizeof(double), nh,
+				hipMemcpyDeviceToHost, stream_));
+		HIP_OK(hipStreamSynchronize(stream_));
+		return true;
+	}
+	bool measure_loudness_rows(const void *rows, size_t pitch, size_t n_rows, size_t frames, bool stereo, uint32_t srate,
+			sauengine::Loudness *out, double *hops_out, size_t hops_cap, std::string &err) override {
+		use_device();
+		const size_t ch = stereo ? 2 : 1, size = sizeof(float);
+		if (!n_rows) return true;
+		if (!rows || ((uintptr_t)rows & 15u) || (pitch & 15u) || !out) { err = "bad argument: rows and pitch_bytes must be multiples of 16"; return false; }
+		if (frames > 0xffffffffull || (n_rows > 1 && frames * ch * size > pitch)) { err = "bad argument: rows longer than their pitch, or than 32 bits of frames"; return false; }
+		if (srate < LOUD_MIN_RATE || n_rows > LOUD_MAX_ROWS) { err = "bad argument: a rate below 2560 Hz, or more than 65535 rows"; return false; }
+		if (frames) { /* the rows are read by kernels: they have to lie inside one allocation of this device */
+			hipPointerAttribute_t at;
+			memset((void *)&at, 0, sizeof at);
+			if (hipPointerGetAttributes(&at, rows) != hipSuccess) { (void)hipGetLastError(); err = "bad argument: rows is not device memory"; return false; }
+			if (at.type != hipMemoryTypeDevice || at.device != dev_) { err = "bad argument: rows must be memory of the batch's device"; return false; }
+			hipDeviceptr_t base = nullptr;
+			size_t span = 0;
+			if (hipMemGetAddressRange(&base, &span, (hipDeviceptr_t)rows) != hipSuccess) { (void)hipGetLastError(); err = "bad argument: rows is not device memory"; return false; }
+			size_t need = 0;
+			const bool wraps = __builtin_mul_overflow(pitch, n_rows - 1, &need) || __builtin_add_overflow(need, frames * ch * size, &need);
+			const size_t ofs = (size_t)((const char *)rows - (const char *)base);
+			if (wraps || ofs > span || need > span - ofs) { err = "bad argument: the rows reach beyond their allocation"; return false; }
+		}
+		const size_t nh = frames / (srate / 10);
+		if (hops_out && hops_cap < n_rows * nh * 2) hops_out = nullptr; /* (nothing is written when the capacity does not suffice) */
+		if (!loud_setup(srate, err) || !loud_make(loud_rows_, n_rows, err)) return false;
+		loud_rows_.channels = (uint32_t)ch;
+		const std::vector<uint32_t> fr(n_rows, (uint32_t)frames);
+		std::vector<double> hops;
+		size_t stride = 0;
+		const bool ok = loud_measure(loud_rows_, rows, pitch, fr.data(), (uint32_t)ch, err) &&
+			loud_read(loud_rows_, out, hops_out ? &hops : nullptr, &stride, err);
+		if (ok && hops_out && !hops.empty()) memcpy(hops_out, hops.data(), hops.size() * sizeof(double)); /* (equal rows: stride == nh) */
+		return ok;
+	}
+
 	const int16_t *device_pcm(uint32_t stream) override { return pcm_.p && !pcm_f32_ ? (const int16_t *)pcm_at(stream) : nullptr; }
 	const float *device_pcm_f32(uint32_t stream) override { return pcm_.p && pcm_f32_ ? (const float *)pcm_at(stream) : nullptr; }
 	size_t device_pcm_pitch() override { return pcm_.p ? pcm_pitch() : 0; }
@@ -1692,6 +1899,16 @@ private:
 	DevBuf<unsigned char> decim_out_;
 	int decim_factor_ = 0;
 	bool decim_stereo_ = false, decim_out_f32_ = false;
+	/* loudness: the streams' records and those of one measure_loudness_rows call, one measurement's scratch (the chunks' zero-state
+	 * results, their start states, their hop sums, the tiles' peaks, the rows' frame counts), the true-peak taps, and the filter
+	 * and chunk map of the rate at hand -- all from the pool, none there until asked for */
+	LoudSet loud_own_, loud_rows_;
+	DevBuf<LoudState> loud_z_, loud_s_;
+	DevBuf<double> loud_parts_, loud_taps_;
+	DevBuf<uint32_t> loud_tp_parts_, loud_frames_;
+	LoudFilter loud_f_;
+	LoudMap loud_m_;
+	uint32_t loud_rate_ = 0;
 	size_t decim_out_pitch_ = 0, decim_out_bytes_ = 0; /* of the last decimated run: between the rows, and of a row's frames */
 	DevBuf<uint32_t> vlists_;   /* [2][n_voices]: analyze_kernel's lists of closed-form and look-back voices (split launches) */
 	/* A chain kernel's workgroup is three waves on a latency-bound recurrence. SAU_AMD_CHAIN_ALONE=1 (a tuning switch): while a

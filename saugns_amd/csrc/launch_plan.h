@@ -779,5 +779,48 @@ inline DecimPlan plan_decimate(uint64_t buf_len, int factor, uint32_t channels, 
 }
 static_assert(2 * DECIM_HALF * 8 * 2 <= DECIM_CARRY_THREADS * 4, "decimate_carry_kernel: a stream's longest history, four floats per thread");
 
+/* ---- loudness and true peak (k_loudness.h) ----
+ * The K-weighting recurrence is made parallel over chunks of LOUD_CHUNK frames: a lane of loud_chunk_kernel owns one chunk of
+ * one (stream, channel). The chunk is part of the result's bits (include/saugns_amd.h: which frames meet in which partial
+ * sum, and where the state is propagated by the 4x4 map instead of frame by frame), so it is a constant and never a function
+ * of the device. A workgroup -- one wave -- owns LOUD_WG_CHUNKS consecutive chunks of one stream and stages them through LDS
+ * LOUD_SUB frames of every chunk at a time: 8 KiB (mono) or 16 KiB (stereo) per step, rows padded by one access width.
+ * The true-peak kernel is laid out like decimate_kernel: a one-wave workgroup owns TP_TILE consecutive frames of one stream,
+ * lane l the TP_PER_LANE frames l, l + 64, ...; its span in LDS is the tile and TP_LEAD frames ahead of it (TP_HIST = 31 of
+ * them are read: the 4x interpolator's 32 taps per phase; 32 are staged and carried so that every 16-byte vector is aligned).
+ * Unlike the chunk, the tile decides speed only: a maximum over bit patterns has no order. */
+constexpr uint32_t LOUD_CHUNK = 256;
+constexpr uint32_t LOUD_THREADS = 64, LOUD_WG_CHUNKS = LOUD_THREADS, LOUD_SUB = 32;
+static_assert(LOUD_CHUNK % LOUD_SUB == 0 && LOUD_SUB % 4 == 0, "a chunk is whole sub-tiles of whole 16-byte vectors");
+constexpr uint32_t LOUD_MIN_RATE = sauengine::LOUD_MIN_RATE;  /* 2560: hop = rate / 10 >= LOUD_CHUNK: a chunk never touches more than two hops */
+constexpr uint32_t TP_FACTOR = 4, TP_HALF = 16, TP_TAPS = 2 * TP_HALF * TP_FACTOR + 1; /* 129 taps g[], 32 per phase */
+constexpr uint32_t TP_HIST = 2 * TP_HALF - 1, TP_LEAD = 2 * TP_HALF;
+static_assert(TP_TAPS == sauengine::TP_TAPS && TP_LEAD == sauengine::TP_LEAD, "engine.h: the host's copies");
+constexpr uint32_t TP_THREADS = 64, TP_PER_LANE = 4, TP_TILE = TP_THREADS * TP_PER_LANE;
+constexpr uint32_t LOUD_MAX_ROWS = 65535; /* grid.y */
+struct LoudPlan {
+	bool ok = false;          /* false: channels not 1 or 2, a rate below LOUD_MIN_RATE, more rows or frames than a grid has */
+	uint32_t hop = 0;         /* frames of a 100 ms hop: rate / 10 */
+	uint32_t chunks = 0;      /* chunks of the longest row (0: nothing to measure, no launch) */
+	uint32_t chunk_grid = 0;  /* grid.x of loud_chunk_kernel: LOUD_WG_CHUNKS chunks per workgroup */
+	uint32_t tiles = 0;       /* grid.x of truepeak_kernel */
+	uint32_t rows = 0;        /* grid.y of both, and the lanes of the scan and finish kernels */
+	uint32_t lane_grid = 0;   /* loud_scan_kernel (a lane per row and channel) and loud_finish_kernel: 64 lanes per workgroup */
+	uint32_t lds_bytes = 0;   /* of loud_chunk_kernel */
+};
+inline LoudPlan plan_loudness(uint64_t max_frames, uint32_t channels, size_t n_rows, uint32_t srate) {
+	LoudPlan p;
+	if ((channels != 1 && channels != 2) || srate < LOUD_MIN_RATE || n_rows > LOUD_MAX_ROWS || max_frames > 0xffffffffull) return p;
+	p.ok = true;
+	p.hop = srate / 10;
+	p.chunks = (uint32_t)((max_frames + LOUD_CHUNK - 1) / LOUD_CHUNK);
+	p.chunk_grid = (p.chunks + LOUD_WG_CHUNKS - 1) / LOUD_WG_CHUNKS;
+	p.tiles = (uint32_t)((max_frames + TP_TILE - 1) / TP_TILE);
+	p.rows = (uint32_t)n_rows;
+	p.lane_grid = (uint32_t)((n_rows * 2 + 63) / 64);
+	p.lds_bytes = LOUD_WG_CHUNKS * (LOUD_SUB * channels + channels) * (uint32_t)sizeof(float);
+	return p;
+}
+
 } /* namespace sauplan */
 #endif

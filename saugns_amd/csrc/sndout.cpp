@@ -16,6 +16,7 @@
 #include "hip_backend.h"
 #include "capi_internal.h"
 #include <float.h>
+#include <math.h>
 #include <stdio.h>
 #include <string.h>
 #include <exception>
@@ -216,6 +217,26 @@ bool measure_program(const sauProgram *prg, uint32_t srate, bool stereo, Backend
 	return ok;
 }
 
+/* Pass 1 of the loudness-normalised writer: the same runs with loudness metering on, nothing fetched -> the program's record.
+ * Every refusal of a backend without float output or loudness metering happens here, before there is a file. */
+bool measure_program_loudness(const sauProgram *prg, uint32_t srate, bool stereo, Backend *backend /* owned */, sauengine::Loudness &ld,
+		std::string &err) {
+	Engine *engine = Engine::create(&prg, 1, srate, backend, err);
+	if (!engine) return false;
+	size_t call, chunk;
+	file_lattice(srate, call, chunk);
+	engine->set_call_len(call);
+	bool ok = engine->set_format(sauengine::SF_F32, err) && engine->set_loudness(true, err);
+	bool more = ok;
+	while (ok && more) {
+		size_t len = 0;
+		ok = engine->run_f32(nullptr, chunk, stereo, &more, &len, err);
+	}
+	ok = ok && engine->loudness(&ld, false, err);
+	delete engine; /* owns the backend */
+	return ok;
+}
+
 /* Pass 2: the same runs on a fresh engine, each through requant_kernel into a device buffer of its own and from there
  * through the two page-locked slots to the file, as render_file_over's chunks go. */
 bool write_scaled(const sauProgram *prg, uint32_t srate, const char *path, int format, int channels, float gain,
@@ -380,6 +401,47 @@ extern "C" bool sauAmd_render_file_normalized(const sauProgram *prg, uint32_t sr
 	try {
 		ok = sauamd_internal::render_file_normalized(prg, srate, path, format, channels, target_peak,
 				[](std::string &e) -> Backend * { return sauhip::create_hip_backend(e); }, frames_out, levels_out, err);
+	} catch (const std::exception &ex) { /* (nothing C++ crosses the C ABI) */
+		err = std::string("internal error: ") + ex.what();
+	}
+	if (!ok) sauamd_internal::set_last_error("output", err);
+	return ok;
+}
+
+bool sauamd_internal::render_file_loudness(const sauProgram *prg, uint32_t srate, const char *path, int format, int channels,
+		double target_lufs, float max_true_peak, const std::function<Backend *(std::string &)> &make_backend, uint64_t *frames_out,
+		sauAmdLoudness *loud_out, float *gain_out, std::string &err) {
+	if (frames_out) *frames_out = 0;
+	if (!prg || !path || (channels != 1 && channels != 2) || format < 0 || format > SAU_AMD_SNDFILE_WAV_F32 ||
+	    !(target_lufs >= -DBL_MAX && target_lufs <= DBL_MAX) || !(max_true_peak > 0.f) || !(max_true_peak <= FLT_MAX) ||
+	    srate < sauengine::LOUD_MIN_RATE) { /* (a NaN fails every comparison) */
+		err = "bad argument";
+		return false;
+	}
+	Backend *first = make_backend(err);
+	if (!first) return false;
+	sauengine::Loudness ld;
+	if (!measure_program_loudness(prg, srate, channels == 2, first, ld, err)) return false;
+	if (loud_out) memcpy(loud_out, &ld, sizeof ld);
+	const float tp = ld.true_peak[0] > ld.true_peak[1] ? ld.true_peak[0] : ld.true_peak[1];
+	float gain = 1.0f;
+	if (ld.integrated > -HUGE_VAL) {
+		gain = (float)pow(10.0, (target_lufs - ld.integrated) / 20.0);
+		if (tp * gain > max_true_peak) gain = max_true_peak / tp; /* the ceiling binds: one f32 division */
+	}
+	if (gain_out) *gain_out = gain;
+	Backend *second = make_backend(err);
+	if (!second) return false;
+	return write_scaled(prg, srate, path, format, channels, gain, second, frames_out, err);
+}
+
+extern "C" bool sauAmd_render_file_loudness(const sauProgram *prg, uint32_t srate, const char *path, int format, int channels,
+		double target_lufs, float max_true_peak, uint64_t *frames_out, sauAmdLoudness *loud_out, float *gain_out) {
+	std::string err;
+	bool ok = false;
+	try {
+		ok = sauamd_internal::render_file_loudness(prg, srate, path, format, channels, target_lufs, max_true_peak,
+				[](std::string &e) -> Backend * { return sauhip::create_hip_backend(e); }, frames_out, loud_out, gain_out, err);
 	} catch (const std::exception &ex) { /* (nothing C++ crosses the C ABI) */
 		err = std::string("internal error: ") + ex.what();
 	}

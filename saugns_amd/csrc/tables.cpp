@@ -192,11 +192,10 @@ double bessel_i0(double x) {
 
 size_t decimator_latency(int factor) { return factor == 2 || factor == 4 || factor == 8 ? DECIM_HALF : 0; }
 
-size_t decimator_taps(int factor, double *out, size_t cap) {
-	if (!decimator_latency(factor)) return 0;
-	const size_t K = (size_t)factor, C = DECIM_HALF * K, L = 2 * C + 1;
-	if (!out || cap < L) return L;
-	const double beta = 10.06, pi = 3.14159265358979323846, i0b = bessel_i0(beta);
+/* g[n], n = 0 .. 2C: the Kaiser-windowed sinc with K input frames per lobe, not normalised (g[C] = 1) */
+static void kaiser_sinc(size_t K, size_t C, double beta, double *out) {
+	const double pi = 3.14159265358979323846, i0b = bessel_i0(beta);
+	const size_t L = 2 * C + 1;
 	for (size_t n = 0; n <= C; ++n) {
 		const double d = (double)n - (double)C; /* n - C */
 		const double t = d / (double)K, r = d / (double)C;
@@ -205,10 +204,125 @@ size_t decimator_taps(int factor, double *out, size_t cap) {
 		out[n] = sinc * bessel_i0(beta * sqrt(w > 0.0 ? w : 0.0)) / i0b;
 	}
 	for (size_t n = 0; n < C; ++n) out[L - 1 - n] = out[n];
+}
+
+size_t decimator_taps(int factor, double *out, size_t cap) {
+	if (!decimator_latency(factor)) return 0;
+	const size_t K = (size_t)factor, C = DECIM_HALF * K, L = 2 * C + 1;
+	if (!out || cap < L) return L;
+	kaiser_sinc(K, C, 10.06, out);
 	double S = 0.0;
 	for (size_t n = 0; n < L; ++n) S += out[n];
 	for (size_t n = 0; n < L; ++n) out[n] /= S;
 	return L;
+}
+
+/* ---- loudness on the host (engine.h; include/saugns_amd.h states every formula and the order of every operation) ---- */
+
+size_t truepeak_taps(double *out, size_t cap) {
+	if (!out || cap < TP_TAPS) return TP_TAPS;
+	kaiser_sinc(4, 64, 5.0, out); /* K = 4, H = 16 input frames: C = H * K */
+	return TP_TAPS;
+}
+
+bool loudness_filter(uint32_t srate, double out[10]) {
+	if (srate < LOUD_MIN_RATE || !out) return false;
+	const double pi = 3.14159265358979323846, fs = (double)srate;
+	{ /* stage 1: high shelf */
+		const double f0 = 1681.974450955533, G = 3.999843853973347, Q = 0.7071752369554196;
+		const double K = tan(pi * f0 / fs), Vh = pow(10.0, G / 20.0), Vb = pow(Vh, 0.4996667741545416), a0 = 1.0 + K / Q + K * K;
+		out[0] = (Vh + Vb * K / Q + K * K) / a0;
+		out[1] = 2.0 * (K * K - Vh) / a0;
+		out[2] = (Vh - Vb * K / Q + K * K) / a0;
+		out[3] = 2.0 * (K * K - 1.0) / a0;
+		out[4] = (1.0 - K / Q + K * K) / a0;
+	}
+	{ /* stage 2: high-pass */
+		const double f0 = 38.13547087602444, Q = 0.5003270373238773;
+		const double K = tan(pi * f0 / fs), a0 = 1.0 + K / Q + K * K;
+		out[5] = 1.0; out[6] = -2.0; out[7] = 1.0;
+		out[8] = 2.0 * (K * K - 1.0) / a0;
+		out[9] = (1.0 - K / Q + K * K) / a0;
+	}
+	return true;
+}
+
+double loudness_step(double st[4], const double f[10], double x) {
+	const double u = f[0] * x + st[0];
+	st[0] = (f[1] * x - f[3] * u) + st[1];
+	st[1] = f[2] * x - f[4] * u;
+	const double y = f[5] * u + st[2];
+	st[2] = (f[6] * u - f[8] * y) + st[3];
+	st[3] = f[7] * u - f[9] * y;
+	return y;
+}
+
+void loudness_chunk_map(const double f[10], uint32_t chunk, double m[16]) {
+	for (int k = 0; k < 4; ++k) {
+		double st[4] = {0.0, 0.0, 0.0, 0.0};
+		st[k] = 1.0;
+		for (uint32_t i = 0; i < chunk; ++i) (void)loudness_step(st, f, 0.0);
+		for (int r = 0; r < 4; ++r) m[4 * r + k] = st[r];
+	}
+}
+
+bool loudness_gate(const double *hops, size_t n_hops, uint32_t hop_frames, int channels, Loudness *out) {
+	if (!out || (n_hops && !hops) || !hop_frames || (channels != 1 && channels != 2)) return false;
+	const size_t n_blocks = n_hops >= 4 ? n_hops - 3 : 0;
+	const double den = 4.0 * (double)hop_frames;
+	auto z_of = [&](size_t j) {
+		double z = 0.0;
+		for (int ch = 0; ch < channels; ++ch) {
+			const double *e = hops + 2 * j + ch;
+			z = z + (((e[0] + e[2]) + e[4]) + e[6]) / den;
+		}
+		return z;
+	};
+	auto lufs = [](double z) { return z > 0.0 ? -0.691 + 10.0 * log10(z) : -HUGE_VAL; };
+	double mmax = -HUGE_VAL, sum_abs = 0.0;
+	size_t n_abs = 0;
+	for (size_t j = 0; j < n_blocks; ++j) {
+		const double z = z_of(j), l = lufs(z);
+		if (l > mmax) mmax = l;
+		if (l > -70.0) { sum_abs += z; ++n_abs; }
+	}
+	double integrated = -HUGE_VAL;
+	size_t n_gated = 0;
+	if (n_abs) {
+		const double rel = lufs(sum_abs / (double)n_abs) - 10.0;
+		double sum = 0.0;
+		for (size_t j = 0; j < n_blocks; ++j) {
+			const double z = z_of(j), l = lufs(z);
+			if (l > -70.0 && l > rel) { sum += z; ++n_gated; }
+		}
+		if (n_gated) integrated = lufs(sum / (double)n_gated);
+	}
+	out->frames = (uint64_t)n_hops * hop_frames;
+	out->blocks = n_blocks;
+	out->gated_blocks = n_gated;
+	out->integrated = integrated;
+	out->momentary_max = mmax;
+	out->true_peak[0] = out->true_peak[1] = 0.f;
+	return true;
+}
+
+void truepeak_tail(const float *hist, int channels, const double *taps, uint32_t *peak_bits) {
+	/* position N + t, t = 0 .. 30: x[N + t - q] is hist frame TP_LEAD + t - q for t - q < 0, else +0 */
+	for (int ch = 0; ch < channels; ++ch)
+		for (int t = 0; t < (int)TP_LEAD - 1; ++t)
+			for (int p = 1; p < 4; ++p) {
+				double acc = 0.0;
+				for (int q = 0; q < 32; ++q) {
+					const int i = (int)TP_LEAD + t - q;
+					const double x = i < (int)TP_LEAD ? (double)hist[i * channels + ch] : 0.0;
+					acc = acc + taps[4 * q + p] * x;
+				}
+				const float w = (float)acc;
+				uint32_t b;
+				memcpy(&b, &w, 4);
+				b &= 0x7fffffffu;
+				if (b < 0x7f800000u && b > peak_bits[ch]) peak_bits[ch] = b;
+			}
 }
 
 } /* namespace sauengine */
