@@ -361,7 +361,7 @@ SAU_AMD_API bool sauAmd_loudness_gate(const double *hops /* [n_hops][2] */, size
  * the device measuring stream i over the frames [0, out_len[i]) of that run -- on the batch's stream, before any copy to the
  * host -- into stream i's record on the device: hop energies (16 bytes per 100 ms, growing with the stream), filter state,
  * true peak, the 31-frame history, the frame count. Independent of sauAmd_Batch_set_metering; both may be on. While on,
- * sauAmd_Batch_run, sauAmd_Batch_run_decimated_f32 and a float run of the other channel layout than the record's are refused
+ * sauAmd_Batch_run, sauAmd_Batch_run_decimated_f32, sauAmd_Batch_run_limited_f32 and a float run of the other channel layout than the record's are refused
  * as a bad argument: nothing is rendered and the batch stands where it stood. False (sauAmd_last_error), with nothing
  * changed, on a backend without it or a batch rate below 2560 Hz; switching it off always succeeds and keeps the records. */
 SAU_AMD_API bool sauAmd_Batch_set_loudness(sauAmdBatch *b, int on);
@@ -388,6 +388,101 @@ SAU_AMD_API bool sauAmd_Batch_measure_loudness_rows(sauAmdBatch *b, const void *
  * or <= 0, srate < 2560 -- or a backend without float output or loudness metering. */
 SAU_AMD_API bool sauAmd_render_file_loudness(const sauProgram *prg, uint32_t srate, const char *path, int format, int channels,
 		double target_lufs, float max_true_peak, uint64_t *frames_out, sauAmdLoudness *loud_out, float *gain_out);
+
+/* ---- Limiter -------------------------------------------------------------------
+ * sauAmd_render_file_loudness lowers the gain of the whole file where true_peak * gain would pass the ceiling, so one loud
+ * transient leaves a file several dB under the loudness asked for. A look-ahead true-peak limiter closes that gap: it lowers
+ * the gain around the peaks only. It runs where the samples are, on the float rows of sauAmd_Batch_run_f32.
+ *
+ * The limiter is feed-forward and non-recursive: its output is a function of the input sequence only, never of how the
+ * sequence is cut into runs, of tiles, or of the partition of the device. The arithmetic is a fixed order of IEEE operations
+ * (the build is -ffp-contract=off), reproducible bit for bit.
+ *
+ * Constants, for the rate fs: look-ahead A = min(max(fs / 200, 16), 1024) frames (integer division: 5 ms, clamped); delay
+ * D = 2 A + 16 frames; g[0 .. 128] the taps of sauAmd_truepeak_taps. Parameters: pre_gain g0 and ceiling c, floats, finite
+ * and > 0. x[i][ch] is the stream's float sample of frame i, counted from the start of the limited sequence; a NaN or +-inf
+ * counts as +0.0f; x is +0.0f for i < 0 and for every frame at or behind the stream's end.
+ *  1. Interpolated points, the loudness section's: for p = 1, 2, 3: acc = +0.0; for q = 0 .. 31 ascending:
+ *     acc = acc + g[4 q + p] * (double)x[m - q][ch]; w[m][p][ch] = (float)acc -- the point at time m - 16 + p / 4.
+ *  2. Envelope, the channels linked: e[i] = the largest, compared as bit patterns, over ch and p, of |x[i][ch]|, every finite
+ *     |w[i + 15][p][ch]| and every finite |w[i + 16][p][ch]|: the sample and the three points on either side of it.
+ *  3. Required gain, f64: E = (double)e[i] * (double)g0 (exact); r[i] = 1.0 when E <= (double)c, else (double)c / E;
+ *     s[i] = 1.0 - r[i].
+ *  4. Hold: d[k] = max(s[k - A .. k + A]) -- exact, so any order of evaluation gives the same value.
+ *  5. Smoothing window, f64 on the host: u[j] = 1.0 + cos(pi * (j - A) / (A + 1)) for j = 0 .. 2A, S the sum of u in
+ *     ascending j, h[j] = u[j] / S (sauAmd_limiter_window).
+ *  6. Gain: acc = +0.0; for j = 0 .. 2A ascending: acc = acc + h[j] * d[i - A + j]; G[i] = min(1.0 - acc, r[i]). Where
+ *     nothing within +-2A frames needs reduction every d is +0.0 and G[i] is exactly 1.0.
+ *  7. Output: y[i][ch] = (float)(((double)x[i][ch] * (double)g0) * G[i]); the int16 formats take pcm16(y), the kernels' own
+ *     rounding, byte-swapped on the device for AU.
+ * Two consequences. |y[i][ch]| <= c as floats, exactly: G <= r, both products round monotonically, and c (1 + 2^-52) rounds
+ * to the float c. Where G[i] == 1.0, y is (float)((double)x * (double)g0): with g0 == 1 the untouched passages pass through
+ * bit for bit.
+ * The true peak of y -- the peaks between its samples -- is NOT bounded exactly: a gain that varies in time moves them.
+ * Measured with the loudness section's interpolator on this arithmetic (noise, a faded quarter-rate sine at 45 degrees, a
+ * 50 Hz sine and a 20x burst, each mono and stereo at 3200, 8000 and 44100 Hz, at 5 to 12 dB of reduction) the true peak of y passed c
+ * by at most +0.0121 dB at 3200 Hz (noise, A = 16), +0.0007 dB at 8000 Hz and less than 0.00001 dB at 44100 Hz; a caller
+ * that needs the ceiling held between the samples at a low rate leaves that margin under it.
+ * Limiting lowers the integrated loudness slightly below the target of sauAmd_render_file_loudness_limited; no third pass
+ * corrects it.
+ * Limits: float runs only; decimated rows are not limited; limited rows are not loudness-metered; the release is the
+ * symmetric window's, no longer. */
+typedef struct sauAmdLimiterStats {
+	uint64_t frames;    /* delivered output frames */
+	uint64_t limited;   /* those of them with G < 1.0 */
+	double   min_gain;  /* the smallest G delivered; 1.0 before any */
+} sauAmdLimiterStats;
+#ifdef __cplusplus
+static_assert(sizeof(sauAmdLimiterStats) == 24, "sauAmdLimiterStats is 24 bytes");
+#else
+_Static_assert(sizeof(sauAmdLimiterStats) == 24, "sauAmdLimiterStats is 24 bytes");
+#endif
+
+/* sauAmd_limiter_window: 2 A + 1, and the window h in out[] when cap >= 2 A + 1 (nothing is written when cap is less; out may
+ * then be NULL). sauAmd_limiter_latency: D. Both 0 for srate == 0. */
+SAU_AMD_API size_t sauAmd_limiter_window(uint32_t srate, double *out, size_t cap);
+SAU_AMD_API size_t sauAmd_limiter_latency(uint32_t srate);
+/* A float run of buf_len frames, then the limiter on the batch's stream. Every stream's limited row -- and bufs[i] when given
+ * (bufs may be NULL) -- holds buf_len valid frames: the sequence delayed by D, so that position P + n of the sequence holds
+ * y[P + n - D] (y[i] = +0.0f for i < 0). The input is zero-extended behind the stream's end: a stream's tail therefore appears
+ * in later runs, and a run after every stream has ended renders nothing and still delivers. more[i] and out_len[i] are the
+ * float run's. The history belongs to a sequence of limited runs with the same (pre_gain, ceiling, stereo): a limited run
+ * that follows any other kind of run, or one with another of the three, starts from zero history. Level metering, when on,
+ * measures the float run as it does for a decimated run. False (sauAmd_last_error) with "bad argument" on parameters that are
+ * not finite and positive, while loudness metering is on (see sauAmd_Batch_set_loudness), and on a backend without a limiter
+ * or float output; nothing is rendered then and the batch stands where it stood. A batch that never makes a limited run
+ * allocates and does nothing for it. */
+SAU_AMD_API bool sauAmd_Batch_run_limited_f32(sauAmdBatch *b, float pre_gain, float ceiling, float *const *bufs, size_t buf_len,
+		bool stereo, bool *more, size_t *out_len);
+/* Device address of stream i's limited float row of the last limited run (NULL before one), and the bytes between the rows of
+ * consecutive streams. The rows are 16-byte aligned and the pitch is a multiple of 256. Valid until the batch's next limited
+ * run (call sauAmd_Batch_sync first: the run is asynchronous). */
+SAU_AMD_API const float *sauAmd_Batch_device_limited_f32(sauAmdBatch *b, size_t stream);
+SAU_AMD_API size_t sauAmd_Batch_device_limited_pitch(sauAmdBatch *b);
+/* Wait for the batch's stream and fetch one record per stream: every frame the batch's limited runs have delivered since the
+ * last reset, the D frames ahead of a sequence's first sample and the tail included. The records run on through the batch's
+ * sequences; reset != 0 then clears them. Empty records (0, 0, 1.0) before any limited run. */
+SAU_AMD_API bool sauAmd_Batch_limiter_stats(sauAmdBatch *b, sauAmdLimiterStats *out /* [streams] */, int reset);
+/* The limiter from zero history on n_rows float32 rows the caller holds on the batch's device, at the rate srate (> 0):
+ * out_rows[r] receives `frames` float frames, time-aligned -- out[i] = y[i], the delay dropped -- and stats_out[r] (may be
+ * NULL) the row's record over those frames. The argument rules are sauAmd_Batch_measure_loudness_rows', for rows and for
+ * out_rows alike (any rate above 0); output rows that overlap the input rows are refused. Synchronous; the batch's own
+ * histories and records are untouched. frames == 0 gives empty records. */
+SAU_AMD_API bool sauAmd_Batch_limit_rows(sauAmdBatch *b, const void *rows, size_t pitch_bytes, size_t n_rows, size_t frames,
+		int channels, uint32_t srate, float pre_gain, float ceiling, void *out_rows, size_t out_pitch_bytes,
+		sauAmdLimiterStats *stats_out /* [n_rows] */);
+/* sauAmd_render_file_loudness with the limiter in place of the lowered gain. Pass 1 is the same; then
+ *   gain = (float)pow(10.0, (target_lufs - integrated) / 20.0), never reduced for the ceiling (1 when integrated is -HUGE_VAL);
+ * pass 2 makes the same runs on the same call lattice, each through the limiter with pre_gain = gain and ceiling =
+ * max_true_peak into rows of the file's format; the first D frames are dropped and one last run of D frames behind the
+ * program's end is made, so the file holds exactly the frames sauAmd_render_file writes. No sample of it exceeds
+ * max_true_peak; its true peak may, by the gap stated above. Limiting lowers the integrated loudness slightly below the
+ * target, and no third pass corrects it. *stats_out (may be NULL) is pass 2's record: it counts the D frames ahead of the
+ * file's first and the rest of the last run behind its last too. The argument refusals are sauAmd_render_file_loudness',
+ * before any file is created; so is that of a backend without float output, loudness metering or a limiter. */
+SAU_AMD_API bool sauAmd_render_file_loudness_limited(const sauProgram *prg, uint32_t srate, const char *path, int format,
+		int channels, double target_lufs, float max_true_peak, uint64_t *frames_out, sauAmdLoudness *loud_out, float *gain_out,
+		sauAmdLimiterStats *stats_out);
 
 #ifdef __cplusplus
 }

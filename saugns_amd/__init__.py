@@ -3,7 +3,8 @@
 The product is ``libsaugns_amd.so`` (HIP kernels + C++ host control plane behind
 the reference's C API); this package builds it in-tree and binds it with ctypes.
 """
-from .api import (Batch, Generator, Levels, Loudness, Program, SNDFILE_AU, SNDFILE_RAW, SNDFILE_WAV,  # noqa: F401
-                  decimator_latency, decimator_taps, get_piluts, last_error, lib, loudness_filter, loudness_gate, render_file,
-                  render_file_loudness, render_file_normalized, render_file_oversampled, set_piluts, truepeak_taps)
+from .api import (Batch, Generator, Levels, LimiterStats, Loudness, Program, SNDFILE_AU, SNDFILE_RAW, SNDFILE_WAV,  # noqa: F401
+                  decimator_latency, decimator_taps, get_piluts, last_error, lib, limiter_latency, limiter_window,
+                  loudness_filter, loudness_gate, render_file, render_file_loudness, render_file_loudness_limited,
+                  render_file_normalized, render_file_oversampled, set_piluts, truepeak_taps)
 from .build import build  # noqa: F401

@@ -124,6 +124,20 @@ class Loudness(C.Structure):
 assert C.sizeof(Loudness) == 48
 
 
+class LimiterStats(C.Structure):
+    """sauAmdLimiterStats (include/saugns_amd.h): what the limiter did to one stream or row."""
+    _fields_ = [("frames", C.c_uint64), ("limited", C.c_uint64), ("min_gain", C.c_double)]
+
+    def as_dict(self):
+        return {"frames": int(self.frames), "limited": int(self.limited), "min_gain": float(self.min_gain)}
+
+    def __repr__(self):
+        return "LimiterStats(%r)" % (self.as_dict(),)
+
+
+assert C.sizeof(LimiterStats) == 24
+
+
 def _declare(L):
     """The C ABI of include/saugns_amd.h on a loaded library."""
     L.sau_create_Generator.restype = C.c_void_p
@@ -213,6 +227,27 @@ def _declare(L):
         L.sauAmd_render_file_loudness.restype = C.c_bool
         L.sauAmd_render_file_loudness.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_int, C.c_int, C.c_double, C.c_float,
                                                   C.POINTER(C.c_uint64), C.POINTER(Loudness), C.POINTER(C.c_float)]
+    if hasattr(L, "sauAmd_Batch_run_limited_f32"):  # the limiter (SAU_AMD_LIB may name an older build)
+        L.sauAmd_limiter_window.restype = C.c_size_t
+        L.sauAmd_limiter_window.argtypes = [C.c_uint32, C.POINTER(C.c_double), C.c_size_t]
+        L.sauAmd_limiter_latency.restype = C.c_size_t
+        L.sauAmd_limiter_latency.argtypes = [C.c_uint32]
+        L.sauAmd_Batch_run_limited_f32.restype = C.c_bool
+        L.sauAmd_Batch_run_limited_f32.argtypes = [C.c_void_p, C.c_float, C.c_float, C.POINTER(C.c_void_p), C.c_size_t, C.c_bool,
+                                                   C.POINTER(C.c_bool), C.POINTER(C.c_size_t)]
+        L.sauAmd_Batch_device_limited_f32.restype = C.c_void_p
+        L.sauAmd_Batch_device_limited_f32.argtypes = [C.c_void_p, C.c_size_t]
+        L.sauAmd_Batch_device_limited_pitch.restype = C.c_size_t
+        L.sauAmd_Batch_device_limited_pitch.argtypes = [C.c_void_p]
+        L.sauAmd_Batch_limiter_stats.restype = C.c_bool
+        L.sauAmd_Batch_limiter_stats.argtypes = [C.c_void_p, C.POINTER(LimiterStats), C.c_int]
+        L.sauAmd_Batch_limit_rows.restype = C.c_bool
+        L.sauAmd_Batch_limit_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_uint32,
+                                              C.c_float, C.c_float, C.c_void_p, C.c_size_t, C.POINTER(LimiterStats)]
+        L.sauAmd_render_file_loudness_limited.restype = C.c_bool
+        L.sauAmd_render_file_loudness_limited.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_int, C.c_int, C.c_double,
+                                                          C.c_float, C.POINTER(C.c_uint64), C.POINTER(Loudness),
+                                                          C.POINTER(C.c_float), C.POINTER(LimiterStats)]
     L.sauAmd_set_piluts.argtypes = [C.c_void_p]
     L.sauAmd_get_piluts.restype = C.POINTER(C.c_float)
     L.sauAmd_last_error.restype = C.c_char_p
@@ -445,6 +480,63 @@ def render_file_loudness(program, srate, path, fmt=SNDFILE_WAV, channels=1, targ
     if not ok:
         raise RuntimeError("sauAmd_render_file_loudness failed: " + last_error(L))
     return n.value, ld, gain.value
+
+
+_limiter_hooks = None
+
+
+def use_limiter_hooks(path):
+    """tests/ only: load the library that runs the limited file writer over an injected backend
+    (tests/hooks_limiter: the product's object files + sauAmd_render_file_loudness_limited_with_backend)."""
+    global _limiter_hooks
+    if _limiter_hooks is None:
+        L = _declare(C.CDLL(path))
+        L.sauAmd_render_file_loudness_limited_with_backend.restype = C.c_bool
+        L.sauAmd_render_file_loudness_limited_with_backend.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_int, C.c_int,
+                                                                       C.c_double, C.c_float, C.c_void_p, C.POINTER(C.c_uint64),
+                                                                       C.POINTER(Loudness), C.POINTER(C.c_float),
+                                                                       C.POINTER(LimiterStats)]
+        _limiter_hooks = L
+    return _limiter_hooks
+
+
+def render_file_loudness_limited(program, srate, path, fmt=SNDFILE_WAV, channels=1, target_lufs=-23.0, max_true_peak=1.0,
+                                 backend=None):
+    """sauAmd_render_file_loudness_limited: render a whole program into a file at the gain that reaches `target_lufs`, with a
+    look-ahead limiter holding every sample at or under `max_true_peak` -> (frames written, Loudness of the render before the
+    gain, the gain, LimiterStats of the writing pass). ``backend`` (tests): a sauengine::Backend* for the first pass, without
+    a GPU."""
+    n, ld, gain, st = C.c_uint64(), Loudness(), C.c_float(), LimiterStats()
+    if backend is None:
+        L = _used(lib())
+        ok = L.sauAmd_render_file_loudness_limited(program.ptr, srate, os.fsencode(path), fmt, channels, target_lufs,
+                                                   max_true_peak, C.byref(n), C.byref(ld), C.byref(gain), C.byref(st))
+    else:
+        if _limiter_hooks is None:
+            raise RuntimeError("the limiter-hook library is not loaded (use_limiter_hooks)")
+        L = _used(_limiter_hooks)
+        ok = L.sauAmd_render_file_loudness_limited_with_backend(program.ptr, srate, os.fsencode(path), fmt, channels, target_lufs,
+                                                                max_true_peak, backend, C.byref(n), C.byref(ld), C.byref(gain),
+                                                                C.byref(st))
+    if not ok:
+        raise RuntimeError("sauAmd_render_file_loudness_limited failed: " + last_error(L))
+    return n.value, ld, gain.value, st
+
+
+def limiter_window(srate):
+    """sauAmd_limiter_window: the limiter's smoothing window h, 2 A + 1 float64 values, for a rate (empty for rate 0) -- the
+    one definition the device, the writer and the tests share."""
+    L = lib()
+    n = int(L.sauAmd_limiter_window(int(srate), None, 0))
+    out = np.zeros(n, np.float64)
+    if n:
+        L.sauAmd_limiter_window(int(srate), out.ctypes.data_as(C.POINTER(C.c_double)), n)
+    return out
+
+
+def limiter_latency(srate):
+    """sauAmd_limiter_latency: the limiter's delay D = 2 A + 16 in frames for a rate (0 for rate 0)."""
+    return int(lib().sauAmd_limiter_latency(int(srate)))
 
 
 def loudness_filter(srate):
@@ -739,6 +831,48 @@ class Batch:
                                                                  hops.ctypes.data_as(C.POINTER(C.c_double)), hops.size):
             raise RuntimeError("sauAmd_Batch_measure_loudness_rows failed: " + last_error(self._L))
         return list(out)[:n_rows], hops
+
+    def run_limited(self, pre_gain, ceiling, buf_len, stereo=False, fetch=True):
+        """sauAmd_Batch_run_limited_f32: a float run of buf_len frames, limited on the device
+        -> (float32 [n, buf_len*ch] or None, more[n], out_len[n]) with more and out_len the float run's. Every row holds buf_len
+        valid frames of the sequence delayed by limiter_latency(rate); the rows stay on the device (device_limited_f32)."""
+        ch = 2 if stereo else 1
+        more = (C.c_bool * self.n)()
+        lens = (C.c_size_t * self.n)()
+        if fetch:
+            pcm = np.zeros((self.n, buf_len * ch), np.float32)
+            ptrs = (C.c_void_p * self.n)(*[pcm[i].ctypes.data for i in range(self.n)])
+        else:
+            pcm, ptrs = None, None
+        ok = _used(self._L).sauAmd_Batch_run_limited_f32(self._b, pre_gain, ceiling, ptrs, buf_len, stereo, more, lens)
+        if not ok:
+            raise RuntimeError("sauAmd_Batch_run_limited_f32 failed: " + last_error(self._L))
+        return pcm, [bool(m) for m in more], [int(x) for x in lens]
+
+    def device_limited_f32(self, stream):
+        """Device address of the stream's limited float32 row of the last limited run; None before one."""
+        return self._L.sauAmd_Batch_device_limited_f32(self._b, stream)
+
+    def device_limited_pitch(self):
+        """Bytes between the limited rows of consecutive streams (a multiple of 256)."""
+        return int(self._L.sauAmd_Batch_device_limited_pitch(self._b))
+
+    def limiter_stats(self, reset=False):
+        """sauAmd_Batch_limiter_stats: wait for the batch's stream -> the streams' records, a list of LimiterStats."""
+        out = (LimiterStats * self.n)()
+        if not _used(self._L).sauAmd_Batch_limiter_stats(self._b, out, 1 if reset else 0):
+            raise RuntimeError("sauAmd_Batch_limiter_stats failed: " + last_error(self._L))
+        return list(out)
+
+    def limit_rows(self, ptr, pitch, n_rows, frames, channels, srate, pre_gain, ceiling, out_ptr, out_pitch):
+        """sauAmd_Batch_limit_rows: the limiter from zero history on n_rows float32 rows of device memory at `ptr`, `pitch`
+        bytes apart, into the float32 rows at `out_ptr`, `out_pitch` bytes apart, time-aligned -> a list of LimiterStats."""
+        n_rows = int(n_rows)
+        out = (LimiterStats * max(n_rows, 1))()
+        if not _used(self._L).sauAmd_Batch_limit_rows(self._b, ptr, pitch, n_rows, int(frames), channels, int(srate), pre_gain,
+                                                      ceiling, out_ptr, out_pitch, out):
+            raise RuntimeError("sauAmd_Batch_limit_rows failed: " + last_error(self._L))
+        return list(out)[:n_rows]
 
     def device_pcm(self, stream):
         """Device address of the stream's int16 row of the last run; None after a float32 run."""

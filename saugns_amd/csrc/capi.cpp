@@ -518,6 +518,61 @@ extern "C" bool sauAmd_Batch_measure_loudness_rows(sauAmdBatch *b, const void *r
 	return false;
 }
 
+static_assert(sizeof(sauAmdLimiterStats) == sizeof(sauengine::LimiterStats) && offsetof(sauAmdLimiterStats, limited) == offsetof(sauengine::LimiterStats, limited) &&
+	offsetof(sauAmdLimiterStats, min_gain) == offsetof(sauengine::LimiterStats, min_gain), "sauengine::LimiterStats is sauAmdLimiterStats");
+
+extern "C" size_t sauAmd_limiter_window(uint32_t srate, double *out, size_t cap) { return sauengine::limiter_window(srate, out, cap); }
+extern "C" size_t sauAmd_limiter_latency(uint32_t srate) { return sauengine::limiter_latency(srate); }
+
+extern "C" bool sauAmd_Batch_run_limited_f32(sauAmdBatch *b, float pre_gain, float ceiling, float *const *bufs, size_t buf_len,
+		bool stereo, bool *more, size_t *out_len) {
+	std::string err;
+	try {
+		if (b->engine->run_limited((void *const *)bufs, sauengine::SF_F32, false, pre_gain, ceiling, buf_len, stereo, more, out_len, err)) return true;
+	} catch (const std::exception &ex) { /* (nothing C++ crosses the C ABI) */
+		err = std::string("internal error: ") + ex.what();
+	}
+	report("batch", err);
+	return false;
+}
+
+extern "C" const float *sauAmd_Batch_device_limited_f32(sauAmdBatch *b, size_t stream) {
+	return b->engine->backend()->device_limited_f32((uint32_t)stream);
+}
+
+extern "C" size_t sauAmd_Batch_device_limited_pitch(sauAmdBatch *b) {
+	return b->engine->backend()->device_limited_pitch();
+}
+
+extern "C" bool sauAmd_Batch_limiter_stats(sauAmdBatch *b, sauAmdLimiterStats *out, int reset) {
+	std::string err;
+	try {
+		if (!out) err = "bad argument";
+		else if (b->engine->limiter_stats((sauengine::LimiterStats *)out, reset != 0, err)) return true;
+	} catch (const std::exception &ex) {
+		err = std::string("internal error: ") + ex.what();
+	}
+	report("batch", err);
+	return false;
+}
+
+extern "C" bool sauAmd_Batch_limit_rows(sauAmdBatch *b, const void *rows, size_t pitch_bytes, size_t n_rows, size_t frames, int channels,
+		uint32_t srate, float pre_gain, float ceiling, void *out_rows, size_t out_pitch_bytes, sauAmdLimiterStats *stats_out) {
+	std::string err;
+	try {
+		if (!rows || !out_rows || ((uintptr_t)rows & 15u) || (pitch_bytes & 15u) || ((uintptr_t)out_rows & 15u) || (out_pitch_bytes & 15u) ||
+		    (channels != 1 && channels != 2) || !srate || !sauengine::limiter_param_ok(pre_gain) || !sauengine::limiter_param_ok(ceiling))
+			err = "bad argument";
+		else if (b->engine->backend()->limit_rows(rows, pitch_bytes, n_rows, frames, channels == 2, srate, pre_gain, ceiling, out_rows,
+				out_pitch_bytes, (sauengine::LimiterStats *)stats_out, err))
+			return true;
+	} catch (const std::exception &ex) {
+		err = std::string("internal error: ") + ex.what();
+	}
+	report("batch", err);
+	return false;
+}
+
 extern "C" bool sauAmd_Batch_sync(sauAmdBatch *b) {
 	std::string err;
 	if (!b->engine->backend()->sync(err)) { report("batch", err); return false; }

@@ -33,6 +33,11 @@ bool render_file_oversampled(const sauProgram *prg, uint32_t srate, int factor, 
 bool render_file_loudness(const sauProgram *prg, uint32_t srate, const char *path, int format, int channels, double target_lufs,
 		float max_true_peak, const std::function<sauengine::Backend *(std::string &)> &make_backend, uint64_t *frames_out,
 		sauAmdLoudness *loud_out, float *gain_out, std::string &err);
+/* sauAmd_render_file_loudness_limited's body (sndout.cpp). As render_file_loudness: two passes, two engines, make_backend asked
+ * once per pass -- after the arguments have been looked at, so a bad argument asks for none. */
+bool render_file_loudness_limited(const sauProgram *prg, uint32_t srate, const char *path, int format, int channels, double target_lufs,
+		float max_true_peak, const std::function<sauengine::Backend *(std::string &)> &make_backend, uint64_t *frames_out,
+		sauAmdLoudness *loud_out, float *gain_out, sauAmdLimiterStats *stats_out, std::string &err);
 /* the thread's sauAmd_last_error text (capi.cpp), with the line on stderr */
 void set_last_error(const char *where, const std::string &err);
 } /* namespace sauamd_internal */

@@ -616,6 +616,7 @@ bool Engine::restore(const Snapshot &s, int slot, std::string &err) {
 	call_len_ = s.call_len; lat_call_ = s.lat_call; call_phase_ = s.call_phase;
 	all_ended_ = false;
 	decim_factor_ = 0; /* (the history is not part of a snapshot) */
+	lim_seq_ = false;
 	return backend_->load_state(slot, err);
 }
 
@@ -634,6 +635,7 @@ bool Engine::run(void *const *host_bufs, SampleFormat format, size_t buf_len, bo
 	/* the run's format, ahead of anything that moves: a backend without float output refuses here */
 	if (!set_format(format, err)) return false;
 	if (!in_decimated_) decim_factor_ = 0; /* (a run of any other kind ends a sequence of decimated runs) */
+	if (!in_limited_) lim_seq_ = false; /* (... and one of limited runs) */
 	const uint32_t total = (uint32_t)buf_len;
 	if (total > reserved_frames_ || (stereo && !reserved_stereo_)) {
 		uint32_t want = std::max(total, reserved_frames_);
@@ -783,6 +785,7 @@ bool Engine::run_decimated(void *const *host_bufs, SampleFormat out_fmt, bool sw
 	if (loudness_) { err = "bad argument: while loudness metering is on only float32 runs are made (decimated rows are not metered)"; return false; }
 	/* the decimator first: a backend without one refuses here, ahead of anything that moves */
 	if ((decim_factor_ != factor || decim_stereo_ != stereo) && !begin_decimated(factor, stereo, err)) return false;
+	lim_seq_ = false; /* (a decimated run ends a sequence of limited runs, also where it renders nothing) */
 	const size_t n = streams_.size();
 	decim_frames_.assign(n, 0);
 	if (all_ended_) { /* nothing left to render: the rows are not read, the history gives the tail */
@@ -809,6 +812,61 @@ bool Engine::run_decimated(void *const *host_bufs, SampleFormat out_fmt, bool sw
 				return false;
 	}
 	return true;
+}
+
+bool Engine::begin_limited(float pre_gain, float ceiling, bool stereo, std::string &err) {
+	if (!limiter_param_ok(pre_gain) || !limiter_param_ok(ceiling)) { err = "bad argument"; return false; }
+	if (!backend_->begin_limiting(stereo, err)) return false;
+	lim_seq_ = lim_begun_ = true;
+	lim_gain_ = pre_gain; lim_ceiling_ = ceiling; lim_stereo_ = stereo;
+	return true;
+}
+
+bool Engine::run_limited(void *const *host_bufs, SampleFormat out_fmt, bool swap_bytes, float pre_gain, float ceiling, size_t buf_len,
+		bool stereo, bool *more, size_t *out_len, std::string &err) {
+	if (!limiter_param_ok(pre_gain) || !limiter_param_ok(ceiling) || buf_len > UINT32_MAX || (out_fmt == SF_F32 && swap_bytes)) {
+		err = "bad argument";
+		return false;
+	}
+	if (loudness_) { err = "bad argument: while loudness metering is on only float32 runs are made (limited rows are not metered)"; return false; }
+	/* the limiter first: a backend without one refuses here, ahead of anything that moves */
+	if (!(lim_seq_ && lim_gain_ == pre_gain && lim_ceiling_ == ceiling && lim_stereo_ == stereo) && !begin_limited(pre_gain, ceiling, stereo, err))
+		return false;
+	const size_t n = streams_.size();
+	decim_frames_.assign(n, 0); /* (per stream: the float run's out_len, as run_decimated keeps it) */
+	if (all_ended_) { /* nothing left to render: the rows are not read, the history gives the tail */
+		for (size_t s = 0; s < n; ++s) {
+			if (more) more[s] = false;
+			if (out_len) out_len[s] = 0;
+		}
+		decim_factor_ = 0; /* (as a run of another kind ends a sequence of decimated runs) */
+	} else {
+		std::vector<size_t> len(n, 0);
+		in_limited_ = true;
+		const bool ok = run(nullptr, SF_F32, buf_len, stereo, more, len.data(), err);
+		in_limited_ = false;
+		if (!ok) { lim_seq_ = false; return false; }
+		for (size_t s = 0; s < n; ++s) {
+			decim_frames_[s] = (uint32_t)len[s];
+			if (out_len) out_len[s] = len[s];
+		}
+	}
+	if (!backend_->limit(decim_frames_.data(), (uint32_t)buf_len, pre_gain, ceiling, stereo, out_fmt, swap_bytes, err)) { lim_seq_ = false; return false; }
+	if (host_bufs) {
+		const size_t bytes = buf_len * (stereo ? 2 : 1) * (out_fmt == SF_F32 ? sizeof(float) : sizeof(int16_t));
+		for (size_t s = 0; s < n; ++s)
+			if (host_bufs[s] && bytes && !(backend_->fetch_limited_async((uint32_t)s, host_bufs[s], bytes, 0, err) && backend_->wait_fetch(0, err)))
+				return false;
+	}
+	return true;
+}
+
+bool Engine::limiter_stats(LimiterStats *out, bool reset, std::string &err) {
+	if (!lim_begun_) { /* (no backend has records yet: what an empty record reads as) */
+		for (size_t s = 0; s < streams_.size(); ++s) out[s] = LimiterStats{0, 0, 1.0};
+		return true;
+	}
+	return backend_->read_limiter_stats(out, reset, err);
 }
 
 bool Engine::levels(Levels *out, bool reset, std::string &err) {

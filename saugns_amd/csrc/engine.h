@@ -67,6 +67,21 @@ constexpr size_t DECIM_HALF = 32;
 size_t decimator_taps(int factor, double *out, size_t cap);
 size_t decimator_latency(int factor);
 
+/* The limiter on the host (tables.cpp; include/saugns_amd.h, section "Limiter"). limiter_lookahead: A = min(max(srate / 200,
+ * 16), 1024) frames (0 for srate == 0); limiter_latency: D = 2 A + 16 (0 likewise); limiter_window: 2 A + 1, and the smoothing
+ * window h in out[] when cap suffices (nothing otherwise), shaped like decimator_taps. LimiterStats is sauAmdLimiterStats. */
+constexpr uint32_t LIM_A_MIN = 16, LIM_A_MAX = 1024;
+struct LimiterStats {
+	uint64_t frames, limited;
+	double min_gain;
+};
+static_assert(sizeof(LimiterStats) == 24, "sauAmdLimiterStats");
+size_t limiter_lookahead(uint32_t srate);
+size_t limiter_latency(uint32_t srate);
+size_t limiter_window(uint32_t srate, double *out, size_t cap);
+/* pre_gain and ceiling: finite and > 0 (a NaN fails every comparison) */
+inline bool limiter_param_ok(float v) { return v > 0.f && v <= 3.402823466e+38f; }
+
 /* Everything the backend needs to render one segment (no events inside). */
 struct SegmentDesc {
 	uint32_t len;             /* frames */
@@ -278,6 +293,40 @@ public:
 		(void)rows; (void)pitch_bytes; (void)n_rows; (void)frames; (void)stereo; (void)srate; (void)out; (void)hops_out; (void)hops_cap;
 		err = "this backend has no loudness metering"; return false;
 	}
+	/* The look-ahead true-peak limiter on float runs (include/saugns_amd.h, section "Limiter"), where the samples are. A backend
+	 * without it refuses -- these defaults -- and nothing changes. begin_limiting: a sequence of limited runs with this channel
+	 * layout starts at the backend's rate: every stream's history is zero. The statistics are not touched. */
+	virtual bool begin_limiting(bool stereo, std::string &err) { (void)stereo; err = "this backend has no limiter"; return false; }
+	/* buf_len output frames of every stream -- the sequence delayed by D -- from the float run just rendered (buf_len frames, of
+	 * which the first frames[s] are stream s's; the rest, whatever the rows hold there, count as +0) and the stream's history,
+	 * into device rows of the backend's own -- float32, or int16 (pcm16 of y; `swap_bytes`: big-endian) -- the history moves on
+	 * and the streams' statistics take the run in: device work on the backend's stream, behind the run's mixers. frames all 0:
+	 * the rows are not read. */
+	virtual bool limit(const uint32_t *frames, uint32_t buf_len, float pre_gain, float ceiling, bool stereo, SampleFormat out_fmt,
+			bool swap_bytes, std::string &err) {
+		(void)frames; (void)buf_len; (void)pre_gain; (void)ceiling; (void)stereo; (void)out_fmt; (void)swap_bytes;
+		err = "this backend has no limiter"; return false;
+	}
+	/* queue the copy of the first `bytes` bytes of stream s's limited row out, like fetch_decimated_async */
+	virtual bool fetch_limited_async(uint32_t stream, void *dst, size_t bytes, int slot, std::string &err) {
+		(void)stream; (void)dst; (void)bytes; (void)slot; err = "this backend has no limiter"; return false;
+	}
+	/* device address of stream s's limited float row of the last limited run (NULL: none, or int16 rows), and the bytes between
+	 * the rows of consecutive streams (a multiple of 256; 0: none) */
+	virtual const float *device_limited_f32(uint32_t stream) { (void)stream; return nullptr; }
+	virtual size_t device_limited_pitch() { return 0; }
+	/* wait for the stream and fetch the streams' statistics; `reset`: empty records behind the read */
+	virtual bool read_limiter_stats(LimiterStats *out, bool reset, std::string &err) {
+		(void)out; (void)reset; err = "this backend has no limiter"; return false;
+	}
+	/* the limiter from zero history on float rows the caller holds on the backend's device, time-aligned (the delay dropped)
+	 * into float rows of the caller's; synchronous, the streams' histories and statistics untouched */
+	virtual bool limit_rows(const void *rows, size_t pitch_bytes, size_t n_rows, size_t frames, bool stereo, uint32_t srate,
+			float pre_gain, float ceiling, void *out_rows, size_t out_pitch_bytes, LimiterStats *stats_out, std::string &err) {
+		(void)rows; (void)pitch_bytes; (void)n_rows; (void)frames; (void)stereo; (void)srate; (void)pre_gain; (void)ceiling;
+		(void)out_rows; (void)out_pitch_bytes; (void)stats_out;
+		err = "this backend has no limiter"; return false;
+	}
 };
 
 /* ---- plan compiler (plan.cpp) -------------------------------------------- */
@@ -382,6 +431,21 @@ public:
 			bool *more, size_t *out_len, std::string &err);
 	/* start such a sequence now (run_decimated does it itself; the file writer asks before it opens a file) */
 	bool begin_decimated(int factor, bool stereo, std::string &err);
+
+	/* A float run of buf_len frames, limited on the device (include/saugns_amd.h: sauAmd_Batch_run_limited_f32). The limited
+	 * rows stay on the device (Backend::device_limited_f32, fetch_limited_async) -- float32, or with out_fmt SF_S16 the kernels'
+	 * own pcm16, byte-swapped on request (the file writer) -- and host_bufs[s], when given, gets stream s's buf_len frames: the
+	 * sequence delayed by limiter_latency(rate). more[s] and out_len[s] are the float run's. The history belongs to a sequence
+	 * of limited runs with one (pre_gain, ceiling, stereo): any other run in between, or another triple, starts it from zero.
+	 * False with "bad argument" on parameters that are not finite and positive or while loudness metering is on, and with the
+	 * backend's text on one without a limiter or float output; nothing is rendered then and the batch stands where it stood.
+	 * Once every stream has ended nothing is rendered; the rows then hold the tail. */
+	bool run_limited(void *const *host_bufs, SampleFormat out_fmt, bool swap_bytes, float pre_gain, float ceiling, size_t buf_len,
+			bool stereo, bool *more, size_t *out_len, std::string &err);
+	/* start such a sequence now (run_limited does it itself; the file writer asks before it opens a file) */
+	bool begin_limited(float pre_gain, float ceiling, bool stereo, std::string &err);
+	/* the streams' statistics, out[n_streams()]; empty ones (0, 0, 1.0) while no limited sequence has ever begun */
+	bool limiter_stats(LimiterStats *out, bool reset, std::string &err);
 
 	/* Level metering (include/saugns_amd.h: sauAmd_Batch_set_metering). On: every run ends with the backend measuring each
 	 * stream's frames [0, out_len) of that run, in the run's format, into the stream's record. Off (the default): run() makes
@@ -512,6 +576,11 @@ private:
 	bool in_decimated_ = false;      /* run() is run_decimated()'s own */
 	bool all_ended_ = false;         /* the last run left no stream with anything to render */
 	std::vector<uint32_t> decim_frames_; /* per stream: the float run's out_len */
+	bool lim_seq_ = false;           /* run_limited(): a sequence is at hand (any other run ends it) */
+	bool lim_begun_ = false;         /* ... one has ever begun: the backend has statistics */
+	float lim_gain_ = 0.f, lim_ceiling_ = 0.f;
+	bool lim_stereo_ = false;
+	bool in_limited_ = false;        /* run() is run_limited()'s own */
 	bool plans_dirty_ = true;
 	/* concatenated plans as uploaded; per (stream,voice) offsets */
 	std::vector<Step> all_steps_;

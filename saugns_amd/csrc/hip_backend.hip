@@ -12,6 +12,7 @@
  *   k_levels.h      levels_kernel, levels_finish_kernel (level metering), requant_kernel (the normalised file writer)
  *   k_decimate.h    decimate_kernel, decimate_carry_kernel (oversampled rendering: the decimating FIR and its history)
  *   k_loudness.h    loud_chunk_kernel, loud_scan_kernel, truepeak_kernel, loud_finish_kernel, loud_carry_kernel (BS.1770 loudness, true peak)
+ *   k_limiter.h     lim_env_kernel, lim_gain_kernel, lim_finish_kernel, lim_carry_kernel (the look-ahead true-peak limiter)
  *   launch_plan.h   (plain C++, no HIP) the tuning switches and every decision about a segment's launches: rows per pass, LDS
  *                   budgets, builds, grids, tasks, chain chunks, the mixer -- a plan per segment, testable without a GPU
  *   (this file)     buffer and stream pools, table sets, the kernel lookup, HipBackendImpl: render() carries a plan out,
@@ -74,6 +75,7 @@ using namespace sauplan;
 #include "k_levels.h"
 #include "k_decimate.h"
 #include "k_loudness.h"
+#include "k_limiter.h"
 static_assert(MISC_BYTES == sizeof(Misc), "launch_plan.h plans the block loop's LDS with this size");
 
 /* ------------------------------------------------------------------------ */
@@ -1670,6 +1672,184 @@ public:
 		return ok;
 	}
 
+	/* ---- the limiter (k_limiter.h; the geometry is launch_plan.h's plan_limit) ---- */
+	/* the window and the true-peak taps of the rate at hand (a limit_rows call at another rate may have been in between) */
+	bool lim_setup(uint32_t srate, std::string &err) {
+		if (!lim_taps_.p) {
+			double g[TP_TAPS];
+			if (sauengine::truepeak_taps(g, TP_TAPS) != TP_TAPS || !lim_taps_.ensure(TP_TAPS, err) || !send(lim_taps_.p, g, sizeof g, err)) return false;
+		}
+		if (lim_rate_ == srate) return true;
+		std::vector<double> h(sauengine::limiter_window(srate, nullptr, 0));
+		if (h.empty() || sauengine::limiter_window(srate, h.data(), h.size()) != h.size()) { err = "bad argument"; return false; }
+		if (!lim_win_.ensure(2 * LIM_A_MAX + 1, err) || !send(lim_win_.p, h.data(), h.size() * sizeof(double), err)) return false;
+		lim_rate_ = srate;
+		return true;
+	}
+	/* the launches of one pass, on the backend's stream; lp carries rows, frames, history, output, statistics and base */
+	template <typename OutT> void lim_launch_gain(const LimitPlan &plan, const LimParams &lp, bool stereo) {
+		const dim3 grid(plan.tiles, plan.streams), block(LIM_THREADS);
+		if (stereo) hipLaunchKernelGGL((lim_gain_kernel<OutT, 2>), grid, block, 0, stream_, lp, (const double *)lim_win_.p);
+		else hipLaunchKernelGGL((lim_gain_kernel<OutT, 1>), grid, block, 0, stream_, lp, (const double *)lim_win_.p);
+	}
+	bool lim_launch(const LimitPlan &plan, LimParams &lp, bool stereo, bool f32, std::string &err) {
+		const size_t sc = plan.scratch_pitch * plan.streams, parts = (size_t)plan.tiles * plan.streams;
+		if (!lim_s_.ensure(sc, err) || !lim_r_.ensure(sc, err) || !lim_part_min_.ensure(parts, err) || !lim_part_cnt_.ensure(parts, err)) return false;
+		lp.s = lim_s_.p; lp.r = lim_r_.p; lp.scratch_pitch = plan.scratch_pitch;
+		lp.part_min = lim_part_min_.p; lp.part_cnt = lim_part_cnt_.p;
+		lp.env_n = plan.env_n; lp.A = plan.A; lp.hist_frames = plan.hist_frames; lp.tiles = plan.tiles; lp.n_streams = plan.streams;
+		const dim3 egrid(plan.env_tiles, plan.streams), block(LIM_THREADS);
+		if (stereo) hipLaunchKernelGGL(lim_env_kernel<2>, egrid, block, 0, stream_, lp, (const double *)lim_taps_.p);
+		else hipLaunchKernelGGL(lim_env_kernel<1>, egrid, block, 0, stream_, lp, (const double *)lim_taps_.p);
+		HIP_OK(hipGetLastError());
+		if (f32) lim_launch_gain<float>(plan, lp, stereo);
+		else lim_launch_gain<int16_t>(plan, lp, stereo);
+		HIP_OK(hipGetLastError());
+		hipLaunchKernelGGL(lim_finish_kernel, dim3(plan.streams), dim3(64), 0, stream_, lp);
+		HIP_OK(hipGetLastError());
+		return true;
+	}
+	bool lim_clear_stats(LimStats *dst, size_t n, std::string &err) {
+		const std::vector<LimStats> empty(n, LimStats{0, 0, 1.0});
+		return send(dst, empty.data(), n * sizeof(LimStats), err);
+	}
+	bool begin_limiting(bool stereo, std::string &err) override {
+		use_device();
+		const LimitPlan plan = plan_limit(0, cfg_.srate, stereo ? 2 : 1, cfg_.n_streams, sizeof(float));
+		if (!plan.ok) { err = "bad argument"; return false; }
+		const size_t hist = (size_t)cfg_.n_streams * plan.hist_frames * 2;
+		if (!lim_hist_[0].ensure(hist, err) || !lim_hist_[1].ensure(hist, err) || !lim_frames_.ensure(cfg_.n_streams, err)) return false;
+		if (!lim_stats_.p) {
+			if (!lim_stats_.ensure(cfg_.n_streams, err) || !lim_clear_stats(lim_stats_.p, cfg_.n_streams, err)) return false;
+		}
+		lim_cur_ = 0;
+		HIP_OK(hipMemsetAsync(lim_hist_[0].p, 0, hist * sizeof(float), stream_)); /* (behind the last sequence's kernels on the one stream) */
+		lim_on_ = true; lim_stereo_ = stereo;
+		return true;
+	}
+	bool limit(const uint32_t *frames, uint32_t buf_len, float pre_gain, float ceiling, bool stereo, sauengine::SampleFormat out_fmt,
+			bool swap_bytes, std::string &err) override {
+		use_device();
+		if (!lim_on_ || stereo != lim_stereo_) { err = "limiting has not begun"; return false; }
+		if (!sauengine::limiter_param_ok(pre_gain) || !sauengine::limiter_param_ok(ceiling)) { err = "bad argument"; return false; }
+		const bool f32 = out_fmt == sauengine::SF_F32;
+		if (f32 && swap_bytes) { err = "float32 samples are not byte-swapped"; return false; }
+		const uint32_t ch = stereo ? 2 : 1;
+		const LimitPlan plan = plan_limit(buf_len, cfg_.srate, ch, cfg_.n_streams, f32 ? sizeof(float) : sizeof(int16_t));
+		if (!plan.ok) { err = "bad argument"; return false; }
+		bool any = false;
+		for (uint32_t s = 0; s < cfg_.n_streams; ++s) {
+			if (frames[s] > buf_len || frames[s] > row_stride_) { err = "frames beyond the streams' rows"; return false; }
+			any = any || frames[s] != 0;
+		}
+		if (any && (!pcm_f32_ || !pcm_.p)) { err = "the last run's samples are not float32"; return false; }
+		lim_out_f32_ = f32; lim_out_pitch_ = plan.out_pitch; lim_out_bytes_ = (size_t)buf_len * ch * (f32 ? sizeof(float) : sizeof(int16_t));
+		if (!plan.tiles) return true; /* no output frame: nothing to launch, and the history stands */
+		if (!lim_setup(cfg_.srate, err) || !lim_out_.ensure(plan.out_pitch * cfg_.n_streams, err)) return false;
+		if (!send(lim_frames_.p, frames, (size_t)cfg_.n_streams * sizeof(uint32_t), err)) return false;
+		LimParams lp;
+		memset((void *)&lp, 0, sizeof lp);
+		lp.rows = (const float *)pcm_.p; lp.row_pitch = pcm_f32_ ? pcm_pitch() : 0;
+		lp.frames = lim_frames_.p;
+		lp.hist = lim_hist_[lim_cur_].p; lp.hist_next = lim_hist_[lim_cur_ ^ 1].p;
+		lp.out = lim_out_.p; lp.out_pitch = plan.out_pitch;
+		lp.stats = lim_stats_.p;
+		lp.base = -(long long)plan.D - 2 * (long long)plan.A; /* output 0 is the sequence's frame (run's first) - D */
+		lp.n_out = buf_len; lp.run_frames = buf_len; lp.swap_bytes = swap_bytes ? 1 : 0;
+		lp.pre_gain = pre_gain; lp.ceiling = ceiling;
+		if (!lim_launch(plan, lp, stereo, f32, err)) return false;
+		hipLaunchKernelGGL(lim_carry_kernel, dim3((plan.hist_frames * ch + LIM_THREADS - 1) / LIM_THREADS, plan.streams), dim3(LIM_THREADS), 0,
+				stream_, lp, ch);
+		HIP_OK(hipGetLastError());
+		lim_cur_ ^= 1;
+		return true;
+	}
+	/* (the next run's kernels are ordered behind this copy on the one stream) */
+	bool fetch_limited_async(uint32_t stream, void *dst, size_t bytes, int slot, std::string &err) override {
+		slot &= 3;
+		use_device();
+		if (stream >= cfg_.n_streams || bytes > lim_out_bytes_ || (bytes && !lim_out_.p)) { err = "more bytes than were limited"; return false; }
+		if (!fetch_ev_[slot]) HIP_OK(hipEventCreateWithFlags(&fetch_ev_[slot], hipEventDisableTiming));
+		if (bytes) {
+			const char *src = (const char *)lim_out_.p + lim_out_pitch_ * stream;
+			if (host_blocks_.count(dst)) HIP_OK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream_));
+			else { /* pageable memory: through the page-locked block, as fetch_pcm goes */
+				if (!h_pcm_.ensure((bytes + 1) / 2, err)) return false;
+				HIP_OK(hipMemcpyAsync(h_pcm_.p, src, bytes, hipMemcpyDeviceToHost, stream_));
+				HIP_OK(hipStreamSynchronize(stream_));
+				memcpy(dst, h_pcm_.p, bytes);
+			}
+		}
+		HIP_OK(hipEventRecord(fetch_ev_[slot], stream_));
+		return true;
+	}
+	const float *device_limited_f32(uint32_t stream) override {
+		return lim_out_.p && lim_out_f32_ && lim_out_bytes_ && stream < cfg_.n_streams ? (const float *)((const char *)lim_out_.p + lim_out_pitch_ * stream) : nullptr;
+	}
+	size_t device_limited_pitch() override { return lim_out_.p && lim_out_bytes_ ? lim_out_pitch_ : 0; }
+	bool read_limiter_stats(sauengine::LimiterStats *out, bool reset, std::string &err) override {
+		use_device();
+		if (!lim_stats_.p) { err = "limiting has not begun"; return false; }
+		HIP_OK(hipMemcpyAsync(out, lim_stats_.p, (size_t)cfg_.n_streams * sizeof(LimStats), hipMemcpyDeviceToHost, stream_));
+		HIP_OK(hipStreamSynchronize(stream_));
+		return !reset || lim_clear_stats(lim_stats_.p, cfg_.n_streams, err);
+	}
+	/* is [p, p + pitch * (n_rows - 1) + row_bytes) inside one allocation of this device? (the rows are read or written by kernels) */
+	bool lim_rows_inside(const void *p, size_t pitch, size_t n_rows, size_t row_bytes, const char *what, std::string &err) {
+		hipPointerAttribute_t at;
+		memset((void *)&at, 0, sizeof at);
+		if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); err = std::string("bad argument: ") + what + " is not device memory"; return false; }
+		if (at.type != hipMemoryTypeDevice || at.device != dev_) { err = std::string("bad argument: ") + what + " must be memory of the batch's device"; return false; }
+		hipDeviceptr_t base = nullptr;
+		size_t span = 0;
+		if (hipMemGetAddressRange(&base, &span, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); err = std::string("bad argument: ") + what + " is not device memory"; return false; }
+		size_t need = 0;
+		const bool wraps = __builtin_mul_overflow(pitch, n_rows - 1, &need) || __builtin_add_overflow(need, row_bytes, &need);
+		const size_t ofs = (size_t)((const char *)p - (const char *)base);
+		if (wraps || ofs > span || need > span - ofs) { err = std::string("bad argument: ") + what + " reaches beyond its allocation"; return false; }
+		return true;
+	}
+	bool limit_rows(const void *rows, size_t pitch, size_t n_rows, size_t frames, bool stereo, uint32_t srate, float pre_gain, float ceiling,
+			void *out_rows, size_t out_pitch, sauengine::LimiterStats *stats_out, std::string &err) override {
+		use_device();
+		const size_t ch = stereo ? 2 : 1, row_bytes = frames * ch * sizeof(float);
+		if (!sauengine::limiter_param_ok(pre_gain) || !sauengine::limiter_param_ok(ceiling) || !srate) { err = "bad argument"; return false; }
+		if (!rows || !out_rows || ((uintptr_t)rows & 15u) || (pitch & 15u) || ((uintptr_t)out_rows & 15u) || (out_pitch & 15u)) {
+			err = "bad argument: rows, out_rows and their pitches must be multiples of 16"; return false;
+		}
+		if (frames > 0xffffffffull - 4 * LIM_A_MAX || (n_rows > 1 && (row_bytes > pitch || row_bytes > out_pitch))) {
+			err = "bad argument: rows longer than their pitch, or than 32 bits of frames"; return false;
+		}
+		if (n_rows > LIM_MAX_STREAMS) { err = "bad argument: more than 65535 rows"; return false; }
+		for (size_t r = 0; stats_out && r < n_rows; ++r) stats_out[r] = sauengine::LimiterStats{0, 0, 1.0};
+		if (!n_rows || !frames) return true;
+		if (!lim_rows_inside(rows, pitch, n_rows, row_bytes, "rows", err) || !lim_rows_inside(out_rows, out_pitch, n_rows, row_bytes, "out_rows", err)) return false;
+		{ /* the two sets of rows may not share a byte: a tile's input reaches into its neighbours' output */
+			const uintptr_t a0 = (uintptr_t)rows, a1 = a0 + pitch * (n_rows - 1) + row_bytes, b0 = (uintptr_t)out_rows, b1 = b0 + out_pitch * (n_rows - 1) + row_bytes;
+			if (a0 < b1 && b0 < a1) { err = "bad argument: out_rows overlaps rows"; return false; }
+		}
+		const LimitPlan plan = plan_limit(frames, srate, (uint32_t)ch, n_rows, sizeof(float));
+		if (!plan.ok) { err = "bad argument"; return false; }
+		if (!lim_setup(srate, err) || !lim_rows_frames_.ensure(n_rows, err) || !lim_rows_stats_.ensure(n_rows, err)) return false;
+		const std::vector<uint32_t> fr(n_rows, (uint32_t)frames);
+		if (!send(lim_rows_frames_.p, fr.data(), n_rows * sizeof(uint32_t), err) || !lim_clear_stats(lim_rows_stats_.p, n_rows, err)) return false;
+		LimParams lp;
+		memset((void *)&lp, 0, sizeof lp);
+		lp.rows = (const float *)rows; lp.row_pitch = pitch;
+		lp.frames = lim_rows_frames_.p;
+		lp.out = out_rows; lp.out_pitch = out_pitch;
+		lp.stats = lim_rows_stats_.p;
+		lp.base = -2 * (long long)plan.A; /* output 0 is the rows' frame 0: the delay is dropped */
+		lp.n_out = (uint32_t)frames; lp.run_frames = (uint32_t)frames;
+		lp.pre_gain = pre_gain; lp.ceiling = ceiling;
+		if (!lim_launch(plan, lp, stereo, true, err)) return false;
+		std::vector<LimStats> st(n_rows);
+		HIP_OK(hipMemcpyAsync(st.data(), lim_rows_stats_.p, n_rows * sizeof(LimStats), hipMemcpyDeviceToHost, stream_));
+		HIP_OK(hipStreamSynchronize(stream_));
+		if (stats_out) memcpy((void *)stats_out, st.data(), n_rows * sizeof(LimStats));
+		return true;
+	}
+
 	const int16_t *device_pcm(uint32_t stream) override { return pcm_.p && !pcm_f32_ ? (const int16_t *)pcm_at(stream) : nullptr; }
 	const float *device_pcm_f32(uint32_t stream) override { return pcm_.p && pcm_f32_ ? (const float *)pcm_at(stream) : nullptr; }
 	size_t device_pcm_pitch() override { return pcm_.p ? pcm_pitch() : 0; }
@@ -1909,6 +2089,18 @@ private:
 	LoudFilter loud_f_;
 	LoudMap loud_m_;
 	uint32_t loud_rate_ = 0;
+	/* the limiter: the streams' histories (two buffers: lim_carry_kernel moves from one into the other), a run's frame counts and
+	 * output rows, the streams' statistics, one pass's scratch (s, r, the tiles' records), the window of the rate at hand and the
+	 * true-peak taps, and what one limit_rows call needs -- all from the pool, none there until a limited run asks for them */
+	DevBuf<float> lim_hist_[2];
+	DevBuf<uint32_t> lim_frames_, lim_rows_frames_, lim_part_cnt_;
+	DevBuf<unsigned char> lim_out_;
+	DevBuf<LimStats> lim_stats_, lim_rows_stats_;
+	DevBuf<double> lim_s_, lim_r_, lim_part_min_, lim_win_, lim_taps_;
+	int lim_cur_ = 0;
+	uint32_t lim_rate_ = 0;
+	bool lim_on_ = false, lim_stereo_ = false, lim_out_f32_ = false;
+	size_t lim_out_pitch_ = 0, lim_out_bytes_ = 0; /* of the last limited run: between the rows, and of a row's frames */
 	size_t decim_out_pitch_ = 0, decim_out_bytes_ = 0; /* of the last decimated run: between the rows, and of a row's frames */
 	DevBuf<uint32_t> vlists_;   /* [2][n_voices]: analyze_kernel's lists of closed-form and look-back voices (split launches) */
 	/* A chain kernel's workgroup is three waves on a latency-bound recurrence. SAU_AMD_CHAIN_ALONE=1 (a tuning switch): while a

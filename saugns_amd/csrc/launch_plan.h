@@ -822,5 +822,55 @@ inline LoudPlan plan_loudness(uint64_t max_frames, uint32_t channels, size_t n_r
 	return p;
 }
 
+/* ---- the limiter (k_limiter.h) ----
+ * Two passes over a run of one stream, both in tiles that decide speed only: the limiter's output is a function of the input
+ * sequence alone (include/saugns_amd.h, section "Limiter"), every value of it has one accumulator of its own, and a maximum
+ * has no order. With A the look-ahead in frames and n output frames, position u of a stream's scratch, u = 0 .. n + 4A - 1,
+ * belongs to the sequence's frame k = first + u - 4A - 16, where `first` is the frame of output 0 plus D = 2A + 16:
+ * lim_env_kernel gives s[k] and r[k] there, and output frame o reads s over u = o .. o + 4A and r at u = o + 2A.
+ * lim_env_kernel: a workgroup of LIM_THREADS owns LIM_ENV_TILE positions; its span in LDS is the tile and TP_LEAD frames
+ * around it, channels apart. lim_gain_kernel: a workgroup owns LIM_TILE output frames, LIM_PER_LANE f64 chains per lane;
+ * its s span is LIM_TILE + 4A doubles -- 36 KiB at A = LIM_A_MAX, inside the static 64 KiB -- in which the sliding maximum
+ * is formed in place. LIM_HIST = 4A + 32 frames of every stream are carried from run to run. */
+constexpr uint32_t LIM_A_MIN = sauengine::LIM_A_MIN, LIM_A_MAX = sauengine::LIM_A_MAX;
+constexpr uint32_t LIM_THREADS = 256, LIM_PER_LANE = 2, LIM_TILE = LIM_THREADS * LIM_PER_LANE;
+constexpr uint32_t LIM_ENV_TILE = LIM_THREADS;
+constexpr uint32_t LIM_SPAN_MAX = LIM_TILE + 4 * LIM_A_MAX; /* doubles of lim_gain_kernel's LDS */
+constexpr uint32_t LIM_SPAN_PER_THREAD = (LIM_SPAN_MAX + LIM_THREADS - 1) / LIM_THREADS;
+static_assert(LIM_SPAN_MAX * sizeof(double) <= 65536, "lim_gain_kernel's span is static LDS");
+constexpr uint32_t LIM_MAX_STREAMS = 65535; /* grid.y */
+struct LimitPlan {
+	bool ok = false;        /* false: rate 0, channels not 1 or 2, more streams or frames than a grid has */
+	uint32_t A = 0, D = 0;  /* look-ahead and delay in frames */
+	uint32_t taps = 0;      /* 2A + 1: the smoothing window, and the hold */
+	uint32_t hist_frames = 0; /* 4A + 32: a stream's history */
+	uint32_t env_n = 0;     /* positions of a stream's scratch: frames + 4A (0: no output frame, no launch) */
+	uint32_t env_tiles = 0; /* grid.x of lim_env_kernel */
+	uint32_t tiles = 0;     /* grid.x of lim_gain_kernel, and the stride of its partial records */
+	uint32_t streams = 0;   /* grid.y of both */
+	uint32_t span = 0;      /* doubles of a gain tile's s span: LIM_TILE + 4A */
+	size_t scratch_pitch = 0; /* doubles between the streams' rows of s and of r: env_n rounded up to 32 */
+	size_t out_pitch = 0;   /* bytes between the output rows: frames * channels samples, rounded up to 256 */
+};
+inline LimitPlan plan_limit(uint64_t frames, uint32_t srate, uint32_t channels, size_t n_streams, size_t sample_bytes) {
+	LimitPlan p;
+	if (!srate || (channels != 1 && channels != 2) || n_streams > LIM_MAX_STREAMS || frames > 0xffffffffull - 4 * LIM_A_MAX) return p;
+	p.ok = true;
+	p.A = srate / 200 < LIM_A_MIN ? LIM_A_MIN : srate / 200 > LIM_A_MAX ? LIM_A_MAX : srate / 200; /* (engine.h: limiter_lookahead) */
+	p.D = 2 * p.A + 16;
+	p.taps = 2 * p.A + 1;
+	p.hist_frames = 4 * p.A + 32;
+	p.streams = (uint32_t)n_streams;
+	p.span = LIM_TILE + 4 * p.A;
+	if (frames) {
+		p.env_n = (uint32_t)frames + 4 * p.A;
+		p.env_tiles = (p.env_n + LIM_ENV_TILE - 1) / LIM_ENV_TILE;
+		p.tiles = (uint32_t)((frames + LIM_TILE - 1) / LIM_TILE);
+	}
+	p.scratch_pitch = ((size_t)p.env_n + 31) & ~(size_t)31;
+	p.out_pitch = ((size_t)frames * channels * sample_bytes + 255) & ~(size_t)255;
+	return p;
+}
+
 } /* namespace sauplan */
 #endif

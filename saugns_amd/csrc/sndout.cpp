@@ -371,6 +371,80 @@ bool write_oversampled(const sauProgram *prg, uint32_t srate, int factor, const 
 	return ok;
 }
 
+/* The limited writer: float runs on render_file_over's lattice, each through the limiter (Engine::run_limited) into rows of
+ * the file's format, and those through the two page-locked slots to the file, as write_oversampled's go. The limiter delays by
+ * D = limiter_latency frames: with y the limited runs end to end and N the frames rendered, the file is y[D .. D + N) --
+ * time-aligned with the input -- and one last run of D frames behind the program's end delivers what of it the runs so far
+ * have not. */
+bool write_limited(const sauProgram *prg, uint32_t srate, const char *path, int format, int channels, float pre_gain, float ceiling,
+		Backend *backend /* owned */, uint64_t *frames_out, sauengine::LimiterStats *stats_out, std::string &err) {
+	Engine *engine = Engine::create(&prg, 1, srate, backend, err);
+	if (!engine) return false;
+	const bool stereo = channels == 2;
+	const bool f32 = format == SAU_AMD_SNDFILE_WAV_F32;
+	const sauengine::SampleFormat out_fmt = f32 ? sauengine::SF_F32 : sauengine::SF_S16;
+	const bool swap = format == SAU_AMD_SNDFILE_AU;
+	const size_t D = sauengine::limiter_latency(srate);
+	size_t call, chunk;
+	file_lattice(srate, call, chunk);
+	engine->set_call_len(call);
+	/* a backend without float output or without a limiter says so here, before there is a file */
+	if (!engine->set_format(sauengine::SF_F32, err) || !engine->begin_limited(pre_gain, ceiling, stereo, err)) { delete engine; return false; }
+	const size_t frame_bytes = (size_t)channels * (f32 ? sizeof(float) : sizeof(int16_t));
+	const size_t slot_frames = chunk > D ? chunk : D;
+	void *host[2] = {backend->alloc_host(slot_frames * frame_bytes), backend->alloc_host(slot_frames * frame_bytes)};
+	SndOut out;
+	bool ok = host[0] && host[1];
+	if (!ok) err = "out of page-locked memory";
+	if (ok && !out.open(path, format, (uint16_t)channels, srate)) {
+		err = std::string("couldn't open \"") + path + "\" for writing";
+		ok = false;
+	}
+	size_t pending[2] = {0, 0}, first[2] = {0, 0}; /* frames of the slot to write, and where they begin in it */
+	int slot = 0;
+	bool more = ok, tail = false;
+	uint64_t y_pos = 0, wanted = 0; /* limited frames made so far; the N frames rendered so far */
+	while (ok && !tail) {
+		tail = !more; /* behind the program's end: the one run for the limiter's tail */
+		const size_t n = tail ? D : chunk;
+		size_t len = 0;
+		ok = engine->run_limited(nullptr, out_fmt, swap, pre_gain, ceiling, n, stereo, &more, &len, err);
+		if (!ok) break;
+		wanted += len;
+		/* the file is y[D, D + wanted): while the program runs that covers every frame of a run but the first D */
+		const uint64_t lo = y_pos > D ? y_pos : D, end = y_pos + n, hi = D + wanted < end ? D + wanted : end;
+		if (hi > lo) {
+			ok = backend->fetch_limited_async(0, host[slot], (size_t)(hi - y_pos) * frame_bytes, slot, err);
+			first[slot] = (size_t)(lo - y_pos);
+			pending[slot] = (size_t)(hi - lo);
+		}
+		y_pos = end;
+		const int other = slot ^ 1;
+		if (ok && pending[other]) {
+			ok = backend->wait_fetch(other, err);
+			if (ok && !out.write((const char *)host[other] + first[other] * frame_bytes, pending[other])) { err = "write failed"; ok = false; }
+			pending[other] = 0;
+		}
+		slot = other;
+	}
+	for (int s = 0; ok && s < 2; ++s) { /* oldest first */
+		const int k = slot ^ s;
+		if (pending[k]) {
+			ok = backend->wait_fetch(k, err);
+			if (ok && !out.write((const char *)host[k] + first[k] * frame_bytes, pending[k])) { err = "write failed"; ok = false; }
+			pending[k] = 0;
+		}
+	}
+	if (ok && stats_out) ok = engine->limiter_stats(stats_out, false, err);
+	{ std::string e2; (void)backend->sync(e2); }
+	if (out.f && out.close() != 0 && ok) { err = "write failed"; ok = false; }
+	if (frames_out) *frames_out = out.frames;
+	backend->free_host(host[0]);
+	backend->free_host(host[1]);
+	delete engine;
+	return ok;
+}
+
 } /* namespace */
 
 bool sauamd_internal::render_file_normalized(const sauProgram *prg, uint32_t srate, const char *path, int format, int channels,
@@ -442,6 +516,48 @@ extern "C" bool sauAmd_render_file_loudness(const sauProgram *prg, uint32_t srat
 	try {
 		ok = sauamd_internal::render_file_loudness(prg, srate, path, format, channels, target_lufs, max_true_peak,
 				[](std::string &e) -> Backend * { return sauhip::create_hip_backend(e); }, frames_out, loud_out, gain_out, err);
+	} catch (const std::exception &ex) { /* (nothing C++ crosses the C ABI) */
+		err = std::string("internal error: ") + ex.what();
+	}
+	if (!ok) sauamd_internal::set_last_error("output", err);
+	return ok;
+}
+
+bool sauamd_internal::render_file_loudness_limited(const sauProgram *prg, uint32_t srate, const char *path, int format, int channels,
+		double target_lufs, float max_true_peak, const std::function<Backend *(std::string &)> &make_backend, uint64_t *frames_out,
+		sauAmdLoudness *loud_out, float *gain_out, sauAmdLimiterStats *stats_out, std::string &err) {
+	if (frames_out) *frames_out = 0;
+	if (!prg || !path || (channels != 1 && channels != 2) || format < 0 || format > SAU_AMD_SNDFILE_WAV_F32 ||
+	    !(target_lufs >= -DBL_MAX && target_lufs <= DBL_MAX) || !(max_true_peak > 0.f) || !(max_true_peak <= FLT_MAX) ||
+	    srate < sauengine::LOUD_MIN_RATE) { /* (a NaN fails every comparison) */
+		err = "bad argument";
+		return false;
+	}
+	Backend *first = make_backend(err);
+	if (!first) return false;
+	sauengine::Loudness ld;
+	if (!measure_program_loudness(prg, srate, channels == 2, first, ld, err)) return false;
+	if (loud_out) memcpy(loud_out, &ld, sizeof ld);
+	float gain = 1.0f; /* never lowered for the ceiling: the limiter holds that */
+	if (ld.integrated > -HUGE_VAL) gain = (float)pow(10.0, (target_lufs - ld.integrated) / 20.0);
+	if (gain_out) *gain_out = gain;
+	if (!(gain > 0.f) || !(gain <= FLT_MAX)) { err = "bad argument: the gain to the target loudness is not a finite positive float"; return false; }
+	Backend *second = make_backend(err);
+	if (!second) return false;
+	sauengine::LimiterStats st{0, 0, 1.0};
+	const bool ok = write_limited(prg, srate, path, format, channels, gain, max_true_peak, second, frames_out, &st, err);
+	if (ok && stats_out) memcpy(stats_out, &st, sizeof st);
+	return ok;
+}
+
+extern "C" bool sauAmd_render_file_loudness_limited(const sauProgram *prg, uint32_t srate, const char *path, int format, int channels,
+		double target_lufs, float max_true_peak, uint64_t *frames_out, sauAmdLoudness *loud_out, float *gain_out,
+		sauAmdLimiterStats *stats_out) {
+	std::string err;
+	bool ok = false;
+	try {
+		ok = sauamd_internal::render_file_loudness_limited(prg, srate, path, format, channels, target_lufs, max_true_peak,
+				[](std::string &e) -> Backend * { return sauhip::create_hip_backend(e); }, frames_out, loud_out, gain_out, stats_out, err);
 	} catch (const std::exception &ex) { /* (nothing C++ crosses the C ABI) */
 		err = std::string("internal error: ") + ex.what();
 	}

@@ -217,6 +217,30 @@ size_t decimator_taps(int factor, double *out, size_t cap) {
 	return L;
 }
 
+/* ---- the limiter's constants and smoothing window (engine.h; include/saugns_amd.h, section "Limiter") ----
+ * A raised cosine over 2 A + 1 frames that never reaches zero: u[j] = 1 + cos(pi (j - A) / (A + 1)), h = u / S with S the sum
+ * of u in ascending j. The upper half is mirrored from the lower (the symmetry is exact). All in f64, on the host. */
+size_t limiter_lookahead(uint32_t srate) {
+	if (!srate) return 0;
+	const uint32_t a = srate / 200;
+	return a < LIM_A_MIN ? LIM_A_MIN : a > LIM_A_MAX ? LIM_A_MAX : a;
+}
+
+size_t limiter_latency(uint32_t srate) { return srate ? 2 * limiter_lookahead(srate) + 16 : 0; }
+
+size_t limiter_window(uint32_t srate, double *out, size_t cap) {
+	if (!srate) return 0;
+	const size_t A = limiter_lookahead(srate), W = 2 * A + 1;
+	if (!out || cap < W) return W;
+	const double pi = 3.14159265358979323846;
+	for (size_t j = 0; j <= A; ++j) out[j] = 1.0 + cos(pi * ((double)j - (double)A) / (double)(A + 1));
+	for (size_t j = 0; j < A; ++j) out[W - 1 - j] = out[j];
+	double S = 0.0;
+	for (size_t j = 0; j < W; ++j) S += out[j];
+	for (size_t j = 0; j < W; ++j) out[j] /= S;
+	return W;
+}
+
 /* ---- loudness on the host (engine.h; include/saugns_amd.h states every formula and the order of every operation) ---- */
 
 size_t truepeak_taps(double *out, size_t cap) {
