@@ -484,6 +484,78 @@ SAU_AMD_API bool sauAmd_render_file_loudness_limited(const sauProgram *prg, uint
 		int channels, double target_lufs, float max_true_peak, uint64_t *frames_out, sauAmdLoudness *loud_out, float *gain_out,
 		sauAmdLimiterStats *stats_out);
 
+/* ---- Spectrum -------------------------------------------------------------------
+ * The oscillators are not band-limited (see "Oversampled rendering"): what did a factor buy, and does a script need one at
+ * all? That takes a spectrum, and fetching every float sample for a host FFT is what the meters above exist to avoid. This is
+ * a Welch / STFT power spectrum of float32 rows in f64, on the device. Unlike loudness and the limiter it is not tied to a
+ * kind of run: it is a meter that is FED rows -- float rows, decimated rows, limited rows, a caller's own device rows alike.
+ *
+ * The arithmetic is a fixed order of IEEE operations (the build is -ffp-contract=off: every product is rounded, then the sum
+ * or difference), reproducible bit for bit: no atomics, no sum whose order depends on scheduling, and the result is a function
+ * of the fed sequence only, never of how it was cut into feeds or of the partition of the device.
+ *
+ * Parameters: log2n = L in 8 .. 12, N = 2^L; hop, an integer with N / 8 <= hop <= N; channels 1, or 2 interleaved.
+ * Tables, in f64 on the host (sauAmd_spectrum_window, sauAmd_spectrum_twiddles; the device uses them as returned there):
+ *   w[j] = 0.5 - 0.5 * cos(2.0 * pi * j / N), j = 0 .. N-1 (the periodic Hann window);
+ *   T[k] = (c_k, d_k) = (cos(2.0 * pi * k / N), -sin(2.0 * pi * k / N)), k = 0 .. N/2 - 1.
+ * A sample is the row's float converted to double; a NaN or +-inf counts as +0.0f.
+ * Segments. A row counts its frames from 0. Segment s covers the frames [s hop, s hop + N) and exists once s hop + N <= P, P
+ * the number of frames so far: S(P) = 0 for P < N, else (P - N) / hop + 1. Frames behind the last complete segment are
+ * pending: they are not measured, and nothing is zero-extended.
+ * One segment and channel, an in-place radix-2 decimation in time:
+ *   for j = 0 .. N-1: re[rev_L(j)] = w[j] * (double)x[j]; im[rev_L(j)] = 0.0   (rev_L: the L-bit reversal)
+ *   for stage t = 1 .. L, with m = 2^t, h = m / 2, st = N / m: for every k0 that is a multiple of m and j = 0 .. h-1, with
+ *   a = k0 + j, b = a + h, (c, d) = T[j st]:
+ *     tr = c * re[b] - d * im[b];  ti = c * im[b] + d * re[b];  ur = re[a];  ui = im[a];
+ *     re[a] = ur + tr;  im[a] = ui + ti;  re[b] = ur - tr;  im[b] = ui - ti;
+ *   p_s[k] = re[k] * re[k] + im[k] * im[k] for k = 0 .. N/2: two rounded products and one sum.
+ * The butterflies of a stage are independent, so any distribution over lanes, and any fusion of consecutive stages in
+ * registers that performs exactly these operations, gives these bits.
+ * Averaging, in an order that does not depend on the device. Group g holds the segments [16 g, 16 g + 16):
+ *   acc_g[k] = +0.0, then acc_g[k] = acc_g[k] + p_s[k] for the group's segments in ascending s;
+ *   total[k] = +0.0, then total[k] = total[k] + acc_g[k] for every COMPLETE group in ascending g.
+ * What is reported is the sum, not the mean, with S: the caller divides. When a record is read, the group at hand, if it
+ * holds at least one segment, is added into the copy that is returned: total[k] + acc[k]; the device state is untouched and
+ * later feeds continue exactly (the rule of the true-peak tail).
+ * Limits: a feed whose groups' sums would take more than 1 GiB of scratch (rows * channels * groups * (N/2 + 1) * 8 bytes) is
+ * refused as a bad argument; feed it in pieces -- the result is the same. At most 65535 rows per meter. */
+typedef struct sauAmdSpectrum sauAmdSpectrum;
+
+/* sauAmd_spectrum_window: N, and the window w in out[] when cap >= N (nothing is written when cap < N; out may then be NULL).
+ * sauAmd_spectrum_twiddles: N, and the N doubles c_0 d_0 c_1 d_1 .. under the same rules. Both 0 for L outside 8 .. 12. */
+SAU_AMD_API size_t sauAmd_spectrum_window(unsigned log2n, double *out, size_t cap);
+SAU_AMD_API size_t sauAmd_spectrum_twiddles(unsigned log2n, double *out, size_t cap);
+/* A meter of n_rows empty records on the batch's device and stream, independent of the batch's own runs and of every other
+ * switch. NULL (sauAmd_last_error) on a bad argument -- L outside 8 .. 12, hop outside [N / 8, N], channels other than 1 or 2,
+ * n_rows == 0 -- or on a backend without it. It must be destroyed before the batch. sauAmd_Spectrum_destroy(NULL) is allowed. */
+SAU_AMD_API sauAmdSpectrum *sauAmd_Batch_create_spectrum(sauAmdBatch *b, size_t n_rows, int channels, unsigned log2n, uint32_t hop);
+SAU_AMD_API void sauAmd_Spectrum_destroy(sauAmdSpectrum *s);
+/* Row r's next frames[r] frames, read from rows + pitch_bytes * r; 0 changes nothing for that row. Queued on the batch's
+ * stream: it may directly follow the run that produced the rows (sauAmd_Batch_device_pcm_f32, _device_decimated_f32,
+ * _device_limited_f32), and the rows may be reused once the batch's stream has passed it. The argument rules are
+ * sauAmd_Batch_measure_rows': `rows` and pitch_bytes multiples of 16, the rows -- as long as the longest frames[r] -- wholly
+ * inside one allocation of that device. False with "bad argument" and nothing changed otherwise. */
+SAU_AMD_API bool sauAmd_Spectrum_feed(sauAmdSpectrum *s, const void *rows, size_t pitch_bytes, const uint32_t *frames /* [n_rows] */);
+/* Wait for the batch's stream and copy out the sums, the group at hand included, and S per row. reset != 0 then clears
+ * position, pending frames and sums. */
+SAU_AMD_API bool sauAmd_Spectrum_read(sauAmdSpectrum *s, double *power_out /* [n_rows][channels][N/2+1] */,
+		uint64_t *segments_out /* [n_rows] */, int reset);
+/* The same from empty records on n_rows rows of `frames` frames each, synchronous; the argument rules are
+ * sauAmd_Batch_measure_loudness_rows'. spectrogram_out may be NULL; otherwise it receives every segment's (float)p_s[k] as
+ * [n_rows][channels][S][N/2+1], and a spectrogram_cap (in floats) below that count is refused as a bad argument before
+ * anything runs. frames == 0, or S == 0, gives zero sums. */
+SAU_AMD_API bool sauAmd_Batch_spectrum_rows(sauAmdBatch *b, const void *rows, size_t pitch_bytes, size_t n_rows, size_t frames,
+		int channels, unsigned log2n, uint32_t hop, double *power_out /* [n_rows][channels][N/2+1] */,
+		uint64_t *segments_out /* [n_rows] */, float *spectrogram_out, size_t spectrogram_cap);
+/* Render prg and measure it, fetching no sample. factor 1: the measured sequence is exactly the floats that
+ * sauAmd_render_file(.., SAU_AMD_SNDFILE_WAV_F32, ..) writes (the same call lattice); factor 2, 4 or 8: exactly those that
+ * sauAmd_render_file_oversampled writes (the filter's delay dropped, its tail kept). *frames_out (may be NULL) = the frames
+ * measured. False (sauAmd_last_error) with "bad argument", before anything renders, on another factor, a bad L, hop or
+ * channels, a NULL pointer or srate * factor beyond 32 bits; also on a backend without a spectrum meter, without float output,
+ * or without a decimator where one is needed. */
+SAU_AMD_API bool sauAmd_render_spectrum(const sauProgram *prg, uint32_t srate, int factor, int channels, unsigned log2n,
+		uint32_t hop, double *power_out /* [channels][N/2+1] */, uint64_t *segments_out, uint64_t *frames_out);
+
 #ifdef __cplusplus
 }
 #endif

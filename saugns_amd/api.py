@@ -9,6 +9,7 @@ library and a GPU, creation fails loudly.
 """
 import ctypes as C
 import os
+import weakref
 
 import numpy as np
 
@@ -248,6 +249,25 @@ def _declare(L):
         L.sauAmd_render_file_loudness_limited.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_int, C.c_int, C.c_double,
                                                           C.c_float, C.POINTER(C.c_uint64), C.POINTER(Loudness),
                                                           C.POINTER(C.c_float), C.POINTER(LimiterStats)]
+    if hasattr(L, "sauAmd_Batch_create_spectrum"):  # the spectrum meter (SAU_AMD_LIB may name an older build)
+        L.sauAmd_spectrum_window.restype = C.c_size_t
+        L.sauAmd_spectrum_window.argtypes = [C.c_uint, C.POINTER(C.c_double), C.c_size_t]
+        L.sauAmd_spectrum_twiddles.restype = C.c_size_t
+        L.sauAmd_spectrum_twiddles.argtypes = [C.c_uint, C.POINTER(C.c_double), C.c_size_t]
+        L.sauAmd_Batch_create_spectrum.restype = C.c_void_p
+        L.sauAmd_Batch_create_spectrum.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_uint, C.c_uint32]
+        L.sauAmd_Spectrum_destroy.argtypes = [C.c_void_p]
+        L.sauAmd_Spectrum_feed.restype = C.c_bool
+        L.sauAmd_Spectrum_feed.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]
+        L.sauAmd_Spectrum_read.restype = C.c_bool
+        L.sauAmd_Spectrum_read.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.c_int]
+        L.sauAmd_Batch_spectrum_rows.restype = C.c_bool
+        L.sauAmd_Batch_spectrum_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_uint,
+                                                 C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_float),
+                                                 C.c_size_t]
+        L.sauAmd_render_spectrum.restype = C.c_bool
+        L.sauAmd_render_spectrum.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_uint, C.c_uint32, C.POINTER(C.c_double),
+                                             C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.sauAmd_set_piluts.argtypes = [C.c_void_p]
     L.sauAmd_get_piluts.restype = C.POINTER(C.c_float)
     L.sauAmd_last_error.restype = C.c_char_p
@@ -521,6 +541,73 @@ def render_file_loudness_limited(program, srate, path, fmt=SNDFILE_WAV, channels
     if not ok:
         raise RuntimeError("sauAmd_render_file_loudness_limited failed: " + last_error(L))
     return n.value, ld, gain.value, st
+
+
+_spectrum_hooks = None
+
+
+def use_spectrum_hooks(path):
+    """tests/ only: load the library that runs sauAmd_render_spectrum over an injected backend and reaches the host's
+    restatement of one segment and the spectrum meter's launch plan (tests/hooks_spectrum: the product's object files +
+    sauAmd_render_spectrum_with_backend, sauAmd_spectrum_segment, sauAmd_spectrum_plan)."""
+    global _spectrum_hooks
+    if _spectrum_hooks is None:
+        L = _declare(C.CDLL(path))
+        L.sauAmd_render_spectrum_with_backend.restype = C.c_bool
+        L.sauAmd_render_spectrum_with_backend.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_uint, C.c_uint32, C.c_void_p,
+                                                          C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.sauAmd_spectrum_segment.restype = C.c_bool
+        L.sauAmd_spectrum_segment.argtypes = [C.c_uint, C.c_void_p, C.c_size_t, C.POINTER(C.c_double)]
+        L.sauAmd_spectrum_plan.restype = C.c_int
+        L.sauAmd_spectrum_plan.argtypes = [C.c_uint, C.c_uint32, C.c_uint32, C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
+                                           C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        _spectrum_hooks = L
+    return _spectrum_hooks
+
+
+def spectrum_window(log2n):
+    """sauAmd_spectrum_window: the periodic Hann window of N = 2^log2n float64 values (empty for log2n outside 8 .. 12) -- the
+    one definition the device and the tests share."""
+    L = lib()
+    n = int(L.sauAmd_spectrum_window(int(log2n), None, 0))
+    out = np.zeros(n, np.float64)
+    if n:
+        L.sauAmd_spectrum_window(int(log2n), out.ctypes.data_as(C.POINTER(C.c_double)), n)
+    return out
+
+
+def spectrum_twiddles(log2n):
+    """sauAmd_spectrum_twiddles: the twiddles (cos, -sin)(2 pi k / N) as a float64 array [N/2, 2] (empty for log2n outside
+    8 .. 12)."""
+    L = lib()
+    n = int(L.sauAmd_spectrum_twiddles(int(log2n), None, 0))
+    out = np.zeros(n, np.float64)
+    if n:
+        L.sauAmd_spectrum_twiddles(int(log2n), out.ctypes.data_as(C.POINTER(C.c_double)), n)
+    return out.reshape(-1, 2)
+
+
+def render_spectrum(program, srate, factor=1, channels=1, log2n=11, hop=1024, backend=None):
+    """sauAmd_render_spectrum: render a whole program (at srate * factor, decimated on the device, for factor 2, 4, 8) and sum
+    the power spectra of its segments on the device, fetching no sample -> (float64 sums [channels, N/2+1], segments, frames
+    measured). ``backend`` (tests): a sauengine::Backend* to run the same loop without a GPU."""
+    log2n = int(log2n)
+    bins = (1 << log2n) // 2 + 1 if 0 <= log2n < 31 else 1
+    power = np.zeros((max(int(channels), 1), bins), np.float64)
+    segs, n = C.c_uint64(), C.c_uint64()
+    if backend is None:
+        L = _used(lib())
+        ok = L.sauAmd_render_spectrum(program.ptr, srate, factor, channels, log2n, hop, power.ctypes.data_as(C.POINTER(C.c_double)),
+                                      C.byref(segs), C.byref(n))
+    else:
+        if _spectrum_hooks is None:
+            raise RuntimeError("the spectrum-hook library is not loaded (use_spectrum_hooks)")
+        L = _used(_spectrum_hooks)
+        ok = L.sauAmd_render_spectrum_with_backend(program.ptr, srate, factor, channels, log2n, hop, backend,
+                                                   power.ctypes.data_as(C.POINTER(C.c_double)), C.byref(segs), C.byref(n))
+    if not ok:
+        raise RuntimeError("sauAmd_render_spectrum failed: " + last_error(L))
+    return power, segs.value, n.value
 
 
 def limiter_window(srate):
@@ -874,6 +961,33 @@ class Batch:
             raise RuntimeError("sauAmd_Batch_limit_rows failed: " + last_error(self._L))
         return list(out)[:n_rows]
 
+    def create_spectrum(self, n_rows, channels, log2n, hop):
+        """sauAmd_Batch_create_spectrum: a Spectrum of n_rows records on the batch's device and stream. Close it before the
+        batch."""
+        return Spectrum(self, n_rows, channels, log2n, hop)
+
+    def spectrum_rows(self, ptr, pitch, n_rows, frames, channels, log2n, hop, spectrogram=False, spectrogram_cap=None):
+        """sauAmd_Batch_spectrum_rows: the summed power spectra of n_rows float32 rows of device memory at `ptr`, `pitch` bytes
+        apart, of `frames` frames of `channels` samples, from empty records -> (float64 sums [n_rows, channels, N/2+1], the
+        segments per row as a list[, the spectrogram, float32 [n_rows, channels, S, N/2+1]]). ``spectrogram_cap`` (tests): the
+        capacity to state instead of the array's."""
+        n_rows, frames, log2n = int(n_rows), int(frames), int(log2n)
+        ok_l = 8 <= log2n <= 12
+        N = 1 << log2n if ok_l else 2
+        bins = N // 2 + 1
+        S = 0 if (frames < N or not hop or not ok_l) else (frames - N) // int(hop) + 1
+        ch = max(int(channels), 1)
+        power = np.zeros((max(n_rows, 1), ch, bins), np.float64)
+        segs = (C.c_uint64 * max(n_rows, 1))()
+        gram = np.zeros((max(n_rows, 1), ch, S, bins), np.float32) if spectrogram else None
+        cap = (gram.size if gram is not None else 0) if spectrogram_cap is None else int(spectrogram_cap)
+        if not _used(self._L).sauAmd_Batch_spectrum_rows(self._b, ptr, pitch, n_rows, frames, channels, log2n, hop,
+                                                        power.ctypes.data_as(C.POINTER(C.c_double)), segs,
+                                                        gram.ctypes.data_as(C.POINTER(C.c_float)) if gram is not None else None, cap):
+            raise RuntimeError("sauAmd_Batch_spectrum_rows failed: " + last_error(self._L))
+        out = (power[:n_rows], [int(x) for x in segs][:n_rows])
+        return out + (gram[:n_rows],) if spectrogram else out
+
     def device_pcm(self, stream):
         """Device address of the stream's int16 row of the last run; None after a float32 run."""
         return self._L.sauAmd_Batch_device_pcm(self._b, stream)
@@ -914,8 +1028,51 @@ class Batch:
 
     def close(self):
         if getattr(self, "_b", None):
+            for ref in getattr(self, "_meters", []):  # (a spectrum meter goes before its batch)
+                m = ref()
+                if m is not None:
+                    m.close()
             self._L.sauAmd_destroy_Batch(self._b)
             self._b = None
+
+    def __del__(self):
+        self.close()
+
+
+class Spectrum:
+    """sauAmdSpectrum: Welch power spectra of float32 rows, summed on the device in f64 (include/saugns_amd.h, section
+    "Spectrum"). A meter that is fed rows: ``feed`` takes row r's next frames[r] frames from device memory, on the batch's stream;
+    ``read`` waits and returns the sums and the segment counts. Close it before its batch."""
+
+    def __init__(self, batch, n_rows, channels, log2n, hop):
+        self._L = batch._L
+        self.n_rows, self.channels, self.log2n, self.hop = int(n_rows), int(channels), int(log2n), int(hop)
+        self._s = _used(self._L).sauAmd_Batch_create_spectrum(batch._b, self.n_rows, self.channels, self.log2n, self.hop)
+        if not self._s:
+            raise RuntimeError("sauAmd_Batch_create_spectrum returned NULL: " + last_error(self._L))
+        self._batch = batch  # (the batch outlives the meter: its close() closes this one first)
+        batch._meters = getattr(batch, "_meters", []) + [weakref.ref(self)]
+        self.bins = (1 << self.log2n) // 2 + 1
+
+    def feed(self, ptr, pitch, frames):
+        """sauAmd_Spectrum_feed: row r's next frames[r] frames from the device rows at `ptr`, `pitch` bytes apart."""
+        fr = (C.c_uint32 * self.n_rows)(*[int(f) for f in frames])
+        if not _used(self._L).sauAmd_Spectrum_feed(self._s, ptr, pitch, fr):
+            raise RuntimeError("sauAmd_Spectrum_feed failed: " + last_error(self._L))
+
+    def read(self, reset=False):
+        """sauAmd_Spectrum_read -> (float64 sums [n_rows, channels, N/2+1], the segments per row as a list)"""
+        power = np.zeros((self.n_rows, self.channels, self.bins), np.float64)
+        segs = (C.c_uint64 * self.n_rows)()
+        if not _used(self._L).sauAmd_Spectrum_read(self._s, power.ctypes.data_as(C.POINTER(C.c_double)), segs, 1 if reset else 0):
+            raise RuntimeError("sauAmd_Spectrum_read failed: " + last_error(self._L))
+        return power, [int(x) for x in segs]
+
+    def close(self):
+        if getattr(self, "_s", None):
+            self._L.sauAmd_Spectrum_destroy(self._s)
+            self._s = None
+            self._batch = None
 
     def __del__(self):
         self.close()

@@ -573,6 +573,74 @@ extern "C" bool sauAmd_Batch_limit_rows(sauAmdBatch *b, const void *rows, size_t
 	return false;
 }
 
+/* ---- the spectrum meter (include/saugns_amd.h, section "Spectrum") ---- */
+struct sauAmdSpectrum {
+	sauengine::SpectrumMeter *meter;
+};
+
+extern "C" size_t sauAmd_spectrum_window(unsigned log2n, double *out, size_t cap) { return sauengine::spectrum_window(log2n, out, cap); }
+extern "C" size_t sauAmd_spectrum_twiddles(unsigned log2n, double *out, size_t cap) { return sauengine::spectrum_twiddles(log2n, out, cap); }
+
+extern "C" sauAmdSpectrum *sauAmd_Batch_create_spectrum(sauAmdBatch *b, size_t n_rows, int channels, unsigned log2n, uint32_t hop) {
+	std::string err;
+	try {
+		if (!b || !n_rows || !sauengine::spectrum_params_ok(channels, log2n, hop)) err = "bad argument";
+		else if (sauengine::SpectrumMeter *m = b->engine->backend()->create_spectrum(n_rows, (uint32_t)channels, log2n, hop, err))
+			return new sauAmdSpectrum{m};
+	} catch (const std::exception &ex) { /* (nothing C++ crosses the C ABI) */
+		err = std::string("internal error: ") + ex.what();
+	}
+	report("spectrum", err);
+	return nullptr;
+}
+
+extern "C" void sauAmd_Spectrum_destroy(sauAmdSpectrum *s) {
+	if (!s) return;
+	delete s->meter;
+	delete s;
+}
+
+extern "C" bool sauAmd_Spectrum_feed(sauAmdSpectrum *s, const void *rows, size_t pitch_bytes, const uint32_t *frames) {
+	std::string err;
+	try {
+		if (!s || !rows || !frames || ((uintptr_t)rows & 15u) || (pitch_bytes & 15u)) err = "bad argument";
+		else if (s->meter->feed(rows, pitch_bytes, frames, err)) return true;
+	} catch (const std::exception &ex) {
+		err = std::string("internal error: ") + ex.what();
+	}
+	report("spectrum", err);
+	return false;
+}
+
+extern "C" bool sauAmd_Spectrum_read(sauAmdSpectrum *s, double *power_out, uint64_t *segments_out, int reset) {
+	std::string err;
+	try {
+		if (!s || !power_out || !segments_out) err = "bad argument";
+		else if (s->meter->read(power_out, segments_out, reset != 0, err)) return true;
+	} catch (const std::exception &ex) {
+		err = std::string("internal error: ") + ex.what();
+	}
+	report("spectrum", err);
+	return false;
+}
+
+extern "C" bool sauAmd_Batch_spectrum_rows(sauAmdBatch *b, const void *rows, size_t pitch_bytes, size_t n_rows, size_t frames, int channels,
+		unsigned log2n, uint32_t hop, double *power_out, uint64_t *segments_out, float *spectrogram_out, size_t spectrogram_cap) {
+	std::string err;
+	try {
+		if (!b || !rows || !power_out || !segments_out || !n_rows || ((uintptr_t)rows & 15u) || (pitch_bytes & 15u) ||
+		    !sauengine::spectrum_params_ok(channels, log2n, hop))
+			err = "bad argument";
+		else if (b->engine->backend()->spectrum_rows(rows, pitch_bytes, n_rows, frames, (uint32_t)channels, log2n, hop, power_out, segments_out,
+				spectrogram_out, spectrogram_cap, err))
+			return true;
+	} catch (const std::exception &ex) {
+		err = std::string("internal error: ") + ex.what();
+	}
+	report("batch", err);
+	return false;
+}
+
 extern "C" bool sauAmd_Batch_sync(sauAmdBatch *b) {
 	std::string err;
 	if (!b->engine->backend()->sync(err)) { report("batch", err); return false; }

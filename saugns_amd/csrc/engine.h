@@ -82,6 +82,35 @@ size_t limiter_window(uint32_t srate, double *out, size_t cap);
 /* pre_gain and ceiling: finite and > 0 (a NaN fails every comparison) */
 inline bool limiter_param_ok(float v) { return v > 0.f && v <= 3.402823466e+38f; }
 
+/* The spectrum meter on the host (tables.cpp; include/saugns_amd.h, section "Spectrum"). N = 2^log2n, log2n in SPEC_L_MIN ..
+ * SPEC_L_MAX; N / 8 <= hop <= N; segments are summed in groups of SPEC_GROUP. spectrum_window: N, and the periodic Hann window
+ * in out[] when cap suffices (nothing otherwise); spectrum_twiddles: N doubles, the N / 2 pairs (cos, -sin); both 0 for another
+ * log2n. spectrum_segment: one segment of one channel, x[j * stride] for j = 0 .. N-1, through re[N] and im[N] into p[N/2 + 1]. */
+constexpr uint32_t SPEC_L_MIN = 8, SPEC_L_MAX = 12, SPEC_GROUP = 16;
+size_t spectrum_window(unsigned log2n, double *out, size_t cap);
+size_t spectrum_twiddles(unsigned log2n, double *out, size_t cap);
+bool spectrum_segment(unsigned log2n, const double *w, const double *tw, const float *x, size_t stride, double *re, double *im,
+		double *p);
+inline bool spectrum_params_ok(int channels, unsigned log2n, uint32_t hop) {
+	return (channels == 1 || channels == 2) && log2n >= SPEC_L_MIN && log2n <= SPEC_L_MAX && hop >= (1u << log2n) / 8 && hop <= (1u << log2n);
+}
+/* S(P): the complete segments of P frames */
+inline uint64_t spectrum_segments(uint64_t frames, uint32_t N, uint32_t hop) { return frames < N ? 0 : (frames - N) / hop + 1; }
+
+/* A spectrum meter of a backend (Backend::create_spectrum): records that are fed rows. Destroyed before its backend. */
+class SpectrumMeter {
+public:
+	virtual ~SpectrumMeter() {}
+	virtual size_t n_rows() const = 0;
+	virtual uint32_t channels() const = 0;
+	virtual uint32_t log2n() const = 0;
+	/* row r's next frames[r] frames, from rows + pitch_bytes * r: device work on the backend's stream */
+	virtual bool feed(const void *rows, size_t pitch_bytes, const uint32_t *frames, std::string &err) = 0;
+	/* wait for the stream; power_out[n_rows][channels][N/2 + 1] the sums (the group at hand added in the copy), segments_out[n_rows];
+	 * `reset`: empty records behind the read */
+	virtual bool read(double *power_out, uint64_t *segments_out, bool reset, std::string &err) = 0;
+};
+
 /* Everything the backend needs to render one segment (no events inside). */
 struct SegmentDesc {
 	uint32_t len;             /* frames */
@@ -326,6 +355,20 @@ public:
 		(void)rows; (void)pitch_bytes; (void)n_rows; (void)frames; (void)stereo; (void)srate; (void)pre_gain; (void)ceiling;
 		(void)out_rows; (void)out_pitch_bytes; (void)stats_out;
 		err = "this backend has no limiter"; return false;
+	}
+	/* Welch power spectra of float rows (include/saugns_amd.h, section "Spectrum"), where the samples are. A backend without
+	 * them refuses -- these defaults -- and nothing changes. create_spectrum: a meter of n_rows empty records on the backend's
+	 * device and stream (the caller owns it and destroys it before the backend); the arguments have been looked at. */
+	virtual SpectrumMeter *create_spectrum(size_t n_rows, uint32_t channels, unsigned log2n, uint32_t hop, std::string &err) {
+		(void)n_rows; (void)channels; (void)log2n; (void)hop; err = "this backend has no spectrum meter"; return nullptr;
+	}
+	/* the same from empty records on rows of `frames` frames each, synchronous; spectrogram_out (may be NULL): every segment's
+	 * (float)p[k], [n_rows][channels][S][N/2 + 1], refused when spectrogram_cap (in floats) does not suffice */
+	virtual bool spectrum_rows(const void *rows, size_t pitch_bytes, size_t n_rows, size_t frames, uint32_t channels, unsigned log2n,
+			uint32_t hop, double *power_out, uint64_t *segments_out, float *spectrogram_out, size_t spectrogram_cap, std::string &err) {
+		(void)rows; (void)pitch_bytes; (void)n_rows; (void)frames; (void)channels; (void)log2n; (void)hop; (void)power_out;
+		(void)segments_out; (void)spectrogram_out; (void)spectrogram_cap;
+		err = "this backend has no spectrum meter"; return false;
 	}
 };
 

@@ -13,6 +13,7 @@
  *   k_decimate.h    decimate_kernel, decimate_carry_kernel (oversampled rendering: the decimating FIR and its history)
  *   k_loudness.h    loud_chunk_kernel, loud_scan_kernel, truepeak_kernel, loud_finish_kernel, loud_carry_kernel (BS.1770 loudness, true peak)
  *   k_limiter.h     lim_env_kernel, lim_gain_kernel, lim_finish_kernel, lim_carry_kernel (the look-ahead true-peak limiter)
+ *   k_spectrum.h    spec_segment_kernel, spec_finish_kernel, spec_carry_kernel (Welch power spectra of fed rows)
  *   launch_plan.h   (plain C++, no HIP) the tuning switches and every decision about a segment's launches: rows per pass, LDS
  *                   budgets, builds, grids, tasks, chain chunks, the mixer -- a plan per segment, testable without a GPU
  *   (this file)     buffer and stream pools, table sets, the kernel lookup, HipBackendImpl: render() carries a plan out,
@@ -76,6 +77,7 @@ using namespace sauplan;
 #include "k_decimate.h"
 #include "k_loudness.h"
 #include "k_limiter.h"
+#include "k_spectrum.h"
 static_assert(MISC_BYTES == sizeof(Misc), "launch_plan.h plans the block loop's LDS with this size");
 
 /* ------------------------------------------------------------------------ */
@@ -1850,6 +1852,141 @@ public:
 		return true;
 	}
 
+	/* ---- the spectrum meter (k_spectrum.h; the geometry is launch_plan.h's plan_spectrum) ----
+	 * A meter is records of its own on this backend's device and stream: sums, the group at hand, the pending frames (two
+	 * buffers: spec_carry_kernel moves from one into the other). Where a row stands is kept on the host -- the frame counts
+	 * of a feed are host values -- and every feed uploads what the kernels need of it (SpecRow). */
+	class Spectrum : public sauengine::SpectrumMeter {
+	public:
+		Spectrum(HipBackendImpl *be, size_t n_rows, uint32_t channels, unsigned log2n, uint32_t hop)
+			: be_(be), n_(n_rows), ch_(channels), L_(log2n), N_(1u << log2n), bins_((1u << log2n) / 2 + 1), hop_(hop), pos_(n_rows, 0) {}
+		~Spectrum() override { /* the buffers go back to the pool (member destructors): nothing may still be using them */
+			be_->use_device();
+			if (be_->stream_) (void)hipStreamSynchronize(be_->stream_);
+		}
+		size_t n_rows() const override { return n_; }
+		uint32_t channels() const override { return ch_; }
+		uint32_t log2n() const override { return L_; }
+		bool init(std::string &err) {
+			const SpectrumPlan plan = plan_spectrum(L_, hop_, ch_, n_, nullptr);
+			if (!plan.ok) { err = "bad argument"; return false; }
+			const size_t sums = n_ * plan.sum_pitch, pend = n_ * plan.pend_pitch;
+			if (!total_.ensure(sums, err) || !acc_.ensure(sums, err) || !pend_[0].ensure(pend, err) || !pend_[1].ensure(pend, err) ||
+			    !desc_.ensure(n_, err) || !win_.ensure(N_, err) || !tw_.ensure(N_, err))
+				return false;
+			std::vector<double> t(N_);
+			if (sauengine::spectrum_window(L_, t.data(), N_) != N_ || !be_->send(win_.p, t.data(), N_ * sizeof(double), err)) return false;
+			if (sauengine::spectrum_twiddles(L_, t.data(), N_) != N_ || !be_->send(tw_.p, t.data(), N_ * sizeof(double), err)) return false;
+			return clear(err);
+		}
+		bool clear(std::string &err) {
+			HIP_OK(hipMemsetAsync(total_.p, 0, n_ * bins_ * ch_ * sizeof(double), be_->stream_)); /* (+0.0; behind the last feed's kernels) */
+			std::fill(pos_.begin(), pos_.end(), 0);
+			return true;
+		}
+		/* sgram: feed()'s segment kernel also writes every segment's (float)p[k] there (spectrum_rows: rows from empty records) */
+		bool feed_into(const void *rows, size_t pitch, const uint32_t *frames, float *sgram, size_t sgram_segs, std::string &err) {
+			be_->use_device();
+			if (!rows || !frames || ((uintptr_t)rows & 15u) || (pitch & 15u)) { err = "bad argument: rows and pitch_bytes must be multiples of 16"; return false; }
+			uint32_t longest = 0;
+			for (size_t r = 0; r < n_; ++r) longest = frames[r] > longest ? frames[r] : longest;
+			if (!longest) return true; /* nothing changes, and the rows are not looked at */
+			const size_t row_bytes = (size_t)longest * ch_ * sizeof(float);
+			if (n_ > 1 && row_bytes > pitch) { err = "bad argument: rows longer than their pitch"; return false; }
+			/* the rows are read by kernels: they have to lie inside one allocation of this device */
+			if (!be_->lim_rows_inside(rows, pitch, n_, row_bytes, "rows", err)) return false;
+			std::vector<SpecRow> d(n_);
+			for (size_t r = 0; r < n_; ++r) d[r] = plan_spectrum_row(pos_[r], frames[r], N_, hop_);
+			const SpectrumPlan plan = plan_spectrum(L_, hop_, ch_, n_, d.data());
+			if (!plan.ok) { err = "bad argument: too many frames for one feed"; return false; }
+			if (plan.scratch && !part_.ensure(plan.scratch, err)) return false;
+			if (!be_->send(desc_.p, d.data(), n_ * sizeof(SpecRow), err)) return false;
+			SpecParams sp;
+			memset((void *)&sp, 0, sizeof sp);
+			sp.rows = (const float *)rows; sp.row_pitch = pitch; sp.desc = desc_.p;
+			sp.pend = pend_[cur_].p; sp.pend_next = pend_[cur_ ^ 1].p; sp.pend_pitch = plan.pend_pitch;
+			sp.acc = acc_.p; sp.total = total_.p; sp.part = part_.p;
+			sp.sgram = sgram; sp.sgram_segs = sgram_segs;
+			sp.win = win_.p; sp.tw = (const double2 *)tw_.p;
+			sp.hop = hop_; sp.channels = ch_; sp.max_groups = plan.max_groups;
+			hipStream_t st = be_->stream_;
+			if (plan.max_groups) {
+				const dim3 grid(plan.max_groups, plan.rows, ch_), block(SPEC_THREADS);
+				switch (L_) {
+				case 8: hipLaunchKernelGGL(spec_segment_kernel<8>, grid, block, plan.lds_bytes, st, sp); break;
+				case 9: hipLaunchKernelGGL(spec_segment_kernel<9>, grid, block, plan.lds_bytes, st, sp); break;
+				case 10: hipLaunchKernelGGL(spec_segment_kernel<10>, grid, block, plan.lds_bytes, st, sp); break;
+				case 11: hipLaunchKernelGGL(spec_segment_kernel<11>, grid, block, plan.lds_bytes, st, sp); break;
+				default: hipLaunchKernelGGL(spec_segment_kernel<12>, grid, block, plan.lds_bytes, st, sp); break;
+				}
+				HIP_OK(hipGetLastError());
+				hipLaunchKernelGGL(spec_finish_kernel, dim3((bins_ + SPEC_THREADS - 1) / SPEC_THREADS, plan.rows, ch_), block, 0, st, sp, bins_);
+				HIP_OK(hipGetLastError());
+			}
+			hipLaunchKernelGGL(spec_carry_kernel, dim3((uint32_t)((plan.pend_pitch + SPEC_THREADS - 1) / SPEC_THREADS), plan.rows), dim3(SPEC_THREADS), 0, st, sp);
+			HIP_OK(hipGetLastError());
+			cur_ ^= 1;
+			for (size_t r = 0; r < n_; ++r) pos_[r] += frames[r];
+			return true;
+		}
+		bool feed(const void *rows, size_t pitch, const uint32_t *frames, std::string &err) override {
+			return feed_into(rows, pitch, frames, nullptr, 0, err);
+		}
+		bool read(double *power_out, uint64_t *segments_out, bool reset, std::string &err) override {
+			be_->use_device();
+			const size_t sums = n_ * bins_ * ch_;
+			std::vector<double> acc(sums);
+			HIP_OK(hipMemcpyAsync(power_out, total_.p, sums * sizeof(double), hipMemcpyDeviceToHost, be_->stream_));
+			HIP_OK(hipMemcpyAsync(acc.data(), acc_.p, sums * sizeof(double), hipMemcpyDeviceToHost, be_->stream_));
+			HIP_OK(hipStreamSynchronize(be_->stream_));
+			for (size_t r = 0; r < n_; ++r) {
+				const uint64_t S = sauengine::spectrum_segments(pos_[r], N_, hop_);
+				segments_out[r] = S;
+				if (S % SPEC_GROUP) /* the group at hand, in the copy: the device state is untouched */
+					for (size_t k = r * bins_ * ch_; k < (r + 1) * bins_ * ch_; ++k) power_out[k] = power_out[k] + acc[k];
+			}
+			return !reset || clear(err);
+		}
+	private:
+		HipBackendImpl *be_;
+		size_t n_;
+		uint32_t ch_, L_, N_, bins_, hop_;
+		std::vector<uint64_t> pos_; /* per row: frames fed so far */
+		DevBuf<double> total_, acc_, part_, win_, tw_;
+		DevBuf<float> pend_[2];
+		DevBuf<SpecRow> desc_;
+		int cur_ = 0;
+	};
+	sauengine::SpectrumMeter *create_spectrum(size_t n_rows, uint32_t channels, unsigned log2n, uint32_t hop, std::string &err) override {
+		use_device();
+		if (!sauengine::spectrum_params_ok((int)channels, log2n, hop) || !n_rows) { err = "bad argument"; return nullptr; }
+		if (n_rows > SPEC_MAX_ROWS) { err = "bad argument: more than 65535 rows"; return nullptr; }
+		Spectrum *m = new Spectrum(this, n_rows, channels, log2n, hop);
+		if (!m->init(err)) { delete m; return nullptr; }
+		return m;
+	}
+	bool spectrum_rows(const void *rows, size_t pitch, size_t n_rows, size_t frames, uint32_t channels, unsigned log2n, uint32_t hop,
+			double *power_out, uint64_t *segments_out, float *spectrogram_out, size_t spectrogram_cap, std::string &err) override {
+		use_device();
+		if (!sauengine::spectrum_params_ok((int)channels, log2n, hop) || !n_rows || !power_out || !segments_out) { err = "bad argument"; return false; }
+		if (!rows || ((uintptr_t)rows & 15u) || (pitch & 15u)) { err = "bad argument: rows and pitch_bytes must be multiples of 16"; return false; }
+		if (n_rows > SPEC_MAX_ROWS || frames > 0xffffffffull) { err = "bad argument: more than 65535 rows, or than 32 bits of frames"; return false; }
+		const uint32_t N = 1u << log2n, bins = N / 2 + 1;
+		const uint64_t S = sauengine::spectrum_segments(frames, N, hop);
+		size_t sg = 0;
+		if (spectrogram_out && (__builtin_mul_overflow((size_t)S, (size_t)bins * channels, &sg) || __builtin_mul_overflow(sg, n_rows, &sg) || sg > spectrogram_cap)) {
+			err = "bad argument: the spectrogram needs more floats than spectrogram_cap"; return false;
+		}
+		Spectrum m(this, n_rows, channels, log2n, hop);
+		if (!m.init(err)) return false;
+		if (spectrogram_out && sg && !spec_gram_.ensure(sg, err)) return false;
+		const std::vector<uint32_t> fr(n_rows, (uint32_t)frames);
+		if (!m.feed_into(rows, pitch, fr.data(), spectrogram_out && sg ? spec_gram_.p : nullptr, (size_t)S, err)) return false;
+		if (!m.read(power_out, segments_out, false, err)) return false;
+		if (spectrogram_out && sg) HIP_OK(hipMemcpy(spectrogram_out, spec_gram_.p, sg * sizeof(float), hipMemcpyDeviceToHost));
+		return true;
+	}
+
 	const int16_t *device_pcm(uint32_t stream) override { return pcm_.p && !pcm_f32_ ? (const int16_t *)pcm_at(stream) : nullptr; }
 	const float *device_pcm_f32(uint32_t stream) override { return pcm_.p && pcm_f32_ ? (const float *)pcm_at(stream) : nullptr; }
 	size_t device_pcm_pitch() override { return pcm_.p ? pcm_pitch() : 0; }
@@ -2101,6 +2238,7 @@ private:
 	uint32_t lim_rate_ = 0;
 	bool lim_on_ = false, lim_stereo_ = false, lim_out_f32_ = false;
 	size_t lim_out_pitch_ = 0, lim_out_bytes_ = 0; /* of the last limited run: between the rows, and of a row's frames */
+	DevBuf<float> spec_gram_; /* spectrum_rows: one call's spectrogram, from the pool, not there until asked for */
 	size_t decim_out_pitch_ = 0, decim_out_bytes_ = 0; /* of the last decimated run: between the rows, and of a row's frames */
 	DevBuf<uint32_t> vlists_;   /* [2][n_voices]: analyze_kernel's lists of closed-form and look-back voices (split launches) */
 	/* A chain kernel's workgroup is three waves on a latency-bound recurrence. SAU_AMD_CHAIN_ALONE=1 (a tuning switch): while a

@@ -872,5 +872,67 @@ inline LimitPlan plan_limit(uint64_t frames, uint32_t srate, uint32_t channels, 
 	return p;
 }
 
+/* ---- the spectrum meter (k_spectrum.h) ----
+ * A feed of one row: the row stood at `pos` frames and takes `frames` more. With S(P) = 0 for P < N, else (P - N) / hop + 1,
+ * the feed completes the segments [S(pos), S(pos + frames)); segment s covers the frames [s hop, s hop + N), of which those
+ * below pos are the row's pending frames -- the pos - S(pos) hop (< N) frames from S(pos) hop on -- and the rest lie in the fed
+ * row. Group g holds the segments [16 g, 16 g + 16): the feed touches the groups g0 = S(pos) / 16 .. (S(pos + frames) - 1) / 16,
+ * one workgroup of spec_segment_kernel per (group, row, channel); the first continues the carried accumulator when S(pos) is no
+ * multiple of 16, and spec_finish_kernel adds the groups that are complete behind the feed into the total in ascending g and
+ * keeps the last one as the carried accumulator when it is not. All of it is a function of (pos, frames, N, hop): the sums
+ * never depend on how a sequence was cut into feeds, on the grid or on the device. */
+constexpr uint32_t SPEC_THREADS = 256, SPEC_GROUP = sauengine::SPEC_GROUP;
+constexpr uint32_t SPEC_MAX_ROWS = 65535;            /* grid.y */
+constexpr uint64_t SPEC_MAX_SCRATCH = 1ull << 27;    /* doubles of one feed's group sums (1 GiB): a longer feed is made in pieces */
+struct SpecRow { /* (what the kernels read of a row's feed: uploaded as it stands) */
+	uint64_t seg0;        /* S(pos): the first segment this feed completes */
+	uint32_t n_seg;       /* how many it completes */
+	uint32_t pend;        /* pending frames ahead of the feed: pos - seg0 * hop */
+	uint32_t pend_next;   /* ... and behind it */
+	uint32_t acc_cnt;     /* segments in the carried accumulator: seg0 % 16 */
+	uint32_t n_groups;    /* groups this feed touches (0: no segment) */
+	uint32_t n_complete;  /* the first so many of them are complete behind the feed */
+};
+static_assert(sizeof(SpecRow) == 32, "SpecRow is uploaded as it stands");
+inline SpecRow plan_spectrum_row(uint64_t pos, uint32_t frames, uint32_t N, uint32_t hop) {
+	SpecRow r;
+	const uint64_t s0 = sauengine::spectrum_segments(pos, N, hop), s1 = sauengine::spectrum_segments(pos + frames, N, hop);
+	r.seg0 = s0;
+	r.n_seg = (uint32_t)(s1 - s0);
+	r.pend = (uint32_t)(pos - s0 * hop);
+	r.pend_next = (uint32_t)(pos + frames - s1 * hop);
+	r.acc_cnt = (uint32_t)(s0 % SPEC_GROUP);
+	r.n_groups = s1 > s0 ? (uint32_t)((s1 - 1) / SPEC_GROUP - s0 / SPEC_GROUP + 1) : 0;
+	r.n_complete = s1 > s0 ? (uint32_t)(s1 / SPEC_GROUP - s0 / SPEC_GROUP) : 0;
+	return r;
+}
+struct SpectrumPlan {
+	bool ok = false;          /* false: log2n, hop or channels out of range, no row or more than a grid has, a feed too long */
+	uint32_t N = 0, bins = 0; /* 2^log2n; N / 2 + 1 */
+	uint32_t rows = 0, channels = 0;
+	uint32_t max_groups = 0;  /* grid.x of spec_segment_kernel, and the groups' stride in the scratch (0: no launch) */
+	size_t lds_bytes = 0;     /* spec_segment_kernel's dynamic LDS: re and im, 16 N bytes */
+	size_t pend_pitch = 0;    /* floats between the rows' pending frames: N * channels */
+	size_t sum_pitch = 0;     /* doubles between the rows' sums: bins * channels */
+	size_t scratch = 0;       /* doubles of the groups' sums: rows * channels * max_groups * bins */
+};
+/* rows: the feed's records (NULL: none, the meter's own sizes only) */
+inline SpectrumPlan plan_spectrum(unsigned log2n, uint32_t hop, uint32_t channels, size_t n_rows, const SpecRow *rows) {
+	SpectrumPlan p;
+	if (!sauengine::spectrum_params_ok((int)channels, log2n, hop) || !n_rows || n_rows > SPEC_MAX_ROWS) return p;
+	p.N = 1u << log2n; p.bins = p.N / 2 + 1;
+	p.rows = (uint32_t)n_rows; p.channels = channels;
+	for (size_t r = 0; rows && r < n_rows; ++r)
+		if (rows[r].n_groups > p.max_groups) p.max_groups = rows[r].n_groups;
+	p.lds_bytes = (size_t)p.N * 2 * sizeof(double);
+	p.pend_pitch = (size_t)p.N * channels;
+	p.sum_pitch = (size_t)p.bins * channels;
+	const uint64_t sc = (uint64_t)n_rows * channels * p.max_groups * p.bins;
+	if (sc > SPEC_MAX_SCRATCH) return p;
+	p.scratch = (size_t)sc;
+	p.ok = true;
+	return p;
+}
+
 } /* namespace sauplan */
 #endif

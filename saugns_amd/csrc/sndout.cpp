@@ -445,6 +445,64 @@ bool write_limited(const sauProgram *prg, uint32_t srate, const char *path, int 
 	return ok;
 }
 
+/* sauAmd_render_spectrum's render: the runs of render_file_over (factor 1: measure_program's loop) or of write_oversampled,
+ * with a feed of the run's device row where those fetch it -- the spectrum meter of one record takes exactly the floats the
+ * float32 file would hold, and no sample leaves the device. The meter goes before the engine, which owns the backend. */
+bool measure_spectrum(const sauProgram *prg, uint32_t srate, int factor, int channels, unsigned log2n, uint32_t hop,
+		Backend *backend /* owned */, double *power_out, uint64_t *segments_out, uint64_t *frames_out, std::string &err) {
+	const uint32_t rate = srate * (uint32_t)factor;
+	Engine *engine = Engine::create(&prg, 1, rate, backend, err);
+	if (!engine) return false;
+	const bool stereo = channels == 2;
+	size_t call, chunk;
+	file_lattice(rate, call, chunk);
+	engine->set_call_len(call);
+	/* a backend without a spectrum meter, float output or a decimator says so here, before anything renders */
+	sauengine::SpectrumMeter *meter = backend->create_spectrum(1, (uint32_t)channels, log2n, hop, err);
+	bool ok = meter && engine->set_format(sauengine::SF_F32, err) && (factor == 1 || engine->begin_decimated(factor, stereo, err));
+	uint64_t fed = 0;
+	if (ok && factor == 1) {
+		bool more = true;
+		while (ok && more) {
+			size_t len = 0;
+			ok = engine->run_f32(nullptr, chunk, stereo, &more, &len, err);
+			if (ok && len) {
+				const uint32_t n = (uint32_t)len;
+				const float *row = backend->device_pcm_f32(0);
+				if (!row) { err = "the backend keeps no float rows on the device"; ok = false; }
+				else ok = meter->feed(row, backend->device_pcm_pitch(), &n, err);
+				fed += len;
+			}
+		}
+	} else if (ok) {
+		const size_t H = sauengine::decimator_latency(factor);
+		bool more = true, tail = false;
+		uint64_t y_pos = 0, wanted = 0; /* as write_oversampled counts them: what is measured is y[H, H + wanted) */
+		while (ok && !tail) {
+			tail = !more;
+			const size_t n = tail ? H : chunk;
+			size_t len = 0;
+			ok = engine->run_decimated(nullptr, sauengine::SF_F32, false, factor, n, stereo, &more, &len, err);
+			if (!ok) break;
+			wanted += len;
+			const uint64_t lo = y_pos > H ? y_pos : H, end = y_pos + n, hi = H + wanted < end ? H + wanted : end;
+			if (hi > lo) {
+				const uint32_t cnt = (uint32_t)(hi - lo);
+				const float *row = backend->device_decimated_f32(0);
+				if (!row) { err = "the backend keeps no decimated rows on the device"; ok = false; }
+				else ok = meter->feed(row + (size_t)(lo - y_pos) * (size_t)channels, backend->device_decimated_pitch(), &cnt, err);
+				fed += cnt;
+			}
+			y_pos = end;
+		}
+	}
+	ok = ok && meter->read(power_out, segments_out, false, err);
+	if (ok && frames_out) *frames_out = fed;
+	delete meter;
+	delete engine; /* owns the backend */
+	return ok;
+}
+
 } /* namespace */
 
 bool sauamd_internal::render_file_normalized(const sauProgram *prg, uint32_t srate, const char *path, int format, int channels,
@@ -608,4 +666,32 @@ extern "C" bool sauAmd_render_file(const sauProgram *prg, uint32_t srate, const 
 bool sauamd_internal::render_file(const sauProgram *prg, uint32_t srate, const char *path, int format, int channels,
 		Backend *injected, uint64_t *frames_out, std::string &err) {
 	return injected && render_file_over(prg, srate, path, format, channels, injected, frames_out, err);
+}
+
+bool sauamd_internal::render_spectrum(const sauProgram *prg, uint32_t srate, int factor, int channels, unsigned log2n, uint32_t hop,
+		const std::function<Backend *(std::string &)> &make_backend, double *power_out, uint64_t *segments_out, uint64_t *frames_out,
+		std::string &err) {
+	if (frames_out) *frames_out = 0;
+	if (!prg || !power_out || !segments_out || !sauengine::spectrum_params_ok(channels, log2n, hop) || !srate ||
+	    (factor != 1 && !sauengine::decimator_latency(factor)) || srate > UINT32_MAX / (uint32_t)factor) {
+		err = "bad argument";
+		return false;
+	}
+	Backend *backend = make_backend(err);
+	if (!backend) return false;
+	return measure_spectrum(prg, srate, factor, channels, log2n, hop, backend, power_out, segments_out, frames_out, err);
+}
+
+extern "C" bool sauAmd_render_spectrum(const sauProgram *prg, uint32_t srate, int factor, int channels, unsigned log2n, uint32_t hop,
+		double *power_out, uint64_t *segments_out, uint64_t *frames_out) {
+	std::string err;
+	bool ok = false;
+	try {
+		ok = sauamd_internal::render_spectrum(prg, srate, factor, channels, log2n, hop,
+				[](std::string &e) -> Backend * { return sauhip::create_hip_backend(e); }, power_out, segments_out, frames_out, err);
+	} catch (const std::exception &ex) { /* (nothing C++ crosses the C ABI) */
+		err = std::string("internal error: ") + ex.what();
+	}
+	if (!ok) sauamd_internal::set_last_error("output", err);
+	return ok;
 }

@@ -241,6 +241,59 @@ size_t limiter_window(uint32_t srate, double *out, size_t cap) {
 	return W;
 }
 
+/* ---- the spectrum meter's tables and one segment on the host (engine.h; include/saugns_amd.h, section "Spectrum") ----
+ * The periodic Hann window and the twiddles of N = 2^L, in f64: the device and the tests' restatement both take them from
+ * here, so no comparison depends on two libm's agreeing. spectrum_segment restates one segment of one channel in plain loops,
+ * every product rounded and then the sum or difference (the build is -ffp-contract=off): what spec_segment_kernel computes. */
+size_t spectrum_window(unsigned log2n, double *out, size_t cap) {
+	if (log2n < SPEC_L_MIN || log2n > SPEC_L_MAX) return 0;
+	const size_t N = (size_t)1 << log2n;
+	if (!out || cap < N) return N;
+	const double pi = 3.14159265358979323846;
+	for (size_t j = 0; j < N; ++j) out[j] = 0.5 - 0.5 * cos(2.0 * pi * (double)j / (double)N);
+	return N;
+}
+
+size_t spectrum_twiddles(unsigned log2n, double *out, size_t cap) {
+	if (log2n < SPEC_L_MIN || log2n > SPEC_L_MAX) return 0;
+	const size_t N = (size_t)1 << log2n;
+	if (!out || cap < N) return N;
+	const double pi = 3.14159265358979323846;
+	for (size_t k = 0; k < N / 2; ++k) {
+		out[2 * k] = cos(2.0 * pi * (double)k / (double)N);
+		out[2 * k + 1] = -sin(2.0 * pi * (double)k / (double)N);
+	}
+	return N;
+}
+
+bool spectrum_segment(unsigned log2n, const double *w, const double *tw, const float *x, size_t stride, double *re, double *im,
+		double *p) {
+	if (log2n < SPEC_L_MIN || log2n > SPEC_L_MAX || !w || !tw || !x || !re || !im || !p) return false;
+	const size_t N = (size_t)1 << log2n;
+	for (size_t j = 0; j < N; ++j) {
+		size_t r = 0;
+		for (unsigned b = 0; b < log2n; ++b) r |= ((j >> b) & 1) << (log2n - 1 - b);
+		uint32_t bits;
+		memcpy(&bits, &x[j * stride], sizeof bits);
+		const float xf = (bits & 0x7fffffffu) < 0x7f800000u ? x[j * stride] : 0.f; /* (a NaN or +-inf counts as +0.0f) */
+		re[r] = w[j] * (double)xf;
+		im[r] = 0.0;
+	}
+	for (unsigned t = 1; t <= log2n; ++t) {
+		const size_t m = (size_t)1 << t, h = m / 2, st = N / m;
+		for (size_t k0 = 0; k0 < N; k0 += m)
+			for (size_t j = 0; j < h; ++j) {
+				const size_t a = k0 + j, b = a + h;
+				const double c = tw[2 * j * st], d = tw[2 * j * st + 1];
+				const double tr = c * re[b] - d * im[b], ti = c * im[b] + d * re[b];
+				const double ur = re[a], ui = im[a];
+				re[a] = ur + tr; im[a] = ui + ti; re[b] = ur - tr; im[b] = ui - ti;
+			}
+	}
+	for (size_t k = 0; k <= N / 2; ++k) p[k] = re[k] * re[k] + im[k] * im[k];
+	return true;
+}
+
 /* ---- loudness on the host (engine.h; include/saugns_amd.h states every formula and the order of every operation) ---- */
 
 size_t truepeak_taps(double *out, size_t cap) {
