@@ -110,7 +110,13 @@ SAU_AMD_API void sauAmd_Batch_timing_ex(sauAmdBatch *b, double *out4, uint64_t *
  * 2 every kernel. The query functions above switch level 2 on when still off. */
 SAU_AMD_API void sauAmd_Batch_set_timing(sauAmdBatch *b, int level);
 
-/* The stream the batch launches its kernels on, as a hipStream_t. */
+/* The stream the batch launches its kernels on, as a hipStream_t, with everything issued for the batch so far ordered on it.
+ * A run's last kernel -- the mixer that writes the PCM rows -- may run on a second stream of the batch's (beside the next
+ * run's set-up); this call, like sauAmd_Batch_device_pcm, _device_pcm_f32 and _device_pcm_pitch, joins it onto the stream it
+ * returns. So a caller that reads a run's rows on the device (bufs == NULL) with work of its own on this stream calls
+ * sauAmd_Batch_stream -- or one of those three -- AFTER that run, every run: the handle and the row pointers stay the same
+ * from run to run, the ordering is what the call makes. Work enqueued on a handle obtained before the run, with no such
+ * call and no sauAmd_Batch_sync in between, is not ordered behind that run's mixer. */
 SAU_AMD_API void *sauAmd_Batch_stream(sauAmdBatch *b);
 
 /* Order b's next run behind what has been issued for `before` so far: the rendering kernels of b's next

@@ -16,6 +16,7 @@
  *   k_spectrum.h    spec_segment_kernel, spec_finish_kernel, spec_carry_kernel (Welch power spectra of fed rows)
  *   launch_plan.h   (plain C++, no HIP) the tuning switches and every decision about a segment's launches: rows per pass, LDS
  *                   budgets, builds, grids, tasks, chain chunks, the mixer -- a plan per segment, testable without a GPU
+ *   mix_overlap.h   (plain C++, no HIP) where the main stream waits for a final mixer that runs on the side stream
  *   (this file)     buffer and stream pools, table sets, the kernel lookup, HipBackendImpl: render() carries a plan out,
  *                   stage by stage in the launch order of DESIGN.md 2
  *
@@ -392,10 +393,54 @@ public:
 	 * the current device) and launches all follow it */
 	void use_device() { (void)hipSetDevice(dev_); }
 
+	/* ---- the final mixer's side stream (mix_overlap.h has the rules; launch_mixer puts the mixer there) ----
+	 * Every override of Backend joins the pending mixer as its first action -- join_mixer(), a wait on the main stream, nothing
+	 * the host blocks on -- so that a method added later is ordered behind the mixer by default. Those that do not:
+	 *   render                         asks the tracker at the points mix_overlap.h names
+	 *   upload_plans, apply_updates    write plans and operator records, which no mixer reads
+	 *   reserve_frames, set_format     join only when they change something (the rows' size, the samples' format)
+	 *   zero_pcm                       joins once it knows that it has frames to clear
+	 *   chain_rows_budget, alloc_host, free_host, wait_fetch   touch nothing on the device that a mixer uses */
+	/* the main stream waits for mixer `t` (0: for nothing); `where`: for SAU_AMD_OVERLAP_REPORT */
+	bool wait_mixer(uint64_t t, const char *where, std::string &err) {
+		if (!t) return true;
+		hipEvent_t done = mix_done_[MixOverlapTracker::slot(t)];
+		if (overlap_report_) { /* (had it finished already? asked only for the report) */
+			const bool was_done = hipEventQuery(done) == hipSuccess;
+			report_waits_ += std::string(" ") + where + ":" + std::to_string(t) + (was_done ? ":done" : ":busy");
+		}
+		HIP_OK(hipStreamWaitEvent(stream_, done, 0));
+		return true;
+	}
+	bool join_mixer(const char *where, std::string &err) { return wait_mixer(mixo_.join(), where, err); }
+	void join_mixer_quiet(const char *where) { std::string e; (void)join_mixer(where, e); }
+	bool ensure_mix_stream(std::string &err) {
+		if (mix_ready_) return true;
+		/* from the chain streams' pool, high priority as they are: a queue of another priority is never the main stream's
+		 * (launch_chains), and two streams on one hardware queue would run the mixer behind the set-up launches after all */
+		if (!mix_stream_) mix_stream_ = StreamPool::get().take(dev_, 1);
+		if (!mix_stream_) {
+			int lo = 0, hi = 0;
+			(void)hipDeviceGetStreamPriorityRange(&lo, &hi);
+			HIP_OK(hipStreamCreateWithPriority(&mix_stream_, hipStreamNonBlocking, hi));
+		}
+		for (uint32_t i = 0; i < MIXO_RING; ++i) { /* (a call that failed midway is taken up where it stopped) */
+			if (!mix_fork_[i]) HIP_OK(hipEventCreateWithFlags(&mix_fork_[i], hipEventDisableTiming));
+			if (!mix_done_[i]) HIP_OK(hipEventCreateWithFlags(&mix_done_[i], hipEventDisableTiming));
+		}
+		mix_ready_ = true;
+		return true;
+	}
+
 	~HipBackendImpl() override {
 		use_device();
 		/* the buffers go back to the pool (member destructors): nothing may still be using them */
-		if (stream_) (void)hipStreamSynchronize(stream_);
+		if (stream_) { join_mixer_quiet("destroy"); (void)hipStreamSynchronize(stream_); }
+		if (mix_stream_) { (void)hipStreamSynchronize(mix_stream_); StreamPool::get().give(dev_, mix_stream_, 1); }
+		for (uint32_t i = 0; i < MIXO_RING; ++i) {
+			if (mix_fork_[i]) (void)hipEventDestroy(mix_fork_[i]);
+			if (mix_done_[i]) (void)hipEventDestroy(mix_done_[i]);
+		}
 		if (chain_stream_) { (void)hipStreamSynchronize(chain_stream_); StreamPool::get().give(dev_, chain_stream_, 1); }
 		for (hipEvent_t e : chain_ev_) (void)hipEventDestroy(e);
 		for (int i = 0; i < 4; ++i) if (fetch_ev_[i]) (void)hipEventDestroy(fetch_ev_[i]);
@@ -437,6 +482,7 @@ public:
 		debug_ = getenv("SAU_AMD_DEBUG") != nullptr;
 		inmix_report_ = tune_env("SAU_AMD_INMIX_REPORT") != nullptr;
 		inner_report_ = tune_env("SAU_AMD_INNER_REPORT") != nullptr; /* (tests: which form the inner launch took) */
+		overlap_report_ = tune_env("SAU_AMD_OVERLAP_REPORT") != nullptr; /* (tests: where the final mixer ran and what waited for it) */
 		if (!ops_.ensure(cfg.op_count ? cfg.op_count : 1, err)) return false;
 		HIP_OK(hipMemsetAsync(ops_.p, 0, ops_.cap * sizeof(DevOp), stream_));
 		tables_ = shared_tables(cfg.piluts, cfg.wconst, err);
@@ -447,13 +493,14 @@ public:
 
 	bool reserve_frames(uint32_t max_frames, bool /* stereo: the rows have room for it either way */, std::string &err) override {
 		use_device();
+		if (!join_mixer("reserve_frames", err)) return false; /* (the rows and the PCM block are sized anew) */
 		HIP_OK(hipStreamSynchronize(stream_));
 		row_stride_ = (max_frames + 63) & ~63u;
 		pcm_row_ = (size_t)row_stride_ * 2; /* room for stereo */
 		/* (not cleared: every frame of a run is written by a mixer or cleared by zero_pcm, and no frame behind a run's
 		 * length is ever handed out -- until round 6 a memset here, 32 us for a config-4 batch's 677 MB) */
 		if (!pcm_.ensure(pcm_row_ * cfg_.n_streams * pcm_units(), err)) return false;
-		set_.vout_rows = 0; /* re-sized on the next render */
+		sets_[0].vout_rows = sets_[1].vout_rows = 0; /* re-sized on the next render */
 		return true;
 	}
 
@@ -467,8 +514,10 @@ public:
 		use_device();
 		const bool f32 = fmt == sauengine::SF_F32;
 		if (f32 == pcm_f32_) return true;
-		/* (no wait: the last run's copies out of the rows and this run's stores are in order on the one stream, and a block
-		 * that moves is freed only once the device has drained -- DevBuf::ensure) */
+		/* (no wait for the host: the last run's copies out of the rows and this run's stores are in order on the main stream --
+		 * behind the last run's mixer, which is joined here -- and a block that moves is freed only once the device has
+		 * drained -- DevBuf::ensure) */
+		if (!join_mixer("set_format", err)) return false;
 		pcm_f32_ = f32;
 		if (pcm_row_ && !pcm_.ensure(pcm_row_ * cfg_.n_streams * pcm_units(), err)) { pcm_f32_ = !f32; return false; }
 		return true;
@@ -528,6 +577,7 @@ public:
 	bool poison_run(uint32_t frames, bool stereo, std::string &err) override {
 		(void)frames; (void)stereo;
 		use_device();
+		if (!join_mixer("poison_run", err)) return false;
 		/* (a float row then reads 0x5a5a5a5a = 1.5e16 per sample: no mix of voices comes near it) */
 		if (pcm_.p) HIP_OK(hipMemsetD16Async((hipDeviceptr_t)pcm_.p, 0x5a5a, pcm_row_ * cfg_.n_streams * pcm_units(), stream_));
 		return true;
@@ -537,6 +587,7 @@ public:
 			std::string &err) override {
 		use_device();
 		if (!pcm_.p || !n_streams || !n_frames) return true;
+		if (!join_mixer("zero_pcm", err)) return false;
 		const size_t fb = (stereo ? 2 : 1) * pcm_units() * sizeof(int16_t); /* bytes per frame (zero bytes are +0.0f too) */
 		char *at = pcm_at(first_stream) + (size_t)first_frame * fb;
 		if (n_streams == 1) HIP_OK(hipMemsetAsync(at, 0, (size_t)n_frames * fb, stream_));
@@ -557,10 +608,13 @@ public:
 		FastParams fp;
 		FastParams cfp;       /* the closed-form launch of a split segment (also what the cub build and repair_kernel run with there) */
 		bool launched = true; /* false: some launch of the time-parallel path failed (err says which) */
-		bool tail_live = false;  /* this segment's look-back launch mixes few-voice streams: mix_few_kernel looks at tail_ok_ */
+		bool tail_live = false;  /* this segment's look-back launch mixes few-voice streams: mix_few_kernel looks at the set's tail_ok */
 		bool inmix_live = false; /* this segment's closed-form launch mixes: mix_kernel looks at the control words */
 		uint32_t early_mixed_blocks = 0; /* 256-frame blocks of this segment that early launches have mixed */
 		uint32_t block_grid = 1;
+		MixOverlap mode = MIXO_OFF; /* where the segment's final mixer runs (launch_plan.h: plan_mix_overlap) */
+		uint32_t set = 0;           /* which of the two sets of records the segment's launches use: segment n, set n mod 2 */
+		uint32_t block = 0;         /* ... and which block of voice and pan rows: 0, or with rows of its own the set's */
 		TimedPair *tf = nullptr;
 		explicit Job(const SegmentDesc &s) : seg(s) { memset(&rp, 0, sizeof rp); memset(&fp, 0, sizeof fp); }
 	};
@@ -575,11 +629,16 @@ public:
 		if (j.in.f32 != pcm_f32_) { err = "a segment of another sample format than the run announced"; return false; }
 		if (j.in.f32 && seg.swap_bytes) { err = "float32 samples are not byte-swapped"; return false; }
 		j.in.row_stride = row_stride_; j.in.pcm_row = pcm_row_; j.in.chain_budget = chain_rows_budget();
+		for (uint32_t s = 0; s < seg.n_streams; ++s) { /* (what the plans read of the streams) */
+			if (seg.streams[s].write_len > j.in.max_write) j.in.max_write = seg.streams[s].write_len;
+			if (seg.streams[s].n_voices > j.in.max_rows) j.in.max_rows = seg.streams[s].n_voices;
+		}
+		j.fk = plan_fast(seg, tun_, lim_, j.in);
+		if (!begin_overlap(j, err)) return false;
 		j.bl = plan_block_loop(seg, tun_, lim_);
 		if (!j.bl.ok) { err = "voice too large for one workgroup's LDS (block buffers + operator states)"; return false; }
 		if (!ensure_rows(j, err) || !upload_descriptors(j, err)) return false;
 		/* ---- time-parallel path first; the block loop continues after it ---- */
-		j.fk = plan_fast(seg, tun_, lim_, j.in);
 		if (!prepare_fast(j, err) || !prepare_chains(j, err)) return false;
 		fill_tables(j);
 		if (!launch_analyze(j, err)) return false;
@@ -597,24 +656,72 @@ public:
 		return launch_mixer(j, err);
 	}
 
+	/* The segment's set and mode, its block of rows, and the first of its waits: nothing of set s is written before the last mixer
+	 * that read set s has finished (two segments ago, normally: no wait then). */
+	bool begin_overlap(Job &j, std::string &err) {
+		const SegmentDesc &seg = j.seg;
+		j.set = mixo_.begin_segment();
+		const size_t rows_bytes = ((size_t)seg.n_voices + seg.n_pan_rows) * row_stride_ * sizeof(float);
+		j.mode = plan_mix_overlap(tun_, j.in, j.fk, rows_bytes, second_refused_);
+		if (j.mode == MIXO_ALTERNATE && j.set == 1 && !second_rows(j)) j.mode = MIXO_SHARED;
+		j.block = MixOverlapTracker::block_of(j.mode, j.set);
+		if (j.mode != MIXO_OFF && !ensure_mix_stream(err)) return false;
+		return wait_mixer(mixo_.before_records(j.set), "records", err);
+	}
+	/* The second block of voice and pan rows, on the first segment that would use it (and when a later one needs more). When the
+	 * device does not give it -- pool_alloc has then consumed the failed call's error -- the two sets share the first block from
+	 * here on, for good on this backend. (SAU_AMD_MIX_OVERLAP_FAIL, tests: refused without asking.) */
+	bool second_rows(Job &j) {
+		const SegmentDesc &seg = j.seg;
+		MixSet &R = sets_[1];
+		const size_t nv = (size_t)seg.n_voices * row_stride_, np = (size_t)seg.n_pan_rows * row_stride_;
+		if (R.vout.p && seg.n_voices <= R.vout_rows && np <= R.pan.cap) return true;
+		std::string why = "refused by SAU_AMD_MIX_OVERLAP_FAIL";
+		bool ok = !tun_.mix_overlap_fail;
+		if (ok && (seg.n_voices > R.vout_rows || !R.vout.p)) {
+			if (R.vout.p) { /* (a block that grows is replaced: nothing may still read the old one) */
+				join_mixer_quiet("second_rows");
+				(void)hipStreamSynchronize(stream_);
+			}
+			ok = R.vout.ensure(nv, why);
+			if (ok) R.vout_rows = seg.n_voices;
+		}
+		if (ok && np) ok = R.pan.ensure(np, why);
+		if (!ok) {
+			second_refused_ = true;
+			/* (shared rows for good: what was had of the second block goes back. No mixer reads it -- one that did was joined when
+			 * it grew, and a fresh block has had none -- and the main stream's launches on it are drained first) */
+			if (R.vout.p || R.pan.p) { join_mixer_quiet("second_rows"); (void)hipStreamSynchronize(stream_); (void)hipStreamSynchronize(mix_stream_ ? mix_stream_ : stream_); }
+			R.vout.release(); R.pan.release(); R.vout_rows = 0;
+			if (debug_) fprintf(stderr, "saugns_amd: no second block of %zu bytes of voice rows (%s): the final mixer's two sets share one\n", nv * sizeof(float), why.c_str());
+		}
+		return ok;
+	}
+	/* before the first launch (or memset) of the segment that writes voice or pan rows: the last mixer that read this block */
+	bool rows_hazard(Job &j, std::string &err) { return wait_mixer(mixo_.before_rows(j.block), "rows", err); }
+	/* before the first launch of the segment that reads or writes PCM: the last mixer */
+	bool pcm_hazard(std::string &err) { return wait_mixer(mixo_.before_pcm(), "pcm", err); }
+
 	/* voice rows, pan rows, per-row and per-stream records */
 	bool ensure_rows(Job &j, std::string &err) {
 		const SegmentDesc &seg = j.seg;
-		MixSet &S = set_;
+		MixSet &S = sets_[j.set], &R = sets_[j.block];
 		if (!voices_.ensure(seg.n_voices, err) || !S.vinfo.ensure(seg.n_voices, err)) return false;
-		if (seg.n_voices > S.vout_rows || !S.vout.p) {
+		if (seg.n_voices > R.vout_rows || !R.vout.p) {
+			if (!join_mixer("ensure_rows", err)) return false; /* (the block is replaced: its last mixer with everything else) */
 			HIP_OK(hipStreamSynchronize(stream_));
-			if (!S.vout.ensure((size_t)seg.n_voices * row_stride_, err)) return false;
-			S.vout_rows = seg.n_voices;
+			if (!R.vout.ensure((size_t)seg.n_voices * row_stride_, err)) return false;
+			R.vout_rows = seg.n_voices;
 		}
-		if (seg.n_pan_rows && !S.pan.ensure((size_t)seg.n_pan_rows * row_stride_, err)) return false;
+		if (seg.n_pan_rows && !R.pan.ensure((size_t)seg.n_pan_rows * row_stride_, err)) return false;
 		/* (SAU_AMD_POISON, tests) the voice and pan rows before the segment's first launch, with a finite value (about 0.32: a
 		 * NaN may come out of the float-to-int16 clamp as 0 and hide the very frames this is meant to show). Nothing in them
 		 * outlives a segment: every kernel that reads a row (the mixers, the launches that mix tiles themselves) reads what this
 		 * segment's launches stored in it, and what a feedback chain carries over lives in chain_rows_, not here. */
 		if (tun_.poison) {
-			HIP_OK(hipMemsetD32Async((hipDeviceptr_t)S.vout.p, 0x3ea5a5a5, (size_t)seg.n_voices * row_stride_, stream_));
-			if (seg.n_pan_rows) HIP_OK(hipMemsetD32Async((hipDeviceptr_t)S.pan.p, 0x3ea5a5a5, (size_t)seg.n_pan_rows * row_stride_, stream_));
+			if (!wait_mixer(mixo_.before_rows(j.block), "poison", err)) return false;
+			HIP_OK(hipMemsetD32Async((hipDeviceptr_t)R.vout.p, 0x3ea5a5a5, (size_t)seg.n_voices * row_stride_, stream_));
+			if (seg.n_pan_rows) HIP_OK(hipMemsetD32Async((hipDeviceptr_t)R.pan.p, 0x3ea5a5a5, (size_t)seg.n_pan_rows * row_stride_, stream_));
 		}
 		return S.mstreams.ensure(seg.n_streams, err);
 	}
@@ -623,7 +730,7 @@ public:
 	 * left it. In steady state (no event between two segments) the descriptors repeat: upload only changes. */
 	bool upload_descriptors(Job &j, std::string &err) {
 		const SegmentDesc &seg = j.seg;
-		MixSet &S = set_;
+		MixSet &S = sets_[j.set];
 		ms_host_.resize(seg.n_streams);
 		for (uint32_t s = 0; s < seg.n_streams; ++s) {
 			MixStream &m = ms_host_[s];
@@ -633,8 +740,6 @@ public:
 			m.amp_scale = seg.streams[s].amp_scale;
 			m.write_len = seg.streams[s].write_len;
 			m.pcm = (int16_t *)pcm_at(s); /* (a row of floats on a float run: the mixers' float forms read it so) */
-			if (m.write_len > j.in.max_write) j.in.max_write = m.write_len;
-			if (m.n_rows > j.in.max_rows) j.in.max_rows = m.n_rows;
 		}
 		const bool same_voices = voices_sent_.size() == seg.n_voices && voices_dev_ == voices_.p &&
 			memcmp(voices_sent_.data(), seg.voices, seg.n_voices * sizeof(VoiceDesc)) == 0;
@@ -658,22 +763,22 @@ public:
 		const SegmentDesc &seg = j.seg;
 		const FastPlan &k = j.fk;
 		FastParams &fp = j.fp;
-		MixSet &S = set_;
+		MixSet &S = sets_[j.set], &R = sets_[j.block];
 		const size_t n_lists = (size_t)FAST_LISTS * seg.n_voices * k.fmax_steps;
 		if (!finfo_.ensure(seg.n_voices, err) || !fdone_.ensure(seg.n_voices, err) ||
-		    !worklist_.ensure(seg.n_voices, err) || !work_count_.ensure(4, err) ||
+		    !worklist_.ensure(seg.n_voices, err) || !S.work_count.ensure(4, err) ||
 		    !fsteps_.ensure(n_lists * sizeof(FastStep), err) || !flines_.ensure(n_lists * sizeof(FastLine), err) ||
 		    !faux_.ensure(n_lists * sizeof(FastAux), err)) return false;
 		fp.voices = voices_.p; fp.steps = steps_.p; fp.fast_ids = fast_ids_.p; fp.op_ids = op_ids_.p; fp.ops = ops_.p;
-		fp.vout = S.vout.p; fp.pan = S.pan.p; fp.info = finfo_.p; fp.fast_done = fdone_.p;
-		fp.worklist = worklist_.p; fp.work_count = work_count_.p; fp.vinfo = S.vinfo.p;
+		fp.vout = R.vout.p; fp.pan = R.pan.p; fp.info = finfo_.p; fp.fast_done = fdone_.p;
+		fp.worklist = worklist_.p; fp.work_count = S.work_count.p; fp.vinfo = S.vinfo.p;
 		fp.g_c23 = tables_->c23; fp.g_c01 = tables_->c01; fp.fsteps = (FastStep *)fsteps_.p; fp.flines = (FastLine *)flines_.p; fp.faux = (FastAux *)faux_.p;
 		fp.row_stride = row_stride_; fp.n_voices = seg.n_voices; fp.n_fast = k.n_fast;
 		fp.seq_enable = k.seq_ok ? 1u : 0u; fp.ids_full_ofs = n_steps_total_;
 		fp.scan = nullptr; fp.scan_groups = k.scan_groups; fp.mode = 0;
 		if (tun_.xcd_queues && lim_.eight_xcds) { /* the closed-form launch's task queues, one per XCD (k_fast_types.h) */
-			if (!inmix_ctl_.ensure(INMIX_WORDS, err)) return false;
-			fp.inmix = inmix_ctl_.p;
+			if (!S.inmix_ctl.ensure(INMIX_WORDS, err)) return false;
+			fp.inmix = S.inmix_ctl.p;
 		}
 		if (k.scan) {
 			if (!scan_.ensure((size_t)seg.n_voices * FAST_MAX_SCAN * k.scan_groups, err)) return false;
@@ -795,6 +900,7 @@ public:
 	 * the lean build has 4, 5 or 6) */
 	bool launch_build(Job &j, std::string &err, int build, uint32_t rows, uint32_t grid, const FastParams *prm = nullptr, bool cf = false,
 			bool wide = false) {
+		if (!rows_hazard(j, err)) return false; /* (every build stores rows) */
 		if (build == 1 && rows > 4) rows = 4;
 		if (build == 3) rows = rows < 5 ? 4 : rows > 6 ? 6 : rows;
 		/* (the look-back build that mixes few-voice streams: round 6, FastParams.tail_ok) */
@@ -832,14 +938,17 @@ public:
 		const SegmentDesc &seg = j.seg;
 		const FastPlan &k = j.fk;
 		FastParams &fp = j.fp, &cfp = j.cfp;
+		MixSet &S = sets_[j.set];
 		if (k.tailmix) {
-			if (!tail_ok_.ensure(seg.n_streams, err)) return false;
-			fp.tail_ok = tail_ok_.p; fp.inmix_stream = set_.mstreams.p;
+			if (!S.tail_ok.ensure(seg.n_streams, err)) return false;
+			fp.tail_ok = S.tail_ok.p; fp.inmix_stream = S.mstreams.p;
 			fp.tail_flags = (seg.stereo ? 1u : 0u) | (seg.swap_bytes ? 2u : 0u);
 			fp.tail_pcm_offset = seg.pcm_offset;
 			hipLaunchKernelGGL(tailmix_kernel, dim3((seg.n_streams + 63) / 64), dim3(64), 0, stream_, fp, seg.n_streams);
 			j.tail_live = true;
 		}
+		if (!rows_hazard(j, err)) return false;
+		if (j.tail_live && !pcm_hazard(err)) return false; /* (the look-back launch stores those streams' PCM) */
 		cfp = fp;
 		cfp.n_fast = k.n_fast_cf; cfp.rows = k.rows_cf; cfp.mode = 0; cfp.only_multi = 0;
 		if (getenv("SAU_AMD_DEBUG_DUO"))
@@ -884,6 +993,7 @@ public:
 	bool launch_sums_and_chains(Job &j, std::string &err) {
 		const SegmentDesc &seg = j.seg;
 		FastParams &fp = j.fp;
+		if (!rows_hazard(j, err)) return false;
 		if (fp.chain_rows && fp.chain_early_ok && !launch_early_chains(j, err)) return false;
 		for (uint32_t pass = 1; pass <= fp.sum_levels && (!fp.look || seg.n_chain_rows); ++pass) {
 			launch_fast(j, err, pass);
@@ -979,7 +1089,8 @@ public:
 			if (k.early_mix && c + 1 < n_chunks && cb[c + 1] > 512) {
 				const uint32_t hi = (cb[c + 1] - 512) / 256;
 				if (hi > mixed_blocks) {
-					MixParams mp = mix_params(j.seg, set_);
+					if (!pcm_hazard(err)) return false; /* (an early launch writes PCM on the main stream) */
+					MixParams mp = mix_params(j);
 					mp.blk_lo = mixed_blocks; mp.blk_hi = hi;
 					TimedPair *tm = timing_on_ ? new_pair(1) : nullptr;
 					if (tm) (void)hipEventRecord(tm->a, stream_);
@@ -1005,7 +1116,7 @@ public:
 			fp.inmix_flags = k.inmix_flags;
 			fp.inmix_div_s = k.div.s; fp.inmix_div_m = k.div.m;
 			if (k.inmix) {
-				fp.inmix_stream = set_.mstreams.p;
+				fp.inmix_stream = sets_[j.set].mstreams.p;
 				fp.inmix_pcm_offset = seg.pcm_offset;
 				hipLaunchKernelGGL(premix_kernel, dim3((seg.n_voices + 63) / 64), dim3(64), 0, stream_, fp);
 				j.inmix_live = true;
@@ -1017,15 +1128,19 @@ public:
 			const size_t lds = k.inner_lds();
 			FastParams ep = fp;
 			ep.mode = 0; ep.edge_only = 1; ep.dyn_static = 1; ep.dyn_chunks = 2; ep.dyn_small = 0; ep.inmix_flags = 0; /* (two tasks a voice: its first group, its last) */
+			/* (the edge launch stores rows and no PCM: with rows of its own it runs beside the last segment's mixer, as
+			 * analyze_kernel, decode_kernel and premix_kernel before it do either way -- launch_build has the rows' wait) */
 			if (!launch_build(j, err, 0, k.rows, k.grid_edge, &ep, false, true)) j.launched = false;
 			fp.mode = 0;
 			void *iargs[] = {(void *)&fp};
 			if (!raise_lds_attr(ik, lds, dev_, err)) return false;
+			if (fp.inmix_flags && !pcm_hazard(err)) return false; /* (the inner launch mixes tiles into the PCM itself) */
 			HIP_OK(hipLaunchKernel(ik, dim3(k.grid), dim3(1024), iargs, lds, stream_));
 			if (inner_report_) fprintf(stderr, "[sau-amd] inner: %s, %u voices\n", lm ? "lane-major" : "row-major", seg.n_voices);
 		} else {
 			/* (a closed-form segment that did not take the two launches, and what kept it from them) */
 			if (inner_report_) fprintf(stderr, "[sau-amd] inner: none (rows %u, wide %d, chunks %u), %u voices\n", k.rows, k.wide_cf ? 1 : 0, fp.dyn_chunks, seg.n_voices);
+			if (fp.inmix_flags && (!rows_hazard(j, err) || !pcm_hazard(err))) return false;
 			launch_fast(j, err, 0);
 		}
 		fp.dyn_chunks = 0; fp.inmix_flags = 0; fp.dyn_small = 0;
@@ -1045,6 +1160,7 @@ public:
 		const void *ck = fast_kernel_fn(0, FAST_CUB_ROWS, FK_CUB);
 		if (!raise_lds_attr(ck, qlds, dev_, err)) return false;
 		void *qargs[] = {(void *)&q};
+		if (!rows_hazard(j, err)) return false;
 		HIP_OK(hipLaunchKernel(ck, dim3(k.grid_cub), dim3(1024), qargs, qlds, stream_));
 		return true;
 	}
@@ -1064,6 +1180,7 @@ public:
 		if (!raise_lds_attr(rk, rlds, dev_, err)) return false;
 		j.fp.mode = 0;
 		void *rargs[] = {(void *)&rpar};
+		if (!rows_hazard(j, err)) return false;
 		HIP_OK(hipLaunchKernel(rk, dim3(k.grid_repair), dim3(1024), rargs, rlds, stream_));
 		return true;
 	}
@@ -1102,13 +1219,13 @@ public:
 		memcpy(rp.tab_of_wave, b.tabs.tab_of_wave, sizeof rp.tab_of_wave);
 		memcpy(rp.wave_of_tab, b.tabs.wave_of_tab, sizeof rp.wave_of_tab);
 		rp.voices = voices_.p; rp.steps = steps_.p; rp.op_ids = op_ids_.p; rp.ops = ops_.p;
-		rp.vout = set_.vout.p; rp.pan = set_.pan.p; rp.vinfo = set_.vinfo.p;
+		rp.vout = sets_[j.block].vout.p; rp.pan = sets_[j.block].pan.p; rp.vinfo = sets_[j.set].vinfo.p;
 		rp.g_c23 = tables_->c23; rp.g_c01 = tables_->c01;
 		rp.row_stride = row_stride_; rp.seg_len = seg.len;
 		rp.n_slots = seg.n_slots; rp.max_ops = seg.max_ops; rp.n_tabs = b.tabs.n;
 		rp.max_steps = seg.max_steps; rp.n_main = seg.n_main;
 		memcpy(rp.wc, wconst_, sizeof wconst_);
-		rp.fast_done = fdone_.p; rp.worklist = worklist_.p; rp.work_count = work_count_.p;
+		rp.fast_done = fdone_.p; rp.worklist = worklist_.p; rp.work_count = sets_[j.set].work_count.p;
 		j.block_grid = b.grid(seg, j.fk.use_fast);
 		if (b.HB) {
 			const size_t stride = ((size_t)seg.n_slots * 64 * sizeof(float) + (size_t)seg.max_ops * sizeof(DevOp) +
@@ -1118,6 +1235,7 @@ public:
 			rp.big_slots = big_slots_.p; rp.big_stride = (uint32_t)stride;
 		}
 		if (!wait_for_predecessor(err)) return false; /* (a segment without the time-parallel path) */
+		if (!rows_hazard(j, err)) return false;
 		TimedPair *tp = timing_on_ ? new_pair(0) : nullptr;
 		if (tp) (void)hipEventRecord(tp->a, stream_);
 		const void *fn = render_kernel_fn(b.W, b.T, b.V, b.HB);
@@ -1127,36 +1245,70 @@ public:
 		HIP_OK(hipLaunchKernel(fn, dim3(j.block_grid), dim3(64 * b.W * b.V), args, b.lds, stream_));
 		HIP_OK(hipGetLastError());
 		if (tp) (void)hipEventRecord(tp->b, stream_);
-		if (debug_) debug_dump("after render", seg, j.block_grid);
+		if (debug_) debug_dump("after render", j);
 		return true;
 	}
 
-	/* (on the generator's one stream, behind the segment's kernels. Round 3 built the mixer on a stream of its own beside the
-	 * next segment's kernels -- ordinary grid or persistent on a few CUs, everything it reads and writes double-buffered --
-	 * and measured it no faster in any form, profiles/r03_headline_ab.json; that code is gone since round 4.) */
+	/* The segment's last mixer launch: on the side stream, behind a fork recorded on the main stream after the block loop, so that
+	 * the next segment's analyze_kernel, decode_kernel, premix_kernel (and, with rows of its own, the edge launch) run beside it --
+	 * they are small grids waiting on latency, the mixer is HBM-bound, and they need finalize_kernel's state of this segment, nothing
+	 * of the mixer's. What it reads is kept apart by the two sets of records (and blocks of rows), what it writes by the waits of
+	 * mix_overlap.h. (Round 3 had a mixer beside the whole next segment, persistent or not, and measured no gain: nothing runs
+	 * beside the rendering launches, which fill every CU's registers. This one asks for the set-up launches' time alone; the
+	 * figures are in profiles/r09_mix_overlap_ab.json.) MIXO_OFF: on the main stream, behind the segment's kernels. */
 	bool launch_mixer(Job &j, std::string &err) {
 		const SegmentDesc &seg = j.seg;
 		const uint32_t max_write = j.in.max_write;
 		const Mixer which = plan_mixer(seg, tun_, j.in, pcm_pitch(), j.inmix_live, j.early_mixed_blocks);
-		if (which == MIX_NONE) return true;
-		MixParams mp = mix_params(seg, set_);
+		if (which == MIX_NONE) { report_overlap(j, 0, false); return true; }
+		MixSet &S = sets_[j.set];
+		MixParams mp = mix_params(j);
 		/* (frames an early launch has mixed are skipped when the device says those results stand: k_finish.h) */
 		mp.early_blocks = j.early_mixed_blocks;
-		mp.inmix = j.inmix_live ? inmix_ctl_.p : nullptr; /* (the closed-form launch has mixed tiles itself: mix_kernel takes what is left) */
-		mp.tail_ok = j.tail_live ? tail_ok_.p : nullptr; /* (the look-back launch has mixed some streams itself: mix_few_kernel leaves them) */
+		mp.inmix = j.inmix_live ? S.inmix_ctl.p : nullptr; /* (the closed-form launch has mixed tiles itself: mix_kernel takes what is left) */
+		mp.tail_ok = j.tail_live ? S.tail_ok.p : nullptr; /* (the look-back launch has mixed some streams itself: mix_few_kernel leaves them) */
+		/* (the pair first: new_pair may drain its pool, which joins the pending mixer -- nothing of this mixer exists yet) */
 		TimedPair *tm = timing_on_ ? new_pair(1) : nullptr;
-		if (tm) (void)hipEventRecord(tm->a, stream_);
+		hipStream_t ms = stream_;
+		/* The tracker learns of the mixer only once its done event is recorded (mixer_launched below): until then no join can
+		 * take the ticket for waited-for, and a launch that fails on the way leaves no ticket without an event behind. */
+		const uint64_t ticket = j.mode == MIXO_OFF ? 0 : mixo_.next_ticket();
+		if (!ticket) {
+			if (!wait_mixer(mixo_.before_pcm(), "mixer", err)) return false; /* (an earlier segment's may still be on the side stream) */
+		} else {
+			hipEvent_t fork = mix_fork_[MixOverlapTracker::slot(ticket)];
+			HIP_OK(hipEventRecord(fork, stream_));
+			HIP_OK(hipStreamWaitEvent(mix_stream_, fork, 0));
+			ms = mix_stream_;
+		}
+		if (tm) (void)hipEventRecord(tm->a, ms);
 		switch (which) {
-		case MIX_FEW_F32: hipLaunchKernelGGL(mix_few_kernel_f32, dim3((max_write + 1023) / 1024, seg.n_streams), dim3(256), 0, stream_, mp); break;
-		case MIX_F32: hipLaunchKernelGGL(mix_kernel_f32, dim3((max_write + 255) / 256, seg.n_streams), dim3(256), 0, stream_, mp); break;
-		case MIX_FEW: hipLaunchKernelGGL(mix_few_kernel, dim3((max_write + 1023) / 1024, seg.n_streams), dim3(256), 0, stream_, mp); break;
-		case MIX_64: hipLaunchKernelGGL(mix_kernel64, dim3((max_write + 63) / 64, seg.n_streams), dim3(64), 0, stream_, mp); break;
-		default: hipLaunchKernelGGL(mix_kernel, dim3((max_write + 255) / 256, seg.n_streams), dim3(256), 0, stream_, mp); break;
+		case MIX_FEW_F32: hipLaunchKernelGGL(mix_few_kernel_f32, dim3((max_write + 1023) / 1024, seg.n_streams), dim3(256), 0, ms, mp); break;
+		case MIX_F32: hipLaunchKernelGGL(mix_kernel_f32, dim3((max_write + 255) / 256, seg.n_streams), dim3(256), 0, ms, mp); break;
+		case MIX_FEW: hipLaunchKernelGGL(mix_few_kernel, dim3((max_write + 1023) / 1024, seg.n_streams), dim3(256), 0, ms, mp); break;
+		case MIX_64: hipLaunchKernelGGL(mix_kernel64, dim3((max_write + 63) / 64, seg.n_streams), dim3(64), 0, ms, mp); break;
+		default: hipLaunchKernelGGL(mix_kernel, dim3((max_write + 255) / 256, seg.n_streams), dim3(256), 0, ms, mp); break;
 		}
 		HIP_OK(hipGetLastError());
-		if (tm) (void)hipEventRecord(tm->b, stream_);
+		if (tm) (void)hipEventRecord(tm->b, ms);
+		if (ticket) {
+			HIP_OK(hipEventRecord(mix_done_[MixOverlapTracker::slot(ticket)], mix_stream_));
+			if (mixo_.mixer_launched(j.set, j.block) != ticket) { err = "internal error: the final mixer's ticket changed under its launch"; return false; }
+		}
+		report_overlap(j, ticket, true);
 		if (mp.inmix && inmix_report_) report_inmix(mp, seg.n_voices, max_write);
 		return true;
+	}
+
+	/* (SAU_AMD_OVERLAP_REPORT, tests: a line per segment -- its mode and set, its mixer's ticket (0: on the main stream, or none),
+	 * and every wait for a mixer issued since the last line, each as where:ticket:done|busy -- had that mixer finished when the
+	 * wait was issued) */
+	void report_overlap(const Job &j, uint64_t ticket, bool mixer) {
+		if (!overlap_report_) return;
+		fprintf(stderr, "[sau-amd] overlap: mode %s set %u block %u mixer %s ticket %llu waits%s\n",
+				j.mode == MIXO_ALTERNATE ? "alternate" : j.mode == MIXO_SHARED ? "shared" : "off", j.set, j.block,
+				!mixer ? "none" : ticket ? "side" : "main", (unsigned long long)ticket, report_waits_.empty() ? " -" : report_waits_.c_str());
+		report_waits_.clear();
 	}
 
 	/* (SAU_AMD_INMIX_REPORT, tests: what the launch mixed itself) */
@@ -1165,7 +1317,7 @@ public:
 		uint32_t g[2] = {0, 0};
 		(void)hipStreamSynchronize(stream_);
 		(void)hipMemcpy(h.data(), mp.inmix, INMIX_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost);
-		(void)hipMemcpy(g, work_count_.p, sizeof g, hipMemcpyDeviceToHost);
+		(void)hipMemcpy(g, mp.guard, sizeof g, hipMemcpyDeviceToHost);
 		const uint32_t nch = h[INMIX_NCH] < INMIX_MAX_CHUNKS ? h[INMIX_NCH] : INMIX_MAX_CHUNKS, tpc = h[INMIX_TPC];
 		uint32_t tiles = 0, whole = 0, all = 0;
 		for (uint32_t k = 0; k < nch; ++k) {
@@ -1183,13 +1335,16 @@ public:
 				n_voices, max_write, nch, h[INMIX_CF], tiles, all, whole, g[0], g[1]);
 	}
 
-	template <typename SetT> MixParams mix_params(const SegmentDesc &seg, const SetT &S) {
+	/* everything a mixer of this segment dereferences but the PCM: the segment's set of records and its block of rows */
+	MixParams mix_params(const Job &j) {
+		const SegmentDesc &seg = j.seg;
+		const MixSet &S = sets_[j.set], &R = sets_[j.block];
 		MixParams mp;
-		mp.streams = S.mstreams.p; mp.vout = S.vout.p; mp.pan = S.pan.p; mp.vinfo = S.vinfo.p;
+		mp.streams = S.mstreams.p; mp.vout = R.vout.p; mp.pan = R.pan.p; mp.vinfo = S.vinfo.p;
 		mp.row_stride = row_stride_; mp.pcm_offset = seg.pcm_offset;
 		mp.stereo = seg.stereo ? 1 : 0;
 		mp.swap_bytes = seg.swap_bytes ? 1 : 0;
-		mp.blk_lo = 0; mp.blk_hi = 0; mp.early_blocks = 0; mp.guard = work_count_.p; mp.inmix = nullptr; mp.tail_ok = nullptr;
+		mp.blk_lo = 0; mp.blk_hi = 0; mp.early_blocks = 0; mp.guard = S.work_count.p; mp.inmix = nullptr; mp.tail_ok = nullptr;
 		return mp;
 	}
 
@@ -1204,6 +1359,7 @@ public:
 	/* n int16 units (a float sample is two) from the start of the stream's row */
 	bool fetch_units(uint32_t stream, int16_t *dst, const size_t n, std::string &err) {
 		use_device();
+		if (!join_mixer("fetch_pcm", err)) return false;
 		/* the caller's memory is pageable: a device copy straight into it costs milliseconds of
 		 * pinning per call, so the PCM goes through a page-locked block (unless dst is one) */
 		const bool pinned = host_blocks_.count(dst) != 0;
@@ -1230,6 +1386,7 @@ public:
 	bool fetch_bytes_async(uint32_t stream, void *dst, size_t bytes, int slot, std::string &err) {
 		slot &= 3;
 		use_device();
+		if (!join_mixer("fetch_pcm_async", err)) return false;
 		if (!fetch_ev_[slot]) HIP_OK(hipEventCreateWithFlags(&fetch_ev_[slot], hipEventDisableTiming));
 		hipStream_t cs = stream_;
 		HIP_OK(hipMemcpyAsync(dst, pcm_at(stream), bytes, hipMemcpyDeviceToHost, cs));
@@ -1260,6 +1417,7 @@ public:
 	/* ---- level metering (k_levels.h; the geometry is launch_plan.h's plan_levels) ---- */
 	bool begin_metering(std::string &err) override {
 		use_device();
+		if (!join_mixer("begin_metering", err)) return false;
 		if (lev_acc_.p) return true;
 		if (!lev_acc_.ensure(cfg_.n_streams, err)) return false;
 		HIP_OK(hipMemsetAsync(lev_acc_.p, 0, (size_t)cfg_.n_streams * sizeof(LevelsAcc), stream_));
@@ -1282,6 +1440,7 @@ public:
 	}
 	bool measure_streams(const uint32_t *frames, bool stereo, sauengine::SampleFormat format, std::string &err) override {
 		use_device();
+		if (!join_mixer("measure_streams", err)) return false;
 		const bool f32 = format == sauengine::SF_F32;
 		if (!lev_acc_.p) { err = "level metering has not begun"; return false; }
 		if (f32 != pcm_f32_ || !pcm_.p) { err = "no rows of that sample format to measure"; return false; }
@@ -1321,6 +1480,7 @@ public:
 	}
 	bool read_levels(sauengine::Levels *out, bool reset, std::string &err) override {
 		use_device();
+		if (!join_mixer("read_levels", err)) return false;
 		if (!lev_acc_.p) { memset((void *)out, 0, sizeof(sauengine::Levels) * cfg_.n_streams); return true; }
 		if (!read_records(lev_acc_.p, cfg_.n_streams, out, err)) return false;
 		if (reset) HIP_OK(hipMemsetAsync(lev_acc_.p, 0, (size_t)cfg_.n_streams * sizeof(LevelsAcc), stream_));
@@ -1329,6 +1489,7 @@ public:
 	bool measure_rows(const void *rows, size_t pitch, size_t n_rows, sauengine::SampleFormat format, size_t frames, bool stereo,
 			sauengine::Levels *out, std::string &err) override {
 		use_device();
+		if (!join_mixer("measure_rows", err)) return false;
 		const bool f32 = format == sauengine::SF_F32;
 		const size_t ch = stereo ? 2 : 1, size = f32 ? sizeof(float) : sizeof(int16_t);
 		if (!n_rows) return true;
@@ -1360,6 +1521,7 @@ public:
 	bool requantize(uint32_t stream, uint32_t frames, bool stereo, float gain, sauengine::SampleFormat out, bool swap_bytes,
 			std::string &err) override {
 		use_device();
+		if (!join_mixer("requantize", err)) return false;
 		if (!pcm_f32_ || !pcm_.p) { err = "the last run's samples are not float32"; return false; }
 		if (stream >= cfg_.n_streams || frames > row_stride_) { err = "frames beyond the stream's row"; return false; }
 		const bool f32 = out == sauengine::SF_F32;
@@ -1379,6 +1541,7 @@ public:
 	bool fetch_requant_async(void *dst, size_t bytes, int slot, std::string &err) override {
 		slot &= 3;
 		use_device();
+		if (!join_mixer("fetch_requant_async", err)) return false;
 		if (bytes > requant_.bytes) { err = "more bytes than were requantised"; return false; }
 		if (!fetch_ev_[slot]) HIP_OK(hipEventCreateWithFlags(&fetch_ev_[slot], hipEventDisableTiming));
 		HIP_OK(hipMemcpyAsync(dst, requant_.p, bytes, hipMemcpyDeviceToHost, stream_));
@@ -1389,6 +1552,7 @@ public:
 	/* ---- the decimator (k_decimate.h; the geometry is launch_plan.h's plan_decimate) ---- */
 	bool begin_decimation(int factor, bool stereo, std::string &err) override {
 		use_device();
+		if (!join_mixer("begin_decimation", err)) return false;
 		const DecimPlan plan = plan_decimate(0, factor, stereo ? 2 : 1, cfg_.n_streams, sizeof(float));
 		if (!plan.ok) { err = "bad argument"; return false; }
 		const size_t hist = (size_t)cfg_.n_streams * plan.hist_floats;
@@ -1408,6 +1572,7 @@ public:
 	bool decimate(const uint32_t *frames_hi, uint32_t buf_len, int factor, bool stereo, sauengine::SampleFormat out_fmt, bool swap_bytes,
 			std::string &err) override {
 		use_device();
+		if (!join_mixer("decimate", err)) return false;
 		if (!decim_hist_.p || factor != decim_factor_ || stereo != decim_stereo_) { err = "decimation has not begun"; return false; }
 		const bool f32 = out_fmt == sauengine::SF_F32;
 		if (f32 && swap_bytes) { err = "float32 samples are not byte-swapped"; return false; }
@@ -1449,6 +1614,7 @@ public:
 	bool fetch_decimated_async(uint32_t stream, void *dst, size_t bytes, int slot, std::string &err) override {
 		slot &= 3;
 		use_device();
+		if (!join_mixer("fetch_decimated_async", err)) return false;
 		if (stream >= cfg_.n_streams || bytes > decim_out_bytes_ || (bytes && !decim_out_.p)) { err = "more bytes than were decimated"; return false; }
 		if (!fetch_ev_[slot]) HIP_OK(hipEventCreateWithFlags(&fetch_ev_[slot], hipEventDisableTiming));
 		if (bytes) {
@@ -1465,9 +1631,10 @@ public:
 		return true;
 	}
 	const float *device_decimated_f32(uint32_t stream) override {
+		join_mixer_quiet("device_decimated");
 		return decim_out_.p && decim_out_f32_ && decim_out_bytes_ && stream < cfg_.n_streams ? (const float *)((const char *)decim_out_.p + decim_out_pitch_ * stream) : nullptr;
 	}
-	size_t device_decimated_pitch() override { return decim_out_.p && decim_out_bytes_ ? decim_out_pitch_ : 0; }
+	size_t device_decimated_pitch() override { join_mixer_quiet("device_decimated"); return decim_out_.p && decim_out_bytes_ ? decim_out_pitch_ : 0; }
 
 	/* ---- loudness and true peak (k_loudness.h; the geometry is launch_plan.h's plan_loudness) ---- */
 	/* the records of a set of rows: the batch's streams, or the foreign rows of one measure_loudness_rows call */
@@ -1609,11 +1776,13 @@ public:
 	}
 	bool begin_loudness(std::string &err) override {
 		use_device();
+		if (!join_mixer("begin_loudness", err)) return false;
 		if (loud_own_.state.p) return true;
 		return loud_setup(cfg_.srate, err) && loud_make(loud_own_, cfg_.n_streams, err);
 	}
 	bool measure_loudness(const uint32_t *frames, bool stereo, std::string &err) override {
 		use_device();
+		if (!join_mixer("measure_loudness", err)) return false;
 		if (!loud_own_.state.p) { err = "loudness metering has not begun"; return false; }
 		if (!pcm_f32_ || !pcm_.p) { err = "the last run's samples are not float32"; return false; }
 		for (uint32_t s = 0; s < cfg_.n_streams; ++s)
@@ -1623,12 +1792,14 @@ public:
 	}
 	bool read_loudness(sauengine::Loudness *out, bool reset, std::string &err) override {
 		use_device();
+		if (!join_mixer("read_loudness", err)) return false;
 		if (!loud_own_.state.p) { err = "loudness metering has not begun"; return false; }
 		if (!loud_setup(cfg_.srate, err) || !loud_read(loud_own_, out, nullptr, nullptr, err)) return false;
 		return !reset || loud_clear(loud_own_, err);
 	}
 	bool read_loudness_hops(uint32_t stream, double *out, size_t cap, size_t *n_hops, std::string &err) override {
 		use_device();
+		if (!join_mixer("read_loudness_hops", err)) return false;
 		if (!loud_own_.state.p || stream >= cfg_.n_streams) { err = "loudness metering has not begun"; return false; }
 		const uint32_t hop = cfg_.srate / 10;
 		const size_t nh = (size_t)(loud_own_.pos_h[stream] / hop), per = (size_t)loud_own_.rows * 2;
@@ -1643,6 +1814,7 @@ public:
 	bool measure_loudness_rows(const void *rows, size_t pitch, size_t n_rows, size_t frames, bool stereo, uint32_t srate,
 			sauengine::Loudness *out, double *hops_out, size_t hops_cap, std::string &err) override {
 		use_device();
+		if (!join_mixer("measure_loudness_rows", err)) return false;
 		const size_t ch = stereo ? 2 : 1, size = sizeof(float);
 		if (!n_rows) return true;
 		if (!rows || ((uintptr_t)rows & 15u) || (pitch & 15u) || !out) { err = "bad argument: rows and pitch_bytes must be multiples of 16"; return false; }
@@ -1717,6 +1889,7 @@ public:
 	}
 	bool begin_limiting(bool stereo, std::string &err) override {
 		use_device();
+		if (!join_mixer("begin_limiting", err)) return false;
 		const LimitPlan plan = plan_limit(0, cfg_.srate, stereo ? 2 : 1, cfg_.n_streams, sizeof(float));
 		if (!plan.ok) { err = "bad argument"; return false; }
 		const size_t hist = (size_t)cfg_.n_streams * plan.hist_frames * 2;
@@ -1732,6 +1905,7 @@ public:
 	bool limit(const uint32_t *frames, uint32_t buf_len, float pre_gain, float ceiling, bool stereo, sauengine::SampleFormat out_fmt,
 			bool swap_bytes, std::string &err) override {
 		use_device();
+		if (!join_mixer("limit", err)) return false;
 		if (!lim_on_ || stereo != lim_stereo_) { err = "limiting has not begun"; return false; }
 		if (!sauengine::limiter_param_ok(pre_gain) || !sauengine::limiter_param_ok(ceiling)) { err = "bad argument"; return false; }
 		const bool f32 = out_fmt == sauengine::SF_F32;
@@ -1770,6 +1944,7 @@ public:
 	bool fetch_limited_async(uint32_t stream, void *dst, size_t bytes, int slot, std::string &err) override {
 		slot &= 3;
 		use_device();
+		if (!join_mixer("fetch_limited_async", err)) return false;
 		if (stream >= cfg_.n_streams || bytes > lim_out_bytes_ || (bytes && !lim_out_.p)) { err = "more bytes than were limited"; return false; }
 		if (!fetch_ev_[slot]) HIP_OK(hipEventCreateWithFlags(&fetch_ev_[slot], hipEventDisableTiming));
 		if (bytes) {
@@ -1786,11 +1961,13 @@ public:
 		return true;
 	}
 	const float *device_limited_f32(uint32_t stream) override {
+		join_mixer_quiet("device_limited");
 		return lim_out_.p && lim_out_f32_ && lim_out_bytes_ && stream < cfg_.n_streams ? (const float *)((const char *)lim_out_.p + lim_out_pitch_ * stream) : nullptr;
 	}
-	size_t device_limited_pitch() override { return lim_out_.p && lim_out_bytes_ ? lim_out_pitch_ : 0; }
+	size_t device_limited_pitch() override { join_mixer_quiet("device_limited"); return lim_out_.p && lim_out_bytes_ ? lim_out_pitch_ : 0; }
 	bool read_limiter_stats(sauengine::LimiterStats *out, bool reset, std::string &err) override {
 		use_device();
+		if (!join_mixer("read_limiter_stats", err)) return false;
 		if (!lim_stats_.p) { err = "limiting has not begun"; return false; }
 		HIP_OK(hipMemcpyAsync(out, lim_stats_.p, (size_t)cfg_.n_streams * sizeof(LimStats), hipMemcpyDeviceToHost, stream_));
 		HIP_OK(hipStreamSynchronize(stream_));
@@ -1814,6 +1991,7 @@ public:
 	bool limit_rows(const void *rows, size_t pitch, size_t n_rows, size_t frames, bool stereo, uint32_t srate, float pre_gain, float ceiling,
 			void *out_rows, size_t out_pitch, sauengine::LimiterStats *stats_out, std::string &err) override {
 		use_device();
+		if (!join_mixer("limit_rows", err)) return false;
 		const size_t ch = stereo ? 2 : 1, row_bytes = frames * ch * sizeof(float);
 		if (!sauengine::limiter_param_ok(pre_gain) || !sauengine::limiter_param_ok(ceiling) || !srate) { err = "bad argument"; return false; }
 		if (!rows || !out_rows || ((uintptr_t)rows & 15u) || (pitch & 15u) || ((uintptr_t)out_rows & 15u) || (out_pitch & 15u)) {
@@ -1862,7 +2040,7 @@ public:
 			: be_(be), n_(n_rows), ch_(channels), L_(log2n), N_(1u << log2n), bins_((1u << log2n) / 2 + 1), hop_(hop), pos_(n_rows, 0) {}
 		~Spectrum() override { /* the buffers go back to the pool (member destructors): nothing may still be using them */
 			be_->use_device();
-			if (be_->stream_) (void)hipStreamSynchronize(be_->stream_);
+			if (be_->stream_) { be_->join_mixer_quiet("spectrum"); (void)hipStreamSynchronize(be_->stream_); }
 		}
 		size_t n_rows() const override { return n_; }
 		uint32_t channels() const override { return ch_; }
@@ -1880,6 +2058,7 @@ public:
 			return clear(err);
 		}
 		bool clear(std::string &err) {
+			if (!be_->join_mixer("spectrum_clear", err)) return false;
 			HIP_OK(hipMemsetAsync(total_.p, 0, n_ * bins_ * ch_ * sizeof(double), be_->stream_)); /* (+0.0; behind the last feed's kernels) */
 			std::fill(pos_.begin(), pos_.end(), 0);
 			return true;
@@ -1887,6 +2066,7 @@ public:
 		/* sgram: feed()'s segment kernel also writes every segment's (float)p[k] there (spectrum_rows: rows from empty records) */
 		bool feed_into(const void *rows, size_t pitch, const uint32_t *frames, float *sgram, size_t sgram_segs, std::string &err) {
 			be_->use_device();
+			if (!be_->join_mixer("spectrum_feed", err)) return false; /* (the rows fed may be the batch's PCM) */
 			if (!rows || !frames || ((uintptr_t)rows & 15u) || (pitch & 15u)) { err = "bad argument: rows and pitch_bytes must be multiples of 16"; return false; }
 			uint32_t longest = 0;
 			for (size_t r = 0; r < n_; ++r) longest = frames[r] > longest ? frames[r] : longest;
@@ -1934,6 +2114,7 @@ public:
 		}
 		bool read(double *power_out, uint64_t *segments_out, bool reset, std::string &err) override {
 			be_->use_device();
+			if (!be_->join_mixer("spectrum_read", err)) return false;
 			const size_t sums = n_ * bins_ * ch_;
 			std::vector<double> acc(sums);
 			HIP_OK(hipMemcpyAsync(power_out, total_.p, sums * sizeof(double), hipMemcpyDeviceToHost, be_->stream_));
@@ -1959,6 +2140,7 @@ public:
 	};
 	sauengine::SpectrumMeter *create_spectrum(size_t n_rows, uint32_t channels, unsigned log2n, uint32_t hop, std::string &err) override {
 		use_device();
+		if (!join_mixer("create_spectrum", err)) return nullptr;
 		if (!sauengine::spectrum_params_ok((int)channels, log2n, hop) || !n_rows) { err = "bad argument"; return nullptr; }
 		if (n_rows > SPEC_MAX_ROWS) { err = "bad argument: more than 65535 rows"; return nullptr; }
 		Spectrum *m = new Spectrum(this, n_rows, channels, log2n, hop);
@@ -1968,6 +2150,7 @@ public:
 	bool spectrum_rows(const void *rows, size_t pitch, size_t n_rows, size_t frames, uint32_t channels, unsigned log2n, uint32_t hop,
 			double *power_out, uint64_t *segments_out, float *spectrogram_out, size_t spectrogram_cap, std::string &err) override {
 		use_device();
+		if (!join_mixer("spectrum_rows", err)) return false;
 		if (!sauengine::spectrum_params_ok((int)channels, log2n, hop) || !n_rows || !power_out || !segments_out) { err = "bad argument"; return false; }
 		if (!rows || ((uintptr_t)rows & 15u) || (pitch & 15u)) { err = "bad argument: rows and pitch_bytes must be multiples of 16"; return false; }
 		if (n_rows > SPEC_MAX_ROWS || frames > 0xffffffffull) { err = "bad argument: more than 65535 rows, or than 32 bits of frames"; return false; }
@@ -1987,12 +2170,15 @@ public:
 		return true;
 	}
 
-	const int16_t *device_pcm(uint32_t stream) override { return pcm_.p && !pcm_f32_ ? (const int16_t *)pcm_at(stream) : nullptr; }
-	const float *device_pcm_f32(uint32_t stream) override { return pcm_.p && pcm_f32_ ? (const float *)pcm_at(stream) : nullptr; }
-	size_t device_pcm_pitch() override { return pcm_.p ? pcm_pitch() : 0; }
+	/* (whoever reads the rows through these pointers orders itself behind the main stream -- sync(), stream_handle() -- and so
+	 * behind the last mixer, joined here) */
+	const int16_t *device_pcm(uint32_t stream) override { join_mixer_quiet("device_pcm"); return pcm_.p && !pcm_f32_ ? (const int16_t *)pcm_at(stream) : nullptr; }
+	const float *device_pcm_f32(uint32_t stream) override { join_mixer_quiet("device_pcm"); return pcm_.p && pcm_f32_ ? (const float *)pcm_at(stream) : nullptr; }
+	size_t device_pcm_pitch() override { join_mixer_quiet("device_pcm"); return pcm_.p ? pcm_pitch() : 0; }
 
 	bool sync(std::string &err) override {
 		use_device();
+		if (!join_mixer("sync", err)) return false;
 		HIP_OK(hipStreamSynchronize(stream_));
 		arena_used_ = 0; /* every staged copy has left the arena */
 		return true;
@@ -2002,6 +2188,7 @@ public:
 	bool save_state(int slot, std::string &err) override {
 		slot &= 3;
 		use_device();
+		if (!join_mixer("save_state", err)) return false;
 		if (!ops_snap_[slot].ensure(ops_.cap, err)) return false;
 		HIP_OK(hipMemcpyAsync(ops_snap_[slot].p, ops_.p, ops_.cap * sizeof(DevOp), hipMemcpyDeviceToDevice, stream_));
 		return true;
@@ -2009,6 +2196,7 @@ public:
 	bool load_state(int slot, std::string &err) override {
 		slot &= 3;
 		use_device();
+		if (!join_mixer("load_state", err)) return false;
 		if (!ops_snap_[slot].p || ops_snap_[slot].cap < ops_.cap) { err = "no operator state was saved under this slot"; return false; }
 		HIP_OK(hipMemcpyAsync(ops_.p, ops_snap_[slot].p, ops_.cap * sizeof(DevOp), hipMemcpyDeviceToDevice, stream_));
 		return true;
@@ -2016,6 +2204,8 @@ public:
 
 	void timing(double *render_ms, double *mix_ms, uint64_t *launches, bool reset) override {
 		if (!timing_on_) { timing_on_ = true; }
+		use_device();
+		join_mixer_quiet("timing"); /* (its pair of events is on the side stream) */
 		(void)hipStreamSynchronize(stream_);
 		drain_pairs();
 		if (render_ms) *render_ms = acc_ms_[0] + acc_ms_[2];
@@ -2025,14 +2215,18 @@ public:
 	}
 
 	size_t chain_rows_budget() override { return sauengine::chain_rows_budget(free_hint_, chain_rows_failures_); }
-	void *stream_handle() override { return (void *)stream_; }
+	/* (what the caller orders behind this stream is behind the last mixer too -- the last one launched when this is called: a
+	 * host asks again after every run whose rows it reads on the device, include/saugns_amd.h) */
+	void *stream_handle() override { use_device(); join_mixer_quiet("stream_handle"); return (void *)stream_; }
 	bool order_after(HipBackend *before, std::string &err) override {
 		HipBackendImpl *o = static_cast<HipBackendImpl *>(before);
 		if (o == this) return true;
 		if (o->dev_ != dev_) { err = "sauAmd_Batch_order_after: the two batches are on different devices"; return false; }
 		use_device();
 		if (!after_ev_) HIP_OK(hipEventCreateWithFlags(&after_ev_, hipEventDisableTiming));
-		/* (everything of `before` ends on its main stream: its chain stream's work is joined there by the final passes) */
+		/* (everything of `before` ends on its main stream: its chain stream's work is joined there by the final passes, its last
+		 * mixer's here) */
+		if (!o->join_mixer("order_after", err)) return false;
 		HIP_OK(hipEventRecord(after_ev_, o->stream_));
 		after_pending_ = true;
 		return true;
@@ -2044,10 +2238,12 @@ public:
 		HIP_OK(hipStreamWaitEvent(stream_, after_ev_, 0));
 		return true;
 	}
-	void set_timing(int level) override { timing_on_ = level > 0; timing_level_ = level; }
+	void set_timing(int level) override { use_device(); join_mixer_quiet("set_timing"); timing_on_ = level > 0; timing_level_ = level; }
 
 	void timing_ex(double *out4, uint64_t *segments, bool reset) override {
 		if (!timing_on_) timing_on_ = true;
+		use_device();
+		join_mixer_quiet("timing");
 		(void)hipStreamSynchronize(stream_);
 		drain_pairs();
 		/* out: time-parallel kernel, block-loop kernel, mixer, analyze+finalize (ms) */
@@ -2056,7 +2252,10 @@ public:
 		if (reset) { acc_ms_[0] = acc_ms_[1] = acc_ms_[2] = acc_ms_[3] = 0; acc_launches_ = 0; }
 	}
 
-	void debug_dump(const char *what, const SegmentDesc &seg, uint32_t block_grid) {
+	void debug_dump(const char *what, const Job &j) {
+		const SegmentDesc &seg = j.seg;
+		const uint32_t block_grid = j.block_grid;
+		const MixSet &S = sets_[j.set];
 		(void)hipStreamSynchronize(stream_);
 		uint32_t n = cfg_.op_count < 8 ? cfg_.op_count : 8;
 		std::vector<DevOp> h(n);
@@ -2068,7 +2267,7 @@ public:
 					seg.voices[v].plan_ofs, seg.voices[v].plan_len, seg.voices[v].ops_ofs, seg.voices[v].nops);
 		{
 			uint32_t wc = 0;
-			(void)hipMemcpy(&wc, work_count_.p, 4, hipMemcpyDeviceToHost);
+			(void)hipMemcpy(&wc, S.work_count.p, 4, hipMemcpyDeviceToHost);
 			{ /* voices the time-parallel path did not finish */
 				std::vector<FastInfo> all(seg.n_voices);
 				(void)hipMemcpy(all.data(), finfo_.p, all.size() * sizeof(FastInfo), hipMemcpyDeviceToHost);
@@ -2085,11 +2284,11 @@ public:
 			std::vector<VoiceOut> vi(seg.n_voices < 4 ? seg.n_voices : 4);
 			std::vector<uint32_t> fd(vi.size());
 			std::vector<FastInfo> fi(vi.size());
-			(void)hipMemcpy(vi.data(), set_.vinfo.p, vi.size() * sizeof(VoiceOut), hipMemcpyDeviceToHost);
+			(void)hipMemcpy(vi.data(), S.vinfo.p, vi.size() * sizeof(VoiceOut), hipMemcpyDeviceToHost);
 			(void)hipMemcpy(fd.data(), fdone_.p, fd.size() * 4, hipMemcpyDeviceToHost);
 			(void)hipMemcpy(fi.data(), finfo_.p, fi.size() * sizeof(FastInfo), hipMemcpyDeviceToHost);
 			float v8[8] = {0};
-			(void)hipMemcpy(v8, set_.vout.p, sizeof v8, hipMemcpyDeviceToHost);
+			(void)hipMemcpy(v8, sets_[j.block].vout.p, sizeof v8, hipMemcpyDeviceToHost);
 			fprintf(stderr, "  work_count %u block_grid %u; row0: %g %g %g %g %g %g\n", wc, block_grid, v8[0], v8[1],
 					v8[2], v8[3], v8[4], v8[5]);
 			for (size_t v = 0; v < vi.size(); ++v)
@@ -2113,7 +2312,7 @@ private:
 	TimedPair *new_pair(int kind) {
 		if (timing_level_ == 1 && kind != 2) return nullptr; /* level 1: dominant kernel only */
 		if (n_used_ == events_.size()) {
-			if (events_.size() >= 4096) { (void)hipStreamSynchronize(stream_); drain_pairs(); }
+			if (events_.size() >= 4096) { join_mixer_quiet("timing"); (void)hipStreamSynchronize(stream_); drain_pairs(); }
 			else {
 				TimedPair p; p.kind = 0; p.used = false;
 				if (hipEventCreate(&p.a) != hipSuccess || hipEventCreate(&p.b) != hipSuccess) return nullptr;
@@ -2152,16 +2351,30 @@ private:
 	uint32_t n_steps_total_ = 0;
 	DevBuf<uint32_t> op_ids_;
 	DevBuf<VoiceDesc> voices_;
-	/* what the mixer reads: voice rows, pan rows, per-row records, stream records */
+	/* What a mixer reads, but for the PCM: voice rows, pan rows, per-row records, stream records, the guard words, the control
+	 * words of a launch that mixes tiles itself, the streams a look-back launch has mixed. Two sets, segment n's launches on set
+	 * n mod 2, so that a segment's final mixer can still be reading its set while the next segment's launches fill the other
+	 * (launch_mixer). The rows are the one large member: set 1 has a block of its own only while plan_mix_overlap says so
+	 * (MIXO_ALTERNATE) and the device gave it; otherwise both sets' segments use set 0's (Job.block). */
 	struct MixSet {
 		DevBuf<float> vout, pan;
 		DevBuf<VoiceOut> vinfo;
 		DevBuf<MixStream> mstreams;
+		DevBuf<uint32_t> work_count; /* four words: [0] the block loop's work list, [1] premix_kernel's verdict -- the mixers' guard */
+		DevBuf<uint32_t> inmix_ctl;
+		DevBuf<uint32_t> tail_ok;    /* [stream]: the look-back launch mixes this stream itself (k_fast_types.h: FastParams.tail_ok) */
 		uint32_t vout_rows = 0;
 		std::vector<MixStream> ms_sent;
 		const void *ms_dev = nullptr;
 	};
-	MixSet set_;
+	MixSet sets_[2];
+	MixOverlapTracker mixo_;       /* where the main stream waits for a mixer on the side stream (mix_overlap.h) */
+	hipStream_t mix_stream_ = nullptr;
+	bool mix_ready_ = false;       /* the side stream and every event of the two rings are there */
+	hipEvent_t mix_fork_[MIXO_RING] = {}, mix_done_[MIXO_RING] = {}; /* per ticket: recorded on the main stream ahead of the mixer, on the side stream behind it */
+	bool second_refused_ = false;  /* the second block of rows was not to be had: shared rows for good */
+	bool overlap_report_ = false;  /* SAU_AMD_OVERLAP_REPORT: a line on stderr per segment (tests) */
+	std::string report_waits_;
 	DevBuf<int16_t> pcm_;
 	DevBuf<OpUpdate> recs_;
 	const TableSet *tables_ = nullptr;
@@ -2178,7 +2391,7 @@ private:
 	uint64_t acc_launches_ = 0;
 	int timing_level_ = 2;
 	DevBuf<FastInfo> finfo_;
-	DevBuf<uint32_t> fdone_, worklist_, work_count_;
+	DevBuf<uint32_t> fdone_, worklist_;
 	DevBuf<float> big_slots_;     /* block buffers of render_kernel<1, 1, 1, true>: [workgroup][slot][64] */
 	DevBuf<unsigned char> fsteps_, flines_, faux_;
 	DevBuf<unsigned long long> scan_;
@@ -2200,8 +2413,6 @@ private:
 	DevBuf<unsigned char> fplines_;
 	hipEvent_t after_ev_ = nullptr; /* order_after() */
 	bool after_pending_ = false;
-	DevBuf<uint32_t> inmix_ctl_;
-	DevBuf<uint32_t> tail_ok_;        /* [stream]: the look-back launch mixes this stream itself (k_fast_types.h: FastParams.tail_ok) */
 	/* level metering: the streams' running records, one measurement's partial records and frame counts, the records of
 	 * foreign rows (measure_rows), and the normalised writer's requantised row -- all from the pool, none there until asked for */
 	DevBuf<LevelsAcc> lev_acc_, lev_out_;

@@ -12,6 +12,7 @@
 #define SAU_LAUNCH_PLAN_H
 
 #include "engine.h"
+#include "mix_overlap.h"
 #include "sau_dev_math.h"
 #include <string.h>
 
@@ -117,6 +118,14 @@ struct Tuning {
 	bool early_mix = true;       /* SAU_AMD_NO_EARLY_MIX: segments with chains in chunks: the mixer follows the final passes chunk by chunk */
 	bool mix64 = true;           /* behind a launch that has mixed most tiles itself: the mixer in blocks of 64 frames (SAU_AMD_NO_MIX64: 256) */
 	bool poison = false;         /* SAU_AMD_POISON: voice and pan rows filled with 0x3ea5a5a5 ahead of every segment (tests) */
+	/* a segment's final mixer on a stream of its own, beside the next segment's set-up launches (mix_overlap.h) */
+	bool mix_overlap = true;     /* SAU_AMD_NO_MIX_OVERLAP: the mixer on the main stream, behind the segment's kernels */
+	bool mix_overlap_shared = false; /* SAU_AMD_MIX_OVERLAP_SHARED: never a second block of voice and pan rows */
+	/* SAU_AMD_MIX_OVERLAP_MB: the second block is asked for only while a segment's voice and pan rows are no more than this. 4 GiB:
+	 * BASELINE config 3's rows are 1.81 GB (1024 voices x 441000 frames x 4 bytes; 2.26 GB as the pool rounds them), admitted with
+	 * as much again to spare, and under 1.5 % of the device's 288 GB */
+	uint32_t mix_overlap_mb = 4096;
+	bool mix_overlap_fail = false; /* SAU_AMD_MIX_OVERLAP_FAIL (tests): the second block's allocation fails, by not being asked for */
 };
 
 /* The switches as the environment has them, with their clamps. `env`: sauengine::tune_env (a name -> its value or NULL). */
@@ -183,6 +192,10 @@ inline Tuning tuning_from_env(const char *(*env)(const char *)) {
 	t.early_mix = off("SAU_AMD_NO_EARLY_MIX");
 	t.mix64 = off("SAU_AMD_NO_MIX64");
 	t.poison = !off("SAU_AMD_POISON");
+	t.mix_overlap = off("SAU_AMD_NO_MIX_OVERLAP");
+	t.mix_overlap_shared = !off("SAU_AMD_MIX_OVERLAP_SHARED");
+	if (const char *mb = env("SAU_AMD_MIX_OVERLAP_MB")) { const long n = atol(mb); t.mix_overlap_mb = n < 0 ? 0u : n > 0x7fffffffl ? 0x7fffffffu : (uint32_t)n; }
+	t.mix_overlap_fail = !off("SAU_AMD_MIX_OVERLAP_FAIL");
 	return t;
 }
 
@@ -705,6 +718,23 @@ inline Mixer plan_mixer(const SegmentDesc &seg, const Tuning &tun, const PlanInp
 	if (few && (seg.pcm_offset & 3u) == 0 && (in.pcm_row & 3u) == 0) return MIX_FEW;
 	if (inmix_live && !early_blocks && tun.mix64) return MIX_64;
 	return MIX_256;
+}
+
+/* Where that mixer runs (mix_overlap.h). On the side stream only for the kind of segment measured to gain by it: one whose
+ * closed-form launch mixes tiles into the PCM itself (BASELINE config 3's kind). There the join sits in front of that launch, so
+ * the mixer runs beside the set-up launches and nothing else. A segment without such a launch has no PCM writer ahead of its own
+ * mixer, and the last segment's mixer would run on beside its rendering launches: measured slower in every such workload --
+ * BASELINE config 2 1.67e9 -> 0.80e9 frames/s, the carrier-FM bank 1.41e8 -> 1.26e8, config 5 (the mixer beside the next step's
+ * chain kernels) 9.8e6 -> 9.4e6, config 4 and the drop-in rate -1 to -2 % (profiles/r09_mix_overlap_ab.json) -- so those keep the
+ * serial order. With the launch split into edge and inner groups the two sets get rows of their own while they are small
+ * enough and the device gives them (the edge launch then runs beside the mixer too); otherwise they share one block.
+ * `rows_bytes`: the segment's voice and pan rows; `second_refused`: the second block's allocation has failed on this backend
+ * (shared rows for good). */
+inline MixOverlap plan_mix_overlap(const Tuning &tun, const PlanInputs &in, const FastPlan &fk, size_t rows_bytes, bool second_refused) {
+	if (!tun.mix_overlap || !in.max_write) return MIXO_OFF; /* (no frame to write: plan_mixer launches nothing) */
+	if (!fk.use_fast || fk.scan || !fk.queues || !fk.inmix) return MIXO_OFF;
+	if (fk.inner == INNER_NONE || tun.mix_overlap_shared || second_refused || rows_bytes > ((size_t)tun.mix_overlap_mb << 20)) return MIXO_SHARED;
+	return MIXO_ALTERNATE;
 }
 
 /* ---- level metering (k_levels.h) ----
