@@ -562,6 +562,116 @@ SAU_AMD_API bool sauAmd_Batch_spectrum_rows(sauAmdBatch *b, const void *rows, si
 SAU_AMD_API bool sauAmd_render_spectrum(const sauProgram *prg, uint32_t srate, int factor, int channels, unsigned log2n,
 		uint32_t hop, double *power_out /* [channels][N/2+1] */, uint64_t *segments_out, uint64_t *frames_out);
 
+/* ---- FLAC -----------------------------------------------------------------------
+ * The meters above spare a fetch; when the audio itself is wanted, every sample still crosses to the host as PCM. This is a
+ * lossless FLAC encoder for int16 rows where they are, on the batch's device. Like the spectrum meter it is FED rows: the rows
+ * of an int16 run (sauAmd_Batch_device_pcm), or a caller's own. What comes back is a sequence of FLAC frames per row; with the
+ * 42 bytes of sauAmd_flac_header ahead of them they are a FLAC file. The bytes are a function of the fed sequence only -- every
+ * choice below is integer arithmetic with stated ties -- never of how the sequence was cut into feeds, of the partition of the
+ * device or of scheduling. sauAmd_flac_encode_block restates one frame on the host, from the same source as the kernels.
+ *
+ * Parameters: channels 1, or 2 interleaved; 16 bits per sample; block_frames B one of 256, 512, 1024, 2048, 4096 (0 means
+ * 4096). Row r's block k covers its frames [k B, k B + B) and becomes FLAC frame number k; frames behind the last complete block
+ * are pending until a later feed completes the block or a finish makes them one last short block. At most 65535 rows per
+ * encoder and 2^31 - 1 blocks per row.
+ * Limits: no MD5 (the field is zeros: "not computed"), no seek table, no comments, no 24-bit output. The float, limited and
+ * oversampled writers have no FLAC variant; the fed encoder takes any int16 device rows.
+ *
+ * All fields are big-endian and packed MSB first.
+ * The header (42 bytes): "fLaC"; one metadata block header, 80 00 00 22 (last = 1, type 0, length 34); STREAMINFO:
+ *   min blocksize 16 bits = B; max blocksize 16 = B; min framesize 24 and max framesize 24 from the record (0 before any
+ *   frame); sample rate 20; channels - 1 in 3; bits per sample - 1 in 5 = 15; total samples 36 = the record's frames; MD5 128
+ *   bits of zeros.
+ * A frame's header:
+ *   FF F8 (the sync code, reserved 0, fixed block size);
+ *   4 bits block size code: 8 + log2(B / 256) for a block of B frames; 0111 for any other length n (also for n <= 256), and
+ *     n - 1 then follows as 16 bits at the header's end;
+ *   4 bits sample rate code 0000 (from STREAMINFO);
+ *   4 bits channel assignment: 0000 mono; 0001 L, R; 1000 left, side; 1001 side, right; 1010 mid, side;
+ *   3 bits sample size 100 (16 bits); one bit 0;
+ *   the block's number within its row in the extended UTF-8 coding: below 0x80 one byte, the number itself; below 0x800 two
+ *     bytes, lead 110xxxxx; below 0x10000 three, 1110xxxx; below 0x200000 four, 11110xxx; below 0x4000000 five, 111110xx; below
+ *     2^31 six, 1111110x; continuation bytes 10xxxxxx, six bits each, the most significant first;
+ *   the 16 bits of n - 1 when the code is 0111;
+ *   CRC-8 of every header byte before it: polynomial 0x07, initial value 0, MSB first ("123456789" gives 0xF4).
+ * A frame's body: the channels' subframes one after another, bit-contiguous; zero bits up to a byte boundary; CRC-16 of the
+ * whole frame from the sync code on: polynomial 0x8005, initial value 0, MSB first, not reflected, high byte first
+ * ("123456789" gives 0xFEE8).
+ * A subframe: one 0 bit, 6 bits of type, one 0 bit (no wasted bits). bps is 16, or 17 for a side channel; samples are two's
+ * complement in bps bits.
+ *   000000 CONSTANT: one sample.  000001 VERBATIM: the n samples.  001ooo FIXED of order o = 0 .. 4: o warm-up samples, then
+ *   the residual: 2 bits 00, 4 bits partition order p, and for each of the 2^p partitions a 4-bit Rice parameter k <= 14
+ *   (never the escape 1111) and the partition's residuals. Partition 0 holds (n >> p) - o residuals, the others n >> p.
+ *   A residual r: u = 2 r for r >= 0, else -2 r - 1; u >> k zero bits, a one bit, the low k bits of u.
+ *   Residuals (integers that fit 32 bits): order 0: s_i; 1: s_i - s_{i-1}; 2: s_i - 2 s_{i-1} + s_{i-2};
+ *   3: s_i - 3 s_{i-1} + 3 s_{i-2} - s_{i-3}; 4: s_i - 4 s_{i-1} + 6 s_{i-2} - 4 s_{i-3} + s_{i-4}.
+ * Stereo: mid = (L + R) >> 1 (an arithmetic shift), side = L - R.
+ * Choices, all in integers, ties to the first named. For a channel candidate of a block of n frames:
+ *   1. all n samples equal: CONSTANT, 8 + bps bits.
+ *   2. the order: 0 for n <= 4; otherwise the o in 0 .. 4 with the least sum of |r_i| of order o over i = 4 .. n-1 (in 64
+ *      bits), the lowest o on ties.
+ *   3. the partitions, with P = 4 for n == B and P = 0 otherwise: for p in 0 .. P and each partition, the cost of k is the sum
+ *      of u >> k over its residuals + (1 + k) * their count; the k in 0 .. 14 with the least cost, the lowest on ties. The cost
+ *      of p is the sum over its partitions of (4 + that least cost); the p with the least cost, the lowest on ties.
+ *   4. FIXED costs 8 + bps * o + 6 + cost(p) bits, VERBATIM 8 + bps * n.
+ *   5. VERBATIM when its cost is <= FIXED's, otherwise FIXED.
+ * Mono encodes its one channel. Stereo evaluates L (16 bits), R (16), M (16), S (17), takes the least of L+R, L+S, S+R, M+S,
+ * in that order on ties, and emits the two channels in the order named.
+ * Consequences: a frame is at most 15 + channels * (1 + 2 n) bytes (13 header bytes, every channel verbatim, the CRC-16). A
+ * sample's code places at most 15 non-zero bits; the unary zeros are what a cleared buffer holds.
+ * The worst case of a feed is that bound summed over the blocks it completes. Unread output lives on the device: a feed whose
+ * worst case would bring the unread total above 1 GiB is refused; read first. (Until a read has fetched the frames' sizes, a
+ * feed counts in that total with its worst case.) */
+typedef struct sauAmdFlac sauAmdFlac;
+typedef struct sauAmdFlacInfo {
+	uint64_t frames;              /* sample frames encoded */
+	uint64_t blocks;              /* FLAC frames made */
+	uint64_t bytes;               /* their bytes */
+	uint32_t min_frame_bytes, max_frame_bytes;   /* 0, 0 before the first */
+} sauAmdFlacInfo;
+#ifdef __cplusplus
+static_assert(sizeof(sauAmdFlacInfo) == 32, "sauAmdFlacInfo is 32 bytes");
+#else
+_Static_assert(sizeof(sauAmdFlacInfo) == 32, "sauAmdFlacInfo is 32 bytes");
+#endif
+
+/* 42, and "fLaC", the metadata block header and STREAMINFO in out[] when cap >= 42 (nothing is written when cap < 42; out may
+ * then be NULL). info may be NULL: an empty record. 0 for srate == 0 or > 655350, channels other than 1 or 2, a block_frames
+ * that is not allowed. */
+SAU_AMD_API size_t sauAmd_flac_header(uint32_t srate, int channels, uint32_t block_frames, const sauAmdFlacInfo *info, uint8_t *out, size_t cap);
+/* The host restatement: one FLAC frame of n (1 .. block_frames) interleaved frames x, numbered frame_number (< 2^31), as the
+ * device makes it. Returns its size; nothing is written when cap is less (out may then be NULL); 0 on a bad argument. */
+SAU_AMD_API size_t sauAmd_flac_encode_block(const int16_t *x, uint32_t n, int channels, uint32_t block_frames, uint32_t frame_number,
+		uint8_t *out, size_t cap);
+/* An encoder of n_rows empty streams on the batch's device and stream, independent of the batch's own runs. NULL
+ * (sauAmd_last_error) on a bad argument -- channels, block_frames, n_rows == 0 or above 65535 -- or on a backend without it. It
+ * must be destroyed before the batch. sauAmd_Flac_destroy(NULL) is allowed. */
+SAU_AMD_API sauAmdFlac *sauAmd_Batch_create_flac(sauAmdBatch *b, size_t n_rows, int channels, uint32_t block_frames);
+SAU_AMD_API void sauAmd_Flac_destroy(sauAmdFlac *e);
+/* Row r's next frames[r] frames, int16 in host order, `channels` interleaved, read from rows + pitch_bytes * r; 0 changes
+ * nothing for that row. Queued on the batch's stream: it may directly follow the run that produced the rows
+ * (sauAmd_Batch_device_pcm), and the rows may be reused once the batch's stream has passed it. The argument rules are
+ * sauAmd_Spectrum_feed's. Every block the feed completes is encoded; the frames behind are pending on the device. finish != 0
+ * encodes each row's pending frames, if there are any, as one last short block and closes the rows: a later feed is refused
+ * until a read with reset != 0. False with "bad argument" and nothing changed otherwise -- also for a feed of more than 2^24
+ * blocks (feed it in pieces: the bytes are the same) and for one that the 1 GiB rule above refuses. */
+SAU_AMD_API bool sauAmd_Flac_feed(sauAmdFlac *e, const void *rows, size_t pitch_bytes, const uint32_t *frames /* [n_rows] */, int finish);
+/* Wait for the batch's stream. bytes_out[r] = the encoded bytes of row r not yet read. With bufs != NULL every caps[r] must
+ * suffice (bufs[r] may be NULL where row r has nothing unread): then the bytes are copied to bufs[r] and consumed; otherwise
+ * false with "bad argument", and nothing is consumed or written. info_out (may be NULL) counts everything since the last
+ * reset. reset != 0 then starts new streams at frame number 0: records, pending frames and whatever is still unread go. */
+SAU_AMD_API bool sauAmd_Flac_read(sauAmdFlac *e, uint8_t *const *bufs, const size_t *caps, size_t *bytes_out /* [n_rows] */,
+		sauAmdFlacInfo *info_out /* [n_rows], may be NULL */, int reset);
+/* Render prg into a FLAC file: the same int16 runs on the same call lattice as sauAmd_render_file(.., SAU_AMD_SNDFILE_RAW, ..),
+ * each run's device row fed where that writer fetches it, the last feed a finish; the encoded bytes go through the two
+ * page-locked slots to the file while the next run renders, and the 42 header bytes are rewritten at the end with the final
+ * record. Decoding the file gives exactly the samples sauAmd_render_file writes. *frames_out and *info_out may be NULL. False
+ * (sauAmd_last_error) with "bad argument" on a NULL pointer, srate == 0 or > 655350, channels other than 1 or 2 or a
+ * block_frames that is not allowed, and on a backend without an encoder -- all before any file is created. */
+SAU_AMD_API bool sauAmd_render_file_flac(const sauProgram *prg, uint32_t srate, const char *path, int channels, uint32_t block_frames,
+		uint64_t *frames_out, sauAmdFlacInfo *info_out);
+
+
 #ifdef __cplusplus
 }
 #endif

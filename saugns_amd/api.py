@@ -139,6 +139,21 @@ class LimiterStats(C.Structure):
 assert C.sizeof(LimiterStats) == 24
 
 
+class FlacInfo(C.Structure):
+    """sauAmdFlacInfo: what an encoder's stream has made since the last reset"""
+    _fields_ = [("frames", C.c_uint64), ("blocks", C.c_uint64), ("bytes", C.c_uint64), ("min_frame_bytes", C.c_uint32),
+                ("max_frame_bytes", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+    def __repr__(self):
+        return "FlacInfo(%r)" % (self.as_dict(),)
+
+
+assert C.sizeof(FlacInfo) == 32
+
+
 def _declare(L):
     """The C ABI of include/saugns_amd.h on a loaded library."""
     L.sau_create_Generator.restype = C.c_void_p
@@ -268,6 +283,22 @@ def _declare(L):
         L.sauAmd_render_spectrum.restype = C.c_bool
         L.sauAmd_render_spectrum.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_uint, C.c_uint32, C.POINTER(C.c_double),
                                              C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    if hasattr(L, "sauAmd_Batch_create_flac"):  # the FLAC encoder (SAU_AMD_LIB may name an older build)
+        L.sauAmd_flac_header.restype = C.c_size_t
+        L.sauAmd_flac_header.argtypes = [C.c_uint32, C.c_int, C.c_uint32, C.POINTER(FlacInfo), C.c_void_p, C.c_size_t]
+        L.sauAmd_flac_encode_block.restype = C.c_size_t
+        L.sauAmd_flac_encode_block.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t]
+        L.sauAmd_Batch_create_flac.restype = C.c_void_p
+        L.sauAmd_Batch_create_flac.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_uint32]
+        L.sauAmd_Flac_destroy.argtypes = [C.c_void_p]
+        L.sauAmd_Flac_feed.restype = C.c_bool
+        L.sauAmd_Flac_feed.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.c_int]
+        L.sauAmd_Flac_read.restype = C.c_bool
+        L.sauAmd_Flac_read.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
+                                       C.POINTER(FlacInfo), C.c_int]
+        L.sauAmd_render_file_flac.restype = C.c_bool
+        L.sauAmd_render_file_flac.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_int, C.c_uint32, C.POINTER(C.c_uint64),
+                                              C.POINTER(FlacInfo)]
     L.sauAmd_set_piluts.argtypes = [C.c_void_p]
     L.sauAmd_get_piluts.restype = C.POINTER(C.c_float)
     L.sauAmd_last_error.restype = C.c_char_p
@@ -608,6 +639,67 @@ def render_spectrum(program, srate, factor=1, channels=1, log2n=11, hop=1024, ba
     if not ok:
         raise RuntimeError("sauAmd_render_spectrum failed: " + last_error(L))
     return power, segs.value, n.value
+
+
+_flac_hooks = None
+
+
+def use_flac_hooks(path):
+    """tests/ only: load the library that runs sauAmd_render_file_flac over an injected backend and reaches the encoder's
+    launch plan (tests/hooks_flac: the product's object files + sauAmd_render_file_flac_with_backend, sauAmd_flac_plan)."""
+    global _flac_hooks
+    if _flac_hooks is None:
+        L = _declare(C.CDLL(path))
+        L.sauAmd_render_file_flac_with_backend.restype = C.c_bool
+        L.sauAmd_render_file_flac_with_backend.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_int, C.c_uint32, C.c_void_p,
+                                                           C.POINTER(C.c_uint64), C.POINTER(FlacInfo)]
+        L.sauAmd_flac_plan.restype = C.c_int
+        L.sauAmd_flac_plan.argtypes = [C.c_uint32, C.c_uint32, C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.c_int,
+                                       C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        _flac_hooks = L
+    return _flac_hooks
+
+
+def flac_header(srate, channels, block_frames, info=None):
+    """sauAmd_flac_header: the 42 bytes ahead of the frames ("fLaC", the metadata block header, STREAMINFO) for a record
+    (a FlacInfo, a dict of its fields, or None: an empty one); b"" for arguments that are refused."""
+    if isinstance(info, dict):
+        info = FlacInfo(**info)
+    out = (C.c_uint8 * 42)()
+    n = lib().sauAmd_flac_header(srate, channels, block_frames, C.byref(info) if info is not None else None, out, 42)
+    return bytes(out) if n == 42 else b""
+
+
+def flac_encode_block(x, channels, block_frames, frame_number):
+    """sauAmd_flac_encode_block: the host's restatement of one frame, from interleaved int16 samples -> bytes (b"" when the
+    arguments are refused)"""
+    x = np.ascontiguousarray(x, np.int16)
+    n = len(x) // max(int(channels), 1)
+    L = lib()
+    size = L.sauAmd_flac_encode_block(x.ctypes.data, n, channels, block_frames, frame_number, None, 0)
+    if not size:
+        return b""
+    out = (C.c_uint8 * size)()
+    assert L.sauAmd_flac_encode_block(x.ctypes.data, n, channels, block_frames, frame_number, out, size) == size
+    return bytes(out)
+
+
+def render_file_flac(program, srate, path, channels=1, block_frames=0, backend=None):
+    """sauAmd_render_file_flac: render a whole program into a FLAC file, encoded on the device -> (frames, FlacInfo).
+    ``backend`` (tests): a sauengine::Backend* to run the same writer without a GPU."""
+    n, info = C.c_uint64(), FlacInfo()
+    if backend is None:
+        L = _used(lib())
+        ok = L.sauAmd_render_file_flac(program.ptr, srate, os.fsencode(path), channels, block_frames, C.byref(n), C.byref(info))
+    else:
+        if _flac_hooks is None:
+            raise RuntimeError("the FLAC-hook library is not loaded (use_flac_hooks)")
+        L = _used(_flac_hooks)
+        ok = L.sauAmd_render_file_flac_with_backend(program.ptr, srate, os.fsencode(path), channels, block_frames, backend,
+                                                    C.byref(n), C.byref(info))
+    if not ok:
+        raise RuntimeError("sauAmd_render_file_flac failed: " + last_error(L))
+    return n.value, info
 
 
 def limiter_window(srate):
@@ -988,6 +1080,11 @@ class Batch:
         out = (power[:n_rows], [int(x) for x in segs][:n_rows])
         return out + (gram[:n_rows],) if spectrogram else out
 
+    def create_flac(self, n_rows, channels, block_frames=0):
+        """sauAmd_Batch_create_flac: a Flac encoder of n_rows streams on the batch's device and stream. Close it before the
+        batch."""
+        return Flac(self, n_rows, channels, block_frames)
+
     def device_pcm(self, stream):
         """Device address of the stream's int16 row of the last run; None after a float32 run."""
         return self._L.sauAmd_Batch_device_pcm(self._b, stream)
@@ -1028,7 +1125,7 @@ class Batch:
 
     def close(self):
         if getattr(self, "_b", None):
-            for ref in getattr(self, "_meters", []):  # (a spectrum meter goes before its batch)
+            for ref in getattr(self, "_meters", []):  # (a spectrum meter or an encoder goes before its batch)
                 m = ref()
                 if m is not None:
                     m.close()
@@ -1072,6 +1169,60 @@ class Spectrum:
         if getattr(self, "_s", None):
             self._L.sauAmd_Spectrum_destroy(self._s)
             self._s = None
+            self._batch = None
+
+    def __del__(self):
+        self.close()
+
+
+class Flac:
+    """sauAmdFlac: a lossless FLAC encoder of int16 rows on the device (include/saugns_amd.h, section "FLAC"). ``feed`` takes
+    row r's next frames[r] frames from device memory, on the batch's stream; ``read`` waits and returns the rows' encoded bytes.
+    Close it before its batch."""
+
+    def __init__(self, batch, n_rows, channels, block_frames=0):
+        self._L = batch._L
+        self.n_rows, self.channels, self.block_frames = int(n_rows), int(channels), int(block_frames)
+        self._e = _used(self._L).sauAmd_Batch_create_flac(batch._b, self.n_rows, self.channels, self.block_frames)
+        if not self._e:
+            raise RuntimeError("sauAmd_Batch_create_flac returned NULL: " + last_error(self._L))
+        self._batch = batch  # (the batch outlives the encoder: its close() closes this one first)
+        batch._meters = getattr(batch, "_meters", []) + [weakref.ref(self)]
+
+    def feed(self, ptr, pitch, frames, finish=False):
+        """sauAmd_Flac_feed: row r's next frames[r] frames from the device rows at `ptr`, `pitch` bytes apart."""
+        fr = (C.c_uint32 * self.n_rows)(*[int(f) for f in frames])
+        if not _used(self._L).sauAmd_Flac_feed(self._e, ptr, pitch, fr, 1 if finish else 0):
+            raise RuntimeError("sauAmd_Flac_feed failed: " + last_error(self._L))
+
+    def unread(self):
+        """sauAmd_Flac_read without buffers -> (the unread bytes per row as a list, the rows' FlacInfo as dicts)"""
+        n = (C.c_size_t * self.n_rows)()
+        info = (FlacInfo * self.n_rows)()
+        if not _used(self._L).sauAmd_Flac_read(self._e, None, None, n, info, 0):
+            raise RuntimeError("sauAmd_Flac_read failed: " + last_error(self._L))
+        return [int(v) for v in n], [i.as_dict() for i in info]
+
+    def read(self, reset=False, caps=None):
+        """sauAmd_Flac_read -> (the rows' unread bytes as a list of bytes objects, the rows' FlacInfo as dicts); the bytes
+        are consumed. ``caps`` (tests): the capacities to state instead of what the rows need."""
+        need, _ = self.unread()
+        bufs = [np.full(max(c, 1) + 8, 0xa5, np.uint8) for c in (need if caps is None else caps)]
+        ptrs = (C.c_void_p * self.n_rows)(*[b.ctypes.data for b in bufs])
+        cap = (C.c_size_t * self.n_rows)(*(need if caps is None else caps))
+        n = (C.c_size_t * self.n_rows)()
+        info = (FlacInfo * self.n_rows)()
+        if not _used(self._L).sauAmd_Flac_read(self._e, ptrs, cap, n, info, 1 if reset else 0):
+            assert all((b == 0xa5).all() for b in bufs), "a refused read has written"
+            raise RuntimeError("sauAmd_Flac_read failed: " + last_error(self._L))
+        for b, v in zip(bufs, n):
+            assert (b[int(v):] == 0xa5).all(), "a store behind the row's bytes"
+        return [bytes(b[:int(v)]) for b, v in zip(bufs, n)], [i.as_dict() for i in info]
+
+    def close(self):
+        if getattr(self, "_e", None):
+            self._L.sauAmd_Flac_destroy(self._e)
+            self._e = None
             self._batch = None
 
     def __del__(self):

@@ -641,6 +641,67 @@ extern "C" bool sauAmd_Batch_spectrum_rows(sauAmdBatch *b, const void *rows, siz
 	return false;
 }
 
+/* ---- the FLAC encoder (include/saugns_amd.h, section "FLAC") ---- */
+struct sauAmdFlac {
+	sauengine::FlacEncoder *enc;
+};
+static_assert(sizeof(sauAmdFlacInfo) == sizeof(sauengine::FlacInfo), "sauAmdFlacInfo is sauengine::FlacInfo");
+
+extern "C" size_t sauAmd_flac_header(uint32_t srate, int channels, uint32_t block_frames, const sauAmdFlacInfo *info, uint8_t *out, size_t cap) {
+	return sauengine::flac_header(srate, channels, block_frames, (const sauengine::FlacInfo *)info, out, cap);
+}
+extern "C" size_t sauAmd_flac_encode_block(const int16_t *x, uint32_t n, int channels, uint32_t block_frames, uint32_t frame_number,
+		uint8_t *out, size_t cap) {
+	try {
+		return sauengine::flac_encode_block(x, n, channels, block_frames, frame_number, out, cap);
+	} catch (const std::exception &) { /* (nothing C++ crosses the C ABI) */
+		return 0;
+	}
+}
+
+extern "C" sauAmdFlac *sauAmd_Batch_create_flac(sauAmdBatch *b, size_t n_rows, int channels, uint32_t block_frames) {
+	std::string err;
+	try {
+		if (!b || !n_rows || n_rows > sauflac::FLAC_MAX_ROWS || !sauengine::flac_params_ok(channels, block_frames)) err = "bad argument";
+		else if (sauengine::FlacEncoder *e = b->engine->backend()->create_flac(n_rows, (uint32_t)channels, block_frames, err))
+			return new sauAmdFlac{e};
+	} catch (const std::exception &ex) {
+		err = std::string("internal error: ") + ex.what();
+	}
+	report("flac", err);
+	return nullptr;
+}
+
+extern "C" void sauAmd_Flac_destroy(sauAmdFlac *e) {
+	if (!e) return;
+	delete e->enc;
+	delete e;
+}
+
+extern "C" bool sauAmd_Flac_feed(sauAmdFlac *e, const void *rows, size_t pitch_bytes, const uint32_t *frames, int finish) {
+	std::string err;
+	try {
+		if (!e || !rows || !frames || ((uintptr_t)rows & 15u) || (pitch_bytes & 15u)) err = "bad argument";
+		else if (e->enc->feed(rows, pitch_bytes, frames, finish != 0, err)) return true;
+	} catch (const std::exception &ex) {
+		err = std::string("internal error: ") + ex.what();
+	}
+	report("flac", err);
+	return false;
+}
+
+extern "C" bool sauAmd_Flac_read(sauAmdFlac *e, uint8_t *const *bufs, const size_t *caps, size_t *bytes_out, sauAmdFlacInfo *info_out, int reset) {
+	std::string err;
+	try {
+		if (!e || !bytes_out || (bufs && !caps)) err = "bad argument";
+		else if (e->enc->read(bufs, caps, bytes_out, (sauengine::FlacInfo *)info_out, reset != 0, err)) return true;
+	} catch (const std::exception &ex) {
+		err = std::string("internal error: ") + ex.what();
+	}
+	report("flac", err);
+	return false;
+}
+
 extern "C" bool sauAmd_Batch_sync(sauAmdBatch *b) {
 	std::string err;
 	if (!b->engine->backend()->sync(err)) { report("batch", err); return false; }

@@ -43,6 +43,12 @@ bool render_file_loudness_limited(const sauProgram *prg, uint32_t srate, const c
 bool render_spectrum(const sauProgram *prg, uint32_t srate, int factor, int channels, unsigned log2n, uint32_t hop,
 		const std::function<sauengine::Backend *(std::string &)> &make_backend, double *power_out, uint64_t *segments_out,
 		uint64_t *frames_out, std::string &err);
+/* sauAmd_render_file_flac's body (sndout.cpp). make_backend is asked once, after the arguments have been looked at (NULL with
+ * err: the render cannot run); the engine made over what it returns owns it. A backend without an encoder is refused before
+ * the file is created. */
+bool render_file_flac(const sauProgram *prg, uint32_t srate, const char *path, int channels, uint32_t block_frames,
+		const std::function<sauengine::Backend *(std::string &)> &make_backend, uint64_t *frames_out, sauAmdFlacInfo *info_out,
+		std::string &err);
 /* the thread's sauAmd_last_error text (capi.cpp), with the line on stderr */
 void set_last_error(const char *where, const std::string &err);
 } /* namespace sauamd_internal */

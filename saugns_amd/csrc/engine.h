@@ -14,6 +14,7 @@
 
 #include "../../include/sau_abi.h"
 #include "sau_dev_types.h"
+#include "sau_flac.h"
 #include <stddef.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -109,6 +110,35 @@ public:
 	/* wait for the stream; power_out[n_rows][channels][N/2 + 1] the sums (the group at hand added in the copy), segments_out[n_rows];
 	 * `reset`: empty records behind the read */
 	virtual bool read(double *power_out, uint64_t *segments_out, bool reset, std::string &err) = 0;
+};
+
+/* The FLAC encoder on the host (tables.cpp; include/saugns_amd.h, section "FLAC"; the arithmetic is sau_flac.h's, which the
+ * kernels use too). FlacInfo is sauAmdFlacInfo. flac_header: 42, and "fLaC", the metadata block header and STREAMINFO in out[]
+ * when cap suffices; 0 on a bad argument. flac_encode_block: one frame of n interleaved frames as the device makes it -> its
+ * size, written when cap suffices; 0 on a bad argument. */
+struct FlacInfo {
+	uint64_t frames, blocks, bytes;
+	uint32_t min_frame_bytes, max_frame_bytes;
+};
+static_assert(sizeof(FlacInfo) == 32, "FlacInfo is sauAmdFlacInfo");
+size_t flac_header(uint32_t srate, int channels, uint32_t block_frames, const FlacInfo *info, uint8_t *out, size_t cap);
+size_t flac_encode_block(const int16_t *x, uint32_t n, int channels, uint32_t block_frames, uint32_t frame_number, uint8_t *out, size_t cap);
+inline bool flac_params_ok(int channels, uint32_t block_frames) {
+	return (channels == 1 || channels == 2) && sauflac::flac_block_frames(block_frames) != 0;
+}
+
+/* A FLAC encoder of a backend (Backend::create_flac): streams that are fed int16 rows. Destroyed before its backend. */
+class FlacEncoder {
+public:
+	virtual ~FlacEncoder() {}
+	virtual size_t n_rows() const = 0;
+	virtual uint32_t channels() const = 0;
+	virtual uint32_t block_frames() const = 0;
+	/* row r's next frames[r] frames, from rows + pitch_bytes * r: device work on the backend's stream; `finish` closes the rows */
+	virtual bool feed(const void *rows, size_t pitch_bytes, const uint32_t *frames, bool finish, std::string &err) = 0;
+	/* wait for the stream; bytes_out[n_rows] the unread bytes; bufs (may be NULL): they are copied there and consumed, every
+	 * caps[r] has to suffice; info_out (may be NULL) [n_rows]; `reset`: new streams behind the read */
+	virtual bool read(uint8_t *const *bufs, const size_t *caps, size_t *bytes_out, FlacInfo *info_out, bool reset, std::string &err) = 0;
 };
 
 /* Everything the backend needs to render one segment (no events inside). */
@@ -361,6 +391,11 @@ public:
 	 * device and stream (the caller owns it and destroys it before the backend); the arguments have been looked at. */
 	virtual SpectrumMeter *create_spectrum(size_t n_rows, uint32_t channels, unsigned log2n, uint32_t hop, std::string &err) {
 		(void)n_rows; (void)channels; (void)log2n; (void)hop; err = "this backend has no spectrum meter"; return nullptr;
+	}
+	/* A FLAC encoder of n_rows streams on the backend's stream (include/saugns_amd.h, section "FLAC"), where the samples are. A
+	 * backend without one refuses -- this default -- and nothing changes. */
+	virtual FlacEncoder *create_flac(size_t n_rows, uint32_t channels, uint32_t block_frames, std::string &err) {
+		(void)n_rows; (void)channels; (void)block_frames; err = "this backend has no FLAC encoder"; return nullptr;
 	}
 	/* the same from empty records on rows of `frames` frames each, synchronous; spectrogram_out (may be NULL): every segment's
 	 * (float)p[k], [n_rows][channels][S][N/2 + 1], refused when spectrogram_cap (in floats) does not suffice */

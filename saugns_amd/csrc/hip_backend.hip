@@ -14,6 +14,7 @@
  *   k_loudness.h    loud_chunk_kernel, loud_scan_kernel, truepeak_kernel, loud_finish_kernel, loud_carry_kernel (BS.1770 loudness, true peak)
  *   k_limiter.h     lim_env_kernel, lim_gain_kernel, lim_finish_kernel, lim_carry_kernel (the look-ahead true-peak limiter)
  *   k_spectrum.h    spec_segment_kernel, spec_finish_kernel, spec_carry_kernel (Welch power spectra of fed rows)
+ *   k_flac.h        flac_analyze_kernel, flac_scan_kernel, flac_write_kernel, flac_carry_kernel (FLAC frames of fed int16 rows)
  *   launch_plan.h   (plain C++, no HIP) the tuning switches and every decision about a segment's launches: rows per pass, LDS
  *                   budgets, builds, grids, tasks, chain chunks, the mixer -- a plan per segment, testable without a GPU
  *   mix_overlap.h   (plain C++, no HIP) where the main stream waits for a final mixer that runs on the side stream
@@ -50,6 +51,7 @@
 #include <string.h>
 #include <deque>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <type_traits>
@@ -79,6 +81,7 @@ using namespace sauplan;
 #include "k_loudness.h"
 #include "k_limiter.h"
 #include "k_spectrum.h"
+#include "k_flac.h"
 static_assert(MISC_BYTES == sizeof(Misc), "launch_plan.h plans the block loop's LDS with this size");
 
 /* ------------------------------------------------------------------------ */
@@ -2168,6 +2171,173 @@ public:
 		if (!m.read(power_out, segments_out, false, err)) return false;
 		if (spectrogram_out && sg) HIP_OK(hipMemcpy(spectrogram_out, spec_gram_.p, sg * sizeof(float), hipMemcpyDeviceToHost));
 		return true;
+	}
+
+	/* ---- the FLAC encoder (k_flac.h; the geometry is launch_plan.h's plan_flac) ----
+	 * An encoder is streams of its own on this backend's device and stream: the pending frames (two buffers, as the spectrum
+	 * meter's), a running record per row, and the output of every feed not yet read -- one block of device memory per feed with
+	 * room for its worst case, in which a row's frames lie back to back from the row's offset on. Where a row stands is kept on
+	 * the host. The unread total that the 1 GiB rule counts is the feeds' worst cases until a read has fetched the sizes. */
+	class Flac : public sauengine::FlacEncoder {
+	public:
+		Flac(HipBackendImpl *be, size_t n_rows, uint32_t channels, uint32_t block_frames)
+			: be_(be), n_(n_rows), ch_(channels), B_(sauflac::flac_block_frames(block_frames)), pos_(n_rows, 0), blocks_(n_rows, 0) {
+			/* (tests: another limit of unread bytes than 1 GiB) */
+			if (const char *v = sauengine::tune_env("SAU_AMD_FLAC_UNREAD_MAX")) { const long long x = atoll(v); if (x > 0) limit_ = (uint64_t)x; }
+		}
+		~Flac() override { /* the buffers go back to the pool (member destructors): nothing may still be using them */
+			be_->use_device();
+			if (be_->stream_) { be_->join_mixer_quiet("flac"); (void)hipStreamSynchronize(be_->stream_); }
+		}
+		size_t n_rows() const override { return n_; }
+		uint32_t channels() const override { return ch_; }
+		uint32_t block_frames() const override { return B_; }
+		bool init(std::string &err) {
+			const FlacPlan plan = plan_flac(B_, ch_, n_, nullptr);
+			if (!plan.ok) { err = "bad argument"; return false; }
+			if (!pend_[0].ensure(n_ * plan.pend_pitch, err) || !pend_[1].ensure(n_ * plan.pend_pitch, err) || !desc_.ensure(n_, err) ||
+			    !stats_.ensure(n_, err))
+				return false;
+			return clear(err);
+		}
+		/* new streams: behind a read, which has waited for the stream */
+		bool clear(std::string &err) {
+			if (!be_->join_mixer("flac_clear", err)) return false;
+			HIP_OK(hipMemsetAsync(stats_.p, 0, n_ * sizeof(FlacStats), be_->stream_));
+			std::fill(pos_.begin(), pos_.end(), 0);
+			std::fill(blocks_.begin(), blocks_.end(), 0);
+			closed_ = false;
+			return true;
+		}
+		bool feed(const void *rows, size_t pitch, const uint32_t *frames, bool finish, std::string &err) override {
+			be_->use_device();
+			if (!be_->join_mixer("flac_feed", err)) return false; /* (the rows fed may be the batch's PCM) */
+			if (!rows || !frames || ((uintptr_t)rows & 15u) || (pitch & 15u)) { err = "bad argument: rows and pitch_bytes must be multiples of 16"; return false; }
+			if (closed_) { err = "bad argument: the streams are finished (read with reset first)"; return false; }
+			uint32_t longest = 0;
+			for (size_t r = 0; r < n_; ++r) longest = frames[r] > longest ? frames[r] : longest;
+			if (!longest && !finish) return true; /* nothing changes, and the rows are not looked at */
+			if (longest) {
+				const size_t row_bytes = (size_t)longest * ch_ * sizeof(int16_t);
+				if (n_ > 1 && row_bytes > pitch) { err = "bad argument: rows longer than their pitch"; return false; }
+				/* the rows are read by kernels: they have to lie inside one allocation of this device */
+				if (!be_->lim_rows_inside(rows, pitch, n_, row_bytes, "rows", err)) return false;
+			}
+			std::vector<FlacRow> d(n_);
+			for (size_t r = 0; r < n_; ++r) d[r] = plan_flac_row(pos_[r], frames[r], B_, finish);
+			const FlacPlan plan = plan_flac(B_, ch_, n_, d.data());
+			if (!plan.ok) { err = "bad argument: too many frames for one feed, or for one stream"; return false; }
+			if (bound_ + plan.worst > limit_) { err = "bad argument: the unread output could pass its limit (read first)"; return false; }
+			std::unique_ptr<Chunk> c;
+			if (plan.jobs) {
+				c.reset(new Chunk);
+				if (!frames_.ensure(plan.jobs, err) || !c->out.ensure(plan.out_bytes, err) || !c->row_bytes.ensure(n_, err)) return false;
+				c->off.resize(n_);
+				for (size_t r = 0; r < n_; ++r) c->off[r] = d[r].out_off;
+			}
+			if (!be_->send(desc_.p, d.data(), n_ * sizeof(FlacRow), err)) return false;
+			FlacParams fp;
+			memset((void *)&fp, 0, sizeof fp);
+			fp.rows = (const int16_t *)rows; fp.row_pitch = pitch; fp.desc = desc_.p;
+			fp.pend = pend_[cur_].p; fp.pend_next = pend_[cur_ ^ 1].p; fp.pend_pitch = plan.pend_pitch;
+			fp.frames = frames_.p; fp.stats = stats_.p;
+			fp.B = B_; fp.channels = ch_; fp.n_rows = (uint32_t)n_; fp.jobs = plan.jobs;
+			hipStream_t st = be_->stream_;
+			if (plan.jobs) {
+				fp.out = c->out.p; fp.row_bytes = c->row_bytes.p;
+				hipLaunchKernelGGL(flac_analyze_kernel, dim3(plan.jobs), dim3(plan.analyze_threads), plan.analyze_lds, st, fp);
+				HIP_OK(hipGetLastError());
+				hipLaunchKernelGGL(flac_scan_kernel, dim3(plan.rows), dim3(FLAC_THREADS), 0, st, fp);
+				HIP_OK(hipGetLastError());
+				hipLaunchKernelGGL(flac_write_kernel, dim3(plan.jobs), dim3(FLAC_THREADS), plan.write_lds, st, fp);
+				HIP_OK(hipGetLastError());
+			}
+			if (!finish) { /* (behind a finish nothing is pending) */
+				hipLaunchKernelGGL(flac_carry_kernel, dim3((uint32_t)((plan.pend_pitch + FLAC_THREADS - 1) / FLAC_THREADS), plan.rows), dim3(FLAC_THREADS), 0, st, fp);
+				HIP_OK(hipGetLastError());
+				cur_ ^= 1;
+			}
+			for (size_t r = 0; r < n_; ++r) { pos_[r] += frames[r]; blocks_[r] += d[r].n_blocks; }
+			if (c) chunks_.push_back(std::move(c));
+			bound_ += plan.worst;
+			closed_ = finish;
+			return true;
+		}
+		bool read(uint8_t *const *bufs, const size_t *caps, size_t *bytes_out, sauengine::FlacInfo *info_out, bool reset, std::string &err) override {
+			be_->use_device();
+			if (!be_->join_mixer("flac_read", err)) return false;
+			if (!bytes_out || (bufs && !caps)) { err = "bad argument"; return false; }
+			HIP_OK(hipStreamSynchronize(be_->stream_));
+			std::vector<uint64_t> total(n_, 0);
+			for (auto &c : chunks_) {
+				if (c->len.empty()) { /* (fetched once: a read that consumes nothing may come again) */
+					c->len.resize(n_);
+					HIP_OK(hipMemcpy(c->len.data(), c->row_bytes.p, n_ * sizeof(uint32_t), hipMemcpyDeviceToHost));
+				}
+				for (size_t r = 0; r < n_; ++r) total[r] += c->len[r];
+			}
+			std::vector<FlacStats> st(n_);
+			HIP_OK(hipMemcpy(st.data(), stats_.p, n_ * sizeof(FlacStats), hipMemcpyDeviceToHost));
+			uint64_t all = 0;
+			for (size_t r = 0; r < n_; ++r) {
+				all += total[r];
+				if (bufs && total[r] && (!bufs[r] || caps[r] < total[r])) { err = "bad argument: a buffer is too small for its row's bytes"; return false; }
+			}
+			if (bufs) {
+				std::vector<size_t> at(n_, 0);
+				for (auto &c : chunks_)
+					for (size_t r = 0; r < n_; ++r)
+						if (c->len[r]) {
+							HIP_OK(hipMemcpyAsync(bufs[r] + at[r], c->out.p + c->off[r], c->len[r], hipMemcpyDeviceToHost, be_->stream_));
+							at[r] += c->len[r];
+						}
+				HIP_OK(hipStreamSynchronize(be_->stream_));
+				chunks_.clear();
+				bound_ = 0;
+			} else
+				bound_ = all; /* (the sizes are known now) */
+			for (size_t r = 0; r < n_; ++r) {
+				bytes_out[r] = (size_t)total[r];
+				if (info_out) {
+					info_out[r].frames = pos_[r]; info_out[r].blocks = blocks_[r]; info_out[r].bytes = st[r].bytes;
+					info_out[r].min_frame_bytes = st[r].min_bytes; info_out[r].max_frame_bytes = st[r].max_bytes;
+				}
+			}
+			if (reset) { /* new streams: what is pending or unread goes */
+				chunks_.clear();
+				bound_ = 0;
+				return clear(err);
+			}
+			return true;
+		}
+	private:
+		struct Chunk { /* one feed's output */
+			DevBuf<uint8_t> out;
+			DevBuf<uint32_t> row_bytes;  /* [rows]: flac_scan_kernel's word on them */
+			std::vector<uint32_t> off;   /* [rows]: where a row's frames begin in `out` */
+			std::vector<uint32_t> len;   /* [rows]: row_bytes on the host, once a read has fetched them */
+		};
+		HipBackendImpl *be_;
+		size_t n_;
+		uint32_t ch_, B_;
+		std::vector<uint64_t> pos_, blocks_; /* per row: frames fed, blocks made */
+		std::vector<std::unique_ptr<Chunk>> chunks_;
+		uint64_t bound_ = 0, limit_ = sauflac::FLAC_MAX_UNREAD;
+		bool closed_ = false;
+		DevBuf<int16_t> pend_[2];
+		DevBuf<FlacRow> desc_;
+		DevBuf<FlacStats> stats_;
+		DevBuf<FlacFrameDesc> frames_;
+		int cur_ = 0;
+	};
+	sauengine::FlacEncoder *create_flac(size_t n_rows, uint32_t channels, uint32_t block_frames, std::string &err) override {
+		use_device();
+		if (!join_mixer("create_flac", err)) return nullptr;
+		if (!sauengine::flac_params_ok((int)channels, block_frames) || !n_rows) { err = "bad argument"; return nullptr; }
+		if (n_rows > sauflac::FLAC_MAX_ROWS) { err = "bad argument: more than 65535 rows"; return nullptr; }
+		Flac *e = new Flac(this, n_rows, channels, block_frames);
+		if (!e->init(err)) { delete e; return nullptr; }
+		return e;
 	}
 
 	/* (whoever reads the rows through these pointers orders itself behind the main stream -- sync(), stream_handle() -- and so

@@ -1,0 +1,307 @@
+/* k_flac.h -- the FLAC encoder of int16 rows: part of hip_backend.hip (inside namespace sauhip). The format and every choice
+ * are stated in include/saugns_amd.h, section "FLAC"; the arithmetic is sau_flac.h's, which the host restatement
+ * (tables.cpp: flac_encode_block) uses too, so the bytes are a function of the fed sequence only.
+ *   flac_analyze_kernel  grid (jobs) x 64 (mono) or 256 (stereo): a workgroup owns one block of one row (a job: launch_plan.h)
+ *       and a wave one candidate channel -- L, R, M, S. The block's frames are staged in LDS as words (L | R << 16); the wave
+ *       finds whether its channel is constant, the sums of |r| of the five orders, for the order chosen the sums of u >> k,
+ *       k = 0 .. 14, per finest partition (B / 16 frames; the whole of a short block), merges them upward (one lane per (p,
+ *       partition)) and chooses; thread 0 then chooses the channel assignment and leaves the frame's record: FlacFrameDesc.
+ *   flac_scan_kernel     grid (rows) x 256: the exclusive sum of a row's frame sizes -> where every frame begins behind the
+ *       row's offset in the feed's output; the row's bytes of this feed and its running record (bytes, least and largest frame).
+ *   flac_write_kernel    grid (jobs) x 256: stages the frames again, builds the frame in LDS words that start out cleared -- the
+ *       header by thread 0; a verbatim sample or a residual's code (at most 15 non-zero bits: the stop bit and the low k bits;
+ *       the unary zeros are what the cleared words hold) by an integer OR into at most two words, at the bit position an
+ *       exclusive sum of the code lengths over the block gives -- and then the CRC-16: every lane takes a run of bytes and
+ *       advances its remainder over what follows (flac_crc16_advance: the CRC is linear), and the remainders are XORed. OR and
+ *       XOR do not depend on their order, so the bytes are reproducible. The finished bytes go to the frame's place.
+ *   flac_carry_kernel    grid (parts, rows): the row's pending frames become those behind the feed, from one buffer into the
+ *       other (the encoder swaps them), as spec_carry_kernel does.
+ * No lane walks a whole block: a lane's run is n / 64 frames in the analysis, n / 256 in the writer.
+ *
+ * LDS. Frame i is kept at word i + (i >> 5): in the partition sums a lane walks a run of consecutive frames (one new word per
+ * frame) and the runs lie B / 64 apart, which without the extra word per 32 would put all lanes on one bank at B = 4096. The
+ * analysis takes 4.1 B bytes + 10 KiB; the writer 4.1 B + the frame's bound, 33 KiB at B = 4096 stereo. */
+#ifndef SAU_K_FLAC_H
+#define SAU_K_FLAC_H
+
+using namespace sauflac;
+
+struct FlacStats { /* per row, since the last reset */
+	unsigned long long bytes;
+	uint32_t min_bytes, max_bytes; /* 0, 0 before the first frame */
+};
+static_assert(sizeof(FlacStats) == 16, "FlacStats is fetched as it stands");
+
+struct FlacParams {
+	const int16_t *rows;      /* the fed rows; not read where a row's feed has no frames */
+	size_t row_pitch;         /* bytes between them */
+	const FlacRow *desc;      /* [n_rows] (launch_plan.h) */
+	const int16_t *pend;      /* [n_rows][pend_pitch], interleaved like the row: the frames from block0 * B on */
+	int16_t *pend_next;       /* flac_carry_kernel's target */
+	size_t pend_pitch;        /* int16 */
+	FlacFrameDesc *frames;    /* [jobs] */
+	uint8_t *out;             /* the feed's output */
+	uint32_t *row_bytes;      /* [n_rows]: what this feed made of each row */
+	FlacStats *stats;         /* [n_rows] */
+	uint32_t B, channels, n_rows, jobs;
+};
+
+__device__ __forceinline__ unsigned flac_ix(const unsigned i) { return i + (i >> 5); }
+
+/* the row a job belongs to: the last one whose job0 is not above it (rows without blocks share the next row's job0) */
+__device__ __forceinline__ unsigned flac_find_row(const FlacRow *__restrict__ desc, const unsigned n_rows, const unsigned job) {
+	unsigned lo = 0, hi = n_rows;
+	while (hi - lo > 1) {
+		const unsigned mid = (lo + hi) >> 1;
+		if (desc[mid].job0 <= job) lo = mid; else hi = mid;
+	}
+	return lo;
+}
+
+/* block j of the row's feed, n frames, into s_w: a pending frame, or one of the fed row */
+__device__ __forceinline__ void flac_stage(const FlacParams &P, const FlacRow &d, const unsigned row, const unsigned j, const unsigned n,
+		uint32_t *s_w) {
+	const char *xrow = (const char *)P.rows + P.row_pitch * row;
+	const int16_t *pend = P.pend + P.pend_pitch * row;
+	const unsigned long long first = (unsigned long long)j * P.B; /* counted from the row's frame block0 * B */
+	for (unsigned i = threadIdx.x; i < n; i += blockDim.x) {
+		const unsigned long long rel = first + i;
+		uint32_t w;
+		if (P.channels == 2) /* (rows and pitches are multiples of 16: a frame is an aligned word, L in its low half) */
+			w = rel < d.pend ? ((const uint32_t *)pend)[rel] : ((const uint32_t *)xrow)[rel - d.pend];
+		else
+			w = flac_pack(rel < d.pend ? pend[rel] : ((const int16_t *)xrow)[rel - d.pend], 0);
+		s_w[flac_ix(i)] = w;
+	}
+}
+
+__device__ __forceinline__ int32_t flac_at(const uint32_t *s_w, const unsigned c, const int i) { return i >= 0 ? flac_cand(s_w[flac_ix((unsigned)i)], c) : 0; }
+
+__device__ __forceinline__ unsigned long long flac_wave_sum(unsigned long long v, const int steps) {
+	for (int m = 1; m < (1 << steps); m <<= 1) v += __shfl_xor(v, m);
+	return v;
+}
+
+__global__ __launch_bounds__(256) void flac_analyze_kernel(const FlacParams P) {
+	extern __shared__ uint32_t flac_lds[];
+	__shared__ uint64_t s_fine[4][FLAC_FINE * FLAC_NK];
+	__shared__ uint64_t s_node_cost[4][32];
+	__shared__ uint8_t s_node_k[4][32];
+	__shared__ FlacSub s_cand[4];
+	uint32_t *s_w = flac_lds;
+	const unsigned job = blockIdx.x, row = flac_find_row(P.desc, P.n_rows, job);
+	const FlacRow d = P.desc[row];
+	const unsigned j = job - d.job0;
+	if (j >= d.n_blocks) return; /* (never: the jobs are the rows' blocks; uniform) */
+	const unsigned n = j == d.n_blocks - 1 ? d.last_n : P.B;
+	flac_stage(P, d, row, j, n, s_w);
+	__syncthreads();
+	const unsigned c = threadIdx.x >> 6, lane = threadIdx.x & 63; /* one wave per candidate */
+	/* constant? and the five orders' sums of |r_i|, i = 4 .. n-1 (a lane's share fits 32 bits: at most 64 values below 2^21) */
+	const int32_t s_first = flac_at(s_w, c, 0);
+	bool eq = true;
+	uint32_t a32[5] = {0, 0, 0, 0, 0};
+	for (unsigned i = lane; i < n; i += 64) {
+		const int32_t s0 = flac_at(s_w, c, (int)i);
+		eq = eq && s0 == s_first;
+		if (i >= 4) {
+			int32_t r[5];
+			flac_residuals(s0, flac_at(s_w, c, (int)i - 1), flac_at(s_w, c, (int)i - 2), flac_at(s_w, c, (int)i - 3), flac_at(s_w, c, (int)i - 4), r);
+#pragma unroll
+			for (int o = 0; o < 5; ++o) a32[o] += flac_abs(r[o]);
+		}
+	}
+	const bool equal = __all(eq ? 1 : 0) != 0;
+	uint64_t abs_sum[5];
+#pragma unroll
+	for (int o = 0; o < 5; ++o) abs_sum[o] = flac_wave_sum(a32[o], 6);
+	const unsigned o = flac_pick_order(n, abs_sum);
+	/* the sums of u >> k per finest partition: a whole block has sixteen, four lanes each, a lane a run of consecutive frames */
+	const unsigned fine_log2 = n == P.B ? 4 : 0;
+	uint32_t f32[FLAC_NK];
+#pragma unroll
+	for (unsigned k = 0; k < FLAC_NK; ++k) f32[k] = 0;
+	if (fine_log2) {
+		const unsigned run = n >> 6, i0 = lane * run; /* (lane >> 2 is the partition) */
+		int32_t s1 = flac_at(s_w, c, (int)i0 - 1), s2 = flac_at(s_w, c, (int)i0 - 2), s3 = flac_at(s_w, c, (int)i0 - 3), s4 = flac_at(s_w, c, (int)i0 - 4);
+		for (unsigned i = i0; i < i0 + run; ++i) {
+			const int32_t s0 = flac_at(s_w, c, (int)i);
+			if (i >= o) {
+				const uint32_t u = flac_zigzag(flac_residual(o, s0, s1, s2, s3, s4));
+#pragma unroll
+				for (unsigned k = 0; k < FLAC_NK; ++k) f32[k] += u >> k;
+			}
+			s4 = s3; s3 = s2; s2 = s1; s1 = s0;
+		}
+	} else {
+		for (unsigned i = lane; i < n; i += 64)
+			if (i >= o) {
+				const uint32_t u = flac_zigzag(flac_residual(o, flac_at(s_w, c, (int)i), flac_at(s_w, c, (int)i - 1), flac_at(s_w, c, (int)i - 2),
+						flac_at(s_w, c, (int)i - 3), flac_at(s_w, c, (int)i - 4)));
+#pragma unroll
+				for (unsigned k = 0; k < FLAC_NK; ++k) f32[k] += u >> k;
+			}
+	}
+#pragma unroll
+	for (unsigned k = 0; k < FLAC_NK; ++k) {
+		const unsigned long long s = flac_wave_sum(f32[k], fine_log2 ? 2 : 6);
+		if (fine_log2 ? (lane & 3) == 0 : lane == 0) s_fine[c][(fine_log2 ? lane >> 2 : 0) * FLAC_NK + k] = s;
+	}
+	__syncthreads();
+	/* one lane per (p, partition): the best k and its cost */
+	if (lane < (fine_log2 ? FLAC_NODES : 1u)) {
+		const unsigned p = 31 - __clz((int)(lane + 1)), part = lane + 1 - (1u << p);
+		unsigned k;
+		s_node_cost[c][lane] = flac_node_cost(s_fine[c], fine_log2, p, part, n, o, &k);
+		s_node_k[c][lane] = (uint8_t)k;
+	}
+	__syncthreads();
+	if (lane == 0) flac_finish_sub(&s_cand[c], c, n, equal, o, fine_log2, s_node_cost[c], s_node_k[c]);
+	__syncthreads();
+	if (threadIdx.x == 0) flac_finish_frame(&P.frames[job], s_cand, P.channels, n, P.B, (uint32_t)(d.block0 + j));
+}
+
+/* the exclusive sum of v over the 256 threads; s_scan[4] holds the waves' totals behind it */
+__device__ __forceinline__ uint32_t flac_block_excl(const uint32_t v, uint32_t *s_scan) {
+	const uint32_t incl = wave_incl_scan_dpp(v);
+	const unsigned wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+	__syncthreads(); /* (whoever still reads the totals of the call before) */
+	if (lane == 63) s_scan[wave] = incl;
+	__syncthreads();
+	uint32_t base = 0;
+	for (unsigned w = 0; w < wave; ++w) base += s_scan[w];
+	return base + incl - v;
+}
+
+__global__ __launch_bounds__(FLAC_THREADS) void flac_scan_kernel(const FlacParams P) {
+	__shared__ uint32_t s_scan[4], s_min, s_max;
+	const unsigned row = blockIdx.x, tid = threadIdx.x;
+	const FlacRow d = P.desc[row];
+	if (tid == 0) { s_min = 0xffffffffu; s_max = 0; }
+	uint32_t running = 0;
+	for (unsigned t0 = 0; t0 < d.n_blocks; t0 += FLAC_THREADS) { /* (uniform) */
+		const unsigned j = t0 + tid;
+		const uint32_t len = j < d.n_blocks ? P.frames[d.job0 + j].bytes : 0;
+		const uint32_t excl = flac_block_excl(len, s_scan);
+		if (j < d.n_blocks) {
+			P.frames[d.job0 + j].off = running + excl;
+			atomicMin(&s_min, len);
+			atomicMax(&s_max, len);
+		}
+		running += s_scan[0] + s_scan[1] + s_scan[2] + s_scan[3];
+	}
+	__syncthreads();
+	if (tid == 0) {
+		P.row_bytes[row] = running;
+		if (d.n_blocks) {
+			FlacStats st = P.stats[row];
+			st.bytes += running;
+			st.min_bytes = st.max_bytes ? (s_min < st.min_bytes ? s_min : st.min_bytes) : s_min;
+			st.max_bytes = s_max > st.max_bytes ? s_max : st.max_bytes;
+			P.stats[row] = st;
+		}
+	}
+}
+
+/* `bits` (1 .. 32) bits of v at bit `pos` of the frame, MSB first, into words that hold zeros there */
+__device__ __forceinline__ void flac_put(uint32_t *s_f, const uint32_t n_words, const uint32_t pos, const uint32_t bits, const uint32_t v) {
+	const uint32_t w = pos >> 5;
+	const unsigned long long x = (unsigned long long)v << (64 - (pos & 31) - bits);
+	const uint32_t hi = (uint32_t)(x >> 32), lo = (uint32_t)x;
+	if (hi && w < n_words) atomicOr(&s_f[w], hi);
+	if (lo && w + 1 < n_words) atomicOr(&s_f[w + 1], lo);
+}
+__device__ __forceinline__ uint32_t flac_byte(const uint32_t *s_f, const uint32_t b) { return (s_f[b >> 2] >> (24 - 8 * (b & 3))) & 0xffu; }
+
+__global__ __launch_bounds__(FLAC_THREADS) void flac_write_kernel(const FlacParams P) {
+	extern __shared__ uint32_t flac_lds[];
+	__shared__ uint32_t s_scan[4], s_crc;
+	__shared__ FlacFrameDesc s_fd; /* (in LDS: its fields are picked by index) */
+	__shared__ uint8_t s_head[16];
+	uint32_t *s_w = flac_lds, *s_f = flac_lds + P.B + (P.B >> 5);
+	const uint32_t n_words = flac_frame_bound(P.B, P.channels) / 4 + 2;
+	const unsigned tid = threadIdx.x, job = blockIdx.x, row = flac_find_row(P.desc, P.n_rows, job);
+	const FlacRow d = P.desc[row];
+	const unsigned j = job - d.job0;
+	if (j >= d.n_blocks) return; /* (never; uniform) */
+	const unsigned n = j == d.n_blocks - 1 ? d.last_n : P.B;
+	if (tid < sizeof(FlacFrameDesc) / 4) ((uint32_t *)&s_fd)[tid] = ((const uint32_t *)&P.frames[job])[tid];
+	__syncthreads();
+	const FlacFrameDesc &fd = s_fd;
+	const uint32_t number = (uint32_t)(d.block0 + j);
+	const uint32_t head = flac_header_len(n, P.B, number);
+	if (fd.n != n || fd.bytes > flac_frame_bound(n, P.channels) || fd.bytes < head + 2 || fd.n_sub > 2) return; /* (never: the record is this block's; uniform) */
+	flac_stage(P, d, row, j, n, s_w);
+	for (unsigned i = tid; i < n_words; i += FLAC_THREADS) s_f[i] = 0;
+	if (tid == 0) s_crc = 0;
+	__syncthreads();
+	if (tid == 0) {
+		const uint32_t hl = flac_frame_header(n, P.B, fd.assign, number, s_head);
+		for (uint32_t i = 0; i < hl; ++i) flac_put(s_f, n_words, 8 * i, 8, s_head[i]);
+	}
+	const unsigned log2B = 31 - __clz((int)P.B);
+	uint32_t pos = 8 * head;
+	for (unsigned si = 0; si < fd.n_sub; ++si) { /* (everything that branches here is the same for the whole workgroup) */
+		const FlacSub &s = fd.sub[si];
+		const unsigned c = s.cand, bps = flac_cand_bps(c);
+		const uint32_t mask = bps == 17 ? 0x1ffffu : 0xffffu;
+		if (tid == 0) flac_put(s_f, n_words, pos, 8, s.type == FLAC_CONSTANT ? 0u : s.type == FLAC_VERBATIM ? 2u : (uint32_t)(0x10u | (s.order << 1)));
+		if (s.type == FLAC_CONSTANT) {
+			if (tid == 0) flac_put(s_f, n_words, pos + 8, bps, (uint32_t)flac_at(s_w, c, 0) & mask);
+		} else if (s.type == FLAC_VERBATIM) {
+			for (unsigned i = tid; i < n; i += FLAC_THREADS) flac_put(s_f, n_words, pos + 8 + bps * i, bps, (uint32_t)flac_at(s_w, c, (int)i) & mask);
+		} else {
+			const unsigned o = s.order, p = s.p;
+			if (tid < o) flac_put(s_f, n_words, pos + 8 + bps * tid, bps, (uint32_t)flac_at(s_w, c, (int)tid) & mask);
+			const uint32_t at_res = pos + 8 + bps * o;
+			if (tid == 0) flac_put(s_f, n_words, at_res, 6, p); /* 00 pppp */
+			/* a thread's run of consecutive frames; partition of frame i: i >> (log2 B - p) -- p > 0 only in a whole block */
+			const unsigned run = (n + FLAC_THREADS - 1) / FLAC_THREADS, i0 = tid * run, i1 = i0 + run < n ? i0 + run : n;
+			const unsigned psh = p ? log2B - p : 31, pmask = p ? (1u << psh) - 1 : 0xffffffffu;
+			uint32_t len = 0;
+			for (unsigned i = i0 > o ? i0 : o; i < i1; ++i) {
+				const unsigned k = s.k[i >> psh];
+				const uint32_t u = flac_zigzag(flac_residual(o, flac_at(s_w, c, (int)i), flac_at(s_w, c, (int)i - 1), flac_at(s_w, c, (int)i - 2),
+						flac_at(s_w, c, (int)i - 3), flac_at(s_w, c, (int)i - 4)));
+				len += (u >> k) + 1 + k + ((i & pmask) == 0 || i == o ? 4 : 0);
+			}
+			uint32_t b = at_res + 6 + flac_block_excl(len, s_scan);
+			for (unsigned i = i0 > o ? i0 : o; i < i1; ++i) {
+				const unsigned k = s.k[i >> psh];
+				const uint32_t u = flac_zigzag(flac_residual(o, flac_at(s_w, c, (int)i), flac_at(s_w, c, (int)i - 1), flac_at(s_w, c, (int)i - 2),
+						flac_at(s_w, c, (int)i - 3), flac_at(s_w, c, (int)i - 4)));
+				if ((i & pmask) == 0 || i == o) { flac_put(s_f, n_words, b, 4, k); b += 4; }
+				b += u >> k;
+				flac_put(s_f, n_words, b, k + 1, (1u << k) | (u & ((1u << k) - 1)));
+				b += k + 1;
+			}
+		}
+		pos += s.bits;
+	}
+	__syncthreads();
+	const uint32_t body = fd.bytes - 2; /* (pos + 7) / 8 by the analysis' count */
+	{ /* CRC-16: a run of bytes per thread, advanced over what follows it, all XORed */
+		const uint32_t run = (body + FLAC_THREADS - 1) / FLAC_THREADS, b0 = tid * run, b1 = b0 + run < body ? b0 + run : body;
+		uint32_t crc = 0;
+		for (uint32_t b = b0; b < b1; ++b) crc = flac_crc16_update(crc, flac_byte(s_f, b));
+		crc = b0 < body ? flac_crc16_advance(crc, body - b1) : 0;
+		for (int m = 1; m < 64; m <<= 1) crc ^= __shfl_xor(crc, m);
+		if ((tid & 63) == 0) atomicXor(&s_crc, crc);
+	}
+	__syncthreads();
+	uint8_t *dst = P.out + d.out_off + fd.off;
+	for (uint32_t b = tid; b < body; b += FLAC_THREADS) dst[b] = (uint8_t)flac_byte(s_f, b);
+	if (tid == 0) { dst[body] = (uint8_t)(s_crc >> 8); dst[body + 1] = (uint8_t)s_crc; }
+}
+
+__global__ __launch_bounds__(FLAC_THREADS) void flac_carry_kernel(const FlacParams P) {
+	const unsigned e = blockIdx.x * FLAC_THREADS + threadIdx.x, row = blockIdx.y, ch = P.channels;
+	const FlacRow d = P.desc[row];
+	if (e >= d.pend_next * ch) return;
+	const int16_t *xrow = (const int16_t *)((const char *)P.rows + P.row_pitch * row);
+	const int16_t *pend = P.pend + P.pend_pitch * row;
+	const unsigned long long at = (unsigned long long)d.n_blocks * P.B * ch + e; /* counted from the row's frame block0 * B, in samples */
+	P.pend_next[P.pend_pitch * row + e] = at < (unsigned long long)d.pend * ch ? pend[at] : xrow[at - (unsigned long long)d.pend * ch];
+}
+
+#endif

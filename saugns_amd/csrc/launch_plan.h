@@ -964,5 +964,84 @@ inline SpectrumPlan plan_spectrum(unsigned log2n, uint32_t hop, uint32_t channel
 	return p;
 }
 
+/* ---- the FLAC encoder (k_flac.h) ----
+ * A feed of one row: the row stood at `pos` frames and takes `frames` more. Block k covers the frames [k B, k B + B); the feed
+ * completes the blocks [pos / B, (pos + frames) / B), and with `finish` the frames behind the last complete block, if there
+ * are any, as one more short block. Of what a block covers, the frames below pos are the row's pending frames -- the pos mod B
+ * frames from (pos / B) B on -- and the rest lie in the fed row. The feed's blocks of all rows are numbered through as jobs, row
+ * after row: one workgroup of flac_analyze_kernel and of flac_write_kernel per job (they find their row by bisection of job0),
+ * one of flac_scan_kernel per row. A row's frames of one feed lie back to back from out_off on in the feed's output, which has
+ * room for every block at its bound: flac_frame_bound. All of it is a function of (pos, frames, B, finish): the bytes never
+ * depend on how a sequence was cut into feeds, on the grid or on the device. */
+constexpr uint32_t FLAC_THREADS = 256;               /* flac_write_kernel, flac_scan_kernel, flac_carry_kernel */
+constexpr uint64_t FLAC_MAX_JOBS = 1ull << 24;       /* blocks of one feed: a longer feed is made in pieces */
+struct FlacRow { /* (what the kernels read of a row's feed: uploaded as it stands) */
+	uint64_t block0;      /* pos / B: the first block this feed completes */
+	uint32_t n_blocks;    /* how many it completes */
+	uint32_t last_n;      /* frames of the last of them: B, or fewer for the short block of a finish */
+	uint32_t pend;        /* pending frames ahead of the feed: pos - block0 * B */
+	uint32_t pend_next;   /* ... and behind it (0 behind a finish) */
+	uint32_t job0;        /* the blocks of the rows before this one (plan_flac) */
+	uint32_t out_off;     /* where the row's frames begin in the feed's output (plan_flac); a multiple of 16 */
+};
+static_assert(sizeof(FlacRow) == 32, "FlacRow is uploaded as it stands");
+inline FlacRow plan_flac_row(uint64_t pos, uint32_t frames, uint32_t B, bool finish) {
+	FlacRow r;
+	const uint64_t end = pos + frames, b0 = pos / B, full = end / B;
+	const uint32_t rem = (uint32_t)(end - full * B);
+	const bool tail = finish && rem;
+	r.block0 = b0;
+	r.n_blocks = (uint32_t)(full - b0) + (tail ? 1 : 0);
+	r.last_n = tail ? rem : B;
+	r.pend = (uint32_t)(pos - b0 * B);
+	r.pend_next = finish ? 0 : rem;
+	r.job0 = 0; r.out_off = 0;
+	return r;
+}
+/* the worst case of a row's feed (include/saugns_amd.h, FLAC: the bound of every block it completes, summed) */
+inline uint64_t flac_row_worst(const FlacRow &r, uint32_t B, uint32_t channels) {
+	if (!r.n_blocks) return 0;
+	return (uint64_t)(r.n_blocks - 1) * sauflac::flac_frame_bound(B, channels) + sauflac::flac_frame_bound(r.last_n, channels);
+}
+struct FlacPlan {
+	bool ok = false;           /* false: B or channels not allowed, no row or more than 65535, a block number beyond 2^31 - 1, a feed
+	                            * with more than FLAC_MAX_JOBS blocks or a worst case above FLAC_MAX_UNREAD */
+	uint32_t B = 0, rows = 0, channels = 0;
+	uint32_t jobs = 0;         /* grid.x of flac_analyze_kernel and flac_write_kernel (0: no launch) */
+	uint32_t analyze_threads = 0; /* one wave per candidate channel: 64 mono; 256 stereo (L, R, M, S) */
+	size_t analyze_lds = 0;    /* the block's frames as words, one more per 32 (k_flac.h: flac_ix) */
+	size_t write_lds = 0;      /* ... and the frame under construction: its bound, in words, and two more */
+	size_t pend_pitch = 0;     /* int16 between the rows' pending frames: B * channels */
+	uint64_t worst = 0;        /* the feed's worst case: what the 1 GiB rule counts */
+	size_t out_bytes = 0;      /* the feed's output: every row's worst case, each rounded up to 16 */
+};
+/* rows: the feed's records (NULL: none, the encoder's own sizes only); job0 and out_off are filled in */
+inline FlacPlan plan_flac(uint32_t block_frames, uint32_t channels, size_t n_rows, FlacRow *rows) {
+	FlacPlan p;
+	const uint32_t B = sauflac::flac_block_frames(block_frames);
+	if (!B || (channels != 1 && channels != 2) || !n_rows || n_rows > sauflac::FLAC_MAX_ROWS) return p;
+	p.B = B; p.rows = (uint32_t)n_rows; p.channels = channels;
+	p.analyze_threads = channels == 2 ? 256 : 64;
+	p.analyze_lds = (size_t)(B + B / 32) * sizeof(uint32_t);
+	p.write_lds = p.analyze_lds + ((size_t)sauflac::flac_frame_bound(B, channels) / 4 + 2) * sizeof(uint32_t);
+	p.pend_pitch = (size_t)B * channels;
+	uint64_t jobs = 0, out = 0;
+	for (size_t r = 0; rows && r < n_rows; ++r) {
+		if (rows[r].block0 + rows[r].n_blocks > sauflac::FLAC_MAX_BLOCKS) return p;
+		if (jobs > FLAC_MAX_JOBS || out > sauflac::FLAC_MAX_UNREAD) return p;
+		rows[r].job0 = (uint32_t)jobs;
+		rows[r].out_off = (uint32_t)out;
+		jobs += rows[r].n_blocks;
+		const uint64_t w = flac_row_worst(rows[r], B, channels);
+		p.worst += w;
+		out += (w + 15) & ~15ull;
+	}
+	if (jobs > FLAC_MAX_JOBS || p.worst > sauflac::FLAC_MAX_UNREAD) return p;
+	p.jobs = (uint32_t)jobs;
+	p.out_bytes = (size_t)out;
+	p.ok = true;
+	return p;
+}
+
 } /* namespace sauplan */
 #endif

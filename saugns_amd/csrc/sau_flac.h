@@ -1,0 +1,220 @@
+/* sau_flac.h -- the FLAC encoder's arithmetic (include/saugns_amd.h, section "FLAC"), shared by the host restatement
+ * (tables.cpp: flac_encode_block) and the kernels (k_flac.h) the way sau_dev_math.h is: candidate samples, residuals, the
+ * zigzag, the cost of a Rice partition, the choice of order, of partitions and of the channel assignment, the frame header and
+ * the two CRCs. Everything is integer arithmetic, so host and device agree by construction; what differs between them is only
+ * who walks the samples. */
+#ifndef SAU_FLAC_H
+#define SAU_FLAC_H
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define SAU_FLAC_HD __host__ __device__ inline
+#else
+#define SAU_FLAC_HD static inline
+#endif
+
+namespace sauflac {
+
+constexpr uint32_t FLAC_MAX_ROWS = 65535;
+constexpr uint64_t FLAC_MAX_BLOCKS = 0x7fffffffull;  /* per row: the frame number's six bytes hold 31 bits */
+constexpr uint64_t FLAC_MAX_UNREAD = 1ull << 30;     /* bytes of unread output on the device */
+constexpr unsigned FLAC_K_MAX = 14, FLAC_NK = 15;    /* Rice parameters 0 .. 14; 15 is the escape, never used */
+constexpr unsigned FLAC_FINE = 16, FLAC_NODES = 31;  /* finest partitions of a whole block; (p, partition) pairs for p = 0 .. 4 */
+enum : uint8_t { FLAC_CONSTANT = 0, FLAC_VERBATIM = 1, FLAC_FIXED = 2 };
+enum : uint8_t { FLAC_CAND_L = 0, FLAC_CAND_R = 1, FLAC_CAND_M = 2, FLAC_CAND_S = 3 };
+
+/* 0 stands for 4096; 0 when the size is not allowed */
+SAU_FLAC_HD uint32_t flac_block_frames(uint32_t b) {
+	if (b == 0) return 4096;
+	return (b == 256 || b == 512 || b == 1024 || b == 2048 || b == 4096) ? b : 0;
+}
+/* the most bytes a frame of n frames takes: 13 header bytes, every channel verbatim, the CRC-16 */
+SAU_FLAC_HD uint32_t flac_frame_bound(uint32_t n, uint32_t channels) { return 15 + channels * (1 + 2 * n); }
+
+/* What a block's choices come to for one channel: kind, order, partition order and the partitions' Rice parameters. */
+struct FlacSub {
+	uint8_t cand;     /* FLAC_CAND_* */
+	uint8_t type;     /* FLAC_CONSTANT, _VERBATIM, _FIXED */
+	uint8_t order;    /* FIXED: 0 .. 4 */
+	uint8_t p;        /* FIXED: partition order, 0 .. 4 */
+	uint8_t k[FLAC_FINE]; /* FIXED: partition j's parameter, j < 2^p */
+	uint32_t bits;    /* the whole subframe */
+};
+static_assert(sizeof(FlacSub) == 24, "FlacSub is read by the kernels as it stands");
+struct FlacFrameDesc {
+	uint32_t n;       /* frames in the block */
+	uint32_t bytes;   /* of the whole frame, CRC-16 included */
+	uint32_t off;     /* where it begins in its row's part of the feed's output (flac_scan_kernel) */
+	uint8_t assign;   /* the channel assignment's four bits */
+	uint8_t n_sub;
+	uint8_t pad_[2];
+	FlacSub sub[2];
+};
+static_assert(sizeof(FlacFrameDesc) == 64, "FlacFrameDesc is read by the kernels as it stands");
+
+/* a frame as one word: the left (or only) sample in the low half, the right one in the high half */
+SAU_FLAC_HD uint32_t flac_pack(int16_t l, int16_t r) { return (uint32_t)(uint16_t)l | ((uint32_t)(uint16_t)r << 16); }
+SAU_FLAC_HD int32_t flac_cand(uint32_t w, unsigned cand) {
+	const int32_t l = (int16_t)(uint16_t)(w & 0xffffu), r = (int16_t)(uint16_t)(w >> 16);
+	switch (cand) {
+	case FLAC_CAND_L: return l;
+	case FLAC_CAND_R: return r;
+	case FLAC_CAND_M: return (l + r) >> 1; /* (arithmetic) */
+	default: return l - r;
+	}
+}
+SAU_FLAC_HD unsigned flac_cand_bps(unsigned cand) { return cand == FLAC_CAND_S ? 17 : 16; }
+
+/* the residuals of all five orders from s_i .. s_{i-4} */
+SAU_FLAC_HD void flac_residuals(int32_t s0, int32_t s1, int32_t s2, int32_t s3, int32_t s4, int32_t r[5]) {
+	r[0] = s0;
+	r[1] = s0 - s1;
+	r[2] = s0 - 2 * s1 + s2;
+	r[3] = s0 - 3 * s1 + 3 * s2 - s3;
+	r[4] = s0 - 4 * s1 + 6 * s2 - 4 * s3 + s4;
+}
+SAU_FLAC_HD int32_t flac_residual(unsigned o, int32_t s0, int32_t s1, int32_t s2, int32_t s3, int32_t s4) {
+	switch (o) {
+	case 0: return s0;
+	case 1: return s0 - s1;
+	case 2: return s0 - 2 * s1 + s2;
+	case 3: return s0 - 3 * s1 + 3 * s2 - s3;
+	default: return s0 - 4 * s1 + 6 * s2 - 4 * s3 + s4;
+	}
+}
+SAU_FLAC_HD uint32_t flac_zigzag(int32_t r) { return r >= 0 ? 2u * (uint32_t)r : 2u * (uint32_t)(-(r + 1)) + 1u; }
+SAU_FLAC_HD uint32_t flac_abs(int32_t r) { return r >= 0 ? (uint32_t)r : (uint32_t)(-(r + 1)) + 1u; }
+
+/* the order with the least sum of |r_i| over i = 4 .. n-1, the lowest on ties; 0 for n <= 4 */
+SAU_FLAC_HD unsigned flac_pick_order(uint32_t n, const uint64_t abs_sum[5]) {
+	if (n <= 4) return 0;
+	unsigned best = 0;
+	uint64_t least = abs_sum[0];
+	for (unsigned o = 1; o < 5; ++o)
+		if (abs_sum[o] < least) { least = abs_sum[o]; best = o; }
+	return best;
+}
+
+/* node (p, part) of a block of n frames whose finest sums are fine[f * 15 + k] = the sum of u >> k over fine partition f
+ * (f < 2^fine_log2; fine_log2 = 4 for a whole block, 0 otherwise): the least cost over k, the lowest k on ties */
+SAU_FLAC_HD uint64_t flac_node_cost(const uint64_t *fine, unsigned fine_log2, unsigned p, unsigned part, uint32_t n, unsigned o, unsigned *k_out) {
+	const unsigned span = 1u << (fine_log2 - p), first = part * span;
+	const uint64_t count = (n >> p) - (part == 0 ? o : 0);
+	uint64_t best = ~0ull;
+	unsigned bk = 0;
+	for (unsigned k = 0; k < FLAC_NK; ++k) {
+		uint64_t s = 0;
+		for (unsigned f = 0; f < span; ++f) s += fine[(first + f) * FLAC_NK + k];
+		const uint64_t cost = s + (1 + k) * count;
+		if (cost < best) { best = cost; bk = k; }
+	}
+	*k_out = bk;
+	return best;
+}
+SAU_FLAC_HD unsigned flac_node_index(unsigned p, unsigned part) { return (1u << p) - 1 + part; }
+
+/* From the nodes' costs and parameters (those of p = 0 .. fine_log2) to the channel's record: the partition order with the
+ * least cost (the lowest on ties), FIXED against VERBATIM (VERBATIM on ties). all_equal: CONSTANT whatever the rest. */
+SAU_FLAC_HD void flac_finish_sub(FlacSub *s, unsigned cand, uint32_t n, bool all_equal, unsigned o, unsigned fine_log2,
+		const uint64_t *node_cost, const uint8_t *node_k) {
+	const unsigned bps = flac_cand_bps(cand);
+	s->cand = (uint8_t)cand; s->order = 0; s->p = 0;
+	for (unsigned j = 0; j < FLAC_FINE; ++j) s->k[j] = 0;
+	if (all_equal) { s->type = FLAC_CONSTANT; s->bits = 8 + bps; return; }
+	uint64_t best = ~0ull;
+	unsigned bp = 0;
+	for (unsigned p = 0; p <= fine_log2; ++p) {
+		uint64_t c = 0;
+		for (unsigned j = 0; j < (1u << p); ++j) c += 4 + node_cost[flac_node_index(p, j)];
+		if (c < best) { best = c; bp = p; }
+	}
+	const uint64_t fixed = 8 + (uint64_t)bps * o + 6 + best, verbatim = 8 + (uint64_t)bps * n;
+	if (verbatim <= fixed) { s->type = FLAC_VERBATIM; s->bits = (uint32_t)verbatim; return; }
+	s->type = FLAC_FIXED; s->order = (uint8_t)o; s->p = (uint8_t)bp; s->bits = (uint32_t)fixed;
+	for (unsigned j = 0; j < (1u << bp); ++j) s->k[j] = node_k[flac_node_index(bp, j)];
+}
+
+/* the bytes of a frame number in the extended UTF-8 coding, and of a frame header: sync and codes, the number, n - 1 where
+ * the block is not a whole one, the CRC-8 */
+SAU_FLAC_HD uint32_t flac_utf8_len(uint32_t v) {
+	return v < 0x80u ? 1 : v < 0x800u ? 2 : v < 0x10000u ? 3 : v < 0x200000u ? 4 : v < 0x4000000u ? 5 : 6;
+}
+SAU_FLAC_HD uint32_t flac_header_len(uint32_t n, uint32_t block_frames, uint32_t number) {
+	return 4 + flac_utf8_len(number) + (n != block_frames ? 2 : 0) + 1;
+}
+/* the frame's record from the candidates' (mono: cand[0] alone; stereo: L, R, M, S): the pair with the fewest bits among
+ * L+R, L+S, S+R, M+S, the first on ties; then the frame's size */
+SAU_FLAC_HD void flac_finish_frame(FlacFrameDesc *d, const FlacSub *cand, uint32_t channels, uint32_t n, uint32_t block_frames, uint32_t number) {
+	d->n = n; d->off = 0; d->pad_[0] = d->pad_[1] = 0;
+	if (channels == 1) {
+		d->assign = 0; d->n_sub = 1; d->sub[0] = cand[0]; d->sub[1] = cand[0];
+	} else {
+		const uint64_t l = cand[FLAC_CAND_L].bits, r = cand[FLAC_CAND_R].bits, m = cand[FLAC_CAND_M].bits, s = cand[FLAC_CAND_S].bits;
+		uint64_t least = l + r;
+		unsigned first = FLAC_CAND_L, second = FLAC_CAND_R;
+		d->assign = 1;
+		if (l + s < least) { least = l + s; d->assign = 8; first = FLAC_CAND_L; second = FLAC_CAND_S; }
+		if (s + r < least) { least = s + r; d->assign = 9; first = FLAC_CAND_S; second = FLAC_CAND_R; }
+		if (m + s < least) { least = m + s; d->assign = 10; first = FLAC_CAND_M; second = FLAC_CAND_S; }
+		d->n_sub = 2; d->sub[0] = cand[first]; d->sub[1] = cand[second];
+	}
+	uint64_t bits = 8ull * flac_header_len(n, block_frames, number);
+	for (unsigned i = 0; i < d->n_sub; ++i) bits += d->sub[i].bits;
+	d->bytes = (uint32_t)((bits + 7) / 8) + 2;
+}
+
+/* ---- CRCs: MSB first, initial value 0, not reflected ---- */
+SAU_FLAC_HD uint32_t flac_crc8_update(uint32_t crc, uint32_t byte) {
+	crc ^= byte & 0xffu;
+	for (int i = 0; i < 8; ++i) crc = (crc & 0x80u) ? ((crc << 1) ^ 0x07u) & 0xffu : (crc << 1) & 0xffu;
+	return crc;
+}
+SAU_FLAC_HD uint32_t flac_crc16_update(uint32_t crc, uint32_t byte) {
+	crc ^= (byte & 0xffu) << 8;
+	for (int i = 0; i < 8; ++i) crc = (crc & 0x8000u) ? ((crc << 1) ^ 0x8005u) & 0xffffu : (crc << 1) & 0xffffu;
+	return crc;
+}
+/* a * b in GF(2)[x] modulo x^16 + x^15 + x^2 + 1 */
+SAU_FLAC_HD uint32_t flac_gf16_mul(uint32_t a, uint32_t b) {
+	uint32_t r = 0;
+	for (int i = 15; i >= 0; --i) {
+		r = (r & 0x8000u) ? ((r << 1) ^ 0x8005u) & 0xffffu : (r << 1) & 0xffffu;
+		if ((b >> i) & 1u) r ^= a;
+	}
+	return r;
+}
+/* the CRC-16 of A followed by `bytes` zero bytes, from crc(A): crc * x^(8 bytes). With initial value 0 the CRC is linear, so
+ * crc(A || B) = flac_crc16_advance(crc(A), |B|) ^ crc(B) */
+SAU_FLAC_HD uint32_t flac_crc16_advance(uint32_t crc, uint32_t bytes) {
+	uint32_t sq = 0x0100u; /* x^8 */
+	for (; bytes; bytes >>= 1) {
+		if (bytes & 1u) crc = flac_gf16_mul(crc, sq);
+		sq = flac_gf16_mul(sq, sq);
+	}
+	return crc;
+}
+
+/* the frame header, CRC-8 included -> its length (at most 13). assign: the channel assignment's four bits. */
+SAU_FLAC_HD uint32_t flac_frame_header(uint32_t n, uint32_t block_frames, uint32_t assign, uint32_t number, uint8_t *out /* [16] */) {
+	uint32_t len = 0;
+	out[len++] = 0xff; out[len++] = 0xf8;
+	uint32_t code = 7;
+	if (n == block_frames) { code = 8; for (uint32_t b = 256; b < block_frames; b <<= 1) ++code; }
+	out[len++] = (uint8_t)(code << 4);
+	out[len++] = (uint8_t)((assign << 4) | (4u << 1));
+	const uint32_t ul = flac_utf8_len(number);
+	if (ul == 1) out[len++] = (uint8_t)number;
+	else {
+		out[len++] = (uint8_t)((0xff00u >> ul) | (number >> (6 * (ul - 1)))); /* ul ones, a zero, the top bits */
+		for (uint32_t i = ul - 1; i-- > 0;) out[len++] = (uint8_t)(0x80u | ((number >> (6 * i)) & 0x3fu));
+	}
+	if (n != block_frames) { out[len++] = (uint8_t)((n - 1) >> 8); out[len++] = (uint8_t)(n - 1); }
+	uint32_t crc = 0;
+	for (uint32_t i = 0; i < len; ++i) crc = flac_crc8_update(crc, out[i]);
+	out[len++] = (uint8_t)crc;
+	return len;
+}
+
+} /* namespace sauflac */
+#endif

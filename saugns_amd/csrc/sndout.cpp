@@ -503,6 +503,81 @@ bool measure_spectrum(const sauProgram *prg, uint32_t srate, int factor, int cha
 	return ok;
 }
 
+/* The FLAC writer: render_file_over's int16 runs (no byte swap) on the same lattice, each run's device row fed to an encoder
+ * of one stream where that writer fetches it, the last feed a finish. A read brings the run's frames into a page-locked slot;
+ * the slot before it goes to the file once the next run has been queued, so the file is written while the device renders.
+ * The encoder goes before the engine, which owns the backend. */
+bool write_flac(const sauProgram *prg, uint32_t srate, const char *path, int channels, uint32_t block_frames,
+		Backend *backend /* owned */, uint64_t *frames_out, sauengine::FlacInfo *info_out, std::string &err) {
+	Engine *engine = Engine::create(&prg, 1, srate, backend, err);
+	if (!engine) return false;
+	const bool stereo = channels == 2;
+	const uint32_t B = sauflac::flac_block_frames(block_frames);
+	size_t call, chunk;
+	file_lattice(srate, call, chunk);
+	engine->set_call_len(call);
+	/* a backend without an encoder says so here, before there is a file */
+	sauengine::FlacEncoder *enc = backend->create_flac(1, (uint32_t)channels, B, err);
+	if (!enc) { delete engine; return false; }
+	/* what a run can come to: the blocks it completes, with what was pending, and a last short one, each at its bound */
+	const size_t slot_bytes = (chunk / B + 2) * (size_t)sauflac::flac_frame_bound(B, (uint32_t)channels);
+	uint8_t *host[2] = {(uint8_t *)backend->alloc_host(slot_bytes), (uint8_t *)backend->alloc_host(slot_bytes)};
+	FILE *f = nullptr;
+	bool ok = host[0] && host[1];
+	if (!ok) err = "out of page-locked memory";
+	uint8_t head[42];
+	sauengine::FlacInfo info{0, 0, 0, 0, 0};
+	if (ok) {
+		f = fopen(path, "wb");
+		if (!f) { err = std::string("couldn't open \"") + path + "\" for writing"; ok = false; }
+		else if (sauengine::flac_header(srate, channels, B, &info, head, sizeof head) != 42 || fwrite(head, 1, 42, f) != 42) { err = "write failed"; ok = false; }
+	}
+	size_t pending[2] = {0, 0};
+	int slot = 0;
+	bool more = ok;
+	while (ok && more) {
+		size_t len = 0;
+		ok = engine->run(nullptr, chunk, stereo, &more, &len, err);
+		if (!ok) break;
+		const uint32_t n = (uint32_t)len;
+		const int16_t *row = backend->device_pcm(0);
+		if (!row) { err = "the backend keeps no int16 rows on the device"; ok = false; break; }
+		ok = enc->feed(row, backend->device_pcm_pitch(), &n, !more, err);
+		/* while this run renders and is encoded, the one before goes to the file */
+		const int other = slot ^ 1;
+		if (ok && pending[other]) {
+			if (fwrite(host[other], 1, pending[other], f) != pending[other]) { err = "write failed"; ok = false; }
+			pending[other] = 0;
+		}
+		if (ok) {
+			uint8_t *const bufs[1] = {host[slot]};
+			size_t got = 0;
+			ok = enc->read(bufs, &slot_bytes, &got, &info, false, err);
+			pending[slot] = got;
+		}
+		slot = other;
+	}
+	for (int s = 0; ok && s < 2; ++s) { /* oldest first: `slot` is the older of the two */
+		const int k = slot ^ s;
+		if (pending[k] && fwrite(host[k], 1, pending[k], f) != pending[k]) { err = "write failed"; ok = false; }
+		pending[k] = 0;
+	}
+	delete enc;
+	{ std::string e2; (void)backend->sync(e2); }
+	if (f) {
+		if (ok && (sauengine::flac_header(srate, channels, B, &info, head, sizeof head) != 42 || fseek(f, 0, SEEK_SET) != 0 ||
+		           fwrite(head, 1, 42, f) != 42)) { err = "write failed"; ok = false; }
+		const int ferr = ferror(f);
+		if ((fclose(f) != 0 || ferr) && ok) { err = "write failed"; ok = false; }
+	}
+	if (frames_out) *frames_out = info.frames;
+	if (ok && info_out) *info_out = info;
+	backend->free_host(host[0]);
+	backend->free_host(host[1]);
+	delete engine; /* owns the backend */
+	return ok;
+}
+
 } /* namespace */
 
 bool sauamd_internal::render_file_normalized(const sauProgram *prg, uint32_t srate, const char *path, int format, int channels,
@@ -689,6 +764,32 @@ extern "C" bool sauAmd_render_spectrum(const sauProgram *prg, uint32_t srate, in
 	try {
 		ok = sauamd_internal::render_spectrum(prg, srate, factor, channels, log2n, hop,
 				[](std::string &e) -> Backend * { return sauhip::create_hip_backend(e); }, power_out, segments_out, frames_out, err);
+	} catch (const std::exception &ex) { /* (nothing C++ crosses the C ABI) */
+		err = std::string("internal error: ") + ex.what();
+	}
+	if (!ok) sauamd_internal::set_last_error("output", err);
+	return ok;
+}
+
+bool sauamd_internal::render_file_flac(const sauProgram *prg, uint32_t srate, const char *path, int channels, uint32_t block_frames,
+		const std::function<Backend *(std::string &)> &make_backend, uint64_t *frames_out, sauAmdFlacInfo *info_out, std::string &err) {
+	if (frames_out) *frames_out = 0;
+	if (!prg || !path || !srate || srate > 655350u || !sauengine::flac_params_ok(channels, block_frames)) {
+		err = "bad argument";
+		return false;
+	}
+	Backend *backend = make_backend(err);
+	if (!backend) return false;
+	return write_flac(prg, srate, path, channels, block_frames, backend, frames_out, (sauengine::FlacInfo *)info_out, err);
+}
+
+extern "C" bool sauAmd_render_file_flac(const sauProgram *prg, uint32_t srate, const char *path, int channels, uint32_t block_frames,
+		uint64_t *frames_out, sauAmdFlacInfo *info_out) {
+	std::string err;
+	bool ok = false;
+	try {
+		ok = sauamd_internal::render_file_flac(prg, srate, path, channels, block_frames,
+				[](std::string &e) -> Backend * { return sauhip::create_hip_backend(e); }, frames_out, info_out, err);
 	} catch (const std::exception &ex) { /* (nothing C++ crosses the C ABI) */
 		err = std::string("internal error: ") + ex.what();
 	}

@@ -402,4 +402,114 @@ void truepeak_tail(const float *hist, int channels, const double *taps, uint32_t
 			}
 }
 
+/* ---- the FLAC encoder on the host (engine.h; include/saugns_amd.h, section "FLAC") ----
+ * flac_encode_block restates in plain loops what flac_analyze_kernel and flac_write_kernel (k_flac.h) make of one block, with
+ * the arithmetic of sau_flac.h that they use too; flac_header is the 42 bytes ahead of the frames. */
+namespace {
+struct FlacBits { /* MSB first into bytes that start out cleared */
+	uint8_t *p;
+	size_t pos = 0;
+	void put(uint32_t v, unsigned bits) {
+		for (unsigned i = bits; i-- > 0; ++pos)
+			if ((v >> i) & 1u) p[pos >> 3] |= (uint8_t)(0x80u >> (pos & 7));
+	}
+	void zeros(size_t n) { pos += n; }
+};
+} /* namespace */
+
+size_t flac_header(uint32_t srate, int channels, uint32_t block_frames, const FlacInfo *info, uint8_t *out, size_t cap) {
+	using namespace sauflac;
+	const uint32_t B = flac_block_frames(block_frames);
+	if (!srate || srate > 655350u || (channels != 1 && channels != 2) || !B) return 0;
+	if (!out || cap < 42) return 42;
+	const uint64_t frames = info ? info->frames : 0;
+	const uint32_t mn = info ? info->min_frame_bytes : 0, mx = info ? info->max_frame_bytes : 0;
+	memset(out, 0, 42);
+	memcpy(out, "fLaC", 4);
+	out[4] = 0x80; out[5] = 0; out[6] = 0; out[7] = 34; /* last = 1, type 0, length 34 */
+	FlacBits w{out + 8};
+	w.put(B, 16); w.put(B, 16);
+	w.put(mn & 0xffffffu, 24); w.put(mx & 0xffffffu, 24);
+	w.put(srate, 20); w.put((uint32_t)channels - 1, 3); w.put(15, 5);
+	w.put((uint32_t)((frames >> 32) & 0xfu), 4); w.put((uint32_t)frames, 32);
+	/* (the MD5 stays zeros: not computed) */
+	return 42;
+}
+
+size_t flac_encode_block(const int16_t *x, uint32_t n, int channels, uint32_t block_frames, uint32_t frame_number, uint8_t *out, size_t cap) {
+	using namespace sauflac;
+	const uint32_t B = flac_block_frames(block_frames);
+	if (!x || !B || !n || n > B || (channels != 1 && channels != 2) || frame_number > FLAC_MAX_BLOCKS) return 0;
+	const unsigned ch = (unsigned)channels, n_cand = ch == 2 ? 4 : 1, fine_log2 = n == B ? 4 : 0, F = 1u << fine_log2;
+	uint32_t *w = new uint32_t[n];
+	for (uint32_t i = 0; i < n; ++i) w[i] = ch == 2 ? flac_pack(x[2 * i], x[2 * i + 1]) : flac_pack(x[i], 0);
+	auto at = [&](unsigned c, int64_t i) -> int32_t { return i >= 0 ? flac_cand(w[i], c) : 0; };
+	auto resid = [&](unsigned c, unsigned o, uint32_t i) { return flac_residual(o, at(c, i), at(c, (int64_t)i - 1), at(c, (int64_t)i - 2), at(c, (int64_t)i - 3), at(c, (int64_t)i - 4)); };
+	FlacSub cand[4];
+	for (unsigned c = 0; c < n_cand; ++c) {
+		bool equal = true;
+		for (uint32_t i = 1; i < n; ++i) equal = equal && at(c, i) == at(c, 0);
+		uint64_t abs_sum[5] = {0, 0, 0, 0, 0};
+		for (uint32_t i = 4; i < n; ++i) {
+			int32_t r[5];
+			flac_residuals(at(c, i), at(c, i - 1), at(c, i - 2), at(c, i - 3), at(c, i - 4), r);
+			for (int o = 0; o < 5; ++o) abs_sum[o] += flac_abs(r[o]);
+		}
+		const unsigned o = flac_pick_order(n, abs_sum);
+		uint64_t fine[FLAC_FINE * FLAC_NK];
+		memset(fine, 0, sizeof fine);
+		const uint32_t plen = n / F; /* (F == 1 unless n == B, a multiple of 16) */
+		for (uint32_t i = o; i < n; ++i) {
+			const uint32_t u = flac_zigzag(resid(c, o, i));
+			for (unsigned k = 0; k < FLAC_NK; ++k) fine[(i / plen) * FLAC_NK + k] += u >> k;
+		}
+		uint64_t node_cost[FLAC_NODES];
+		uint8_t node_k[FLAC_NODES];
+		for (unsigned p = 0; p <= fine_log2; ++p)
+			for (unsigned j = 0; j < (1u << p); ++j) {
+				unsigned k;
+				node_cost[flac_node_index(p, j)] = flac_node_cost(fine, fine_log2, p, j, n, o, &k);
+				node_k[flac_node_index(p, j)] = (uint8_t)k;
+			}
+		flac_finish_sub(&cand[c], c, n, equal, o, fine_log2, node_cost, node_k);
+	}
+	FlacFrameDesc d;
+	flac_finish_frame(&d, cand, ch, n, B, frame_number);
+	if (!out || cap < d.bytes) { delete[] w; return d.bytes; }
+	memset(out, 0, d.bytes);
+	uint8_t hdr[16];
+	const uint32_t hl = flac_frame_header(n, B, d.assign, frame_number, hdr);
+	memcpy(out, hdr, hl);
+	FlacBits bw{out, (size_t)hl * 8};
+	for (unsigned si = 0; si < d.n_sub; ++si) {
+		const FlacSub &s = d.sub[si];
+		const unsigned c = s.cand, bps = flac_cand_bps(c);
+		const uint32_t mask = bps == 17 ? 0x1ffffu : 0xffffu;
+		bw.put(s.type == FLAC_CONSTANT ? 0u : s.type == FLAC_VERBATIM ? 2u : (uint32_t)(0x10u | (s.order << 1)), 8); /* 0 tttttt 0 */
+		if (s.type == FLAC_CONSTANT) bw.put((uint32_t)at(c, 0) & mask, bps);
+		else if (s.type == FLAC_VERBATIM) for (uint32_t i = 0; i < n; ++i) bw.put((uint32_t)at(c, i) & mask, bps);
+		else {
+			for (uint32_t i = 0; i < s.order; ++i) bw.put((uint32_t)at(c, i) & mask, bps);
+			bw.put(s.p, 6); /* 00 pppp */
+			const uint32_t plen = n >> s.p;
+			for (uint32_t j = 0; j < (1u << s.p); ++j) {
+				const unsigned k = s.k[j];
+				bw.put(k, 4);
+				for (uint32_t i = j ? j * plen : s.order; i < (j + 1) * plen; ++i) {
+					const uint32_t u = flac_zigzag(resid(c, s.order, i));
+					bw.zeros(u >> k);
+					bw.put((1u << k) | (u & ((1u << k) - 1)), k + 1);
+				}
+			}
+		}
+	}
+	delete[] w;
+	const size_t body = (bw.pos + 7) / 8;
+	if (body + 2 != d.bytes) return 0; /* (the analysis and the writer disagree: never) */
+	uint32_t crc = 0;
+	for (size_t i = 0; i < body; ++i) crc = flac_crc16_update(crc, out[i]);
+	out[body] = (uint8_t)(crc >> 8); out[body + 1] = (uint8_t)crc;
+	return d.bytes;
+}
+
 } /* namespace sauengine */
