@@ -574,8 +574,10 @@ SAU_AMD_API bool sauAmd_render_spectrum(const sauProgram *prg, uint32_t srate, i
  * 4096). Row r's block k covers its frames [k B, k B + B) and becomes FLAC frame number k; frames behind the last complete block
  * are pending until a later feed completes the block or a finish makes them one last short block. At most 65535 rows per
  * encoder and 2^31 - 1 blocks per row.
- * Limits: no MD5 (the field is zeros: "not computed"), no seek table, no comments, no 24-bit output. The float, limited and
- * oversampled writers have no FLAC variant; the fed encoder takes any int16 device rows.
+ * Limits: no MD5 (the field is zeros: "not computed"), no seek table, no comments, no 24-bit output, no wasted-bits detection,
+ * no escape partitions; LPC only on request (max_lpc_order, "The LPC mode" below), of order <= 8 with 12-bit coefficients, one
+ * precision and one window. The float, limited and oversampled writers have no FLAC variant; the fed encoder takes any int16
+ * device rows.
  *
  * All fields are big-endian and packed MSB first.
  * The header (42 bytes): "fLaC"; one metadata block header, 80 00 00 22 (last = 1, type 0, length 34); STREAMINFO:
@@ -619,6 +621,52 @@ SAU_AMD_API bool sauAmd_render_spectrum(const sauProgram *prg, uint32_t srate, i
  * in that order on ties, and emits the two channels in the order named.
  * Consequences: a frame is at most 15 + channels * (1 + 2 n) bytes (13 header bytes, every channel verbatim, the CRC-16). A
  * sample's code places at most 15 non-zero bits; the unary zeros are what a cleared buffer holds.
+ *
+ * The LPC mode. A further parameter max_lpc_order M in 0 .. 8 (the entry points whose names end in _lpc); M = 0 is everything
+ * above and nothing else. With M > 0 a channel candidate is also tried with a linear predictor when the block is a whole one
+ * (n == B), the candidate is not constant and R[0] of step 2 is not 0; a short last block is encoded as with M = 0. The bytes stay
+ * a function of the fed sequence and (B, channels, M) only: whatever is summed over the block is summed in integers, which is
+ * exact and so free of any order, and the floating-point steps 4 and 5 are a short serial sequence of IEEE 754 binary64
+ * operations in the order written, every product rounded before the sum it enters (no fused multiply-add). The coefficient
+ * precision is 12 bits. >> is an arithmetic shift throughout. With Lg = log2 B:
+ *   1. the window, W[j] = (B B - (2 j + 1 - B)^2) >> (2 Lg - 12) for j = 0 .. B-1 (a Welch window, 0 .. 4095), and the windowed
+ *      samples ws[j] = (s[j] W[j]) >> 3, |ws| < 2^25.
+ *   2. the autocorrelation R[l] = the sum over j = l .. n-1 of ws[j] ws[j - l], l = 0 .. M, in 64-bit integers (a product is
+ *      below 2^50, a sum below 2^62).
+ *   3. g is the least shift >= 0 with R[0] >> g < 2^53, and r[l] = (double)(R[l] >> g): |R[l]| <= R[0], so every conversion is
+ *      exact.
+ *   4. Levinson-Durbin: a[0 .. M-1] = 0, err = r[0]; for i = 0 .. M-1:
+ *        acc = r[i + 1]; for j = 0 .. i-1 ascending: acc = acc + a[j] * r[i - j];
+ *        k = -acc / err; a[i] = k;
+ *        for j = 0 .. i/2 - 1 (i/2 rounded down): t = a[j]; u = a[i - 1 - j]; a[j] = t + k * u; a[i - 1 - j] = u + k * t;
+ *        if i is odd: t = a[i/2]; a[i/2] = t + k * t;
+ *        err = err * (1.0 - k * k);
+ *        if !(err > 0.0) or err is not finite: stop -- neither order i + 1 nor a higher one is a candidate;
+ *        otherwise order m = i + 1 has the coefficients c[j] = -a[j], j = 0 .. m-1: the prediction of s_i is the sum of
+ *        c[j] s_{i-1-j}.
+ *   5. the quantisation of order m: cmax = the largest |c[j]|; the order is no candidate when cmax is 0, subnormal or not
+ *      finite. e is the integer with 2^(e-1) <= cmax < 2^e, read from cmax's exponent field (the field - 1022);
+ *      shift = 11 - e; a shift above 15 becomes 15; with a shift below 0 the order is no candidate. E = 0.0, then for j
+ *      ascending: E = E + c[j] * 2^shift (the scaling is exact); q[j] = floor(E + 0.5) clamped to -2048 .. 2047;
+ *      E = E - (double)q[j].
+ *   6. the residual of order m, r_i = s_i - ((the sum over j = 0 .. m-1 of q[j] s_{i-1-j}) >> shift) for i >= m. The sum is at
+ *      most 8 * 2048 * 65535 < 2^30 in size and |r_i| < 2^31: everything fits 32 bits (17 + 12 + 3 = 32 is also what lets a
+ *      decoder use 32-bit accumulators).
+ *   7. the order: for each candidate order m, A_m = the sum of |r_i| over i = M .. n-1 (from M on whatever m is, in 64 bits) and
+ *      est(m) = the least over k = 0 .. 14 of ((1 + k) (n - M) + ((2 A_m) >> k)), plus m (bps + 12). The m with the least est,
+ *      the lowest on ties. No candidate order: no LPC for this channel candidate.
+ *   8. the partitions: rule 3 above with o = m (P = 4; partition 0 holds (n >> p) - m residuals; the same costs and ties,
+ *      k <= 14, never the escape).
+ *   9. LPC costs 8 + bps * m + 4 + 5 + 12 * m + 6 + cost(p) bits, and rule 5 becomes: VERBATIM when its cost is <= both
+ *      others'; otherwise FIXED when its cost is <= LPC's; otherwise LPC. The stereo rule is unchanged.
+ *  10. the subframe (RFC 9639): one 0 bit, the type 1ooooo with ooooo = m - 1, one 0 bit; the m warm-up samples of bps bits;
+ *      4 bits 1011 (the precision - 1); 5 bits shift, two's complement (never negative); the coefficients q[0] .. q[m-1] in
+ *      that order -- q[0] belongs to the most recent sample --, 12 bits each, two's complement; then the residual exactly as
+ *      in FIXED: 00, the partition order, the parameters, the codes.
+ * A candidate's LPC subframe is taken only where it is cheaper, so no frame is longer than with M = 0; the frame bound holds
+ * (VERBATIM still caps every channel), and so does "a sample's code places at most 15 non-zero bits". The streams stay inside
+ * FLAC's streamable subset (order <= 12 at up to 48 kHz, Rice parameter <= 14).
+ *
  * The worst case of a feed is that bound summed over the blocks it completes. Unread output lives on the device: a feed whose
  * worst case would bring the unread total above 1 GiB is refused; read first. (Until a read has fetched the frames' sizes, a
  * feed counts in that total with its worst case.) */
@@ -643,10 +691,16 @@ SAU_AMD_API size_t sauAmd_flac_header(uint32_t srate, int channels, uint32_t blo
  * device makes it. Returns its size; nothing is written when cap is less (out may then be NULL); 0 on a bad argument. */
 SAU_AMD_API size_t sauAmd_flac_encode_block(const int16_t *x, uint32_t n, int channels, uint32_t block_frames, uint32_t frame_number,
 		uint8_t *out, size_t cap);
+/* ... with the LPC mode's max_lpc_order (0 .. 8; above 8 is a bad argument: 0). With 0 it is sauAmd_flac_encode_block. */
+SAU_AMD_API size_t sauAmd_flac_encode_block_lpc(const int16_t *x, uint32_t n, int channels, uint32_t block_frames, uint32_t frame_number,
+		uint32_t max_lpc_order, uint8_t *out, size_t cap);
 /* An encoder of n_rows empty streams on the batch's device and stream, independent of the batch's own runs. NULL
  * (sauAmd_last_error) on a bad argument -- channels, block_frames, n_rows == 0 or above 65535 -- or on a backend without it. It
  * must be destroyed before the batch. sauAmd_Flac_destroy(NULL) is allowed. */
 SAU_AMD_API sauAmdFlac *sauAmd_Batch_create_flac(sauAmdBatch *b, size_t n_rows, int channels, uint32_t block_frames);
+/* ... whose streams are encoded in the LPC mode with max_lpc_order (0 .. 8; above 8 is a bad argument: NULL). With 0 it is
+ * sauAmd_Batch_create_flac. */
+SAU_AMD_API sauAmdFlac *sauAmd_Batch_create_flac_lpc(sauAmdBatch *b, size_t n_rows, int channels, uint32_t block_frames, uint32_t max_lpc_order);
 SAU_AMD_API void sauAmd_Flac_destroy(sauAmdFlac *e);
 /* Row r's next frames[r] frames, int16 in host order, `channels` interleaved, read from rows + pitch_bytes * r; 0 changes
  * nothing for that row. Queued on the batch's stream: it may directly follow the run that produced the rows
@@ -670,6 +724,10 @@ SAU_AMD_API bool sauAmd_Flac_read(sauAmdFlac *e, uint8_t *const *bufs, const siz
  * block_frames that is not allowed, and on a backend without an encoder -- all before any file is created. */
 SAU_AMD_API bool sauAmd_render_file_flac(const sauProgram *prg, uint32_t srate, const char *path, int channels, uint32_t block_frames,
 		uint64_t *frames_out, sauAmdFlacInfo *info_out);
+/* ... in the LPC mode with max_lpc_order (0 .. 8; above 8 is a bad argument, refused before any file is created). With 0 it is
+ * sauAmd_render_file_flac. The file decodes to the same samples and is never longer. */
+SAU_AMD_API bool sauAmd_render_file_flac_lpc(const sauProgram *prg, uint32_t srate, const char *path, int channels, uint32_t block_frames,
+		uint32_t max_lpc_order, uint64_t *frames_out, sauAmdFlacInfo *info_out);
 
 
 #ifdef __cplusplus

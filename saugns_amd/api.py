@@ -299,6 +299,15 @@ def _declare(L):
         L.sauAmd_render_file_flac.restype = C.c_bool
         L.sauAmd_render_file_flac.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_int, C.c_uint32, C.POINTER(C.c_uint64),
                                               C.POINTER(FlacInfo)]
+    if hasattr(L, "sauAmd_Batch_create_flac_lpc"):  # the encoder's LPC mode (SAU_AMD_LIB may name an older build)
+        L.sauAmd_flac_encode_block_lpc.restype = C.c_size_t
+        L.sauAmd_flac_encode_block_lpc.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                                   C.c_size_t]
+        L.sauAmd_Batch_create_flac_lpc.restype = C.c_void_p
+        L.sauAmd_Batch_create_flac_lpc.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.c_uint32]
+        L.sauAmd_render_file_flac_lpc.restype = C.c_bool
+        L.sauAmd_render_file_flac_lpc.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_int, C.c_uint32, C.c_uint32,
+                                                  C.POINTER(C.c_uint64), C.POINTER(FlacInfo)]
     L.sauAmd_set_piluts.argtypes = [C.c_void_p]
     L.sauAmd_get_piluts.restype = C.POINTER(C.c_float)
     L.sauAmd_last_error.restype = C.c_char_p
@@ -670,27 +679,46 @@ def flac_header(srate, channels, block_frames, info=None):
     return bytes(out) if n == 42 else b""
 
 
-def flac_encode_block(x, channels, block_frames, frame_number):
-    """sauAmd_flac_encode_block: the host's restatement of one frame, from interleaved int16 samples -> bytes (b"" when the
-    arguments are refused)"""
+def _lpc_order(max_lpc_order):
+    """0 .. 2^32 - 1 as the library takes it (it refuses what is above 8); anything else is refused here the same way"""
+    m = int(max_lpc_order)
+    return m if 0 <= m < 1 << 32 else 0xffffffff
+
+
+def flac_encode_block(x, channels, block_frames, frame_number, max_lpc_order=0):
+    """sauAmd_flac_encode_block, or with max_lpc_order != 0 sauAmd_flac_encode_block_lpc: the host's restatement of one frame,
+    from interleaved int16 samples -> bytes (b"" when the arguments are refused)"""
     x = np.ascontiguousarray(x, np.int16)
     n = len(x) // max(int(channels), 1)
     L = lib()
-    size = L.sauAmd_flac_encode_block(x.ctypes.data, n, channels, block_frames, frame_number, None, 0)
+    if max_lpc_order:
+        def call(out, cap):
+            return L.sauAmd_flac_encode_block_lpc(x.ctypes.data, n, channels, block_frames, frame_number, _lpc_order(max_lpc_order), out, cap)
+    else:
+        def call(out, cap):
+            return L.sauAmd_flac_encode_block(x.ctypes.data, n, channels, block_frames, frame_number, out, cap)
+    size = call(None, 0)
     if not size:
         return b""
     out = (C.c_uint8 * size)()
-    assert L.sauAmd_flac_encode_block(x.ctypes.data, n, channels, block_frames, frame_number, out, size) == size
+    assert call(out, size) == size
     return bytes(out)
 
 
-def render_file_flac(program, srate, path, channels=1, block_frames=0, backend=None):
-    """sauAmd_render_file_flac: render a whole program into a FLAC file, encoded on the device -> (frames, FlacInfo).
-    ``backend`` (tests): a sauengine::Backend* to run the same writer without a GPU."""
+def render_file_flac(program, srate, path, channels=1, block_frames=0, backend=None, max_lpc_order=0):
+    """sauAmd_render_file_flac, or with max_lpc_order != 0 sauAmd_render_file_flac_lpc: render a whole program into a FLAC file,
+    encoded on the device -> (frames, FlacInfo). ``backend`` (tests): a sauengine::Backend* to run the same writer without a
+    GPU (without the LPC mode)."""
     n, info = C.c_uint64(), FlacInfo()
-    if backend is None:
+    if backend is None and max_lpc_order:
+        L = _used(lib())
+        ok = L.sauAmd_render_file_flac_lpc(program.ptr, srate, os.fsencode(path), channels, block_frames, _lpc_order(max_lpc_order),
+                                           C.byref(n), C.byref(info))
+    elif backend is None:
         L = _used(lib())
         ok = L.sauAmd_render_file_flac(program.ptr, srate, os.fsencode(path), channels, block_frames, C.byref(n), C.byref(info))
+    elif max_lpc_order:
+        raise ValueError("the FLAC-hook library runs the writer without the LPC mode")
     else:
         if _flac_hooks is None:
             raise RuntimeError("the FLAC-hook library is not loaded (use_flac_hooks)")
@@ -1080,10 +1108,15 @@ class Batch:
         out = (power[:n_rows], [int(x) for x in segs][:n_rows])
         return out + (gram[:n_rows],) if spectrogram else out
 
-    def create_flac(self, n_rows, channels, block_frames=0):
-        """sauAmd_Batch_create_flac: a Flac encoder of n_rows streams on the batch's device and stream. Close it before the
-        batch."""
-        return Flac(self, n_rows, channels, block_frames)
+    def create_flac(self, n_rows, channels, block_frames=0, max_lpc_order=0):
+        """sauAmd_Batch_create_flac, or with max_lpc_order != 0 sauAmd_Batch_create_flac_lpc: a Flac encoder of n_rows streams on
+        the batch's device and stream. Close it before the batch."""
+        return Flac(self, n_rows, channels, block_frames, max_lpc_order)
+
+    def create_flac_lpc(self, n_rows, channels, block_frames=0, max_lpc_order=0):
+        """(tests) sauAmd_Batch_create_flac_lpc whatever max_lpc_order is -- create_flac reaches it only with an order above 0 --:
+        with 0 the encoder create_flac makes, by the other entry point"""
+        return Flac(self, n_rows, channels, block_frames, max_lpc_order, lpc_entry=True)
 
     def device_pcm(self, stream):
         """Device address of the stream's int16 row of the last run; None after a float32 run."""
@@ -1180,12 +1213,18 @@ class Flac:
     row r's next frames[r] frames from device memory, on the batch's stream; ``read`` waits and returns the rows' encoded bytes.
     Close it before its batch."""
 
-    def __init__(self, batch, n_rows, channels, block_frames=0):
+    def __init__(self, batch, n_rows, channels, block_frames=0, max_lpc_order=0, lpc_entry=False):
         self._L = batch._L
         self.n_rows, self.channels, self.block_frames = int(n_rows), int(channels), int(block_frames)
-        self._e = _used(self._L).sauAmd_Batch_create_flac(batch._b, self.n_rows, self.channels, self.block_frames)
+        self.max_lpc_order = _lpc_order(max_lpc_order)
+        entry = "sauAmd_Batch_create_flac_lpc" if self.max_lpc_order or lpc_entry else "sauAmd_Batch_create_flac"
+        if self.max_lpc_order or lpc_entry:  # (lpc_entry, tests: the _lpc entry point with order 0 too)
+            self._e = _used(self._L).sauAmd_Batch_create_flac_lpc(batch._b, self.n_rows, self.channels, self.block_frames,
+                                                                  self.max_lpc_order)
+        else:
+            self._e = _used(self._L).sauAmd_Batch_create_flac(batch._b, self.n_rows, self.channels, self.block_frames)
         if not self._e:
-            raise RuntimeError("sauAmd_Batch_create_flac returned NULL: " + last_error(self._L))
+            raise RuntimeError(entry + " returned NULL: " + last_error(self._L))
         self._batch = batch  # (the batch outlives the encoder: its close() closes this one first)
         batch._meters = getattr(batch, "_meters", []) + [weakref.ref(self)]
 

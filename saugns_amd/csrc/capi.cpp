@@ -659,6 +659,29 @@ extern "C" size_t sauAmd_flac_encode_block(const int16_t *x, uint32_t n, int cha
 	}
 }
 
+extern "C" size_t sauAmd_flac_encode_block_lpc(const int16_t *x, uint32_t n, int channels, uint32_t block_frames, uint32_t frame_number,
+		uint32_t max_lpc_order, uint8_t *out, size_t cap) {
+	try {
+		return sauengine::flac_encode_block_lpc(x, n, channels, block_frames, frame_number, max_lpc_order, out, cap);
+	} catch (const std::exception &) { /* (nothing C++ crosses the C ABI) */
+		return 0;
+	}
+}
+
+extern "C" sauAmdFlac *sauAmd_Batch_create_flac_lpc(sauAmdBatch *b, size_t n_rows, int channels, uint32_t block_frames, uint32_t max_lpc_order) {
+	std::string err;
+	try {
+		if (!b || !n_rows || n_rows > sauflac::FLAC_MAX_ROWS || !sauengine::flac_params_ok(channels, block_frames) ||
+		    max_lpc_order > sauflac::FLAC_LPC_MAX) err = "bad argument";
+		else if (sauengine::FlacEncoder *e = b->engine->backend()->create_flac_lpc(n_rows, (uint32_t)channels, block_frames, max_lpc_order, err))
+			return new sauAmdFlac{e};
+	} catch (const std::exception &ex) {
+		err = std::string("internal error: ") + ex.what();
+	}
+	report("flac", err);
+	return nullptr;
+}
+
 extern "C" sauAmdFlac *sauAmd_Batch_create_flac(sauAmdBatch *b, size_t n_rows, int channels, uint32_t block_frames) {
 	std::string err;
 	try {

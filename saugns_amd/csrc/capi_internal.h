@@ -49,6 +49,10 @@ bool render_spectrum(const sauProgram *prg, uint32_t srate, int factor, int chan
 bool render_file_flac(const sauProgram *prg, uint32_t srate, const char *path, int channels, uint32_t block_frames,
 		const std::function<sauengine::Backend *(std::string &)> &make_backend, uint64_t *frames_out, sauAmdFlacInfo *info_out,
 		std::string &err);
+/* sauAmd_render_file_flac_lpc's body: the same with the LPC mode's max_lpc_order (0: render_file_flac) */
+bool render_file_flac_lpc(const sauProgram *prg, uint32_t srate, const char *path, int channels, uint32_t block_frames, uint32_t max_lpc_order,
+		const std::function<sauengine::Backend *(std::string &)> &make_backend, uint64_t *frames_out, sauAmdFlacInfo *info_out,
+		std::string &err);
 /* the thread's sauAmd_last_error text (capi.cpp), with the line on stderr */
 void set_last_error(const char *where, const std::string &err);
 } /* namespace sauamd_internal */

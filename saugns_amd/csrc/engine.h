@@ -123,6 +123,9 @@ struct FlacInfo {
 static_assert(sizeof(FlacInfo) == 32, "FlacInfo is sauAmdFlacInfo");
 size_t flac_header(uint32_t srate, int channels, uint32_t block_frames, const FlacInfo *info, uint8_t *out, size_t cap);
 size_t flac_encode_block(const int16_t *x, uint32_t n, int channels, uint32_t block_frames, uint32_t frame_number, uint8_t *out, size_t cap);
+/* ... with the LPC mode's max_lpc_order (0 .. 8; 0: flac_encode_block) */
+size_t flac_encode_block_lpc(const int16_t *x, uint32_t n, int channels, uint32_t block_frames, uint32_t frame_number, uint32_t max_lpc_order,
+		uint8_t *out, size_t cap);
 inline bool flac_params_ok(int channels, uint32_t block_frames) {
 	return (channels == 1 || channels == 2) && sauflac::flac_block_frames(block_frames) != 0;
 }
@@ -396,6 +399,12 @@ public:
 	 * backend without one refuses -- this default -- and nothing changes. */
 	virtual FlacEncoder *create_flac(size_t n_rows, uint32_t channels, uint32_t block_frames, std::string &err) {
 		(void)n_rows; (void)channels; (void)block_frames; err = "this backend has no FLAC encoder"; return nullptr;
+	}
+	/* ... with the LPC mode's max_lpc_order (0 .. 8). 0 is create_flac; this default refuses every other value: a backend whose
+	 * FLAC encoder predates the LPC mode keeps working as it is. */
+	virtual FlacEncoder *create_flac_lpc(size_t n_rows, uint32_t channels, uint32_t block_frames, uint32_t max_lpc_order, std::string &err) {
+		if (!max_lpc_order) return create_flac(n_rows, channels, block_frames, err);
+		err = "this backend's FLAC encoder has no LPC mode"; return nullptr;
 	}
 	/* the same from empty records on rows of `frames` frames each, synchronous; spectrogram_out (may be NULL): every segment's
 	 * (float)p[k], [n_rows][channels][S][N/2 + 1], refused when spectrogram_cap (in floats) does not suffice */

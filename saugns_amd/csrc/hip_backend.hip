@@ -14,7 +14,8 @@
  *   k_loudness.h    loud_chunk_kernel, loud_scan_kernel, truepeak_kernel, loud_finish_kernel, loud_carry_kernel (BS.1770 loudness, true peak)
  *   k_limiter.h     lim_env_kernel, lim_gain_kernel, lim_finish_kernel, lim_carry_kernel (the look-ahead true-peak limiter)
  *   k_spectrum.h    spec_segment_kernel, spec_finish_kernel, spec_carry_kernel (Welch power spectra of fed rows)
- *   k_flac.h        flac_analyze_kernel, flac_scan_kernel, flac_write_kernel, flac_carry_kernel (FLAC frames of fed int16 rows)
+ *   k_flac.h        flac_analyze_kernel, flac_scan_kernel, flac_write_kernel, flac_carry_kernel (FLAC frames of fed int16 rows;
+ *                   the <true> builds of the first and the third hold the LPC mode)
  *   launch_plan.h   (plain C++, no HIP) the tuning switches and every decision about a segment's launches: rows per pass, LDS
  *                   budgets, builds, grids, tasks, chain chunks, the mixer -- a plan per segment, testable without a GPU
  *   mix_overlap.h   (plain C++, no HIP) where the main stream waits for a final mixer that runs on the side stream
@@ -2180,8 +2181,8 @@ public:
 	 * the host. The unread total that the 1 GiB rule counts is the feeds' worst cases until a read has fetched the sizes. */
 	class Flac : public sauengine::FlacEncoder {
 	public:
-		Flac(HipBackendImpl *be, size_t n_rows, uint32_t channels, uint32_t block_frames)
-			: be_(be), n_(n_rows), ch_(channels), B_(sauflac::flac_block_frames(block_frames)), pos_(n_rows, 0), blocks_(n_rows, 0) {
+		Flac(HipBackendImpl *be, size_t n_rows, uint32_t channels, uint32_t block_frames, uint32_t max_lpc_order)
+			: be_(be), n_(n_rows), ch_(channels), B_(sauflac::flac_block_frames(block_frames)), M_(max_lpc_order), pos_(n_rows, 0), blocks_(n_rows, 0) {
 			/* (tests: another limit of unread bytes than 1 GiB) */
 			if (const char *v = sauengine::tune_env("SAU_AMD_FLAC_UNREAD_MAX")) { const long long x = atoll(v); if (x > 0) limit_ = (uint64_t)x; }
 		}
@@ -2241,15 +2242,18 @@ public:
 			fp.rows = (const int16_t *)rows; fp.row_pitch = pitch; fp.desc = desc_.p;
 			fp.pend = pend_[cur_].p; fp.pend_next = pend_[cur_ ^ 1].p; fp.pend_pitch = plan.pend_pitch;
 			fp.frames = frames_.p; fp.stats = stats_.p;
-			fp.B = B_; fp.channels = ch_; fp.n_rows = (uint32_t)n_; fp.jobs = plan.jobs;
+			fp.B = B_; fp.channels = ch_; fp.n_rows = (uint32_t)n_; fp.jobs = plan.jobs; fp.max_lpc = M_;
 			hipStream_t st = be_->stream_;
 			if (plan.jobs) {
 				fp.out = c->out.p; fp.row_bytes = c->row_bytes.p;
-				hipLaunchKernelGGL(flac_analyze_kernel, dim3(plan.jobs), dim3(plan.analyze_threads), plan.analyze_lds, st, fp);
+				/* (max_lpc_order 0 runs the kernels without the LPC mode's code: the encoder as it was before that mode) */
+				if (M_) hipLaunchKernelGGL(flac_analyze_kernel<true>, dim3(plan.jobs), dim3(plan.analyze_threads), plan.analyze_lds, st, fp);
+				else hipLaunchKernelGGL(flac_analyze_kernel<false>, dim3(plan.jobs), dim3(plan.analyze_threads), plan.analyze_lds, st, fp);
 				HIP_OK(hipGetLastError());
 				hipLaunchKernelGGL(flac_scan_kernel, dim3(plan.rows), dim3(FLAC_THREADS), 0, st, fp);
 				HIP_OK(hipGetLastError());
-				hipLaunchKernelGGL(flac_write_kernel, dim3(plan.jobs), dim3(FLAC_THREADS), plan.write_lds, st, fp);
+				if (M_) hipLaunchKernelGGL(flac_write_kernel<true>, dim3(plan.jobs), dim3(FLAC_THREADS), plan.write_lds, st, fp);
+				else hipLaunchKernelGGL(flac_write_kernel<false>, dim3(plan.jobs), dim3(FLAC_THREADS), plan.write_lds, st, fp);
 				HIP_OK(hipGetLastError());
 			}
 			if (!finish) { /* (behind a finish nothing is pending) */
@@ -2319,7 +2323,7 @@ public:
 		};
 		HipBackendImpl *be_;
 		size_t n_;
-		uint32_t ch_, B_;
+		uint32_t ch_, B_, M_;
 		std::vector<uint64_t> pos_, blocks_; /* per row: frames fed, blocks made */
 		std::vector<std::unique_ptr<Chunk>> chunks_;
 		uint64_t bound_ = 0, limit_ = sauflac::FLAC_MAX_UNREAD;
@@ -2331,11 +2335,14 @@ public:
 		int cur_ = 0;
 	};
 	sauengine::FlacEncoder *create_flac(size_t n_rows, uint32_t channels, uint32_t block_frames, std::string &err) override {
+		return create_flac_lpc(n_rows, channels, block_frames, 0, err);
+	}
+	sauengine::FlacEncoder *create_flac_lpc(size_t n_rows, uint32_t channels, uint32_t block_frames, uint32_t max_lpc_order, std::string &err) override {
 		use_device();
 		if (!join_mixer("create_flac", err)) return nullptr;
-		if (!sauengine::flac_params_ok((int)channels, block_frames) || !n_rows) { err = "bad argument"; return nullptr; }
+		if (!sauengine::flac_params_ok((int)channels, block_frames) || !n_rows || max_lpc_order > sauflac::FLAC_LPC_MAX) { err = "bad argument"; return nullptr; }
 		if (n_rows > sauflac::FLAC_MAX_ROWS) { err = "bad argument: more than 65535 rows"; return nullptr; }
-		Flac *e = new Flac(this, n_rows, channels, block_frames);
+		Flac *e = new Flac(this, n_rows, channels, block_frames, max_lpc_order);
 		if (!e->init(err)) { delete e; return nullptr; }
 		return e;
 	}

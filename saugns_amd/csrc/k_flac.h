@@ -16,11 +16,20 @@
  *       XOR do not depend on their order, so the bytes are reproducible. The finished bytes go to the frame's place.
  *   flac_carry_kernel    grid (parts, rows): the row's pending frames become those behind the feed, from one buffer into the
  *       other (the encoder swaps them), as spec_carry_kernel does.
+ * The LPC mode (the header's "The LPC mode", max_lpc_order > 0) is a second build of the first and the third kernel,
+ * flac_analyze_kernel<true> and flac_write_kernel<true>; the <false> builds hold none of its code and are what an encoder of
+ * order 0 launches. In the analysis of a whole block the candidate's wave goes on behind the FIXED choice (flac_analyze_lpc):
+ * the windowed autocorrelation in 64-bit integers, a lane a run of n / 64 frames, the shares added by the xor-shuffle sum;
+ * the Levinson-Durbin recursion and the quantisation of every order in f64 on lane 0, serial, in the header's order; the
+ * orders' coefficient tables stay in LDS (a run-time index into registers would be scratch); the sums of |r| of all candidate
+ * orders in one walk of the lane's run; the chosen order's sums of u >> k per finest partition in 64 bits, merged and priced
+ * as the FIXED ones; then LPC takes the record where it is cheaper. The writer reads the coefficients from the record in LDS.
  * No lane walks a whole block: a lane's run is n / 64 frames in the analysis, n / 256 in the writer.
  *
  * LDS. Frame i is kept at word i + (i >> 5): in the partition sums a lane walks a run of consecutive frames (one new word per
  * frame) and the runs lie B / 64 apart, which without the extra word per 32 would put all lanes on one bank at B = 4096. The
- * analysis takes 4.1 B bytes + 10 KiB; the writer 4.1 B + the frame's bound, 33 KiB at B = 4096 stereo. */
+ * analysis takes 4.1 B bytes + 10 KiB (the LPC build's tables are 1.1 KiB of them); the writer 4.1 B + the frame's bound,
+ * 33 KiB at B = 4096 stereo. */
 #ifndef SAU_K_FLAC_H
 #define SAU_K_FLAC_H
 
@@ -44,6 +53,7 @@ struct FlacParams {
 	uint32_t *row_bytes;      /* [n_rows]: what this feed made of each row */
 	FlacStats *stats;         /* [n_rows] */
 	uint32_t B, channels, n_rows, jobs;
+	uint32_t max_lpc;         /* the LPC mode's largest order, 1 .. 8, for the <true> kernels; 0 for the <false> ones */
 };
 
 __device__ __forceinline__ unsigned flac_ix(const unsigned i) { return i + (i >> 5); }
@@ -82,6 +92,125 @@ __device__ __forceinline__ unsigned long long flac_wave_sum(unsigned long long v
 	return v;
 }
 
+/* the sum of q[j] * s_{i-1-j}, j < m (i >= m): the coefficients are read from LDS, where a run-time index costs nothing */
+__device__ __forceinline__ int32_t flac_lpc_sum(const uint32_t *s_w, const unsigned c, const int16_t *q, const unsigned m, const unsigned i) {
+	int32_t sum = 0;
+	for (unsigned j = 0; j < m; ++j) sum += (int32_t)q[j] * flac_cand(s_w[flac_ix(i - 1 - j)], c);
+	return sum;
+}
+
+/* What the LPC mode adds to a wave's analysis of its candidate (whole blocks only; every wave of the workgroup comes here,
+ * since there are barriers inside): the windowed autocorrelation from the staged words -- a lane a run of n / 64 consecutive
+ * frames, the window's value computed where it is used, products and sums in 64-bit integers, the lanes' shares added by the
+ * xor-shuffle sum --, steps 3 to 5 on lane 0 with the orders' coefficient tables left in LDS, the sums of |r| of all
+ * candidate orders in one walk of the lane's run, the chosen order's sums of u >> k per finest partition (64 bits: an LPC
+ * residual may take 32), the nodes' costs, and the choice against what flac_finish_sub has left in s_cand[c]. */
+struct FlacLpcLds {
+	double r[4][FLAC_LPC_MAX + 1];
+	double a[4][FLAC_LPC_MAX];
+	int16_t q[4][FLAC_LPC_MAX * FLAC_LPC_MAX];
+	uint8_t shift[4][FLAC_LPC_MAX];
+	uint32_t mask[4];
+};
+__device__ __forceinline__ void flac_analyze_lpc(const FlacParams &P, const uint32_t *s_w, FlacLpcLds &L, uint64_t (*s_fine)[FLAC_FINE * FLAC_NK],
+		uint64_t (*s_node_cost)[32], uint8_t (*s_node_k)[32], FlacSub *s_cand, const unsigned c, const unsigned lane, const bool equal) {
+	const unsigned n = P.B, M = P.max_lpc, log2B = 31 - __clz((int)P.B), bps = flac_cand_bps(c);
+	const unsigned run = n >> 6, i0 = lane * run;
+	/* steps 1 and 2 */
+	long long R[FLAC_LPC_MAX + 1];
+#pragma unroll
+	for (unsigned l = 0; l <= FLAC_LPC_MAX; ++l) R[l] = 0;
+	if (!equal) {
+		int32_t h[FLAC_LPC_MAX + 1]; /* h[l] = ws[i - l] */
+#pragma unroll
+		for (unsigned l = 1; l <= FLAC_LPC_MAX; ++l)
+			h[l] = i0 + 1 >= l + 1 ? flac_lpc_windowed(flac_at(s_w, c, (int)(i0 - l)), flac_lpc_window(i0 - l, n, log2B)) : 0;
+		for (unsigned i = i0; i < i0 + run; ++i) {
+			h[0] = flac_lpc_windowed(flac_at(s_w, c, (int)i), flac_lpc_window(i, n, log2B));
+#pragma unroll
+			for (unsigned l = 0; l <= FLAC_LPC_MAX; ++l) R[l] += (long long)h[0] * h[l]; /* (h[l] is 0 where i < l; orders above M are not read) */
+#pragma unroll
+			for (unsigned l = FLAC_LPC_MAX; l > 0; --l) h[l] = h[l - 1];
+		}
+	}
+#pragma unroll
+	for (unsigned l = 0; l <= FLAC_LPC_MAX; ++l) R[l] = (long long)flac_wave_sum((unsigned long long)R[l], 6);
+	const bool on = !equal && R[0] != 0; /* (the same in every lane of the wave) */
+	/* steps 3 to 5, one lane */
+	if (lane == 0) {
+		uint32_t mask = 0;
+		if (on) {
+			const unsigned g = flac_lpc_f64_shift(R[0]);
+#pragma unroll
+			for (unsigned l = 0; l <= FLAC_LPC_MAX; ++l) L.r[c][l] = (double)(R[l] >> g);
+			mask = flac_lpc_orders(L.r[c], M, L.a[c], L.q[c], L.shift[c]);
+		}
+		L.mask[c] = mask;
+	}
+	__syncthreads();
+	const uint32_t mask = on ? L.mask[c] : 0;
+	/* step 7: A_m of every candidate order over i = M .. n-1 */
+	unsigned long long A[FLAC_LPC_MAX];
+#pragma unroll
+	for (unsigned m = 1; m <= FLAC_LPC_MAX; ++m) A[m - 1] = 0;
+	if (mask)
+		for (unsigned i = i0 > M ? i0 : M; i < i0 + run; ++i) {
+			const int32_t s0 = flac_at(s_w, c, (int)i);
+			int32_t hs[FLAC_LPC_MAX];
+#pragma unroll
+			for (unsigned j = 0; j < FLAC_LPC_MAX; ++j) hs[j] = j < M ? flac_at(s_w, c, (int)(i - 1 - j)) : 0;
+#pragma unroll
+			for (unsigned m = 1; m <= FLAC_LPC_MAX; ++m)
+				if (mask & (1u << (m - 1))) {
+					int32_t sum = 0;
+#pragma unroll
+					for (unsigned j = 0; j < m; ++j) sum += (int32_t)L.q[c][(m - 1) * FLAC_LPC_MAX + j] * hs[j];
+					A[m - 1] += flac_abs(flac_lpc_residual(s0, sum, L.shift[c][m - 1]));
+				}
+		}
+#pragma unroll
+	for (unsigned m = 1; m <= FLAC_LPC_MAX; ++m) A[m - 1] = flac_wave_sum(A[m - 1], 6);
+	unsigned m = 0;
+	{ /* (flac_lpc_pick_order with the sums in registers) */
+		uint64_t least = ~0ull;
+#pragma unroll
+		for (unsigned t = 1; t <= FLAC_LPC_MAX; ++t)
+			if (mask & (1u << (t - 1))) {
+				const uint64_t e = flac_lpc_est(A[t - 1], n, M, t, bps);
+				if (e < least) { least = e; m = t; }
+			}
+	}
+	/* step 8: the chosen order's sums of u >> k per finest partition */
+	unsigned long long f64[FLAC_NK];
+#pragma unroll
+	for (unsigned k = 0; k < FLAC_NK; ++k) f64[k] = 0;
+	/* (m == 0, no candidate order: q and shift are then order 1's places, which nobody may have written -- they are not used;
+	 * the lanes still store their zero sums and reach the barriers with the other waves) */
+	const int16_t *q = &L.q[c][(m ? m - 1 : 0) * FLAC_LPC_MAX];
+	const unsigned shift = L.shift[c][m ? m - 1 : 0];
+	if (m)
+		for (unsigned i = i0 > m ? i0 : m; i < i0 + run; ++i) {
+			const uint32_t u = flac_zigzag(flac_lpc_residual(flac_at(s_w, c, (int)i), flac_lpc_sum(s_w, c, q, m, i), shift));
+#pragma unroll
+			for (unsigned k = 0; k < FLAC_NK; ++k) f64[k] += u >> k;
+		}
+#pragma unroll
+	for (unsigned k = 0; k < FLAC_NK; ++k) {
+		const unsigned long long s = flac_wave_sum(f64[k], 2);
+		if ((lane & 3) == 0) s_fine[c][(lane >> 2) * FLAC_NK + k] = s;
+	}
+	__syncthreads();
+	if (m && lane < FLAC_NODES) {
+		const unsigned p = 31 - __clz((int)(lane + 1)), part = lane + 1 - (1u << p);
+		unsigned k;
+		s_node_cost[c][lane] = flac_node_cost(s_fine[c], 4, p, part, n, m, &k);
+		s_node_k[c][lane] = (uint8_t)k;
+	}
+	__syncthreads();
+	if (m && lane == 0) flac_lpc_choose(&s_cand[c], n, m, q, shift, 4, s_node_cost[c], s_node_k[c]);
+}
+
+template <bool LPC>
 __global__ __launch_bounds__(256) void flac_analyze_kernel(const FlacParams P) {
 	extern __shared__ uint32_t flac_lds[];
 	__shared__ uint64_t s_fine[4][FLAC_FINE * FLAC_NK];
@@ -158,6 +287,11 @@ __global__ __launch_bounds__(256) void flac_analyze_kernel(const FlacParams P) {
 	__syncthreads();
 	if (lane == 0) flac_finish_sub(&s_cand[c], c, n, equal, o, fine_log2, s_node_cost[c], s_node_k[c]);
 	__syncthreads();
+	if (LPC && n == P.B) { /* (the same for the whole workgroup) */
+		__shared__ FlacLpcLds s_lpc;
+		flac_analyze_lpc(P, s_w, s_lpc, s_fine, s_node_cost, s_node_k, s_cand, c, lane, equal);
+		__syncthreads();
+	}
 	if (threadIdx.x == 0) flac_finish_frame(&P.frames[job], s_cand, P.channels, n, P.B, (uint32_t)(d.block0 + j));
 }
 
@@ -213,6 +347,15 @@ __device__ __forceinline__ void flac_put(uint32_t *s_f, const uint32_t n_words, 
 }
 __device__ __forceinline__ uint32_t flac_byte(const uint32_t *s_f, const uint32_t b) { return (s_f[b >> 2] >> (24 - 8 * (b & 3))) & 0xffu; }
 
+/* the residual of frame i (>= the order) of a FIXED subframe, or, in the <true> kernel, of an LPC one */
+template <bool LPC>
+__device__ __forceinline__ int32_t flac_sub_residual(const uint32_t *s_w, const FlacSub &s, const unsigned c, const unsigned o, const unsigned i) {
+	if (LPC && s.type == FLAC_LPC) return flac_lpc_residual(flac_at(s_w, c, (int)i), flac_lpc_sum(s_w, c, s.q, o, i), s.shift);
+	return flac_residual(o, flac_at(s_w, c, (int)i), flac_at(s_w, c, (int)i - 1), flac_at(s_w, c, (int)i - 2), flac_at(s_w, c, (int)i - 3),
+			flac_at(s_w, c, (int)i - 4));
+}
+
+template <bool LPC>
 __global__ __launch_bounds__(FLAC_THREADS) void flac_write_kernel(const FlacParams P) {
 	extern __shared__ uint32_t flac_lds[];
 	__shared__ uint32_t s_scan[4], s_crc;
@@ -245,7 +388,9 @@ __global__ __launch_bounds__(FLAC_THREADS) void flac_write_kernel(const FlacPara
 		const FlacSub &s = fd.sub[si];
 		const unsigned c = s.cand, bps = flac_cand_bps(c);
 		const uint32_t mask = bps == 17 ? 0x1ffffu : 0xffffu;
-		if (tid == 0) flac_put(s_f, n_words, pos, 8, s.type == FLAC_CONSTANT ? 0u : s.type == FLAC_VERBATIM ? 2u : (uint32_t)(0x10u | (s.order << 1)));
+		const bool lpc = LPC && s.type == FLAC_LPC;
+		if (tid == 0) flac_put(s_f, n_words, pos, 8, s.type == FLAC_CONSTANT ? 0u : s.type == FLAC_VERBATIM ? 2u :
+				lpc ? (uint32_t)(0x40u | ((s.order - 1u) << 1)) : (uint32_t)(0x10u | (s.order << 1)));
 		if (s.type == FLAC_CONSTANT) {
 			if (tid == 0) flac_put(s_f, n_words, pos + 8, bps, (uint32_t)flac_at(s_w, c, 0) & mask);
 		} else if (s.type == FLAC_VERBATIM) {
@@ -253,7 +398,14 @@ __global__ __launch_bounds__(FLAC_THREADS) void flac_write_kernel(const FlacPara
 		} else {
 			const unsigned o = s.order, p = s.p;
 			if (tid < o) flac_put(s_f, n_words, pos + 8 + bps * tid, bps, (uint32_t)flac_at(s_w, c, (int)tid) & mask);
-			const uint32_t at_res = pos + 8 + bps * o;
+			uint32_t at_res = pos + 8 + bps * o;
+			if (lpc) { /* 1011, the shift, the coefficients */
+				if (tid == 0) {
+					flac_put(s_f, n_words, at_res, 9, ((FLAC_LPC_PREC - 1) << 5) | s.shift);
+					for (unsigned j = 0; j < o; ++j) flac_put(s_f, n_words, at_res + 9 + FLAC_LPC_PREC * j, FLAC_LPC_PREC, (uint32_t)s.q[j] & 0xfffu);
+				}
+				at_res += 9 + FLAC_LPC_PREC * o;
+			}
 			if (tid == 0) flac_put(s_f, n_words, at_res, 6, p); /* 00 pppp */
 			/* a thread's run of consecutive frames; partition of frame i: i >> (log2 B - p) -- p > 0 only in a whole block */
 			const unsigned run = (n + FLAC_THREADS - 1) / FLAC_THREADS, i0 = tid * run, i1 = i0 + run < n ? i0 + run : n;
@@ -261,15 +413,13 @@ __global__ __launch_bounds__(FLAC_THREADS) void flac_write_kernel(const FlacPara
 			uint32_t len = 0;
 			for (unsigned i = i0 > o ? i0 : o; i < i1; ++i) {
 				const unsigned k = s.k[i >> psh];
-				const uint32_t u = flac_zigzag(flac_residual(o, flac_at(s_w, c, (int)i), flac_at(s_w, c, (int)i - 1), flac_at(s_w, c, (int)i - 2),
-						flac_at(s_w, c, (int)i - 3), flac_at(s_w, c, (int)i - 4)));
+				const uint32_t u = flac_zigzag(flac_sub_residual<LPC>(s_w, s, c, o, i));
 				len += (u >> k) + 1 + k + ((i & pmask) == 0 || i == o ? 4 : 0);
 			}
 			uint32_t b = at_res + 6 + flac_block_excl(len, s_scan);
 			for (unsigned i = i0 > o ? i0 : o; i < i1; ++i) {
 				const unsigned k = s.k[i >> psh];
-				const uint32_t u = flac_zigzag(flac_residual(o, flac_at(s_w, c, (int)i), flac_at(s_w, c, (int)i - 1), flac_at(s_w, c, (int)i - 2),
-						flac_at(s_w, c, (int)i - 3), flac_at(s_w, c, (int)i - 4)));
+				const uint32_t u = flac_zigzag(flac_sub_residual<LPC>(s_w, s, c, o, i));
 				if ((i & pmask) == 0 || i == o) { flac_put(s_f, n_words, b, 4, k); b += 4; }
 				b += u >> k;
 				flac_put(s_f, n_words, b, k + 1, (1u << k) | (u & ((1u << k) - 1)));

@@ -1,8 +1,9 @@
 /* sau_flac.h -- the FLAC encoder's arithmetic (include/saugns_amd.h, section "FLAC"), shared by the host restatement
  * (tables.cpp: flac_encode_block) and the kernels (k_flac.h) the way sau_dev_math.h is: candidate samples, residuals, the
  * zigzag, the cost of a Rice partition, the choice of order, of partitions and of the channel assignment, the frame header and
- * the two CRCs. Everything is integer arithmetic, so host and device agree by construction; what differs between them is only
- * who walks the samples. */
+ * the two CRCs, and the LPC mode's window, Levinson-Durbin recursion, quantisation and choice. Everything summed over a block
+ * is integer arithmetic, and the LPC mode's few f64 steps are serial with a stated order, so host and device agree by
+ * construction; what differs between them is only who walks the samples. */
 #ifndef SAU_FLAC_H
 #define SAU_FLAC_H
 #include <stdint.h>
@@ -21,7 +22,8 @@ constexpr uint64_t FLAC_MAX_BLOCKS = 0x7fffffffull;  /* per row: the frame numbe
 constexpr uint64_t FLAC_MAX_UNREAD = 1ull << 30;     /* bytes of unread output on the device */
 constexpr unsigned FLAC_K_MAX = 14, FLAC_NK = 15;    /* Rice parameters 0 .. 14; 15 is the escape, never used */
 constexpr unsigned FLAC_FINE = 16, FLAC_NODES = 31;  /* finest partitions of a whole block; (p, partition) pairs for p = 0 .. 4 */
-enum : uint8_t { FLAC_CONSTANT = 0, FLAC_VERBATIM = 1, FLAC_FIXED = 2 };
+enum : uint8_t { FLAC_CONSTANT = 0, FLAC_VERBATIM = 1, FLAC_FIXED = 2, FLAC_LPC = 3 };
+constexpr unsigned FLAC_LPC_MAX = 8, FLAC_LPC_PREC = 12; /* max_lpc_order's largest value; bits of a quantised coefficient */
 enum : uint8_t { FLAC_CAND_L = 0, FLAC_CAND_R = 1, FLAC_CAND_M = 2, FLAC_CAND_S = 3 };
 
 /* 0 stands for 4096; 0 when the size is not allowed */
@@ -35,13 +37,16 @@ SAU_FLAC_HD uint32_t flac_frame_bound(uint32_t n, uint32_t channels) { return 15
 /* What a block's choices come to for one channel: kind, order, partition order and the partitions' Rice parameters. */
 struct FlacSub {
 	uint8_t cand;     /* FLAC_CAND_* */
-	uint8_t type;     /* FLAC_CONSTANT, _VERBATIM, _FIXED */
-	uint8_t order;    /* FIXED: 0 .. 4 */
-	uint8_t p;        /* FIXED: partition order, 0 .. 4 */
-	uint8_t k[FLAC_FINE]; /* FIXED: partition j's parameter, j < 2^p */
+	uint8_t type;     /* FLAC_CONSTANT, _VERBATIM, _FIXED, _LPC */
+	uint8_t order;    /* FIXED: 0 .. 4; LPC: 1 .. 8 */
+	uint8_t p;        /* FIXED, LPC: partition order, 0 .. 4 */
+	uint8_t k[FLAC_FINE]; /* FIXED, LPC: partition j's parameter, j < 2^p */
 	uint32_t bits;    /* the whole subframe */
+	int16_t q[FLAC_LPC_MAX]; /* LPC: the quantised coefficients, q[0] the most recent sample's; zeros otherwise */
+	uint8_t shift;    /* LPC: 0 .. 15 */
+	uint8_t pad_[3];
 };
-static_assert(sizeof(FlacSub) == 24, "FlacSub is read by the kernels as it stands");
+static_assert(sizeof(FlacSub) == 44, "FlacSub is read by the kernels as it stands");
 struct FlacFrameDesc {
 	uint32_t n;       /* frames in the block */
 	uint32_t bytes;   /* of the whole frame, CRC-16 included */
@@ -51,7 +56,7 @@ struct FlacFrameDesc {
 	uint8_t pad_[2];
 	FlacSub sub[2];
 };
-static_assert(sizeof(FlacFrameDesc) == 64, "FlacFrameDesc is read by the kernels as it stands");
+static_assert(sizeof(FlacFrameDesc) == 104, "FlacFrameDesc is read by the kernels as it stands");
 
 /* a frame as one word: the left (or only) sample in the low half, the right one in the high half */
 SAU_FLAC_HD uint32_t flac_pack(int16_t l, int16_t r) { return (uint32_t)(uint16_t)l | ((uint32_t)(uint16_t)r << 16); }
@@ -121,6 +126,8 @@ SAU_FLAC_HD void flac_finish_sub(FlacSub *s, unsigned cand, uint32_t n, bool all
 	const unsigned bps = flac_cand_bps(cand);
 	s->cand = (uint8_t)cand; s->order = 0; s->p = 0;
 	for (unsigned j = 0; j < FLAC_FINE; ++j) s->k[j] = 0;
+	for (unsigned j = 0; j < FLAC_LPC_MAX; ++j) s->q[j] = 0;
+	s->shift = 0; s->pad_[0] = s->pad_[1] = s->pad_[2] = 0;
 	if (all_equal) { s->type = FLAC_CONSTANT; s->bits = 8 + bps; return; }
 	uint64_t best = ~0ull;
 	unsigned bp = 0;
@@ -133,6 +140,111 @@ SAU_FLAC_HD void flac_finish_sub(FlacSub *s, unsigned cand, uint32_t n, bool all
 	if (verbatim <= fixed) { s->type = FLAC_VERBATIM; s->bits = (uint32_t)verbatim; return; }
 	s->type = FLAC_FIXED; s->order = (uint8_t)o; s->p = (uint8_t)bp; s->bits = (uint32_t)fixed;
 	for (unsigned j = 0; j < (1u << bp); ++j) s->k[j] = node_k[flac_node_index(bp, j)];
+}
+
+/* ---- the LPC mode (include/saugns_amd.h, FLAC, "The LPC mode": the steps' numbers are those of that text) ----
+ * Sums over a block are integers, so whoever adds them in whatever order gets the same; the floating-point steps are a short
+ * serial sequence of IEEE f64 operations in a stated order (the build is -ffp-contract=off), done by one lane or one thread. */
+/* step 1: the window's value at j, 0 .. 4095, and a windowed sample (|s| < 2^17: the product fits 32 bits) */
+SAU_FLAC_HD int32_t flac_lpc_window(uint32_t j, uint32_t B, unsigned log2B) {
+	const int32_t d = (int32_t)(2 * j + 1) - (int32_t)B;
+	return (int32_t)((B * B - (uint32_t)(d * d)) >> (2 * log2B - 12));
+}
+SAU_FLAC_HD int32_t flac_lpc_windowed(int32_t s, int32_t w) { return (s * w) >> 3; }
+/* step 3: the least shift that brings R[0] below 2^53 */
+SAU_FLAC_HD unsigned flac_lpc_f64_shift(int64_t r0) {
+	unsigned g = 0;
+	while ((r0 >> g) >= (1ll << 53)) ++g;
+	return g;
+}
+SAU_FLAC_HD uint64_t flac_f64_bits(double x) { uint64_t b; __builtin_memcpy(&b, &x, 8); return b; }
+SAU_FLAC_HD double flac_f64_of_bits(uint64_t b) { double x; __builtin_memcpy(&x, &b, 8); return x; }
+/* steps 4 and 5: from r[0 .. M] the quantised coefficients of every candidate order m: q[(m - 1) * 8 + j], shift[m - 1]; bit
+ * m - 1 of the result is set where order m is a candidate. a[M] is work space (the kernels hand in LDS: every array here is
+ * indexed at run time). */
+SAU_FLAC_HD uint32_t flac_lpc_orders(const double *r, unsigned M, double *a, int16_t *q, uint8_t *shift) {
+	uint32_t mask = 0;
+	for (unsigned j = 0; j < M; ++j) a[j] = 0.0;
+	double err = r[0];
+	for (unsigned i = 0; i < M; ++i) {
+		double acc = r[i + 1];
+		for (unsigned j = 0; j < i; ++j) acc = acc + a[j] * r[i - j];
+		const double k = -acc / err;
+		a[i] = k;
+		for (unsigned j = 0; j < i / 2; ++j) {
+			const double t = a[j], u = a[i - 1 - j];
+			a[j] = t + k * u;
+			a[i - 1 - j] = u + k * t;
+		}
+		if (i & 1u) { const double t = a[i / 2]; a[i / 2] = t + k * t; }
+		err = err * (1.0 - k * k);
+		if (!(err > 0.0) || ((flac_f64_bits(err) >> 52) & 0x7ffu) == 0x7ffu) break;
+		const unsigned m = i + 1;
+		double cmax = 0.0;
+		for (unsigned j = 0; j < m; ++j) {
+			const double x = flac_f64_of_bits(flac_f64_bits(a[j]) & 0x7fffffffffffffffull);
+			if (x > cmax) cmax = x;
+		}
+		const unsigned field = (unsigned)(flac_f64_bits(cmax) >> 52) & 0x7ffu;
+		if (field == 0 || field == 0x7ffu) continue; /* 0 or subnormal; not finite */
+		int sh = (int)FLAC_LPC_PREC - 1 - ((int)field - 1022);
+		if (sh > 15) sh = 15;
+		if (sh < 0) continue;
+		const double scale = flac_f64_of_bits((uint64_t)(1023 + sh) << 52);
+		double E = 0.0;
+		for (unsigned j = 0; j < m; ++j) {
+			E = E + (-a[j]) * scale;
+			const double v = __builtin_floor(E + 0.5);
+			const int32_t qi = v < -2048.0 ? -2048 : v > 2047.0 ? 2047 : (int32_t)v;
+			q[i * FLAC_LPC_MAX + j] = (int16_t)qi;
+			E = E - (double)qi;
+		}
+		shift[i] = (uint8_t)sh;
+		mask |= 1u << i;
+	}
+	return mask;
+}
+/* step 6 from the sum of q[j] * s_{i-1-j} */
+SAU_FLAC_HD int32_t flac_lpc_residual(int32_t s0, int32_t sum, unsigned shift) { return s0 - (sum >> shift); }
+/* step 7: what order m is estimated to cost, from A_m */
+SAU_FLAC_HD uint64_t flac_lpc_est(uint64_t abs_sum, uint32_t n, unsigned M, unsigned m, unsigned bps) {
+	uint64_t best = ~0ull;
+	for (unsigned k = 0; k < FLAC_NK; ++k) {
+		const uint64_t c = (uint64_t)(1 + k) * (n - M) + ((2 * abs_sum) >> k);
+		if (c < best) best = c;
+	}
+	return best + (uint64_t)m * (bps + FLAC_LPC_PREC);
+}
+/* the candidate order with the least estimate, the lowest on ties; 0 when there is none */
+SAU_FLAC_HD unsigned flac_lpc_pick_order(uint32_t mask, const uint64_t *abs_sum /* [m - 1] */, uint32_t n, unsigned M, unsigned bps) {
+	unsigned best = 0;
+	uint64_t least = ~0ull;
+	for (unsigned m = 1; m <= M; ++m)
+		if (mask & (1u << (m - 1))) {
+			const uint64_t e = flac_lpc_est(abs_sum[m - 1], n, M, m, bps);
+			if (e < least) { least = e; best = m; }
+		}
+	return best;
+}
+/* steps 8 and 9 on a record flac_finish_sub has left as VERBATIM or FIXED (the cheaper of the two, VERBATIM on ties): LPC of
+ * order m takes its place where it costs less. node_cost, node_k: the nodes of the LPC residual's partitions (o = m). */
+SAU_FLAC_HD void flac_lpc_choose(FlacSub *s, uint32_t n, unsigned m, const int16_t *q, unsigned shift, unsigned fine_log2,
+		const uint64_t *node_cost, const uint8_t *node_k) {
+	if (s->type == FLAC_CONSTANT) return;
+	const unsigned bps = flac_cand_bps(s->cand);
+	uint64_t best = ~0ull;
+	unsigned bp = 0;
+	for (unsigned p = 0; p <= fine_log2; ++p) {
+		uint64_t c = 0;
+		for (unsigned j = 0; j < (1u << p); ++j) c += 4 + node_cost[flac_node_index(p, j)];
+		if (c < best) { best = c; bp = p; }
+	}
+	const uint64_t lpc = 8 + (uint64_t)bps * m + 4 + 5 + (uint64_t)FLAC_LPC_PREC * m + 6 + best;
+	if (lpc >= s->bits) return;
+	s->type = FLAC_LPC; s->order = (uint8_t)m; s->p = (uint8_t)bp; s->bits = (uint32_t)lpc; s->shift = (uint8_t)shift;
+	for (unsigned j = 0; j < FLAC_FINE; ++j) s->k[j] = 0;
+	for (unsigned j = 0; j < (1u << bp); ++j) s->k[j] = node_k[flac_node_index(bp, j)];
+	for (unsigned j = 0; j < m; ++j) s->q[j] = q[j];
 }
 
 /* the bytes of a frame number in the extended UTF-8 coding, and of a frame header: sync and codes, the number, n - 1 where

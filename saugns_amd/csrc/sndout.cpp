@@ -507,7 +507,7 @@ bool measure_spectrum(const sauProgram *prg, uint32_t srate, int factor, int cha
  * of one stream where that writer fetches it, the last feed a finish. A read brings the run's frames into a page-locked slot;
  * the slot before it goes to the file once the next run has been queued, so the file is written while the device renders.
  * The encoder goes before the engine, which owns the backend. */
-bool write_flac(const sauProgram *prg, uint32_t srate, const char *path, int channels, uint32_t block_frames,
+bool write_flac(const sauProgram *prg, uint32_t srate, const char *path, int channels, uint32_t block_frames, uint32_t max_lpc_order,
 		Backend *backend /* owned */, uint64_t *frames_out, sauengine::FlacInfo *info_out, std::string &err) {
 	Engine *engine = Engine::create(&prg, 1, srate, backend, err);
 	if (!engine) return false;
@@ -517,7 +517,7 @@ bool write_flac(const sauProgram *prg, uint32_t srate, const char *path, int cha
 	file_lattice(srate, call, chunk);
 	engine->set_call_len(call);
 	/* a backend without an encoder says so here, before there is a file */
-	sauengine::FlacEncoder *enc = backend->create_flac(1, (uint32_t)channels, B, err);
+	sauengine::FlacEncoder *enc = backend->create_flac_lpc(1, (uint32_t)channels, B, max_lpc_order, err);
 	if (!enc) { delete engine; return false; }
 	/* what a run can come to: the blocks it completes, with what was pending, and a last short one, each at its bound */
 	const size_t slot_bytes = (chunk / B + 2) * (size_t)sauflac::flac_frame_bound(B, (uint32_t)channels);
@@ -773,14 +773,20 @@ extern "C" bool sauAmd_render_spectrum(const sauProgram *prg, uint32_t srate, in
 
 bool sauamd_internal::render_file_flac(const sauProgram *prg, uint32_t srate, const char *path, int channels, uint32_t block_frames,
 		const std::function<Backend *(std::string &)> &make_backend, uint64_t *frames_out, sauAmdFlacInfo *info_out, std::string &err) {
+	return render_file_flac_lpc(prg, srate, path, channels, block_frames, 0, make_backend, frames_out, info_out, err);
+}
+
+bool sauamd_internal::render_file_flac_lpc(const sauProgram *prg, uint32_t srate, const char *path, int channels, uint32_t block_frames,
+		uint32_t max_lpc_order, const std::function<Backend *(std::string &)> &make_backend, uint64_t *frames_out, sauAmdFlacInfo *info_out,
+		std::string &err) {
 	if (frames_out) *frames_out = 0;
-	if (!prg || !path || !srate || srate > 655350u || !sauengine::flac_params_ok(channels, block_frames)) {
+	if (!prg || !path || !srate || srate > 655350u || !sauengine::flac_params_ok(channels, block_frames) || max_lpc_order > sauflac::FLAC_LPC_MAX) {
 		err = "bad argument";
 		return false;
 	}
 	Backend *backend = make_backend(err);
 	if (!backend) return false;
-	return write_flac(prg, srate, path, channels, block_frames, backend, frames_out, (sauengine::FlacInfo *)info_out, err);
+	return write_flac(prg, srate, path, channels, block_frames, max_lpc_order, backend, frames_out, (sauengine::FlacInfo *)info_out, err);
 }
 
 extern "C" bool sauAmd_render_file_flac(const sauProgram *prg, uint32_t srate, const char *path, int channels, uint32_t block_frames,
@@ -789,6 +795,20 @@ extern "C" bool sauAmd_render_file_flac(const sauProgram *prg, uint32_t srate, c
 	bool ok = false;
 	try {
 		ok = sauamd_internal::render_file_flac(prg, srate, path, channels, block_frames,
+				[](std::string &e) -> Backend * { return sauhip::create_hip_backend(e); }, frames_out, info_out, err);
+	} catch (const std::exception &ex) { /* (nothing C++ crosses the C ABI) */
+		err = std::string("internal error: ") + ex.what();
+	}
+	if (!ok) sauamd_internal::set_last_error("output", err);
+	return ok;
+}
+
+extern "C" bool sauAmd_render_file_flac_lpc(const sauProgram *prg, uint32_t srate, const char *path, int channels, uint32_t block_frames,
+		uint32_t max_lpc_order, uint64_t *frames_out, sauAmdFlacInfo *info_out) {
+	std::string err;
+	bool ok = false;
+	try {
+		ok = sauamd_internal::render_file_flac_lpc(prg, srate, path, channels, block_frames, max_lpc_order,
 				[](std::string &e) -> Backend * { return sauhip::create_hip_backend(e); }, frames_out, info_out, err);
 	} catch (const std::exception &ex) { /* (nothing C++ crosses the C ABI) */
 		err = std::string("internal error: ") + ex.what();

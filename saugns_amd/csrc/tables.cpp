@@ -437,14 +437,33 @@ size_t flac_header(uint32_t srate, int channels, uint32_t block_frames, const Fl
 }
 
 size_t flac_encode_block(const int16_t *x, uint32_t n, int channels, uint32_t block_frames, uint32_t frame_number, uint8_t *out, size_t cap) {
+	return flac_encode_block_lpc(x, n, channels, block_frames, frame_number, 0, out, cap);
+}
+
+size_t flac_encode_block_lpc(const int16_t *x, uint32_t n, int channels, uint32_t block_frames, uint32_t frame_number, uint32_t max_lpc_order,
+		uint8_t *out, size_t cap) {
 	using namespace sauflac;
 	const uint32_t B = flac_block_frames(block_frames);
-	if (!x || !B || !n || n > B || (channels != 1 && channels != 2) || frame_number > FLAC_MAX_BLOCKS) return 0;
+	if (!x || !B || !n || n > B || (channels != 1 && channels != 2) || frame_number > FLAC_MAX_BLOCKS || max_lpc_order > FLAC_LPC_MAX) return 0;
+	const unsigned M = max_lpc_order;
 	const unsigned ch = (unsigned)channels, n_cand = ch == 2 ? 4 : 1, fine_log2 = n == B ? 4 : 0, F = 1u << fine_log2;
 	uint32_t *w = new uint32_t[n];
 	for (uint32_t i = 0; i < n; ++i) w[i] = ch == 2 ? flac_pack(x[2 * i], x[2 * i + 1]) : flac_pack(x[i], 0);
 	auto at = [&](unsigned c, int64_t i) -> int32_t { return i >= 0 ? flac_cand(w[i], c) : 0; };
 	auto resid = [&](unsigned c, unsigned o, uint32_t i) { return flac_residual(o, at(c, i), at(c, (int64_t)i - 1), at(c, (int64_t)i - 2), at(c, (int64_t)i - 3), at(c, (int64_t)i - 4)); };
+	auto resid_lpc = [&](unsigned c, const int16_t *q, unsigned m, unsigned shift, uint32_t i) { /* (i >= m) */
+		int32_t sum = 0;
+		for (unsigned j = 0; j < m; ++j) sum += (int32_t)q[j] * at(c, (int64_t)i - 1 - j);
+		return flac_lpc_residual(at(c, i), sum, shift);
+	};
+	auto nodes = [&](const uint64_t *fine, unsigned fine_log2, unsigned o, uint64_t *node_cost, uint8_t *node_k) {
+		for (unsigned p = 0; p <= fine_log2; ++p)
+			for (unsigned j = 0; j < (1u << p); ++j) {
+				unsigned k;
+				node_cost[flac_node_index(p, j)] = flac_node_cost(fine, fine_log2, p, j, n, o, &k);
+				node_k[flac_node_index(p, j)] = (uint8_t)k;
+			}
+	};
 	FlacSub cand[4];
 	for (unsigned c = 0; c < n_cand; ++c) {
 		bool equal = true;
@@ -465,13 +484,40 @@ size_t flac_encode_block(const int16_t *x, uint32_t n, int channels, uint32_t bl
 		}
 		uint64_t node_cost[FLAC_NODES];
 		uint8_t node_k[FLAC_NODES];
-		for (unsigned p = 0; p <= fine_log2; ++p)
-			for (unsigned j = 0; j < (1u << p); ++j) {
-				unsigned k;
-				node_cost[flac_node_index(p, j)] = flac_node_cost(fine, fine_log2, p, j, n, o, &k);
-				node_k[flac_node_index(p, j)] = (uint8_t)k;
-			}
+		nodes(fine, fine_log2, o, node_cost, node_k);
 		flac_finish_sub(&cand[c], c, n, equal, o, fine_log2, node_cost, node_k);
+		if (!M || n != B || equal) continue;
+		/* the LPC mode: the windowed autocorrelation in integers, the orders' coefficients, the order, its partitions */
+		unsigned log2B = 0;
+		while ((1u << log2B) < B) ++log2B;
+		int64_t R[FLAC_LPC_MAX + 1];
+		for (unsigned l = 0; l <= M; ++l) {
+			R[l] = 0;
+			for (uint32_t i = l; i < n; ++i)
+				R[l] += (int64_t)flac_lpc_windowed(at(c, i), flac_lpc_window(i, B, log2B)) * flac_lpc_windowed(at(c, i - l), flac_lpc_window(i - l, B, log2B));
+		}
+		if (R[0] == 0) continue;
+		const unsigned g = flac_lpc_f64_shift(R[0]);
+		double r[FLAC_LPC_MAX + 1], a[FLAC_LPC_MAX];
+		for (unsigned l = 0; l <= M; ++l) r[l] = (double)(R[l] >> g);
+		int16_t q[FLAC_LPC_MAX * FLAC_LPC_MAX];
+		uint8_t shift[FLAC_LPC_MAX];
+		const uint32_t mask = flac_lpc_orders(r, M, a, q, shift);
+		uint64_t lpc_abs[FLAC_LPC_MAX];
+		for (unsigned m = 1; m <= M; ++m) {
+			lpc_abs[m - 1] = 0;
+			if (mask & (1u << (m - 1)))
+				for (uint32_t i = M; i < n; ++i) lpc_abs[m - 1] += flac_abs(resid_lpc(c, q + (m - 1) * FLAC_LPC_MAX, m, shift[m - 1], i));
+		}
+		const unsigned m = flac_lpc_pick_order(mask, lpc_abs, n, M, flac_cand_bps(c));
+		if (!m) continue;
+		memset(fine, 0, sizeof fine);
+		for (uint32_t i = m; i < n; ++i) {
+			const uint32_t u = flac_zigzag(resid_lpc(c, q + (m - 1) * FLAC_LPC_MAX, m, shift[m - 1], i));
+			for (unsigned k = 0; k < FLAC_NK; ++k) fine[(i / plen) * FLAC_NK + k] += u >> k;
+		}
+		nodes(fine, fine_log2, m, node_cost, node_k);
+		flac_lpc_choose(&cand[c], n, m, q + (m - 1) * FLAC_LPC_MAX, shift[m - 1], fine_log2, node_cost, node_k);
 	}
 	FlacFrameDesc d;
 	flac_finish_frame(&d, cand, ch, n, B, frame_number);
@@ -485,18 +531,24 @@ size_t flac_encode_block(const int16_t *x, uint32_t n, int channels, uint32_t bl
 		const FlacSub &s = d.sub[si];
 		const unsigned c = s.cand, bps = flac_cand_bps(c);
 		const uint32_t mask = bps == 17 ? 0x1ffffu : 0xffffu;
-		bw.put(s.type == FLAC_CONSTANT ? 0u : s.type == FLAC_VERBATIM ? 2u : (uint32_t)(0x10u | (s.order << 1)), 8); /* 0 tttttt 0 */
+		bw.put(s.type == FLAC_CONSTANT ? 0u : s.type == FLAC_VERBATIM ? 2u : s.type == FLAC_LPC ? (uint32_t)(0x40u | ((s.order - 1u) << 1)) :
+				(uint32_t)(0x10u | (s.order << 1)), 8); /* 0 tttttt 0 */
 		if (s.type == FLAC_CONSTANT) bw.put((uint32_t)at(c, 0) & mask, bps);
 		else if (s.type == FLAC_VERBATIM) for (uint32_t i = 0; i < n; ++i) bw.put((uint32_t)at(c, i) & mask, bps);
 		else {
 			for (uint32_t i = 0; i < s.order; ++i) bw.put((uint32_t)at(c, i) & mask, bps);
+			if (s.type == FLAC_LPC) {
+				bw.put(FLAC_LPC_PREC - 1, 4);
+				bw.put(s.shift, 5);
+				for (uint32_t i = 0; i < s.order; ++i) bw.put((uint32_t)s.q[i] & 0xfffu, FLAC_LPC_PREC);
+			}
 			bw.put(s.p, 6); /* 00 pppp */
 			const uint32_t plen = n >> s.p;
 			for (uint32_t j = 0; j < (1u << s.p); ++j) {
 				const unsigned k = s.k[j];
 				bw.put(k, 4);
 				for (uint32_t i = j ? j * plen : s.order; i < (j + 1) * plen; ++i) {
-					const uint32_t u = flac_zigzag(resid(c, s.order, i));
+					const uint32_t u = flac_zigzag(s.type == FLAC_LPC ? resid_lpc(c, s.q, s.order, s.shift, i) : resid(c, s.order, i));
 					bw.zeros(u >> k);
 					bw.put((1u << k) | (u & ((1u << k) - 1)), k + 1);
 				}
