@@ -254,9 +254,10 @@ static bool raise_lds_attr(const void *fn, size_t lds, int dev, std::string &err
  * build's 8-row one). Forms: wide table blocks in LDS (k_fast_types.h: FkTab -- the closed-form build at 6, 8, 10 and 12 rows,
  * the look-back build at 8: round 5, where the lean buffer numbering leaves LDS for them), the look-back build that mixes
  * few-voice streams (round 6: FastParams.tail_ok), the builds with the loop tails of `cub` R segments, the inner launch of the
- * 12-row build (k_fast_voice.h: INNER) and its lane-major form (k_fast_group_lm.h).
+ * 12-row build (k_fast_voice.h: INNER), its lane-major form (k_fast_group_lm.h) and that form for launches of one table
+ * (round 10: fk_entry's TAB0; only in a -DFK_LM_TAB0=1 build -- by default every launch takes the form that adds the table's base).
  * (The table's order is the order the instantiations take in the code object.) */
-enum : unsigned { FK_WIDE = 1, FK_TAIL = 2, FK_CUB = 4, FK_INNER = 8, FK_LANEMAJOR = 16 };
+enum : unsigned { FK_WIDE = 1, FK_TAIL = 2, FK_CUB = 4, FK_INNER = 8, FK_LANEMAJOR = 16, FK_TAB0 = 32 };
 static const void *fast_kernel_fn(int build, uint32_t rows, unsigned form) {
 	struct Entry { int build; uint32_t rows; unsigned form; const void *fn; };
 #define FK(build, form, ...) {build, FK_ROWS(__VA_ARGS__), form, (const void *)fast_kernel<__VA_ARGS__>}
@@ -270,6 +271,9 @@ static const void *fast_kernel_fn(int build, uint32_t rows, unsigned form) {
 		FK(2, FK_WIDE | FK_TAIL, 8, 2, false, true, true), FK(2, FK_WIDE, 8, 2, false, true), FK(2, FK_TAIL, 8, 2, false, false, true),
 		FK(2, FK_CUB, (int)FAST_CUB_ROWS, 2, true),
 		FK(0, FK_WIDE | FK_INNER | FK_LANEMAJOR, 12, 0, false, true, false, true, true), FK(0, FK_WIDE | FK_INNER, 12, 0, false, true, false, true),
+#if FK_LM_TAB0
+		FK(0, FK_WIDE | FK_INNER | FK_LANEMAJOR | FK_TAB0, 12, 0, false, true, false, true, true, true),
+#endif
 		FK(0, FK_CUB, (int)FAST_CUB_ROWS, 0, true)};
 #undef FK
 #undef FK_ROWS
@@ -277,6 +281,13 @@ static const void *fast_kernel_fn(int build, uint32_t rows, unsigned form) {
 		if (e.build == build && e.rows == rows && e.form == form) return e.fn;
 	return nullptr;
 }
+#if FK_LM_TAB0
+/* fk_entry's TAB0 form reads the table at LDS address 0: only while the kernel has no static __shared__ ahead of its dynamic block */
+static bool tab0_kernel_ok(const void *fn) {
+	static const bool ok = [&] { hipFuncAttributes a; return fn && hipFuncGetAttributes(&a, fn) == hipSuccess && a.sharedSizeBytes == 0; }();
+	return ok;
+}
+#endif
 static const void *repair_kernel_fn(uint32_t rows, bool wide) {
 	if (wide)
 		return rows == 12 ? (const void *)repair_kernel<12, true> : rows == 10 ? (const void *)repair_kernel<10, true>
@@ -1128,7 +1139,13 @@ public:
 		}
 		if (k.inner != INNER_NONE) {
 			const bool lm = k.inner == INNER_LANE_MAJOR;
-			const void *ik = fast_kernel_fn(0, 12, FK_WIDE | FK_INNER | (lm ? FK_LANEMAJOR : 0u));
+#if FK_LM_TAB0
+			const bool tab0 = lm && k.inner_tab0 && tab0_kernel_ok(fast_kernel_fn(0, 12, FK_WIDE | FK_INNER | FK_LANEMAJOR | FK_TAB0)); /* (one table: the instantiation whose table address is the index alone) */
+#else
+			const bool tab0 = false;
+#endif
+			const void *ik = fast_kernel_fn(0, 12, FK_WIDE | FK_INNER | (lm ? FK_LANEMAJOR : 0u) | (tab0 ? FK_TAB0 : 0u));
+			if (!ik) { err = "no inner instantiation of fast_kernel for this form"; return false; }
 			const size_t lds = k.inner_lds();
 			FastParams ep = fp;
 			ep.mode = 0; ep.edge_only = 1; ep.dyn_static = 1; ep.dyn_chunks = 2; ep.dyn_small = 0; ep.inmix_flags = 0; /* (two tasks a voice: its first group, its last) */
@@ -1140,7 +1157,7 @@ public:
 			if (!raise_lds_attr(ik, lds, dev_, err)) return false;
 			if (fp.inmix_flags && !pcm_hazard(err)) return false; /* (the inner launch mixes tiles into the PCM itself) */
 			HIP_OK(hipLaunchKernel(ik, dim3(k.grid), dim3(1024), iargs, lds, stream_));
-			if (inner_report_) fprintf(stderr, "[sau-amd] inner: %s, %u voices\n", lm ? "lane-major" : "row-major", seg.n_voices);
+			if (inner_report_) fprintf(stderr, "[sau-amd] inner: %s, %u voices, %u tables%s\n", lm ? "lane-major" : "row-major", seg.n_voices, k.tabs.n, tab0 ? ", tab0" : "");
 		} else {
 			/* (a closed-form segment that did not take the two launches, and what kept it from them) */
 			if (inner_report_) fprintf(stderr, "[sau-amd] inner: none (rows %u, wide %d, chunks %u), %u voices\n", k.rows, k.wide_cf ? 1 : 0, fp.dyn_chunks, seg.n_voices);

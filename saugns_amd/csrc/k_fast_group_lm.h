@@ -106,9 +106,95 @@
 						}
 						if (ok) {
 							const uint32_t ltab = tabs + (uint32_t)f.tab * FkTab<WIDE>::BYTES;
-							double Is[T];
+							/* The Hermite values in frame order, handed to `sink` two samples at a time (k of the first, the two values).
+							 * FK_LM_AHEAD: a window of table entries, a pair of samples to a slot -- the gathers of the pairs ahead are
+							 * issued, then (a fence for the compiler's scheduler, no instruction) this pair's arithmetic, which the sink's
+							 * FK_LM_PIN ends: its waits count only its own entries' reads, and the later pairs' stay in flight across it.
+							 * Left to itself the compiler puts each pair's gather right ahead of its polynomials and waits there, six
+							 * times per operator and group. */
+							static_assert(T % 2 == 0, "pairs of samples");
+							auto hermite = [&](auto &&sink) {
+#if FK_LM_AHEAD > 0
+								constexpr int NP2 = T / 2, A = FK_LM_AHEAD < NP2 ? FK_LM_AHEAD : NP2 - 1, NS = A + 1;
+								FkHerp q[2 * NS];
 #pragma unroll
-							for (int k = 0; k < T; ++k) Is[k] = fk_poly(fk_entry<WIDE>(ltab, ph[k]), ph[k]);
+								for (int p = 0; p < A; ++p) {
+									q[2 * p] = fk_entry<WIDE, TAB0, true>(ltab, ph[2 * p]);
+									q[2 * p + 1] = fk_entry<WIDE, TAB0, true>(ltab, ph[2 * p + 1]);
+								}
+#pragma unroll
+								for (int p = 0; p < NP2; ++p) {
+									if (p + A < NP2) {
+										const int sl = (p + A) % NS;
+										q[2 * sl] = fk_entry<WIDE, TAB0, true>(ltab, ph[2 * (p + A)]);
+										q[2 * sl + 1] = fk_entry<WIDE, TAB0, true>(ltab, ph[2 * (p + A) + 1]);
+									}
+									__builtin_amdgcn_sched_barrier(0);
+									const int sl = p % NS;
+									sink(2 * p, fk_poly(q[2 * sl], ph[2 * p]), fk_poly(q[2 * sl + 1], ph[2 * p + 1]));
+								}
+#define FK_LM_PIN(...) asm volatile("" : __VA_ARGS__) /* (the values are computed here, ahead of the next fence) */
+#else
+#pragma unroll
+								for (int k = 0; k < T; k += 2)
+									sink(k, fk_poly(fk_entry<WIDE, TAB0>(ltab, ph[k]), ph[k]), fk_poly(fk_entry<WIDE, TAB0>(ltab, ph[k + 1]), ph[k + 1]));
+#define FK_LM_PIN(...) ((void)0)
+#endif
+							};
+#if FK_LM_ONE_PHASE_SET
+							/* A sample's differentiator right behind its polynomial: it reads ph[k] and ph[k - 1] there, so the phases' last
+							 * use is inside the Hermite loop and they live in one register set (as two loops the compiler kept a second copy
+							 * for the differentiators: 6-18 moves per operator and group and twelve registers), and of the Hermite values
+							 * only the one before and the lane's first are kept, not T. Register 0's output comes last: its frame before
+							 * is lane l - 1's register T - 1. The same operations on the same operands as the two loops. */
+							double I0 = 0., Ip = 0.;
+							if (FK_CONSTD && !has_pm && f.inc != 0) {
+								/* unmodulated: every phase step is inc, one division serves all */
+								const double x = (double)div_f32_normal(f.diff_scale, (float)(int32_t)f.inc);
+								hermite([&](const int k, const double Ia, const double Ib) {
+									if (k == 0) I0 = Ia;
+									else s[k] = (float)((Ia - Ip) * x + (double)f.diff_offset);
+									s[k + 1] = (float)((Ib - Ia) * x + (double)f.diff_offset);
+									Ip = Ib;
+									if (k == 0) FK_LM_PIN("+v"(I0), "+v"(s[1]));
+									else FK_LM_PIN("+v"(s[k]), "+v"(s[k + 1]));
+								});
+								s[0] = (float)((I0 - lane_prev(Ip)) * x + (double)f.diff_offset);
+								done = true;
+							} else {
+								/* a phase step of zero anywhere: the unsigned minimum of the steps (v_min_u32, k_fast_group.h) */
+								uint32_t dmin = 0xffffffffu;
+								uint32_t pp = lane_prev(ph[T - 1]);
+								asm("" : "+v"(pp)); /* (keeps the DPP move a move: k_fast_group.h) */
+								const int32_t d0 = (int32_t)(ph[0] - pp);
+								/* (this branch takes the phases through an empty asm: the two copies of the Hermite loop then share no
+								 * expression, and the compiler does not compute all T addresses and fractions -- 36 registers -- ahead of
+								 * the branch for both) */
+#pragma unroll
+								for (int k = 0; k < T; ++k) asm volatile("" : "+v"(ph[k]));
+								double x0 = 0.;
+								hermite([&](const int k, const double Ia, const double Ib) {
+									/* wosc_diff (sau_dev_math.h) on the two samples, their divisions as one packed sequence */
+									const int32_t da = k == 0 ? d0 : (int32_t)(ph[k] - ph[k - 1]), db = (int32_t)(ph[k + 1] - ph[k]);
+									dmin = min(dmin, min((uint32_t)da, (uint32_t)db));
+									const fk_f32x2 dv = {(float)da, (float)db};
+									const fk_f32x2 x = fk_div_diff_scale2(f.diff_scale, dv);
+									if (k == 0) { I0 = Ia; x0 = (double)x.x; }
+									else s[k] = (float)((Ia - Ip) * (double)x.x + (double)f.diff_offset);
+									s[k + 1] = (float)((Ib - Ia) * (double)x.y + (double)f.diff_offset);
+									Ip = Ib;
+									if (k == 0) FK_LM_PIN("+v"(I0), "+v"(x0), "+v"(s[1]), "+v"(dmin));
+									else FK_LM_PIN("+v"(s[k]), "+v"(s[k + 1]), "+v"(dmin));
+								});
+								s[0] = (float)((I0 - lane_prev(Ip)) * x0 + (double)f.diff_offset);
+								/* (a zero: the general path below, which starts from the step again, tells zeros on defined frames from
+								 * those on lead-in frames, which may have any, and computes every other frame as here -- the phases are
+								 * not kept for that test) */
+								done = !__any(dmin == 0u);
+							}
+#else
+							double Is[T];
+							hermite([&](const int k, const double Ia, const double Ib) { Is[k] = Ia; Is[k + 1] = Ib; FK_LM_PIN("+v"(Is[k]), "+v"(Is[k + 1])); });
 							if (FK_CONSTD && !has_pm && f.inc != 0) {
 								/* unmodulated: every phase step is inc, one division serves all */
 								const double x = (double)div_f32_normal(f.diff_scale, (float)(int32_t)f.inc);
@@ -136,6 +222,8 @@
 									done = !__any((hz & dm) != 0u);
 								}
 							}
+#endif
+#undef FK_LM_PIN
 						}
 					}
 					if (!done) {
@@ -143,9 +231,16 @@
 						double Is[T];
 						float fv[T]; /* frequency per frame (freq-scaled PM reads it) */
 						{
-							uint32_t acc = f.phase0 + f.inc * (uint32_t)(t0 + 1);
+							uint32_t inc = f.inc;
+#if FK_LM_ONE_PHASE_SET
+							/* (an increment the compiler cannot see through: these phases are computed here, where the rare step needs
+							 * them. As the common path's own expressions they were computed once ahead of both paths and the T
+							 * unmodulated phases held in registers across the common path for this one) */
+							asm volatile("" : "+s"(inc));
+#endif
+							uint32_t acc = f.phase0 + inc * (uint32_t)(t0 + 1);
 #pragma unroll
-							for (int k = 0; k < T; ++k) { ph[k] = acc; acc += f.inc; fv[k] = f.fc; }
+							for (int k = 0; k < T; ++k) { ph[k] = acc; acc += inc; fv[k] = f.fc; }
 						}
 						if (has_pm && !has_fpm) {
 							float pm[T];
@@ -169,7 +264,7 @@
 						if (f.tab >= 0) {
 							const uint32_t ltab = tabs + (uint32_t)f.tab * FkTab<WIDE>::BYTES;
 #pragma unroll
-							for (int k = 0; k < T; ++k) Is[k] = fk_poly(fk_entry<WIDE>(ltab, ph[k]), ph[k]);
+							for (int k = 0; k < T; ++k) Is[k] = fk_poly(fk_entry<WIDE, TAB0>(ltab, ph[k]), ph[k]);
 						} else {
 							const uint32_t wave = (f.type >> 8) & 0xff;
 							const HerpC23 *g23 = P.g_c23 + (size_t)wave * WAVE_LEN;

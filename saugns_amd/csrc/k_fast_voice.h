@@ -22,6 +22,19 @@
 #define FK_CLOAD(p) (*(p))
 #endif
 
+/* Round 10, the lane-major inner build's wave oscillator (k_fast_group_lm.h): three forms, each behind a macro
+ * (defaults: launch_plan.h, which plans by them); -D... builds the others (python saugns_amd/build.py --variant NAME DEFS...:
+ * the A/B libraries from one tree). (a) and (c) together take 5 % off config 3's inner launch as shipped (1.655 -> 1.574 ms).
+ * FK_LM_ONE_PHASE_SET  (a, on) the phases live in ONE register set: a sample's differentiator runs right behind its polynomial,
+ *                      so the Hermite loop holds each phase's last use (0: all the polynomials, then all the differentiators)
+ * FK_LM_TAB0           (b, off: measured, within noise) the instantiation for launches of one table, whose address is the index
+ *                      alone (fk_entry<true, true>)
+ * FK_LM_AHEAD          (c, on) the table gathers of the next FK_LM_AHEAD pairs of samples are issued before this pair's
+ *                      arithmetic (0: the compiler's own schedule, which waits for every pair's gather where it is issued) */
+#if FK_LM_ONE_PHASE_SET && !FK_LM_AHEAD
+#error "FK_LM_ONE_PHASE_SET needs FK_LM_AHEAD: without its fences the compiler's schedule of the one loop spills (216 VGPRs)"
+#endif
+
 /* lane l receives lane l-1's value (lane 0: zero; it is lead-in) */
 __device__ __forceinline__ uint32_t lane_prev(uint32_t x) {
 	return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x138 /* wave_shr:1 */, 0xf, 0xf, true);
@@ -39,15 +52,34 @@ typedef float __attribute__((ext_vector_type(4))) fk_f32x4;
 typedef const fk_f64x2 __attribute__((address_space(3))) *fk_lds_f64x2;
 typedef const fk_f32x2 __attribute__((address_space(3))) *fk_lds_f32x2;
 struct FkHerp { double c3, c2, c1, c0; };
-template <bool WIDE, bool TAB0 = false>
+typedef const volatile fk_f64x2 __attribute__((address_space(3))) *fk_lds_f64x2_ord;
+/* ORDERED (k_fast_group_lm.h: FK_LM_AHEAD): the two reads stay where they are written among the fences of the compiler's
+ * scheduler -- as plain loads from a table nobody writes they are tied to nothing, and instruction selection puts them where
+ * it likes (all twelve samples' ahead of the first polynomial: 96 registers). The same ds_read_b128. */
+template <bool WIDE, bool TAB0 = false, bool ORDERED = false>
 __device__ __forceinline__ FkHerp fk_entry(const uint32_t tab, const uint32_t ph) {
 	FkHerp h;
-	if (WIDE && TAB0) {
+	static_assert(!ORDERED || WIDE, "the ordered reads exist for the wide table block");
+	if (WIDE && ORDERED) {
+		uint32_t a;
+		if (TAB0) a = (ph >> (SLEN_BITS - 4)) & ((WAVE_LEN - 1) << 4);
+		else {
+			uint32_t ind = ph >> SLEN_BITS;
+			asm("" : "+v"(ind));
+			a = tab + (ind << 4);
+		}
+		const fk_f64x2 hi = *(fk_lds_f64x2_ord)(uintptr_t)a;
+		const fk_f64x2 lo = *(fk_lds_f64x2_ord)(uintptr_t)(a + FkTab<true>::C01);
+		h.c3 = hi.x; h.c2 = hi.y; h.c1 = lo.x; h.c0 = lo.y;
+	} else if (WIDE && TAB0) {
 		/* the table block at LDS address 0 (a launch's first table: every operator of a one-wave bank): the address is the
 		 * index alone, (ph >> 17) & 0x7ff0 -- two 2-cycle instructions where v_lshrrev + v_lshl_add (a 4-cycle one) stand --
-		 * and the [c1, c0] entry's 32 KiB go into the read's offset field. Round 5, measured and not used: a second copy of
-		 * the Hermite block under a uniform test of the table's address cost fast_kernel<12, 0, false, true> ten spilled VGPRs
-		 * and everything the cheaper address bought (1.784 against 1.757 ms per launch, profiles/r05_headline_ab.json) */
+		 * and the [c1, c0] entry's 32 KiB go into the read's offset field. Round 5 measured it as a second copy of the
+		 * Hermite block under a uniform test of the table's address inside fast_kernel<12, 0, false, true>: ten spilled VGPRs,
+		 * and everything the cheaper address bought gone (1.784 against 1.757 ms per launch, profiles/r05_headline_ab.json).
+		 * Round 10: an instantiation of its own of the lane-major inner build (fast_kernel's TAB0), which the host picks for
+		 * launches that stage ONE table (launch_plan.h: FastPlan.inner_tab0) -- no test of the address and no second copy of
+		 * the block inside any kernel. Within noise on config 3, so only a -DFK_LM_TAB0=1 build has it */
 		const uint32_t a = (ph >> (SLEN_BITS - 4)) & ((WAVE_LEN - 1) << 4);
 		const fk_f64x2 hi = *(fk_lds_f64x2)(uintptr_t)a;
 		const fk_f64x2 lo = *(fk_lds_f64x2)(uintptr_t)(a + FkTab<true>::C01);
@@ -77,6 +109,15 @@ __device__ __forceinline__ double fk_poly(const FkHerp &h, const uint32_t ph) {
 __device__ __forceinline__ double fk_poly_rise(const FkHerp &h, const uint32_t ph) {
 	const double x = (double)(ph & (SLEN - 1));
 	return ((h.c3 * x + h.c2) * x + h.c1) * x;
+}
+/* div_diff_scale (sau_dev_math.h) for two divisors at once: the same operations on each, as packed instructions (what the
+ * compiler's vectoriser made of two neighbouring samples' divisions where it found them) */
+__device__ __forceinline__ fk_f32x2 fk_div_diff_scale2(const float a, const fk_f32x2 b) {
+	fk_f32x2 r;
+	r.x = __builtin_amdgcn_rcpf(b.x); r.y = __builtin_amdgcn_rcpf(b.y);
+	const fk_f32x2 av = {a, a};
+	const fk_f32x2 q = av * r;
+	return __builtin_elementwise_fma(__builtin_elementwise_fma(-b, q, av), r, q);
 }
 /* stage the tables a launch uses into its LDS blocks (all threads of the workgroup; a barrier follows) */
 template <bool WIDE>
@@ -113,7 +154,8 @@ __device__ __forceinline__ FastStep load_step_uniform(const FastStep *p) {
  * (frequency ramps, FM); the plain build stays as lean as closed-form voices
  * need it (the same code with the running-sum branches compiled in was 27 %
  * slower on them), and a kernel that may meet both kinds holds both copies. */
-template <int T, int SCAN, bool REPAIR = false, bool CUB = false, bool WIDE = false, int SPLIT = 0 /* 1: three loops, 2: the groups between only, 3: the same in the lane-major form */, bool TAIL = false>
+template <int T, int SCAN, bool REPAIR = false, bool CUB = false, bool WIDE = false, int SPLIT = 0 /* 1: three loops, 2: the groups between only, 3: the same in the lane-major form */, bool TAIL = false,
+		bool TAB0 = false /* SPLIT 3: the launch has one table, at LDS address 0 */>
 __device__ __forceinline__ void fast_voice(const FastParams &P, const uint32_t v, const FastInfo &fi,
 		float *slots, unsigned long long *carry, const uint32_t tabs /* LDS address of the launch's table blocks */, const int l,
 		const uint32_t wpv, const uint32_t cstart, unsigned long long *lring = nullptr,
@@ -220,7 +262,12 @@ __device__ __forceinline__ void fast_voice(const FastParams &P, const uint32_t v
 #define FKG_ADVANCE() (it += gstride, cgm = cgm + wpv >= lk_ring ? cgm + wpv - lk_ring : cgm + wpv)
 	if constexpr (SPLIT == 3 && SCAN == 0 && !REPAIR && !CUB && !TAIL) {
 		/* (the same groups in the lane-major form, k_fast_group_lm.h; fast_kernel's other builds never reach it) */
-		for (uint32_t it = it_lo + cstart; it < n_iter; FKG_ADVANCE()) {
+		/* TAB0 reads the table at LDS address 0, which holds while the kernel has no static __shared__ ahead of the dynamic
+		 * block. The host asks the code object before it picks this instantiation (hip_backend.hip: tab0_kernel_ok), so this
+		 * test never fires in a launch the host makes; it is the kernel's own word that it reads no wrong address. Should the
+		 * block ever start elsewhere, no group is evaluated and the voice goes to the block loop. */
+		if (TAB0 && tabs != 0u) zero_acc = 1;
+		else for (uint32_t it = it_lo + cstart; it < n_iter; FKG_ADVANCE()) {
 			if (it == 0 || it == last_group) continue;
 			const uint32_t cg = it;
 #include "k_fast_group_lm.h"
@@ -485,8 +532,10 @@ __device__ __forceinline__ void inmix_after(const InmixArgs &A, const uint32_t k
  * rendered by a launch of the plain build ahead of this one (FastParams.edge_only). The three-loop form of fast_voice, which holds
  * both forms in one kernel, spilled 175 vector registers at 12 rows. */
 /* LM (round 7): the INNER build's groups in the lane-major form (k_fast_group_lm.h); the row-major one stays for A/B (SAU_AMD_NO_LANEMAJOR) */
-template <int T, int SCAN, bool CUB = false, bool WIDE = false, bool TAIL = false, bool INNER = false, bool LM = false>
+/* TAB0 (round 10): the lane-major form for launches that stage one table -- its LDS address is the index alone (fk_entry) */
+template <int T, int SCAN, bool CUB = false, bool WIDE = false, bool TAIL = false, bool INNER = false, bool LM = false, bool TAB0 = false>
 __global__ void FK_ATTR fast_kernel(FastParams P) {
+	static_assert(!TAB0 || LM, "the one-table address form exists for the lane-major inner build");
 	static_assert(!INNER || (SCAN == 0 && WIDE && T == 12 && !CUB && !TAIL), "the inner-groups-only form exists for the 12-row wide closed-form build");
 	static_assert(!LM || INNER, "the lane-major form exists for the inner-groups-only build");
 	static_assert(!WIDE || ((SCAN == 0 || SCAN == 2) && !CUB), "only the closed-form and the look-back builds have a wide-table form");
@@ -555,7 +604,7 @@ __global__ void FK_ATTR fast_kernel(FastParams P) {
 			const uint32_t vi = task / K;
 			const uint32_t v = P.split_cf ? P.vlists[vi] : vi;
 			const FastInfo fi = P.info[v];
-			fast_voice<T, 0, false, CUB, WIDE, SPLIT>(P, v, fi, slots, carry, tabs, l, 1u, 0u, nullptr, task - vi * K, K);
+			fast_voice<T, 0, false, CUB, WIDE, SPLIT, false, TAB0>(P, v, fi, slots, carry, tabs, l, 1u, 0u, nullptr, task - vi * K, K);
 			if (!CUB && mixing) {
 				const InmixArgs A = inmix_args(NVc);
 				inmix_after(A, task - vi * K, vi, l);

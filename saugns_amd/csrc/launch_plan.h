@@ -104,6 +104,11 @@ struct Tuning {
 	bool inmix_taper = false;    /* SAU_AMD_INMIX_TAPER: the queues' last eight chunks are short ones, so that less is left to mix_kernel. Measured
 	                              * slower on config 3 (2.04 -> 2.08 ms per step, the launch 1.91 -> 1.94: profiles/r06_ab.txt): off */
 	uint32_t inmix_at = 13;      /* which of a chunk's tasks mix the chunk before: from this many sixteenths into it (SAU_AMD_INMIX_AT) */
+	uint32_t inmix_at_lm = 15;   /* ... in the lane-major inner launch with its round-10 forms (FK_LM_SHORT_TASKS): a task mixes a tile of the chunk
+	                              * before only if it finds that chunk whole, and at 13 the shorter tasks looked too early (the step 1.1 % slower
+	                              * for a launch 7 % shorter). From ONE scan of config 3, ms per step at 9 ... 15: 1.778, 1.778, 1.791, 1.779,
+	                              * 1.782, 1.761, 1.741 -- the end of the range; the forms before are slower at 15 than at 13
+	                              * (profiles/r10_inner_issue_ab.json). SAU_AMD_INMIX_AT sets both */
 	bool inmix_dry = false;      /* SAU_AMD_INMIX_DRY: timing aid (FastParams.inmix_flags bit 4) */
 	bool inner = true;           /* the 12-row wide closed-form build as two launches, edges and inner groups (SAU_AMD_NO_INNER: one) */
 	bool lanemajor = true;       /* ... its groups between in the lane-major form (SAU_AMD_NO_LANEMAJOR: row-major) */
@@ -180,7 +185,7 @@ inline Tuning tuning_from_env(const char *(*env)(const char *)) {
 	num("SAU_AMD_INMIX_MIN_VOICES", t.inmix_min_voices);
 	num("SAU_AMD_INMIX_MIN_STEPS", t.inmix_min_steps);
 	t.inmix_taper = !off("SAU_AMD_INMIX_TAPER");
-	if (const char *ia = env("SAU_AMD_INMIX_AT")) t.inmix_at = (uint32_t)atoi(ia) & 15u;
+	if (const char *ia = env("SAU_AMD_INMIX_AT")) t.inmix_at = t.inmix_at_lm = (uint32_t)atoi(ia) & 15u;
 	t.inmix_dry = !off("SAU_AMD_INMIX_DRY");
 	t.inner = off("SAU_AMD_NO_INNER");
 	t.lanemajor = off("SAU_AMD_NO_LANEMAJOR");
@@ -418,6 +423,18 @@ inline uint32_t magic_quotient(uint32_t q, MagicDiv d) {
 }
 
 /* ---- the time-parallel path ---- */
+/* The forms of the lane-major inner launch's wave oscillator (k_fast_voice.h has what each is): defaults here, because the
+ * plan depends on them -- with (a) and (c) the launch's tasks are shorter and mix later into a chunk (Tuning.inmix_at_lm). */
+#ifndef FK_LM_ONE_PHASE_SET
+#define FK_LM_ONE_PHASE_SET 1
+#endif
+#ifndef FK_LM_TAB0
+#define FK_LM_TAB0 0
+#endif
+#ifndef FK_LM_AHEAD
+#define FK_LM_AHEAD 1
+#endif
+constexpr bool FK_LM_SHORT_TASKS = FK_LM_ONE_PHASE_SET && FK_LM_AHEAD;
 enum Inner : uint32_t { INNER_NONE = 0, INNER_ROW_MAJOR = 1, INNER_LANE_MAJOR = 2 };
 enum Mixer : uint32_t { MIX_NONE = 0, MIX_FEW_F32, MIX_F32, MIX_FEW, MIX_64, MIX_256 };
 
@@ -465,6 +482,7 @@ struct FastPlan {
 	uint32_t inmix_flags = 0;
 	MagicDiv div;
 	Inner inner = INNER_NONE;
+	bool inner_tab0 = false;   /* the lane-major inner launch stages ONE table: the instantiation that reads it at LDS address 0 */
 	Tasks tasks, tasks_cf, tasks_cub;
 	uint32_t groups = 0, groups_cf = 0;
 	uint32_t grid = 1, grid_cf = 1, grid_look = 1, grid_edge = 1, grid_cub = 1, grid_repair = 1;
@@ -677,6 +695,10 @@ inline void plan_closed_form(FastPlan &p, const SegmentDesc &seg, const Tuning &
 	 * kernel relies on, said here and not left to the sizes) */
 	if (tun.inner && p.main_build == 0 && p.wide_cf && p.rows == 12 && p.tasks.dyn_chunks >= 3)
 		p.inner = tun.lanemajor && p.n_fast == 1 ? INNER_LANE_MAJOR : INNER_ROW_MAJOR;
+	/* (round 10) ... and a lane-major launch of one table has that table at LDS address 0: the kernel whose table address is the
+	 * index alone (k_fast_voice.h: fk_entry's TAB0). Two tables or more: the form that adds the table's base. */
+	p.inner_tab0 = p.inner == INNER_LANE_MAJOR && p.tabs.n == 1;
+	if (FK_LM_SHORT_TASKS && p.inmix && p.inner == INNER_LANE_MAJOR) p.inmix_flags = (p.inmix_flags & ~(15u << 8)) | ((tun.inmix_at_lm & 15u) << 8);
 	p.grid_edge = wave_grid(2ull * seg.n_voices, dev.fk_grid); /* (two tasks a voice: its first group, its last) */
 }
 

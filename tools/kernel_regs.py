@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Registers, LDS and scratch of every kernel in a built library (default: the in-tree one):
+"""Registers, static LDS and scratch of every kernel in a built library (default: the in-tree one; `lds` is the kernel's own
+static __shared__, which comes ahead of a launch's dynamic block -- 0 is what fk_entry's TAB0 form relies on):
     python tools/kernel_regs.py [lib.so] [name filter]"""
 import os
 import re
@@ -23,7 +24,7 @@ for blk in txt.split("- .agpr_count")[1:]:
         return m.group(1) if m else "?"
     name = subprocess.run(["c++filt", g("name")], capture_output=True, text=True).stdout.strip().split("(")[0]
     if flt in name:
-        rows.append("%-62s vgpr %4s sgpr %4s spill v%s s%s scratch %5s maxwg %s" % (
+        rows.append("%-62s vgpr %4s sgpr %4s spill v%s s%s scratch %5s lds %s maxwg %s" % (
             name.replace("sauhip::", "").replace("void ", ""), g("vgpr_count"), g("sgpr_count"), g("vgpr_spill_count"),
-            g("sgpr_spill_count"), g("private_segment_fixed_size"), g("max_flat_workgroup_size")))
+            g("sgpr_spill_count"), g("private_segment_fixed_size"), g("group_segment_fixed_size"), g("max_flat_workgroup_size")))
 print("\n".join(sorted(rows)))
