@@ -6,6 +6,7 @@ every reserved bit, k <= 14, and for LPC the precision code 1011, a shift in 0 .
 has read these streams: tests/golden/flac_lpc_pm_stereo_b256.flac is there for anyone who has one."""
 import math
 import struct
+from fractions import Fraction
 
 import numpy as np
 
@@ -52,6 +53,53 @@ def quiet_sine(frames, channels):
     return x.astype(np.int16).reshape(-1)
 
 
+def ar(p, frames, seed):
+    """int64 [frames]: an all-pole process of order p -- the reflection coefficients (0.92 for even m, -0.85 for odd m) * (1 - 0.03 m),
+    m = 0 .. p-1, stepped up to the direct form, driven by unit Gaussian noise, the first 64 frames discarded, scaled to a peak of
+    6000 and rounded. Its best predictor has exactly p taps: the material that makes the encoder choose every order."""
+    a = []
+    for m in range(p):
+        k = (0.92 if m % 2 == 0 else -0.85) * (1 - 0.03 * m)
+        a = [a[j] + k * a[m - 1 - j] for j in range(m)] + [k]
+    e = np.random.default_rng(seed).standard_normal(frames + 64)
+    y = np.zeros(frames + 64)
+    for i in range(len(y)):
+        y[i] = e[i] - sum(a[j] * y[i - 1 - j] for j in range(min(p, i)))
+    y = y[64:]
+    return np.round(y * (6000 / np.abs(y).max())).astype(np.int64)
+
+
+def impulse(frames, B):
+    """int64 [frames]: zeros and one sample of 1000 in the middle of every block: R[1 ..] = 0, no candidate order"""
+    s = np.zeros(frames, np.int64)
+    s[B // 2::B] = 1000
+    return s
+
+
+def pair(frames, B):
+    """int64 [frames]: two samples of 1000 two frames apart in every block: R[1] = 0 and R[2] != 0, so order 1 is no candidate (its
+    cmax is 0) and order 2 is one"""
+    s = impulse(frames, B)
+    s[B // 2 + 2::B] = 1000
+    return s
+
+
+def edge(frames, B, v):
+    """int64 [frames]: zeros but the first sample of every block, v -- where the window is smallest: W[0] is 1 at B = 4096 and 7 at
+    B = 1024, so ws[0] = (v W[0]) >> 3 is 0 for v = +7 resp. +1 (a block that is not constant with R[0] == 0) and -1 for v = -1 at
+    B = 4096 (R[0] = 1)"""
+    s = np.zeros(frames, np.int64)
+    s[::B] = v
+    return s
+
+
+def rows(L, R=None):
+    """int16 [frames * channels], interleaved, of one or two int64 channels"""
+    x = L[:, None] if R is None else np.stack([L, R], 1)
+    assert x.min() >= -32768 and x.max() <= 32767
+    return x.astype(np.int16).reshape(-1)
+
+
 # ---- the encoder: steps 1 .. 9 -------------------------------------------------------------------------------------------
 
 def window(B):
@@ -70,31 +118,54 @@ def autocorrelation(s, B, M):
     return [int((ws[l:] * ws[:n - l]).sum()) for l in range(M + 1)]
 
 
-def orders(R, M):
-    """steps 3 .. 5: {m: (q[0 .. m-1], shift)} of the candidate orders"""
+def _muladd(x, y, z, fused):
+    """x * y + z: the product rounded before the sum as the header has it, or (fused) the whole as one correctly rounded operation,
+    which is what a fused multiply-add instruction gives"""
+    if not fused or not all(map(math.isfinite, (x, y, z))):
+        return x * y + z
+    exact = Fraction(x) * Fraction(y) + Fraction(z)
+    if exact == 0:
+        return x * y + z  # (the sign of an exact zero is the sum's)
+    try:
+        return float(exact)  # (an int / int division: correctly rounded)
+    except OverflowError:
+        return math.copysign(math.inf, exact)
+
+
+def levinson(R, M, fused=False):
+    """steps 3 .. 5 for one autocorrelation R[0 .. M] (more values are not read) -> (g, the mask of the candidate orders with bit
+    m - 1 for order m, {m: (q[0 .. m-1], shift)}, the bit patterns of a[0 .. M-1] as they stand when the loop ends, the i at which
+    the recursion stopped or None, what happened on the way: dict(stop: that i, cmax_zero: the orders skipped because cmax is 0
+    or subnormal, shift15: those whose shift was above 15, qmax: those with a q clamped to +2047, qmin: those with a q at -2048
+    -- the clamp's other end: |c 2^shift| < 2048 and E >= -0.5 keep floor(E + 0.5) from passing it)).
+    fused=True does every `z + x * y` of steps 4 and 5 (1.0 - k * k and E + c[j] * 2^shift among them) as one rounded operation:
+    what a build that contracts products into sums computes. Nothing but tests/test_flac_lpc_steps_host.py's proof that its
+    inputs tell the two apart uses it."""
     g = 0
     while (R[0] >> g) >= 1 << 53:
         g += 1
-    r = [float(v >> g) for v in R]
+    r = [float(v >> g) for v in R[:M + 1]]
     assert all(int(v) == w >> g for v, w in zip(r, R))
     a = [0.0] * M
     err = r[0]
-    out = {}
+    out, mask, stop = {}, 0, None
+    seen = dict(stop=None, cmax_zero=[], shift15=[], qmax=[], qmin=[])
     for i in range(M):
         acc = r[i + 1]
         for j in range(i):
-            acc = acc + a[j] * r[i - j]
+            acc = _muladd(a[j], r[i - j], acc, fused)
         k = -acc / err
         a[i] = k
         for j in range(i // 2):
             t, u = a[j], a[i - 1 - j]
-            a[j] = t + k * u
-            a[i - 1 - j] = u + k * t
+            a[j] = _muladd(k, u, t, fused)
+            a[i - 1 - j] = _muladd(k, t, u, fused)
         if i % 2 == 1:
             t = a[i // 2]
-            a[i // 2] = t + k * t
-        err = err * (1.0 - k * k)
+            a[i // 2] = _muladd(k, t, t, fused)
+        err = err * _muladd(-k, k, 1.0, fused)
         if not err > 0.0 or math.isinf(err):
+            stop = seen["stop"] = i
             break
         m = i + 1
         c = [-a[j] for j in range(m)]
@@ -104,19 +175,35 @@ def orders(R, M):
                 cmax = abs(v)
         field = (_bits(cmax) >> 52) & 0x7ff
         if field == 0 or field == 0x7ff:  # 0 or subnormal; not finite
+            if field == 0:
+                seen["cmax_zero"].append(m)
             continue
         e = field - 1022  # 2^(e-1) <= cmax < 2^e
-        shift = min(PRECISION - 1 - e, 15)
+        shift = PRECISION - 1 - e
+        if shift > 15:
+            seen["shift15"].append(m)
+            shift = 15
         if shift < 0:
             continue
         E, q = 0.0, []
         for j in range(m):
-            E = E + c[j] * float(1 << shift)
-            v = max(-2048, min(2047, int(math.floor(E + 0.5))))
+            E = _muladd(c[j], float(1 << shift), E, fused)
+            v = int(math.floor(E + 0.5))
+            if v > 2047 and m not in seen["qmax"]:
+                seen["qmax"].append(m)
+            if v <= -2048 and m not in seen["qmin"]:
+                seen["qmin"].append(m)
+            v = max(-2048, min(2047, v))
             q.append(v)
             E = E - float(v)
         out[m] = (q, shift)
-    return out
+        mask |= 1 << i
+    return g, mask, out, [_bits(v) for v in a], stop, seen
+
+
+def orders(R, M):
+    """steps 3 .. 5: {m: (q[0 .. m-1], shift)} of the candidate orders"""
+    return levinson(R, M)[2]
 
 
 def lpc_residual(s, q, shift):

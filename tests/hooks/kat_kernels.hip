@@ -1,10 +1,11 @@
 /* kat_kernels.hip -- TEST INFRASTRUCTURE (tests/hooks/libsaugns_amd_hooks.so only): known-answer probes of the shared
- * arithmetic (saugns_amd/csrc/sau_dev_math.h) as hipcc compiles it for gfx950, with the product's flags. Until round 4
+ * arithmetic (saugns_amd/csrc/sau_dev_math.h, sau_flac.h) as hipcc compiles it for gfx950, with the product's flags. Until round 4
  * these kernels sat in the product library; VERDICT r04 item 9 moved them here. */
 #include <hip/hip_runtime.h>
 #include "../../saugns_amd/csrc/sau_dev_ops.h"
 #include <stdint.h>
 #include "../../saugns_amd/csrc/k_wave_scan.h"
+#include "../../saugns_amd/csrc/sau_flac.h"
 
 using namespace saudev;
 
@@ -230,5 +231,62 @@ bool kat_round32(int fn, int scattered, unsigned long long *counts, uint32_t *fi
 	}
 	if (d_n) (void)hipFree(d_n);
 	if (d_f) (void)hipFree(d_f);
+	return ok;
+}
+
+/* Steps 3 to 5 of the FLAC encoder's LPC mode (sau_flac.h: flac_lpc_f64_shift, the conversions, flac_lpc_orders) as
+ * flac_analyze_lpc (k_flac.h) strings them together: workgroups of 256, lane 0 of each of the four waves takes one
+ * autocorrelation, and r, a, q and shift lie in LDS laid out like that kernel's FlacLpcLds, so that the function indexes LDS at
+ * run time here as it does there. The wave then copies out what the function wrote -- q and shift of the orders in the mask,
+ * a[0 .. M-1] as bit patterns -- with ordinary stores; everything else in the host's buffers keeps the host's pattern. */
+struct KatLpcLds {
+	double r[4][sauflac::FLAC_LPC_MAX + 1];
+	double a[4][sauflac::FLAC_LPC_MAX];
+	int16_t q[4][sauflac::FLAC_LPC_MAX * sauflac::FLAC_LPC_MAX];
+	uint8_t shift[4][sauflac::FLAC_LPC_MAX];
+	uint32_t mask[4];
+};
+__global__ __launch_bounds__(256) void kat_flac_lpc_orders_kernel(const long long *R, const uint32_t *M, uint32_t n, uint32_t *g_out,
+		uint32_t *mask_out, int16_t *q_out, uint8_t *shift_out, unsigned long long *a_out) {
+	using namespace sauflac;
+	__shared__ KatLpcLds L;
+	const unsigned c = threadIdx.x >> 6, lane = threadIdx.x & 63;
+	const uint32_t v = blockIdx.x * 4 + c;
+	if (lane == 0 && v < n) {
+		const long long *Rv = R + (size_t)v * (FLAC_LPC_MAX + 1);
+		const unsigned g = flac_lpc_f64_shift(Rv[0]);
+		for (unsigned l = 0; l <= FLAC_LPC_MAX; ++l) L.r[c][l] = (double)(Rv[l] >> g);
+		L.mask[c] = flac_lpc_orders(L.r[c], M[v], L.a[c], L.q[c], L.shift[c]);
+		g_out[v] = g;
+	}
+	__syncthreads();
+	if (v < n) {
+		const uint32_t mask = L.mask[c];
+		const unsigned m1 = lane >> 3, j = lane & 7; /* q[(m - 1) * 8 + j] */
+		if (((mask >> m1) & 1u) && j <= m1) q_out[(size_t)v * 64 + lane] = L.q[c][lane];
+		if (lane < FLAC_LPC_MAX && ((mask >> lane) & 1u)) shift_out[(size_t)v * FLAC_LPC_MAX + lane] = L.shift[c][lane];
+		if (lane < M[v]) a_out[(size_t)v * FLAC_LPC_MAX + lane] = flac_f64_bits(L.a[c][lane]);
+		if (lane == 0) mask_out[v] = mask;
+	}
+}
+/* (the host's buffers go to the device as they are and come back: what the kernel leaves alone keeps the caller's pattern) */
+bool kat_flac_lpc_orders(const int64_t *R, const uint32_t *M, uint32_t n, uint32_t *g, uint32_t *mask, int16_t *q, uint8_t *shift,
+		uint64_t *a_bits) {
+	const size_t nb[7] = {(size_t)n * 9 * sizeof(int64_t), n * sizeof(uint32_t), n * sizeof(uint32_t), n * sizeof(uint32_t),
+		(size_t)n * 64 * sizeof(int16_t), (size_t)n * 8, (size_t)n * 8 * sizeof(uint64_t)};
+	const void *src[7] = {R, M, g, mask, q, shift, a_bits};
+	void *dst[7] = {nullptr, nullptr, g, mask, q, shift, a_bits};
+	void *d[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+	bool ok = true;
+	for (int i = 0; i < 7 && ok; ++i)
+		ok = hipMalloc(&d[i], nb[i]) == hipSuccess && hipMemcpy(d[i], src[i], nb[i], hipMemcpyHostToDevice) == hipSuccess;
+	if (ok) {
+		hipLaunchKernelGGL(kat_flac_lpc_orders_kernel, dim3((n + 3) / 4), dim3(256), 0, 0, (const long long *)d[0], (const uint32_t *)d[1], n,
+			(uint32_t *)d[2], (uint32_t *)d[3], (int16_t *)d[4], (uint8_t *)d[5], (unsigned long long *)d[6]);
+		ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+	}
+	for (int i = 2; i < 7 && ok; ++i) ok = hipMemcpy(dst[i], d[i], nb[i], hipMemcpyDeviceToHost) == hipSuccess;
+	for (int i = 0; i < 7; ++i)
+		if (d[i]) (void)hipFree(d[i]);
 	return ok;
 }

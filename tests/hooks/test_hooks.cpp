@@ -8,10 +8,13 @@
  *   sauAmd_launch_plan: what saugns_amd/csrc/launch_plan.h decides for a segment given as scalars (no GPU, no pointers)
  *   sauAmd_kat_line_device / _host, sauAmd_kat_div_device: the shared arithmetic as compiled for the device and the host
  *   sauAmd_kat_scan64_device: the kernels' 64-bit wave scan and sum (k_wave_scan.h) over caller-supplied values
- *   sauAmd_kat_round32_device: the 32-bit rounding forms of phases (sau_dev_math.h, k_common.h) on every bit pattern */
+ *   sauAmd_kat_round32_device: the 32-bit rounding forms of phases (sau_dev_math.h, k_common.h) on every bit pattern
+ *   sauAmd_kat_flac_lpc_orders_host / _device: steps 3 to 5 of the FLAC encoder's LPC mode (sau_flac.h: flac_lpc_orders) on
+ *     caller-supplied autocorrelations, with the recursion's work array a[] as bit patterns */
 #include "../../saugns_amd/csrc/capi_internal.h"
 #include "../../saugns_amd/csrc/sau_dev_ops.h"
 #include "../../saugns_amd/csrc/launch_plan.h"
+#include "../../saugns_amd/csrc/sau_flac.h"
 #include <stdio.h>
 #include <string.h>
 
@@ -23,6 +26,39 @@ bool kat_line(const saudev::LineState &st, uint32_t len, const float *mul, float
 bool kat_scan64(const unsigned long long *in, unsigned long long *scan, unsigned long long *sum, uint32_t n_waves);
 bool kat_rint64(int scattered, unsigned long long *mismatches, uint32_t *first_bad);
 bool kat_round32(int fn, int scattered, unsigned long long *counts, uint32_t *first_bad);
+bool kat_flac_lpc_orders(const int64_t *R, const uint32_t *M, uint32_t n, uint32_t *g, uint32_t *mask, int16_t *q, uint8_t *shift,
+		uint64_t *a_bits);
+#endif
+
+/* Steps 3 to 5 of the LPC mode for n autocorrelations R[v][0 .. 8] with their own largest order M[v] in 1 .. 8, strung together as
+ * the analysis does (k_flac.h: flac_analyze_lpc; tables.cpp: flac_encode_block): g, the conversions (double)(R[l] >> g),
+ * flac_lpc_orders. -> g[v], mask[v], q[v][(m - 1) * 8 + j] and shift[v][m - 1] where flac_lpc_orders wrote them, and a[0 .. M-1]
+ * as it stands behind the call, as bit patterns. What the function does not write keeps what the caller put there. 0 for a bad
+ * argument (the _device twin: or a device error). */
+HOOK int sauAmd_kat_flac_lpc_orders_host(const int64_t *R /* [n][9] */, const uint32_t *M, uint32_t n, uint32_t *g, uint32_t *mask,
+		int16_t *q /* [n][64] */, uint8_t *shift /* [n][8] */, uint64_t *a_bits /* [n][8] */) {
+	using namespace sauflac;
+	if (!R || !M || !g || !mask || !q || !shift || !a_bits) return 0;
+	for (uint32_t v = 0; v < n; ++v)
+		if (M[v] < 1 || M[v] > FLAC_LPC_MAX) return 0;
+	for (uint32_t v = 0; v < n; ++v) {
+		const int64_t *Rv = R + (size_t)v * (FLAC_LPC_MAX + 1);
+		double r[FLAC_LPC_MAX + 1], a[FLAC_LPC_MAX];
+		g[v] = flac_lpc_f64_shift(Rv[0]);
+		for (unsigned l = 0; l <= FLAC_LPC_MAX; ++l) r[l] = (double)(Rv[l] >> g[v]);
+		mask[v] = flac_lpc_orders(r, M[v], a, q + (size_t)v * FLAC_LPC_MAX * FLAC_LPC_MAX, shift + (size_t)v * FLAC_LPC_MAX);
+		for (unsigned j = 0; j < M[v]; ++j) a_bits[(size_t)v * FLAC_LPC_MAX + j] = flac_f64_bits(a[j]);
+	}
+	return 1;
+}
+#ifndef SAU_HOOKS_NO_HIP
+HOOK int sauAmd_kat_flac_lpc_orders_device(const int64_t *R, const uint32_t *M, uint32_t n, uint32_t *g, uint32_t *mask, int16_t *q,
+		uint8_t *shift, uint64_t *a_bits) {
+	if (!R || !M || !g || !mask || !q || !shift || !a_bits) return 0;
+	for (uint32_t v = 0; v < n; ++v)
+		if (M[v] < 1 || M[v] > sauflac::FLAC_LPC_MAX) return 0;
+	return n == 0 || kat_flac_lpc_orders(R, M, n, g, mask, q, shift, a_bits) ? 1 : 0;
+}
 #endif
 
 HOOK sauGenerator *sauAmd_create_Generator_with_backend(const sauProgram *prg, uint32_t srate, void *backend) {
