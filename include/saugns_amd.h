@@ -81,7 +81,8 @@ SAU_AMD_API const int16_t *sauAmd_Batch_device_pcm(sauAmdBatch *b, size_t stream
  * sauAmd_Batch_set_call_len mean what they mean there), with the mixer's f32 accumulator stored as it stands: the reference's
  * ordered voice sum (generator.c:749-788), L, R interleaved when stereo, else (L + R) * 0.5f -- not clamped to +-1, not
  * rounded to 15 bits, a NaN left a NaN; frames of [0, out_len) in which nothing sounds are +0.0f. The int16 sample of
- * sauAmd_Batch_run is this one clamped and rounded. The format belongs to the call: run and run_f32 calls may alternate on
+ * sauAmd_Batch_run is this one clamped and rounded. The claim is tested against the oracle's float output (ora_run_f32), bit for
+ * bit, a NaN for a NaN (tests/test_gpu_f32_oracle.py). The format belongs to the call: run and run_f32 calls may alternate on
  * one batch in any order, each continues where the last one stopped. False (sauAmd_last_error) on a backend without float
  * output: nothing is rendered then and the batch stands where it stood. */
 SAU_AMD_API bool sauAmd_Batch_run_f32(sauAmdBatch *b, float *const *bufs, size_t buf_len,

@@ -54,6 +54,9 @@ def oracle():
         lib.ora_run.restype = C.c_bool
         lib.ora_run.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_bool,
                                 C.POINTER(C.c_size_t)]
+        lib.ora_run_f32.restype = C.c_bool
+        lib.ora_run_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_bool,
+                                    C.POINTER(C.c_size_t)]
         lib.ora_destroy.argtypes = [C.c_void_p]
         lib.ora_set_block_len.argtypes = [C.c_void_p, C.c_uint32]
         lib.ora_set_piluts.argtypes = [C.c_void_p]
@@ -134,14 +137,15 @@ def ref_piluts():
                      for i in range(12)])
 
 
-def _render(create, run, destroy, prg, srate, stereo, chunk, max_frames, post_create=None):
+def _render(create, run, destroy, prg, srate, stereo, chunk, max_frames, post_create=None,
+            dtype=np.int16):
     g = create(prg, srate)
     if not g:
         raise RuntimeError("generator creation failed")
     if post_create:
         post_create(g)
     ch = 2 if stereo else 1
-    buf = np.zeros(chunk * ch, dtype=np.int16)
+    buf = np.zeros(chunk * ch, dtype=dtype)
     n = C.c_size_t()
     out = []
     total = 0
@@ -154,7 +158,7 @@ def _render(create, run, destroy, prg, srate, stereo, chunk, max_frames, post_cr
                 break
     finally:
         destroy(g)
-    pcm = np.concatenate(out) if out else np.zeros(0, np.int16)
+    pcm = np.concatenate(out) if out else np.zeros(0, dtype)
     if max_frames:
         pcm = pcm[: max_frames * ch]
     return pcm
@@ -171,6 +175,37 @@ def oracle_render(prg, srate=44100, stereo=False, chunk=11289, max_frames=0, blo
     post = (lambda g: lib.ora_set_block_len(g, block_len)) if block_len else None
     return _render(lib.ora_create, lib.ora_run, lib.ora_destroy, prg, srate, stereo,
                    chunk, max_frames, post)
+
+
+def oracle_render_f32(prg, srate=44100, stereo=False, chunk=11289, max_frames=0, block_len=0):
+    """oracle_render with float32 samples (ora_run_f32): the mix accumulator as it stands, not
+    clamped and not rounded, +0.0f where nothing sounds."""
+    lib = oracle()
+    post = (lambda g: lib.ora_set_block_len(g, block_len)) if block_len else None
+    return _render(lib.ora_create, lib.ora_run_f32, lib.ora_destroy, prg, srate, stereo,
+                   chunk, max_frames, post, dtype=np.float32)
+
+
+def oracle_calls_f32(prg, srate=44100, stereo=False, chunk=11289, max_calls=0):
+    """ora_run_f32 call by call -> a list of (the whole float32 buffer of `chunk` frames as the call
+    left it, more, out_len): what one run of a batch is compared with. Stops behind the call that
+    returns false, or behind `max_calls` calls."""
+    lib = oracle()
+    g = lib.ora_create(prg, srate)
+    if not g:
+        raise RuntimeError("generator creation failed")
+    buf = np.zeros(chunk * (2 if stereo else 1), dtype=np.float32)
+    n = C.c_size_t()
+    calls = []
+    try:
+        while True:
+            more = bool(lib.ora_run_f32(g, buf.ctypes.data, chunk, stereo, C.byref(n)))
+            calls.append((buf.copy(), more, int(n.value)))
+            if not more or (max_calls and len(calls) >= max_calls):
+                break
+    finally:
+        lib.ora_destroy(g)
+    return calls
 
 
 def oracle_sndfile_bytes(fmt, channels, srate, pcm):

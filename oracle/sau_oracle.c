@@ -1526,9 +1526,12 @@ static inline float clampf(float x, float lo, float hi) {
 	return x;
 }
 
-/* generator.c:854-878 with 734-740 and 795-825 */
-static uint32_t run_span(OraGen *o, uint32_t time, int16_t *buf, bool stereo) {
+/* generator.c:854-878 with 734-740 and 795-825; with `fbuf` set (ora_run_f32) the last step stores the
+ * accumulator as it stands instead: no clamp, no rounding, and a plain store -- adding to the +0.0f the buffer
+ * holds would turn a -0.0f of the mix into +0.0f */
+static uint32_t run_span(OraGen *o, uint32_t time, int16_t *buf, float *fbuf, bool stereo) {
 	int16_t *sp = buf;
+	float *fp = fbuf;
 	uint32_t gen_len = 0;
 	while (time > 0) {
 		uint32_t len = (time < o->block_len) ? time : o->block_len;
@@ -1550,7 +1553,17 @@ static uint32_t run_span(OraGen *o, uint32_t time, int16_t *buf, bool stereo) {
 			gen_len += last_len;
 			o->out_dirty_cleared = false;
 			const float *l = o->mix[0], *r = o->mix[1];
-			if (stereo) {
+			if (fbuf) {
+				if (stereo) {
+					for (uint32_t i = 0; i < last_len; ++i) {
+						*fp++ = l[i];
+						*fp++ = r[i];
+					}
+				} else {
+					for (uint32_t i = 0; i < last_len; ++i)
+						*fp++ = (l[i] + r[i]) * 0.5f;
+				}
+			} else if (stereo) {
 				for (uint32_t i = 0; i < last_len; ++i) {
 					float sl = clampf(l[i], -1.f, 1.f);
 					float sr = clampf(r[i], -1.f, 1.f);
@@ -1569,13 +1582,17 @@ static uint32_t run_span(OraGen *o, uint32_t time, int16_t *buf, bool stereo) {
 	return gen_len;
 }
 
-/* generator.c:905-973 */
-ORA_API bool ora_run(OraGen *o, int16_t *buf, size_t buf_len, bool stereo,
+/* generator.c:905-973; one of `buf` (int16) and `fbuf` (float) is set */
+static bool run_any(OraGen *o, int16_t *buf, float *fbuf, size_t buf_len, bool stereo,
 		size_t *out_len) {
-	int16_t *sp = buf;
+	size_t sp = 0; /* samples before the span in hand */
 	uint32_t len = buf_len;
 	uint32_t skip_len, last_len, gen_len = 0;
-	if (!o->out_dirty_cleared) {
+	if (fbuf) {
+		/* every call: a run of silence is +0.0f whatever the last call left in the buffer */
+		memset(fbuf, 0, sizeof(float) * (stereo ? len * 2 : len));
+		o->out_dirty_cleared = false;
+	} else if (!o->out_dirty_cleared) {
 		o->out_dirty_cleared = true;
 		memset(buf, 0, sizeof(int16_t) * (stereo ? len * 2 : len));
 	}
@@ -1596,7 +1613,7 @@ ORA_API bool ora_run(OraGen *o, int16_t *buf, size_t buf_len, bool stereo,
 			++o->event;
 			o->event_pos = 0;
 		}
-		last_len = run_span(o, len, sp, stereo);
+		last_len = run_span(o, len, buf ? buf + sp : NULL, fbuf ? fbuf + sp : NULL, stereo);
 		if (skip_len > 0) {
 			gen_len += len;
 			sp += stereo ? len * 2 : len;
@@ -1617,6 +1634,19 @@ ORA_API bool ora_run(OraGen *o, int16_t *buf, size_t buf_len, bool stereo,
 	}
 	if (out_len) *out_len = buf_len;
 	return true;
+}
+
+ORA_API bool ora_run(OraGen *o, int16_t *buf, size_t buf_len, bool stereo,
+		size_t *out_len) {
+	return run_any(o, buf, NULL, buf_len, stereo, out_len);
+}
+
+/** ora_run with float output: the same event loop, block lattice, voice_run / voice_mix and sample
+ * pointer arithmetic; the mix accumulator is stored as it stands (mono: (l + r) * 0.5f), +0.0f where
+ * nothing sounds. A generator is run through one entry only. */
+ORA_API bool ora_run_f32(OraGen *o, float *buf, size_t buf_len, bool stereo,
+		size_t *out_len) {
+	return run_any(o, NULL, buf, buf_len, stereo, out_len);
 }
 
 /* ---- kernel-level entry points for known-answer tests ------------------- */

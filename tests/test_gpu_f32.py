@@ -1,7 +1,8 @@
 """Float32 sample output (include/saugns_amd.h: sauAmd_Batch_run_f32, sauAmd_Batch_device_pcm_f32, SAU_AMD_SNDFILE_WAV_F32): the mixers
 store their f32 accumulator as it stands -- no clamp, no rounding to 15 bits -- in the reference's order and association.
 
-The oracle produces int16 only, so the float samples are checked through it without a tolerance: amp_scale = 0.5 * ampmult /
+Here the float samples are checked through the oracle's int16 output without a tolerance (tests/test_gpu_f32_oracle.py compares
+them with the oracle's float output bit for bit; this is a second, independent route): amp_scale = 0.5 * ampmult /
 vo_count multiplies every voice sample BEFORE the ordered sum, so scaling ampmult by 2^k scales every intermediate of the mix
 exactly, and for every frame
 
