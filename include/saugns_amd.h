@@ -575,10 +575,12 @@ SAU_AMD_API bool sauAmd_render_spectrum(const sauProgram *prg, uint32_t srate, i
  * 4096). Row r's block k covers its frames [k B, k B + B) and becomes FLAC frame number k; frames behind the last complete block
  * are pending until a later feed completes the block or a finish makes them one last short block. At most 65535 rows per
  * encoder and 2^31 - 1 blocks per row.
- * Limits: no MD5 (the field is zeros: "not computed"), no seek table, no comments, no 24-bit output, no wasted-bits detection,
- * no escape partitions; LPC only on request (max_lpc_order, "The LPC mode" below), of order <= 8 with 12-bit coefficients, one
- * precision and one window. The float, limited and oversampled writers have no FLAC variant; the fed encoder takes any int16
- * device rows.
+ * Limits: no MD5 (the field is zeros: "not computed"), no seek table, no comments, no wasted-bits detection, no escape
+ * partitions, no dither; LPC only on request (max_lpc_order, "The LPC mode" below), of order <= 8 with 12-bit coefficients, one
+ * precision and one window, and at 16 bits only: max_lpc_order > 0 with bits == 24 is a bad argument everywhere (its products
+ * pass 32 bits, and the window scaling would pass 64). 24-bit output comes from float rows only ("24 bits" below). The
+ * peak-normalised and oversampled writers have no FLAC variant; the fed encoders take any int16 or float device rows, decimated
+ * ones included.
  *
  * All fields are big-endian and packed MSB first.
  * The header (42 bytes): "fLaC"; one metadata block header, 80 00 00 22 (last = 1, type 0, length 34); STREAMINFO:
@@ -668,6 +670,26 @@ SAU_AMD_API bool sauAmd_render_spectrum(const sauProgram *prg, uint32_t srate, i
  * (VERBATIM still caps every channel), and so does "a sample's code places at most 15 non-zero bits". The streams stay inside
  * FLAC's streamable subset (order <= 12 at up to 48 kHz, Rice parameter <= 14).
  *
+ * 24 bits. A float-fed encoder (sauAmd_Batch_create_flac_f32, sauAmd_Flac_feed_f32) quantises float rows on the device and
+ * encodes the result; `bits` is 16 or 24. The quantiser: y = x * gain[row], one f32 multiply; a NaN becomes -1; y is clamped to
+ * [-1, 1]; bits 16: the int16 the runs themselves store (the nearest integer to y * 32767 in f32, ties to even); bits 24: the
+ * nearest integer to (double)y * 8388607.0, ties to even -- the product is exact in f64, so there is one rounding --, in
+ * -8388607 .. 8388607. sauAmd_flac_quantize restates it on the host. With bits == 16 there is no new format: the stream is
+ * exactly what the int16 encoder makes of those samples, max_lpc_order 0 .. 8 allowed. With bits == 24 everything of the 16-bit
+ * text holds with these differences:
+ *   STREAMINFO: bits per sample - 1 = 23. Frame header: sample size code 110.
+ *   bps is 24, or 25 for a side channel. Samples are any value in -2^23 .. 2^23 - 1 (the quantiser makes only +-8388607).
+ *   A FIXED residual is at most 16 * 2^24 = 2^28 in size and fits 32 bits; its u is below 2^30.
+ *   The residual: 2 bits 01 (coding method 1), 4 bits partition order, and 5-bit Rice parameters k in 0 .. 30, never the escape
+ *   11111.
+ *   Rule 3: candidates k = 0 .. 30, the lowest on ties; a partition costs 5 + its least cost.
+ *   Rule 4: FIXED costs 8 + bps * o + 6 + cost(p), VERBATIM 8 + bps * n, with those bps.
+ *   Unchanged: P = 4 for whole blocks, the order rule (sums of |r| over i >= 4, in 64 bits), the stereo rule and every tie.
+ *   A frame is at most 15 + channels * (1 + 3 n) bytes. A code's non-zero part is at most 31 bits: the stop bit and k low bits.
+ *   No LPC (Limits).
+ * sauAmd_flac_encode_block_s32 restates one such frame on the host. The bytes are a function of the fed floats, the gains and
+ * (B, channels, bits, M) only, never of how the sequence was cut into feeds.
+ *
  * The worst case of a feed is that bound summed over the blocks it completes. Unread output lives on the device: a feed whose
  * worst case would bring the unread total above 1 GiB is refused; read first. (Until a read has fetched the frames' sizes, a
  * feed counts in that total with its worst case.) */
@@ -730,6 +752,46 @@ SAU_AMD_API bool sauAmd_render_file_flac(const sauProgram *prg, uint32_t srate, 
 SAU_AMD_API bool sauAmd_render_file_flac_lpc(const sauProgram *prg, uint32_t srate, const char *path, int channels, uint32_t block_frames,
 		uint32_t max_lpc_order, uint64_t *frames_out, sauAmdFlacInfo *info_out);
 
+/* ---- 24 bits and float-fed encoders ("24 bits" above) ---- */
+/* sauAmd_flac_header with STREAMINFO's bits per sample: `bits` 16 (sauAmd_flac_header's bytes) or 24; anything else: 0. */
+SAU_AMD_API size_t sauAmd_flac_header_bits(uint32_t srate, int channels, uint32_t block_frames, int bits, const sauAmdFlacInfo *info,
+		uint8_t *out, size_t cap);
+/* The host restatement for int32 samples. bits == 16: every sample must fit int16, and the bytes are
+ * sauAmd_flac_encode_block_lpc's. bits == 24: every sample must lie in -2^23 .. 2^23 - 1 and max_lpc_order must be 0. Otherwise,
+ * and for other bits, 0. */
+SAU_AMD_API size_t sauAmd_flac_encode_block_s32(const int32_t *x, uint32_t n, int channels, uint32_t block_frames, uint32_t frame_number,
+		int bits, uint32_t max_lpc_order, uint8_t *out, size_t cap);
+/* The quantiser on the host: out[i] = what a float-fed encoder of `bits` makes of x[i] with `gain`. False for bits other than 16
+ * or 24, or a NULL pointer with n > 0. */
+SAU_AMD_API bool sauAmd_flac_quantize(const float *x, size_t n, float gain, int bits, int32_t *out);
+/* A float-fed encoder: sauAmd_Batch_create_flac_lpc's rules, and bits 16 or 24; 24 with max_lpc_order > 0 is a bad argument. */
+SAU_AMD_API sauAmdFlac *sauAmd_Batch_create_flac_f32(sauAmdBatch *b, size_t n_rows, int channels, uint32_t block_frames, int bits,
+		uint32_t max_lpc_order);
+/* sauAmd_Flac_feed for a float-fed encoder: row r's next frames[r] float frames times gains[r] (gains NULL: 1.0f everywhere; a
+ * gain that is not finite is a bad argument). rows and pitch_bytes must be multiples of 4 (not 16: a feed may begin anywhere in
+ * a float row); otherwise the argument rules are sauAmd_Spectrum_feed's. The floats are quantised into rows of the encoder's own,
+ * so the fed rows may be reused once the batch's stream has passed the feed. An encoder is of one kind: sauAmd_Flac_feed on a
+ * float-fed encoder, and this on an int16-fed one, is a bad argument that changes nothing. sauAmd_Flac_read and
+ * sauAmd_Flac_destroy serve both kinds. */
+SAU_AMD_API bool sauAmd_Flac_feed_f32(sauAmdFlac *e, const void *rows, size_t pitch_bytes, const uint32_t *frames /* [n_rows] */,
+		const float *gains /* [n_rows]; NULL: 1.0f */, int finish);
+/* Render prg into a FLAC file of `bits` per sample from float runs: sauAmd_render_file_normalized's second pass with a
+ * sauAmd_Flac_feed_f32 of the run's device row (gain `gain`) where that writer requantises and fetches; the file I/O is
+ * sauAmd_render_file_flac's. The file decodes to the quantiser's values of x * gain for the floats x that
+ * sauAmd_render_file(.., SAU_AMD_SNDFILE_WAV_F32, ..) writes. False with "bad argument" on what sauAmd_render_file_flac_lpc
+ * refuses, bits other than 16 or 24, 24 with max_lpc_order > 0, a gain that is not finite, and on a backend without the encoder
+ * or float output -- all before any file is created. */
+SAU_AMD_API bool sauAmd_render_file_flac_f32(const sauProgram *prg, uint32_t srate, const char *path, int channels, uint32_t block_frames,
+		int bits, uint32_t max_lpc_order, float gain, uint64_t *frames_out, sauAmdFlacInfo *info_out);
+/* The loudness-normalised writers with FLAC output. Pass 1 is sauAmd_render_file_loudness's. limited == 0: the gain follows that
+ * writer's rule and pass 2 is sauAmd_render_file_flac_f32's with it. limited != 0: the gain follows
+ * sauAmd_render_file_loudness_limited's rule, and pass 2 is that writer's with float limited rows fed with gain 1 -- the first D
+ * frames skipped, the D-frame tail run fed too. Either way the file holds the samples the WAV_F32 variant of that writer holds,
+ * quantised, and exactly as many frames. Refusals: those writers', and sauAmd_render_file_flac_f32's, all before any file is
+ * created. The out pointers may be NULL; stats_out is written only when limited. */
+SAU_AMD_API bool sauAmd_render_file_flac_loudness(const sauProgram *prg, uint32_t srate, const char *path, int channels,
+		uint32_t block_frames, int bits, uint32_t max_lpc_order, double target_lufs, float max_true_peak, int limited,
+		uint64_t *frames_out, sauAmdLoudness *loud_out, float *gain_out, sauAmdLimiterStats *stats_out, sauAmdFlacInfo *info_out);
 
 #ifdef __cplusplus
 }

@@ -308,6 +308,25 @@ def _declare(L):
         L.sauAmd_render_file_flac_lpc.restype = C.c_bool
         L.sauAmd_render_file_flac_lpc.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_int, C.c_uint32, C.c_uint32,
                                                   C.POINTER(C.c_uint64), C.POINTER(FlacInfo)]
+    if hasattr(L, "sauAmd_Batch_create_flac_f32"):  # 24 bits and float-fed encoders (SAU_AMD_LIB may name an older build)
+        L.sauAmd_flac_header_bits.restype = C.c_size_t
+        L.sauAmd_flac_header_bits.argtypes = [C.c_uint32, C.c_int, C.c_uint32, C.c_int, C.POINTER(FlacInfo), C.c_void_p, C.c_size_t]
+        L.sauAmd_flac_encode_block_s32.restype = C.c_size_t
+        L.sauAmd_flac_encode_block_s32.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32,
+                                                   C.c_void_p, C.c_size_t]
+        L.sauAmd_flac_quantize.restype = C.c_bool
+        L.sauAmd_flac_quantize.argtypes = [C.c_void_p, C.c_size_t, C.c_float, C.c_int, C.c_void_p]
+        L.sauAmd_Batch_create_flac_f32.restype = C.c_void_p
+        L.sauAmd_Batch_create_flac_f32.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.c_int, C.c_uint32]
+        L.sauAmd_Flac_feed_f32.restype = C.c_bool
+        L.sauAmd_Flac_feed_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.c_int]
+        L.sauAmd_render_file_flac_f32.restype = C.c_bool
+        L.sauAmd_render_file_flac_f32.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_int, C.c_uint32, C.c_int, C.c_uint32,
+                                                  C.c_float, C.POINTER(C.c_uint64), C.POINTER(FlacInfo)]
+        L.sauAmd_render_file_flac_loudness.restype = C.c_bool
+        L.sauAmd_render_file_flac_loudness.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_int, C.c_uint32, C.c_int, C.c_uint32,
+                                                       C.c_double, C.c_float, C.c_int, C.POINTER(C.c_uint64), C.POINTER(Loudness),
+                                                       C.POINTER(C.c_float), C.POINTER(LimiterStats), C.POINTER(FlacInfo)]
     L.sauAmd_set_piluts.argtypes = [C.c_void_p]
     L.sauAmd_get_piluts.restype = C.POINTER(C.c_float)
     L.sauAmd_last_error.restype = C.c_char_p
@@ -669,14 +688,46 @@ def use_flac_hooks(path):
     return _flac_hooks
 
 
-def flac_header(srate, channels, block_frames, info=None):
-    """sauAmd_flac_header: the 42 bytes ahead of the frames ("fLaC", the metadata block header, STREAMINFO) for a record
-    (a FlacInfo, a dict of its fields, or None: an empty one); b"" for arguments that are refused."""
+def flac_header(srate, channels, block_frames, info=None, bits=None):
+    """sauAmd_flac_header, or with ``bits`` (16 or 24) sauAmd_flac_header_bits: the 42 bytes ahead of the frames ("fLaC", the
+    metadata block header, STREAMINFO) for a record (a FlacInfo, a dict of its fields, or None: an empty one); b"" for arguments
+    that are refused."""
     if isinstance(info, dict):
         info = FlacInfo(**info)
     out = (C.c_uint8 * 42)()
-    n = lib().sauAmd_flac_header(srate, channels, block_frames, C.byref(info) if info is not None else None, out, 42)
+    ref = C.byref(info) if info is not None else None
+    if bits is None:
+        n = lib().sauAmd_flac_header(srate, channels, block_frames, ref, out, 42)
+    else:
+        n = lib().sauAmd_flac_header_bits(srate, channels, block_frames, int(bits), ref, out, 42)
     return bytes(out) if n == 42 else b""
+
+
+def flac_quantize(x, gain=1.0, bits=24):
+    """sauAmd_flac_quantize: what a float-fed encoder of ``bits`` makes of the float32 samples x with ``gain`` -> int32 array
+    (None when the library refuses the bits)"""
+    x = np.ascontiguousarray(x, np.float32)
+    out = np.zeros(x.shape, np.int32)
+    ok = lib().sauAmd_flac_quantize(x.ctypes.data, x.size, float(gain), int(bits), out.ctypes.data)
+    return out if ok else None
+
+
+def flac_encode_block_s32(x, channels, block_frames, frame_number, bits=24, max_lpc_order=0):
+    """sauAmd_flac_encode_block_s32: the host's restatement of one frame of ``bits`` per sample from interleaved int32 samples
+    -> bytes (b"" when the arguments are refused)"""
+    x = np.ascontiguousarray(x, np.int32)
+    n = len(x) // max(int(channels), 1)
+    L = lib()
+
+    def call(out, cap):
+        return L.sauAmd_flac_encode_block_s32(x.ctypes.data, n, channels, block_frames, frame_number, int(bits),
+                                              _lpc_order(max_lpc_order), out, cap)
+    size = call(None, 0)
+    if not size:
+        return b""
+    out = (C.c_uint8 * size)()
+    assert call(out, size) == size
+    return bytes(out)
 
 
 def _lpc_order(max_lpc_order):
@@ -728,6 +779,74 @@ def render_file_flac(program, srate, path, channels=1, block_frames=0, backend=N
     if not ok:
         raise RuntimeError("sauAmd_render_file_flac failed: " + last_error(L))
     return n.value, info
+
+
+_flac24_hooks = None
+
+
+def use_flac24_hooks(path):
+    """tests/ only: load the library that runs the float-fed FLAC writers over an injected backend and reaches the encoder's
+    launch plan at a sample width (tests/hooks_flac24: the product's object files + the two _with_backend entry points and
+    sauAmd_flac_plan_bits)."""
+    global _flac24_hooks
+    if _flac24_hooks is None:
+        L = _declare(C.CDLL(path))
+        L.sauAmd_render_file_flac_f32_with_backend.restype = C.c_bool
+        L.sauAmd_render_file_flac_f32_with_backend.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_int, C.c_uint32, C.c_int,
+                                                               C.c_uint32, C.c_float, C.c_void_p, C.POINTER(C.c_uint64),
+                                                               C.POINTER(FlacInfo)]
+        L.sauAmd_render_file_flac_loudness_with_backends.restype = C.c_bool
+        L.sauAmd_render_file_flac_loudness_with_backends.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_int, C.c_uint32, C.c_int,
+                                                                     C.c_uint32, C.c_double, C.c_float, C.c_int, C.c_void_p, C.c_void_p,
+                                                                     C.POINTER(C.c_uint64)]
+        L.sauAmd_flac_plan_bits.restype = C.c_int
+        L.sauAmd_flac_plan_bits.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t, C.POINTER(C.c_uint64),
+                                            C.POINTER(C.c_uint32), C.c_int, C.POINTER(C.c_uint64)]
+        _flac24_hooks = L
+    return _flac24_hooks
+
+
+def render_file_flac_f32(program, srate, path, channels=1, block_frames=0, bits=24, max_lpc_order=0, gain=1.0, backend=None):
+    """sauAmd_render_file_flac_f32: render a whole program in float32 into a FLAC file of ``bits`` per sample, scaled by
+    ``gain``, quantised and encoded on the device -> (frames, FlacInfo). ``backend`` (tests): a sauengine::Backend* to run the
+    same writer without a GPU."""
+    n, info = C.c_uint64(), FlacInfo()
+    if backend is None:
+        L = _used(lib())
+        ok = L.sauAmd_render_file_flac_f32(program.ptr, srate, os.fsencode(path), channels, block_frames, int(bits),
+                                           _lpc_order(max_lpc_order), gain, C.byref(n), C.byref(info))
+    else:
+        if _flac24_hooks is None:
+            raise RuntimeError("the FLAC-24 hook library is not loaded (use_flac24_hooks)")
+        L = _used(_flac24_hooks)
+        ok = L.sauAmd_render_file_flac_f32_with_backend(program.ptr, srate, os.fsencode(path), channels, block_frames, int(bits),
+                                                        _lpc_order(max_lpc_order), gain, backend, C.byref(n), C.byref(info))
+    if not ok:
+        raise RuntimeError("sauAmd_render_file_flac_f32 failed: " + last_error(L))
+    return n.value, info
+
+
+def render_file_flac_loudness(program, srate, path, channels=1, block_frames=0, bits=24, max_lpc_order=0, target_lufs=-23.0,
+                              max_true_peak=1.0, limited=False, backends=None):
+    """sauAmd_render_file_flac_loudness: the loudness-normalised writer (``limited``: the limited one) with FLAC output of
+    ``bits`` per sample -> (frames, Loudness, gain, LimiterStats or None, FlacInfo). ``backends`` (tests): two
+    sauengine::Backend*, one per pass, to run the same writer without a GPU."""
+    n, ld, gain, st, info = C.c_uint64(), Loudness(), C.c_float(), LimiterStats(), FlacInfo()
+    if backends is None:
+        L = _used(lib())
+        ok = L.sauAmd_render_file_flac_loudness(program.ptr, srate, os.fsencode(path), channels, block_frames, int(bits),
+                                                _lpc_order(max_lpc_order), target_lufs, max_true_peak, 1 if limited else 0,
+                                                C.byref(n), C.byref(ld), C.byref(gain), C.byref(st), C.byref(info))
+    else:
+        if _flac24_hooks is None:
+            raise RuntimeError("the FLAC-24 hook library is not loaded (use_flac24_hooks)")
+        L = _used(_flac24_hooks)
+        ok = L.sauAmd_render_file_flac_loudness_with_backends(program.ptr, srate, os.fsencode(path), channels, block_frames,
+                                                              int(bits), _lpc_order(max_lpc_order), target_lufs, max_true_peak,
+                                                              1 if limited else 0, backends[0], backends[1], C.byref(n))
+    if not ok:
+        raise RuntimeError("sauAmd_render_file_flac_loudness failed: " + last_error(L))
+    return n.value, ld, gain.value, (st if limited else None), info
 
 
 def limiter_window(srate):
@@ -1113,6 +1232,11 @@ class Batch:
         the batch's device and stream. Close it before the batch."""
         return Flac(self, n_rows, channels, block_frames, max_lpc_order)
 
+    def create_flac_f32(self, n_rows, channels, block_frames=0, bits=24, max_lpc_order=0):
+        """sauAmd_Batch_create_flac_f32: a float-fed Flac encoder of ``bits`` (16 or 24) per sample; ``feed_f32`` takes float
+        rows and per-row gains. Close it before the batch."""
+        return Flac(self, n_rows, channels, block_frames, max_lpc_order, bits=bits)
+
     def create_flac_lpc(self, n_rows, channels, block_frames=0, max_lpc_order=0):
         """(tests) sauAmd_Batch_create_flac_lpc whatever max_lpc_order is -- create_flac reaches it only with an order above 0 --:
         with 0 the encoder create_flac makes, by the other entry point"""
@@ -1213,12 +1337,17 @@ class Flac:
     row r's next frames[r] frames from device memory, on the batch's stream; ``read`` waits and returns the rows' encoded bytes.
     Close it before its batch."""
 
-    def __init__(self, batch, n_rows, channels, block_frames=0, max_lpc_order=0, lpc_entry=False):
+    def __init__(self, batch, n_rows, channels, block_frames=0, max_lpc_order=0, lpc_entry=False, bits=None):
         self._L = batch._L
         self.n_rows, self.channels, self.block_frames = int(n_rows), int(channels), int(block_frames)
         self.max_lpc_order = _lpc_order(max_lpc_order)
+        self.bits = None if bits is None else int(bits)  # (None: fed int16 rows; 16 or 24: fed float rows)
         entry = "sauAmd_Batch_create_flac_lpc" if self.max_lpc_order or lpc_entry else "sauAmd_Batch_create_flac"
-        if self.max_lpc_order or lpc_entry:  # (lpc_entry, tests: the _lpc entry point with order 0 too)
+        if self.bits is not None:
+            entry = "sauAmd_Batch_create_flac_f32"
+            self._e = _used(self._L).sauAmd_Batch_create_flac_f32(batch._b, self.n_rows, self.channels, self.block_frames,
+                                                                  self.bits, self.max_lpc_order)
+        elif self.max_lpc_order or lpc_entry:  # (lpc_entry, tests: the _lpc entry point with order 0 too)
             self._e = _used(self._L).sauAmd_Batch_create_flac_lpc(batch._b, self.n_rows, self.channels, self.block_frames,
                                                                   self.max_lpc_order)
         else:
@@ -1233,6 +1362,14 @@ class Flac:
         fr = (C.c_uint32 * self.n_rows)(*[int(f) for f in frames])
         if not _used(self._L).sauAmd_Flac_feed(self._e, ptr, pitch, fr, 1 if finish else 0):
             raise RuntimeError("sauAmd_Flac_feed failed: " + last_error(self._L))
+
+    def feed_f32(self, ptr, pitch, frames, gains=None, finish=False):
+        """sauAmd_Flac_feed_f32: row r's next frames[r] float frames from the device rows at `ptr`, `pitch` bytes apart, times
+        gains[r] (None: 1.0)."""
+        fr = (C.c_uint32 * self.n_rows)(*[int(f) for f in frames])
+        g = None if gains is None else (C.c_float * self.n_rows)(*[float(v) for v in gains])
+        if not _used(self._L).sauAmd_Flac_feed_f32(self._e, ptr, pitch, fr, g, 1 if finish else 0):
+            raise RuntimeError("sauAmd_Flac_feed_f32 failed: " + last_error(self._L))
 
     def unread(self):
         """sauAmd_Flac_read without buffers -> (the unread bytes per row as a list, the rows' FlacInfo as dicts)"""

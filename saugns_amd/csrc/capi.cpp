@@ -713,6 +713,50 @@ extern "C" bool sauAmd_Flac_feed(sauAmdFlac *e, const void *rows, size_t pitch_b
 	return false;
 }
 
+/* ---- 24 bits and float-fed encoders (include/saugns_amd.h, FLAC, "24 bits") ---- */
+extern "C" size_t sauAmd_flac_header_bits(uint32_t srate, int channels, uint32_t block_frames, int bits, const sauAmdFlacInfo *info,
+		uint8_t *out, size_t cap) {
+	return sauengine::flac_header_bits(srate, channels, block_frames, bits, (const sauengine::FlacInfo *)info, out, cap);
+}
+extern "C" size_t sauAmd_flac_encode_block_s32(const int32_t *x, uint32_t n, int channels, uint32_t block_frames, uint32_t frame_number,
+		int bits, uint32_t max_lpc_order, uint8_t *out, size_t cap) {
+	try {
+		return sauengine::flac_encode_block_s32(x, n, channels, block_frames, frame_number, bits, max_lpc_order, out, cap);
+	} catch (const std::exception &) { /* (nothing C++ crosses the C ABI) */
+		return 0;
+	}
+}
+extern "C" bool sauAmd_flac_quantize(const float *x, size_t n, float gain, int bits, int32_t *out) {
+	return sauengine::flac_quantize(x, n, gain, bits, out);
+}
+
+extern "C" sauAmdFlac *sauAmd_Batch_create_flac_f32(sauAmdBatch *b, size_t n_rows, int channels, uint32_t block_frames, int bits,
+		uint32_t max_lpc_order) {
+	std::string err;
+	try {
+		if (!b || !n_rows || n_rows > sauflac::FLAC_MAX_ROWS || !sauengine::flac_params_ok(channels, block_frames) ||
+		    !sauflac::flac_bits_ok(bits) || max_lpc_order > sauflac::FLAC_LPC_MAX || (bits == 24 && max_lpc_order)) err = "bad argument";
+		else if (sauengine::FlacEncoder *e = b->engine->backend()->create_flac_f32(n_rows, (uint32_t)channels, block_frames, bits, max_lpc_order, err))
+			return new sauAmdFlac{e};
+	} catch (const std::exception &ex) {
+		err = std::string("internal error: ") + ex.what();
+	}
+	report("flac", err);
+	return nullptr;
+}
+
+extern "C" bool sauAmd_Flac_feed_f32(sauAmdFlac *e, const void *rows, size_t pitch_bytes, const uint32_t *frames, const float *gains, int finish) {
+	std::string err;
+	try {
+		if (!e || !rows || !frames || ((uintptr_t)rows & 3u) || (pitch_bytes & 3u)) err = "bad argument";
+		else if (e->enc->feed_f32(rows, pitch_bytes, frames, gains, finish != 0, err)) return true;
+	} catch (const std::exception &ex) {
+		err = std::string("internal error: ") + ex.what();
+	}
+	report("flac", err);
+	return false;
+}
+
 extern "C" bool sauAmd_Flac_read(sauAmdFlac *e, uint8_t *const *bufs, const size_t *caps, size_t *bytes_out, sauAmdFlacInfo *info_out, int reset) {
 	std::string err;
 	try {

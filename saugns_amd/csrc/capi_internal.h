@@ -53,6 +53,16 @@ bool render_file_flac(const sauProgram *prg, uint32_t srate, const char *path, i
 bool render_file_flac_lpc(const sauProgram *prg, uint32_t srate, const char *path, int channels, uint32_t block_frames, uint32_t max_lpc_order,
 		const std::function<sauengine::Backend *(std::string &)> &make_backend, uint64_t *frames_out, sauAmdFlacInfo *info_out,
 		std::string &err);
+/* sauAmd_render_file_flac_f32's body (sndout.cpp): as render_file_flac_lpc, over float runs and a float-fed encoder of `bits` */
+bool render_file_flac_f32(const sauProgram *prg, uint32_t srate, const char *path, int channels, uint32_t block_frames, int bits,
+		uint32_t max_lpc_order, float gain, const std::function<sauengine::Backend *(std::string &)> &make_backend, uint64_t *frames_out,
+		sauAmdFlacInfo *info_out, std::string &err);
+/* sauAmd_render_file_flac_loudness's body (sndout.cpp). As render_file_loudness and render_file_loudness_limited: two passes, two
+ * engines, make_backend asked once per pass -- after the arguments have been looked at, so a bad argument asks for none. */
+bool render_file_flac_loudness(const sauProgram *prg, uint32_t srate, const char *path, int channels, uint32_t block_frames, int bits,
+		uint32_t max_lpc_order, double target_lufs, float max_true_peak, bool limited,
+		const std::function<sauengine::Backend *(std::string &)> &make_backend, uint64_t *frames_out, sauAmdLoudness *loud_out,
+		float *gain_out, sauAmdLimiterStats *stats_out, sauAmdFlacInfo *info_out, std::string &err);
 /* the thread's sauAmd_last_error text (capi.cpp), with the line on stderr */
 void set_last_error(const char *where, const std::string &err);
 } /* namespace sauamd_internal */

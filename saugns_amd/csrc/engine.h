@@ -126,6 +126,14 @@ size_t flac_encode_block(const int16_t *x, uint32_t n, int channels, uint32_t bl
 /* ... with the LPC mode's max_lpc_order (0 .. 8; 0: flac_encode_block) */
 size_t flac_encode_block_lpc(const int16_t *x, uint32_t n, int channels, uint32_t block_frames, uint32_t frame_number, uint32_t max_lpc_order,
 		uint8_t *out, size_t cap);
+/* 24 bits and float-fed encoders (the header's "24 bits"). flac_header_bits: flac_header with STREAMINFO's bits per sample, 16 or
+ * 24. flac_encode_block_s32: one frame of int32 samples -- bits 16: every sample fits int16, the bytes of flac_encode_block_lpc;
+ * bits 24: every sample in -2^23 .. 2^23 - 1 and max_lpc_order 0 -- else 0. flac_quantize: what flac_quant_kernel makes,
+ * pcm16(x * gain) or pcm24(x * gain); false for other bits. */
+size_t flac_header_bits(uint32_t srate, int channels, uint32_t block_frames, int bits, const FlacInfo *info, uint8_t *out, size_t cap);
+size_t flac_encode_block_s32(const int32_t *x, uint32_t n, int channels, uint32_t block_frames, uint32_t frame_number, int bits,
+		uint32_t max_lpc_order, uint8_t *out, size_t cap);
+bool flac_quantize(const float *x, size_t n, float gain, int bits, int32_t *out);
 inline bool flac_params_ok(int channels, uint32_t block_frames) {
 	return (channels == 1 || channels == 2) && sauflac::flac_block_frames(block_frames) != 0;
 }
@@ -139,6 +147,12 @@ public:
 	virtual uint32_t block_frames() const = 0;
 	/* row r's next frames[r] frames, from rows + pitch_bytes * r: device work on the backend's stream; `finish` closes the rows */
 	virtual bool feed(const void *rows, size_t pitch_bytes, const uint32_t *frames, bool finish, std::string &err) = 0;
+	/* a float-fed encoder (Backend::create_flac_f32): row r's next frames[r] float frames times gains[r] (NULL: 1.0f), quantised
+	 * into rows of the encoder's own and fed from there. An encoder is of one kind: the other kind's feed is a bad argument. */
+	virtual bool feed_f32(const void *rows, size_t pitch_bytes, const uint32_t *frames, const float *gains, bool finish, std::string &err) {
+		(void)rows; (void)pitch_bytes; (void)frames; (void)gains; (void)finish; err = "bad argument: this encoder is fed int16 rows"; return false;
+	}
+	virtual uint32_t bits() const { return 16; }
 	/* wait for the stream; bytes_out[n_rows] the unread bytes; bufs (may be NULL): they are copied there and consumed, every
 	 * caps[r] has to suffice; info_out (may be NULL) [n_rows]; `reset`: new streams behind the read */
 	virtual bool read(uint8_t *const *bufs, const size_t *caps, size_t *bytes_out, FlacInfo *info_out, bool reset, std::string &err) = 0;
@@ -405,6 +419,11 @@ public:
 	virtual FlacEncoder *create_flac_lpc(size_t n_rows, uint32_t channels, uint32_t block_frames, uint32_t max_lpc_order, std::string &err) {
 		if (!max_lpc_order) return create_flac(n_rows, channels, block_frames, err);
 		err = "this backend's FLAC encoder has no LPC mode"; return nullptr;
+	}
+	/* A float-fed encoder of 16 or 24 bits per sample (FlacEncoder::feed_f32); 24 with max_lpc_order 0 only. */
+	virtual FlacEncoder *create_flac_f32(size_t n_rows, uint32_t channels, uint32_t block_frames, int bits, uint32_t max_lpc_order, std::string &err) {
+		(void)n_rows; (void)channels; (void)block_frames; (void)bits; (void)max_lpc_order;
+		err = "this backend has no float-fed FLAC encoder"; return nullptr;
 	}
 	/* the same from empty records on rows of `frames` frames each, synchronous; spectrogram_out (may be NULL): every segment's
 	 * (float)p[k], [n_rows][channels][S][N/2 + 1], refused when spectrogram_cap (in floats) does not suffice */

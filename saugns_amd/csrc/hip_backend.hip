@@ -15,7 +15,8 @@
  *   k_limiter.h     lim_env_kernel, lim_gain_kernel, lim_finish_kernel, lim_carry_kernel (the look-ahead true-peak limiter)
  *   k_spectrum.h    spec_segment_kernel, spec_finish_kernel, spec_carry_kernel (Welch power spectra of fed rows)
  *   k_flac.h        flac_analyze_kernel, flac_scan_kernel, flac_write_kernel, flac_carry_kernel (FLAC frames of fed int16 rows;
- *                   the <true> builds of the first and the third hold the LPC mode)
+ *                   the <true> builds of the first and the third hold the LPC mode), flac_quant_kernel (a float-fed encoder's
+ *                   rows), flac_analyze_wide_kernel, flac_write_wide_kernel, flac_carry_wide_kernel (24 bits: int32 samples)
  *   launch_plan.h   (plain C++, no HIP) the tuning switches and every decision about a segment's launches: rows per pass, LDS
  *                   budgets, builds, grids, tasks, chain chunks, the mixer -- a plan per segment, testable without a GPU
  *   mix_overlap.h   (plain C++, no HIP) where the main stream waits for a final mixer that runs on the side stream
@@ -47,6 +48,7 @@
 #include "hip_backend.h"
 #include "launch_plan.h"
 #include "sau_dev_ops.h"
+#include <float.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -2198,8 +2200,10 @@ public:
 	 * the host. The unread total that the 1 GiB rule counts is the feeds' worst cases until a read has fetched the sizes. */
 	class Flac : public sauengine::FlacEncoder {
 	public:
-		Flac(HipBackendImpl *be, size_t n_rows, uint32_t channels, uint32_t block_frames, uint32_t max_lpc_order)
-			: be_(be), n_(n_rows), ch_(channels), B_(sauflac::flac_block_frames(block_frames)), M_(max_lpc_order), pos_(n_rows, 0), blocks_(n_rows, 0) {
+		/* f32: a float-fed encoder of `bits` per sample (feed_f32); else the int16-fed one (bits 16) */
+		Flac(HipBackendImpl *be, size_t n_rows, uint32_t channels, uint32_t block_frames, uint32_t max_lpc_order, bool f32 = false, uint32_t bits = 16)
+			: be_(be), n_(n_rows), ch_(channels), B_(sauflac::flac_block_frames(block_frames)), M_(max_lpc_order), f32_(f32), bits_(bits),
+			  pos_(n_rows, 0), blocks_(n_rows, 0) {
 			/* (tests: another limit of unread bytes than 1 GiB) */
 			if (const char *v = sauengine::tune_env("SAU_AMD_FLAC_UNREAD_MAX")) { const long long x = atoll(v); if (x > 0) limit_ = (uint64_t)x; }
 		}
@@ -2210,12 +2214,13 @@ public:
 		size_t n_rows() const override { return n_; }
 		uint32_t channels() const override { return ch_; }
 		uint32_t block_frames() const override { return B_; }
+		uint32_t bits() const override { return bits_; }
 		bool init(std::string &err) {
-			const FlacPlan plan = plan_flac(B_, ch_, n_, nullptr);
+			const FlacPlan plan = plan_flac(B_, ch_, n_, nullptr, bits_);
 			if (!plan.ok) { err = "bad argument"; return false; }
-			if (!pend_[0].ensure(n_ * plan.pend_pitch, err) || !pend_[1].ensure(n_ * plan.pend_pitch, err) || !desc_.ensure(n_, err) ||
-			    !stats_.ensure(n_, err))
-				return false;
+			const size_t pend = n_ * plan.pend_pitch * (bits_ == 24 ? 2 : 1); /* (int16 units: the wide kernels' pending samples are int32) */
+			if (!pend_[0].ensure(pend, err) || !pend_[1].ensure(pend, err) || !desc_.ensure(n_, err) || !stats_.ensure(n_, err)) return false;
+			if (f32_ && !qdesc_.ensure(n_, err)) return false;
 			return clear(err);
 		}
 		/* new streams: behind a read, which has waited for the stream */
@@ -2228,22 +2233,39 @@ public:
 			return true;
 		}
 		bool feed(const void *rows, size_t pitch, const uint32_t *frames, bool finish, std::string &err) override {
+			if (f32_) { err = "bad argument: this encoder is fed float rows (feed_f32)"; return false; }
+			return feed_any(rows, pitch, frames, nullptr, finish, err);
+		}
+		bool feed_f32(const void *rows, size_t pitch, const uint32_t *frames, const float *gains, bool finish, std::string &err) override {
+			if (!f32_) { err = "bad argument: this encoder is fed int16 rows (feed)"; return false; }
+			return feed_any(rows, pitch, frames, gains, finish, err);
+		}
+		/* a float-fed encoder's feed differs in what it asks of the rows, and in the quantiser ahead of the other kernels, which
+		 * then read the encoder's own rows; every refusal comes before anything is queued or changed */
+		bool feed_any(const void *rows, size_t pitch, const uint32_t *frames, const float *gains, bool finish, std::string &err) {
 			be_->use_device();
 			if (!be_->join_mixer("flac_feed", err)) return false; /* (the rows fed may be the batch's PCM) */
-			if (!rows || !frames || ((uintptr_t)rows & 15u) || (pitch & 15u)) { err = "bad argument: rows and pitch_bytes must be multiples of 16"; return false; }
+			const uintptr_t align = f32_ ? 3u : 15u;
+			if (!rows || !frames || ((uintptr_t)rows & align) || (pitch & align)) {
+				err = f32_ ? "bad argument: rows and pitch_bytes must be multiples of 4" : "bad argument: rows and pitch_bytes must be multiples of 16";
+				return false;
+			}
+			for (size_t r = 0; f32_ && gains && r < n_; ++r)
+				if (!(gains[r] >= -FLT_MAX && gains[r] <= FLT_MAX)) { err = "bad argument: a gain is not finite"; return false; }
 			if (closed_) { err = "bad argument: the streams are finished (read with reset first)"; return false; }
 			uint32_t longest = 0;
 			for (size_t r = 0; r < n_; ++r) longest = frames[r] > longest ? frames[r] : longest;
 			if (!longest && !finish) return true; /* nothing changes, and the rows are not looked at */
 			if (longest) {
-				const size_t row_bytes = (size_t)longest * ch_ * sizeof(int16_t);
+				const size_t row_bytes = (size_t)longest * ch_ * (f32_ ? sizeof(float) : sizeof(int16_t));
 				if (n_ > 1 && row_bytes > pitch) { err = "bad argument: rows longer than their pitch"; return false; }
 				/* the rows are read by kernels: they have to lie inside one allocation of this device */
 				if (!be_->lim_rows_inside(rows, pitch, n_, row_bytes, "rows", err)) return false;
 			}
+			const bool wide = bits_ == 24;
 			std::vector<FlacRow> d(n_);
 			for (size_t r = 0; r < n_; ++r) d[r] = plan_flac_row(pos_[r], frames[r], B_, finish);
-			const FlacPlan plan = plan_flac(B_, ch_, n_, d.data());
+			const FlacPlan plan = plan_flac(B_, ch_, n_, d.data(), bits_);
 			if (!plan.ok) { err = "bad argument: too many frames for one feed, or for one stream"; return false; }
 			if (bound_ + plan.worst > limit_) { err = "bad argument: the unread output could pass its limit (read first)"; return false; }
 			std::unique_ptr<Chunk> c;
@@ -2253,14 +2275,52 @@ public:
 				c->off.resize(n_);
 				for (size_t r = 0; r < n_; ++r) c->off[r] = d[r].out_off;
 			}
+			/* a float-fed encoder's own rows: as long as the feed's longest row, on a pitch that is a multiple of 256 */
+			const size_t q_pitch = ((size_t)longest * ch_ * (wide ? sizeof(int32_t) : sizeof(int16_t)) + 255) & ~(size_t)255;
+			if (f32_ && longest && !qrows_.ensure(n_ * q_pitch, err)) return false;
 			if (!be_->send(desc_.p, d.data(), n_ * sizeof(FlacRow), err)) return false;
+			hipStream_t st = be_->stream_;
+			if (f32_ && longest) {
+				std::vector<FlacQuantRow> q(n_);
+				for (size_t r = 0; r < n_; ++r) { q[r].n = (unsigned long long)frames[r] * ch_; q[r].gain = gains ? gains[r] : 1.0f; q[r].pad_ = 0; }
+				if (!be_->send(qdesc_.p, q.data(), n_ * sizeof(FlacQuantRow), err)) return false;
+				FlacQuantParams qp;
+				qp.src = (const float *)rows; qp.src_pitch = pitch; qp.dst = qrows_.p; qp.dst_pitch = q_pitch; qp.rows = qdesc_.p;
+				/* thread 0 of a row takes the samples ahead of the first 16-byte boundary, every other thread four */
+				const dim3 grid((uint32_t)(((unsigned long long)longest * ch_ / 4 + 2 + 255) / 256), (uint32_t)n_);
+				if (wide) hipLaunchKernelGGL(flac_quant_kernel<int32_t>, grid, dim3(256), 0, st, qp);
+				else hipLaunchKernelGGL(flac_quant_kernel<int16_t>, grid, dim3(256), 0, st, qp);
+				HIP_OK(hipGetLastError());
+				rows = qrows_.p; pitch = q_pitch;
+			}
 			FlacParams fp;
 			memset((void *)&fp, 0, sizeof fp);
 			fp.rows = (const int16_t *)rows; fp.row_pitch = pitch; fp.desc = desc_.p;
 			fp.pend = pend_[cur_].p; fp.pend_next = pend_[cur_ ^ 1].p; fp.pend_pitch = plan.pend_pitch;
 			fp.frames = frames_.p; fp.stats = stats_.p;
 			fp.B = B_; fp.channels = ch_; fp.n_rows = (uint32_t)n_; fp.jobs = plan.jobs; fp.max_lpc = M_;
-			hipStream_t st = be_->stream_;
+			if (wide) { /* the sibling kernels of int32 samples; flac_scan_kernel is the same */
+				FlacWideParams wp;
+				memset((void *)&wp, 0, sizeof wp);
+				wp.rows = (const int32_t *)rows; wp.row_pitch = pitch; wp.desc = desc_.p;
+				wp.pend = (const int32_t *)pend_[cur_].p; wp.pend_next = (int32_t *)pend_[cur_ ^ 1].p; wp.pend_pitch = plan.pend_pitch;
+				wp.frames = frames_.p;
+				wp.B = B_; wp.channels = ch_; wp.n_rows = (uint32_t)n_; wp.jobs = plan.jobs;
+				if (plan.jobs) {
+					wp.out = fp.out = c->out.p; fp.row_bytes = c->row_bytes.p;
+					hipLaunchKernelGGL(flac_analyze_wide_kernel, dim3(plan.jobs), dim3(plan.analyze_threads), plan.analyze_lds, st, wp);
+					HIP_OK(hipGetLastError());
+					hipLaunchKernelGGL(flac_scan_kernel, dim3(plan.rows), dim3(FLAC_THREADS), 0, st, fp);
+					HIP_OK(hipGetLastError());
+					hipLaunchKernelGGL(flac_write_wide_kernel, dim3(plan.jobs), dim3(FLAC_THREADS), plan.write_lds, st, wp);
+					HIP_OK(hipGetLastError());
+				}
+				if (!finish) {
+					hipLaunchKernelGGL(flac_carry_wide_kernel, dim3((uint32_t)((plan.pend_pitch + FLAC_THREADS - 1) / FLAC_THREADS), plan.rows), dim3(FLAC_THREADS), 0, st, wp);
+					HIP_OK(hipGetLastError());
+					cur_ ^= 1;
+				}
+			} else {
 			if (plan.jobs) {
 				fp.out = c->out.p; fp.row_bytes = c->row_bytes.p;
 				/* (max_lpc_order 0 runs the kernels without the LPC mode's code: the encoder as it was before that mode) */
@@ -2277,6 +2337,7 @@ public:
 				hipLaunchKernelGGL(flac_carry_kernel, dim3((uint32_t)((plan.pend_pitch + FLAC_THREADS - 1) / FLAC_THREADS), plan.rows), dim3(FLAC_THREADS), 0, st, fp);
 				HIP_OK(hipGetLastError());
 				cur_ ^= 1;
+			}
 			}
 			for (size_t r = 0; r < n_; ++r) { pos_[r] += frames[r]; blocks_[r] += d[r].n_blocks; }
 			if (c) chunks_.push_back(std::move(c));
@@ -2341,6 +2402,8 @@ public:
 		HipBackendImpl *be_;
 		size_t n_;
 		uint32_t ch_, B_, M_;
+		bool f32_;                           /* fed float rows (feed_f32), quantised into qrows_ */
+		uint32_t bits_;                      /* 16, or 24: the wide kernels */
 		std::vector<uint64_t> pos_, blocks_; /* per row: frames fed, blocks made */
 		std::vector<std::unique_ptr<Chunk>> chunks_;
 		uint64_t bound_ = 0, limit_ = sauflac::FLAC_MAX_UNREAD;
@@ -2349,6 +2412,8 @@ public:
 		DevBuf<FlacRow> desc_;
 		DevBuf<FlacStats> stats_;
 		DevBuf<FlacFrameDesc> frames_;
+		DevBuf<unsigned char> qrows_;        /* a float-fed encoder's quantised rows of the feed at hand */
+		DevBuf<FlacQuantRow> qdesc_;
 		int cur_ = 0;
 	};
 	sauengine::FlacEncoder *create_flac(size_t n_rows, uint32_t channels, uint32_t block_frames, std::string &err) override {
@@ -2360,6 +2425,16 @@ public:
 		if (!sauengine::flac_params_ok((int)channels, block_frames) || !n_rows || max_lpc_order > sauflac::FLAC_LPC_MAX) { err = "bad argument"; return nullptr; }
 		if (n_rows > sauflac::FLAC_MAX_ROWS) { err = "bad argument: more than 65535 rows"; return nullptr; }
 		Flac *e = new Flac(this, n_rows, channels, block_frames, max_lpc_order);
+		if (!e->init(err)) { delete e; return nullptr; }
+		return e;
+	}
+	sauengine::FlacEncoder *create_flac_f32(size_t n_rows, uint32_t channels, uint32_t block_frames, int bits, uint32_t max_lpc_order, std::string &err) override {
+		use_device();
+		if (!join_mixer("create_flac", err)) return nullptr;
+		if (!sauengine::flac_params_ok((int)channels, block_frames) || !n_rows || !sauflac::flac_bits_ok(bits) || max_lpc_order > sauflac::FLAC_LPC_MAX) { err = "bad argument"; return nullptr; }
+		if (bits == 24 && max_lpc_order) { err = "bad argument: no LPC mode at 24 bits"; return nullptr; }
+		if (n_rows > sauflac::FLAC_MAX_ROWS) { err = "bad argument: more than 65535 rows"; return nullptr; }
+		Flac *e = new Flac(this, n_rows, channels, block_frames, max_lpc_order, true, (uint32_t)bits);
 		if (!e->init(err)) { delete e; return nullptr; }
 		return e;
 	}

@@ -25,6 +25,8 @@
  * orders in one walk of the lane's run; the chosen order's sums of u >> k per finest partition in 64 bits, merged and priced
  * as the FIXED ones; then LPC takes the record where it is cheaper. The writer reads the coefficients from the record in LDS.
  * No lane walks a whole block: a lane's run is n / 64 frames in the analysis, n / 256 in the writer.
+ * The float-fed encoders' quantiser and the 24-bit siblings of the analysis, writer and carry kernels stand at the end of this
+ * file, with a comment of their own; nothing above them is changed by them.
  *
  * LDS. Frame i is kept at word i + (i >> 5): in the partition sums a lane walks a run of consecutive frames (one new word per
  * frame) and the runs lie B / 64 apart, which without the extra word per 32 would put all lanes on one bank at B = 4096. The
@@ -450,6 +452,283 @@ __global__ __launch_bounds__(FLAC_THREADS) void flac_carry_kernel(const FlacPara
 	if (e >= d.pend_next * ch) return;
 	const int16_t *xrow = (const int16_t *)((const char *)P.rows + P.row_pitch * row);
 	const int16_t *pend = P.pend + P.pend_pitch * row;
+	const unsigned long long at = (unsigned long long)d.n_blocks * P.B * ch + e; /* counted from the row's frame block0 * B, in samples */
+	P.pend_next[P.pend_pitch * row + e] = at < (unsigned long long)d.pend * ch ? pend[at] : xrow[at - (unsigned long long)d.pend * ch];
+}
+
+/* ---- 24 bits (the header's "24 bits"): sibling kernels of int32 rows; flac_scan_kernel serves both widths ----
+ *   flac_quant_kernel<OutT>   grid (runs of 1024 samples, rows) x 256: dst = pcm16(x * gain[row]) or pcm24(x * gain[row]) of a
+ *       float-fed encoder's rows, into rows of the encoder's own. A source row need only be float-aligned: thread 0 takes the
+ *       samples ahead of the row's first 16-byte boundary one by one, every other thread four from a 16-byte load, the row's
+ *       end again one by one.
+ *   flac_analyze_wide_kernel, flac_write_wide_kernel, flac_carry_wide_kernel: the <false> builds' structure with int32
+ *       samples. L and R are staged as two arrays, each with flac_ix's padding, R behind L; M and S are formed where they are
+ *       read. Every sum of a lane is 64-bit (an order-4 residual takes 29 bits, u 30), the parameters are 0 .. 30 with five
+ *       bits each, s_fine is [4][16 * 31]. The analysis takes 8.25 B bytes (stereo) + 17 KiB: 51 KiB at B = 4096; the writer
+ *       8.25 B + the frame's bound: 57 KiB. The 31 accumulators are registers with compile-time indices; the frame's record
+ *       and its k[] are read from LDS as in the 16-bit writer. */
+struct FlacQuantRow {
+	unsigned long long n;     /* samples of the row's feed */
+	float gain;
+	uint32_t pad_;
+};
+static_assert(sizeof(FlacQuantRow) == 16, "FlacQuantRow is uploaded as it stands");
+struct FlacQuantParams {
+	const float *src;         /* the fed rows */
+	size_t src_pitch;         /* bytes */
+	void *dst;                /* the encoder's rows: 256-byte aligned */
+	size_t dst_pitch;         /* bytes, a multiple of 256 */
+	const FlacQuantRow *rows; /* [grid.y] */
+};
+template <typename OutT>
+__global__ __launch_bounds__(256) void flac_quant_kernel(const FlacQuantParams P) {
+	typedef float __attribute__((ext_vector_type(4))) f32x4;
+	typedef uint32_t __attribute__((ext_vector_type(2))) u32x2;
+	typedef int32_t __attribute__((ext_vector_type(4))) i32x4;
+	const unsigned row = blockIdx.y;
+	const FlacQuantRow d = P.rows[row];
+	const float *src = (const float *)((const char *)P.src + P.src_pitch * row);
+	OutT *dst = (OutT *)((char *)P.dst + P.dst_pitch * row);
+	const unsigned head = (unsigned)((16u - (unsigned)((uintptr_t)src & 15u)) & 15u) >> 2; /* samples ahead of the first 16-byte boundary */
+	const unsigned long long t = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+	const unsigned long long i0 = t ? head + (t - 1) * 4 : 0;
+	const unsigned cnt = t ? 4 : head;
+	if (i0 >= d.n) return;
+	auto one = [&](float x) -> OutT {
+		const float y = x * d.gain;
+		if constexpr (std::is_same<OutT, int16_t>::value) return pcm16(y);
+		else return pcm24(y);
+	};
+	if (cnt == 4 && i0 + 4 <= d.n) {
+		const f32x4 q = __builtin_nontemporal_load((const f32x4 *)(src + i0));
+		const OutT a = one(q.x), b = one(q.y), c = one(q.z), e = one(q.w);
+		if (head) { dst[i0] = a; dst[i0 + 1] = b; dst[i0 + 2] = c; dst[i0 + 3] = e; }
+		else if constexpr (std::is_same<OutT, int16_t>::value) {
+			u32x2 w;
+			w.x = (uint32_t)(uint16_t)a | ((uint32_t)(uint16_t)b << 16);
+			w.y = (uint32_t)(uint16_t)c | ((uint32_t)(uint16_t)e << 16);
+			*(u32x2 *)(dst + i0) = w;
+		} else {
+			i32x4 w; w.x = a; w.y = b; w.z = c; w.w = e;
+			*(i32x4 *)(dst + i0) = w;
+		}
+		return;
+	}
+	const unsigned long long i1 = i0 + cnt < d.n ? i0 + cnt : d.n;
+	for (unsigned long long i = i0; i < i1; ++i) dst[i] = one(src[i]);
+}
+
+struct FlacWideParams {
+	const int32_t *rows;      /* the encoder's quantised rows (or fed int32 rows); 16-byte aligned */
+	size_t row_pitch;         /* bytes between them */
+	const FlacRow *desc;      /* [n_rows] */
+	const int32_t *pend;      /* [n_rows][pend_pitch], interleaved like the row */
+	int32_t *pend_next;
+	size_t pend_pitch;        /* int32 */
+	FlacFrameDesc *frames;    /* [jobs] */
+	uint8_t *out;
+	uint32_t B, channels, n_rows, jobs;
+};
+
+/* block j of the row's feed, n frames: L (or the one channel) into s_w, R into s_w + R0 */
+__device__ __forceinline__ void flac_stage_wide(const FlacWideParams &P, const FlacRow &d, const unsigned row, const unsigned j, const unsigned n,
+		int32_t *s_w, const unsigned R0) {
+	const char *xrow = (const char *)P.rows + P.row_pitch * row;
+	const int32_t *pend = P.pend + P.pend_pitch * row;
+	const unsigned long long first = (unsigned long long)j * P.B;
+	for (unsigned i = threadIdx.x; i < n; i += blockDim.x) {
+		const unsigned long long rel = first + i;
+		if (P.channels == 2) { /* (rows and pitches are multiples of 16: a frame is an aligned pair of words) */
+			const int2 f = rel < d.pend ? ((const int2 *)pend)[rel] : ((const int2 *)xrow)[rel - d.pend];
+			s_w[flac_ix(i)] = f.x;
+			s_w[R0 + flac_ix(i)] = f.y;
+		} else
+			s_w[flac_ix(i)] = rel < d.pend ? pend[rel] : ((const int32_t *)xrow)[rel - d.pend];
+	}
+}
+/* candidate c's sample i (0 below the block's start). c is the same for a whole wave; mono has c == 0 only and no R array. */
+__device__ __forceinline__ int32_t flac_at_wide(const int32_t *s_w, const unsigned R0, const unsigned c, const int i) {
+	if (i < 0) return 0;
+	const unsigned x = flac_ix((unsigned)i);
+	if (c == FLAC_CAND_L) return s_w[x];
+	if (c == FLAC_CAND_R) return s_w[R0 + x];
+	return flac_cand_w(s_w[x], s_w[R0 + x], c);
+}
+
+__global__ __launch_bounds__(256) void flac_analyze_wide_kernel(const FlacWideParams P) {
+	extern __shared__ uint32_t flac_lds[];
+	__shared__ uint64_t s_fine[4][FLAC_FINE * FLAC_NK_W];
+	__shared__ uint64_t s_node_cost[4][32];
+	__shared__ uint8_t s_node_k[4][32];
+	__shared__ FlacSub s_cand[4];
+	int32_t *s_w = (int32_t *)flac_lds;
+	const unsigned R0 = P.B + (P.B >> 5);
+	const unsigned job = blockIdx.x, row = flac_find_row(P.desc, P.n_rows, job);
+	const FlacRow d = P.desc[row];
+	const unsigned j = job - d.job0;
+	if (j >= d.n_blocks) return; /* (never: the jobs are the rows' blocks; uniform) */
+	const unsigned n = j == d.n_blocks - 1 ? d.last_n : P.B;
+	flac_stage_wide(P, d, row, j, n, s_w, R0);
+	__syncthreads();
+	const unsigned c = threadIdx.x >> 6, lane = threadIdx.x & 63; /* one wave per candidate */
+	/* constant? and the five orders' sums of |r_i|, i = 4 .. n-1: 64 bits already in the lane (64 values of up to 2^28) */
+	const int32_t s_first = flac_at_wide(s_w, R0, c, 0);
+	bool eq = true;
+	unsigned long long a64[5] = {0, 0, 0, 0, 0};
+	for (unsigned i = lane; i < n; i += 64) {
+		const int32_t s0 = flac_at_wide(s_w, R0, c, (int)i);
+		eq = eq && s0 == s_first;
+		if (i >= 4) {
+			int32_t r[5];
+			flac_residuals(s0, flac_at_wide(s_w, R0, c, (int)i - 1), flac_at_wide(s_w, R0, c, (int)i - 2), flac_at_wide(s_w, R0, c, (int)i - 3),
+					flac_at_wide(s_w, R0, c, (int)i - 4), r);
+#pragma unroll
+			for (int o = 0; o < 5; ++o) a64[o] += flac_abs(r[o]);
+		}
+	}
+	const bool equal = __all(eq ? 1 : 0) != 0;
+	uint64_t abs_sum[5];
+#pragma unroll
+	for (int o = 0; o < 5; ++o) abs_sum[o] = flac_wave_sum(a64[o], 6);
+	const unsigned o = flac_pick_order(n, abs_sum);
+	/* the sums of u >> k, k = 0 .. 30, per finest partition: sixteen in a whole block, four lanes each, a lane a run of consecutive frames */
+	const unsigned fine_log2 = n == P.B ? 4 : 0;
+	unsigned long long f64[FLAC_NK_W];
+#pragma unroll
+	for (unsigned k = 0; k < FLAC_NK_W; ++k) f64[k] = 0;
+	if (fine_log2) {
+		const unsigned run = n >> 6, i0 = lane * run; /* (lane >> 2 is the partition) */
+		int32_t s1 = flac_at_wide(s_w, R0, c, (int)i0 - 1), s2 = flac_at_wide(s_w, R0, c, (int)i0 - 2), s3 = flac_at_wide(s_w, R0, c, (int)i0 - 3),
+			s4 = flac_at_wide(s_w, R0, c, (int)i0 - 4);
+		for (unsigned i = i0; i < i0 + run; ++i) {
+			const int32_t s0 = flac_at_wide(s_w, R0, c, (int)i);
+			if (i >= o) {
+				const uint32_t u = flac_zigzag(flac_residual(o, s0, s1, s2, s3, s4));
+#pragma unroll
+				for (unsigned k = 0; k < FLAC_NK_W; ++k) f64[k] += u >> k;
+			}
+			s4 = s3; s3 = s2; s2 = s1; s1 = s0;
+		}
+	} else {
+		for (unsigned i = lane; i < n; i += 64)
+			if (i >= o) {
+				const uint32_t u = flac_zigzag(flac_residual(o, flac_at_wide(s_w, R0, c, (int)i), flac_at_wide(s_w, R0, c, (int)i - 1),
+						flac_at_wide(s_w, R0, c, (int)i - 2), flac_at_wide(s_w, R0, c, (int)i - 3), flac_at_wide(s_w, R0, c, (int)i - 4)));
+#pragma unroll
+				for (unsigned k = 0; k < FLAC_NK_W; ++k) f64[k] += u >> k;
+			}
+	}
+#pragma unroll
+	for (unsigned k = 0; k < FLAC_NK_W; ++k) {
+		const unsigned long long s = flac_wave_sum(f64[k], fine_log2 ? 2 : 6);
+		if (fine_log2 ? (lane & 3) == 0 : lane == 0) s_fine[c][(fine_log2 ? lane >> 2 : 0) * FLAC_NK_W + k] = s;
+	}
+	__syncthreads();
+	/* one lane per (p, partition): the best k and its cost */
+	if (lane < (fine_log2 ? FLAC_NODES : 1u)) {
+		const unsigned p = 31 - __clz((int)(lane + 1)), part = lane + 1 - (1u << p);
+		unsigned k;
+		s_node_cost[c][lane] = flac_node_cost_w(s_fine[c], fine_log2, p, part, n, o, &k);
+		s_node_k[c][lane] = (uint8_t)k;
+	}
+	__syncthreads();
+	if (lane == 0) flac_finish_sub_w(&s_cand[c], c, n, equal, o, fine_log2, s_node_cost[c], s_node_k[c]);
+	__syncthreads();
+	if (threadIdx.x == 0) flac_finish_frame(&P.frames[job], s_cand, P.channels, n, P.B, (uint32_t)(d.block0 + j));
+}
+
+__device__ __forceinline__ int32_t flac_sub_residual_wide(const int32_t *s_w, const unsigned R0, const unsigned c, const unsigned o, const unsigned i) {
+	return flac_residual(o, flac_at_wide(s_w, R0, c, (int)i), flac_at_wide(s_w, R0, c, (int)i - 1), flac_at_wide(s_w, R0, c, (int)i - 2),
+			flac_at_wide(s_w, R0, c, (int)i - 3), flac_at_wide(s_w, R0, c, (int)i - 4));
+}
+
+__global__ __launch_bounds__(FLAC_THREADS) void flac_write_wide_kernel(const FlacWideParams P) {
+	extern __shared__ uint32_t flac_lds[];
+	__shared__ uint32_t s_scan[4], s_crc;
+	__shared__ FlacFrameDesc s_fd; /* (in LDS: its fields are picked by index) */
+	__shared__ uint8_t s_head[16];
+	const unsigned R0 = P.B + (P.B >> 5);
+	int32_t *s_w = (int32_t *)flac_lds;
+	uint32_t *s_f = flac_lds + R0 * P.channels;
+	const uint32_t n_words = flac_frame_bound_bits(P.B, P.channels, 24) / 4 + 2;
+	const unsigned tid = threadIdx.x, job = blockIdx.x, row = flac_find_row(P.desc, P.n_rows, job);
+	const FlacRow d = P.desc[row];
+	const unsigned j = job - d.job0;
+	if (j >= d.n_blocks) return; /* (never; uniform) */
+	const unsigned n = j == d.n_blocks - 1 ? d.last_n : P.B;
+	if (tid < sizeof(FlacFrameDesc) / 4) ((uint32_t *)&s_fd)[tid] = ((const uint32_t *)&P.frames[job])[tid];
+	__syncthreads();
+	const FlacFrameDesc &fd = s_fd;
+	const uint32_t number = (uint32_t)(d.block0 + j);
+	const uint32_t head = flac_header_len(n, P.B, number);
+	if (fd.n != n || fd.bytes > flac_frame_bound_bits(n, P.channels, 24) || fd.bytes < head + 2 || fd.n_sub > 2) return; /* (never: the record is this block's; uniform) */
+	flac_stage_wide(P, d, row, j, n, s_w, R0);
+	for (unsigned i = tid; i < n_words; i += FLAC_THREADS) s_f[i] = 0;
+	if (tid == 0) s_crc = 0;
+	__syncthreads();
+	if (tid == 0) {
+		const uint32_t hl = flac_frame_header_bits(n, P.B, fd.assign, number, 24, s_head);
+		for (uint32_t i = 0; i < hl; ++i) flac_put(s_f, n_words, 8 * i, 8, s_head[i]);
+	}
+	const unsigned log2B = 31 - __clz((int)P.B);
+	uint32_t pos = 8 * head;
+	for (unsigned si = 0; si < fd.n_sub; ++si) { /* (everything that branches here is the same for the whole workgroup) */
+		const FlacSub &s = fd.sub[si];
+		const unsigned c = s.cand, bps = flac_cand_bps_w(c);
+		const uint32_t mask = bps == 25 ? 0x1ffffffu : 0xffffffu;
+		if (tid == 0) flac_put(s_f, n_words, pos, 8, s.type == FLAC_CONSTANT ? 0u : s.type == FLAC_VERBATIM ? 2u : (uint32_t)(0x10u | (s.order << 1)));
+		if (s.type == FLAC_CONSTANT) {
+			if (tid == 0) flac_put(s_f, n_words, pos + 8, bps, (uint32_t)flac_at_wide(s_w, R0, c, 0) & mask);
+		} else if (s.type == FLAC_VERBATIM) {
+			for (unsigned i = tid; i < n; i += FLAC_THREADS) flac_put(s_f, n_words, pos + 8 + bps * i, bps, (uint32_t)flac_at_wide(s_w, R0, c, (int)i) & mask);
+		} else {
+			const unsigned o = s.order, p = s.p;
+			if (tid < o) flac_put(s_f, n_words, pos + 8 + bps * tid, bps, (uint32_t)flac_at_wide(s_w, R0, c, (int)tid) & mask);
+			const uint32_t at_res = pos + 8 + bps * o;
+			if (tid == 0) flac_put(s_f, n_words, at_res, 6, 0x10u | p); /* 01 pppp */
+			/* a thread's run of consecutive frames; partition of frame i: i >> (log2 B - p) -- p > 0 only in a whole block */
+			const unsigned run = (n + FLAC_THREADS - 1) / FLAC_THREADS, i0 = tid * run, i1 = i0 + run < n ? i0 + run : n;
+			const unsigned psh = p ? log2B - p : 31, pmask = p ? (1u << psh) - 1 : 0xffffffffu;
+			uint32_t len = 0; /* (32 bits: the subframe is cheaper than its verbatim form, below 2^18 bits) */
+			for (unsigned i = i0 > o ? i0 : o; i < i1; ++i) {
+				const unsigned k = s.k[i >> psh];
+				const uint32_t u = flac_zigzag(flac_sub_residual_wide(s_w, R0, c, o, i));
+				len += (u >> k) + 1 + k + ((i & pmask) == 0 || i == o ? 5 : 0);
+			}
+			uint32_t b = at_res + 6 + flac_block_excl(len, s_scan);
+			for (unsigned i = i0 > o ? i0 : o; i < i1; ++i) {
+				const unsigned k = s.k[i >> psh];
+				const uint32_t u = flac_zigzag(flac_sub_residual_wide(s_w, R0, c, o, i));
+				if ((i & pmask) == 0 || i == o) { flac_put(s_f, n_words, b, 5, k); b += 5; }
+				b += u >> k;
+				flac_put(s_f, n_words, b, k + 1, (1u << k) | (u & ((1u << k) - 1))); /* (at most 31 bits) */
+				b += k + 1;
+			}
+		}
+		pos += s.bits;
+	}
+	__syncthreads();
+	const uint32_t body = fd.bytes - 2; /* (pos + 7) / 8 by the analysis' count */
+	{ /* CRC-16: a run of bytes per thread, advanced over what follows it, all XORed */
+		const uint32_t run = (body + FLAC_THREADS - 1) / FLAC_THREADS, b0 = tid * run, b1 = b0 + run < body ? b0 + run : body;
+		uint32_t crc = 0;
+		for (uint32_t b = b0; b < b1; ++b) crc = flac_crc16_update(crc, flac_byte(s_f, b));
+		crc = b0 < body ? flac_crc16_advance(crc, body - b1) : 0;
+		for (int m = 1; m < 64; m <<= 1) crc ^= __shfl_xor(crc, m);
+		if ((tid & 63) == 0) atomicXor(&s_crc, crc);
+	}
+	__syncthreads();
+	uint8_t *dst = P.out + d.out_off + fd.off;
+	for (uint32_t b = tid; b < body; b += FLAC_THREADS) dst[b] = (uint8_t)flac_byte(s_f, b);
+	if (tid == 0) { dst[body] = (uint8_t)(s_crc >> 8); dst[body + 1] = (uint8_t)s_crc; }
+}
+
+__global__ __launch_bounds__(FLAC_THREADS) void flac_carry_wide_kernel(const FlacWideParams P) {
+	const unsigned e = blockIdx.x * FLAC_THREADS + threadIdx.x, row = blockIdx.y, ch = P.channels;
+	const FlacRow d = P.desc[row];
+	if (e >= d.pend_next * ch) return;
+	const int32_t *xrow = (const int32_t *)((const char *)P.rows + P.row_pitch * row);
+	const int32_t *pend = P.pend + P.pend_pitch * row;
 	const unsigned long long at = (unsigned long long)d.n_blocks * P.B * ch + e; /* counted from the row's frame block0 * B, in samples */
 	P.pend_next[P.pend_pitch * row + e] = at < (unsigned long long)d.pend * ch ? pend[at] : xrow[at - (unsigned long long)d.pend * ch];
 }

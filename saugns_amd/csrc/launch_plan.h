@@ -1021,9 +1021,9 @@ inline FlacRow plan_flac_row(uint64_t pos, uint32_t frames, uint32_t B, bool fin
 	return r;
 }
 /* the worst case of a row's feed (include/saugns_amd.h, FLAC: the bound of every block it completes, summed) */
-inline uint64_t flac_row_worst(const FlacRow &r, uint32_t B, uint32_t channels) {
+inline uint64_t flac_row_worst(const FlacRow &r, uint32_t B, uint32_t channels, unsigned bits = 16) {
 	if (!r.n_blocks) return 0;
-	return (uint64_t)(r.n_blocks - 1) * sauflac::flac_frame_bound(B, channels) + sauflac::flac_frame_bound(r.last_n, channels);
+	return (uint64_t)(r.n_blocks - 1) * sauflac::flac_frame_bound_bits(B, channels, bits) + sauflac::flac_frame_bound_bits(r.last_n, channels, bits);
 }
 struct FlacPlan {
 	bool ok = false;           /* false: B or channels not allowed, no row or more than 65535, a block number beyond 2^31 - 1, a feed
@@ -1031,21 +1031,22 @@ struct FlacPlan {
 	uint32_t B = 0, rows = 0, channels = 0;
 	uint32_t jobs = 0;         /* grid.x of flac_analyze_kernel and flac_write_kernel (0: no launch) */
 	uint32_t analyze_threads = 0; /* one wave per candidate channel: 64 mono; 256 stereo (L, R, M, S) */
-	size_t analyze_lds = 0;    /* the block's frames as words, one more per 32 (k_flac.h: flac_ix) */
+	size_t analyze_lds = 0;    /* the block's frames as words, one more per 32 (k_flac.h: flac_ix); at 24 bits a word per sample */
 	size_t write_lds = 0;      /* ... and the frame under construction: its bound, in words, and two more */
-	size_t pend_pitch = 0;     /* int16 between the rows' pending frames: B * channels */
+	size_t pend_pitch = 0;     /* samples (int16; int32 at 24 bits) between the rows' pending frames: B * channels */
 	uint64_t worst = 0;        /* the feed's worst case: what the 1 GiB rule counts */
 	size_t out_bytes = 0;      /* the feed's output: every row's worst case, each rounded up to 16 */
 };
-/* rows: the feed's records (NULL: none, the encoder's own sizes only); job0 and out_off are filled in */
-inline FlacPlan plan_flac(uint32_t block_frames, uint32_t channels, size_t n_rows, FlacRow *rows) {
+/* rows: the feed's records (NULL: none, the encoder's own sizes only); job0 and out_off are filled in. bits: 16, or 24 for the
+ * wide kernels -- a word per sample in LDS, three bytes per sample in a frame's bound. */
+inline FlacPlan plan_flac(uint32_t block_frames, uint32_t channels, size_t n_rows, FlacRow *rows, unsigned bits = 16) {
 	FlacPlan p;
 	const uint32_t B = sauflac::flac_block_frames(block_frames);
-	if (!B || (channels != 1 && channels != 2) || !n_rows || n_rows > sauflac::FLAC_MAX_ROWS) return p;
+	if (!B || (channels != 1 && channels != 2) || !n_rows || n_rows > sauflac::FLAC_MAX_ROWS || !sauflac::flac_bits_ok((int)bits)) return p;
 	p.B = B; p.rows = (uint32_t)n_rows; p.channels = channels;
 	p.analyze_threads = channels == 2 ? 256 : 64;
-	p.analyze_lds = (size_t)(B + B / 32) * sizeof(uint32_t);
-	p.write_lds = p.analyze_lds + ((size_t)sauflac::flac_frame_bound(B, channels) / 4 + 2) * sizeof(uint32_t);
+	p.analyze_lds = (size_t)(B + B / 32) * sizeof(uint32_t) * (bits == 24 ? channels : 1);
+	p.write_lds = p.analyze_lds + ((size_t)sauflac::flac_frame_bound_bits(B, channels, bits) / 4 + 2) * sizeof(uint32_t);
 	p.pend_pitch = (size_t)B * channels;
 	uint64_t jobs = 0, out = 0;
 	for (size_t r = 0; rows && r < n_rows; ++r) {
@@ -1054,7 +1055,7 @@ inline FlacPlan plan_flac(uint32_t block_frames, uint32_t channels, size_t n_row
 		rows[r].job0 = (uint32_t)jobs;
 		rows[r].out_off = (uint32_t)out;
 		jobs += rows[r].n_blocks;
-		const uint64_t w = flac_row_worst(rows[r], B, channels);
+		const uint64_t w = flac_row_worst(rows[r], B, channels, bits);
 		p.worst += w;
 		out += (w + 15) & ~15ull;
 	}

@@ -1169,6 +1169,18 @@ SAU_HD int16_t pcm16(float s) {
 	return (int16_t)lrintf(s * (float)INT16_MAX);
 #endif
 }
+/* the 24-bit FLAC encoder's quantiser: pcm16's NaN rule and clamp, then the nearest integer to s * 8388607, ties to even. The
+ * product of a 24-bit significand and a 23-bit constant is exact in f64: one rounding, and nothing to contract.
+ * -8388607 .. 8388607 */
+SAU_HD int32_t pcm24(float s) {
+	if (s != s) s = -1.f;
+	s = clampf(s, -1.f, 1.f);
+#if defined(__HIP_DEVICE_COMPILE__)
+	return __double2int_rn((double)s * 8388607.0);
+#else
+	return (int32_t)lrint((double)s * 8388607.0);
+#endif
+}
 
 } /* namespace saudev */
 #endif /* SAU_DEV_MATH_H */

@@ -328,5 +328,73 @@ SAU_FLAC_HD uint32_t flac_frame_header(uint32_t n, uint32_t block_frames, uint32
 	return len;
 }
 
+/* ---- the 24-bit format (include/saugns_amd.h, FLAC, "24 bits"): what differs from the 16-bit arithmetic above ----
+ * Samples are int32 in -2^23 .. 2^23 - 1; the side channel takes 25 bits. A FIXED residual is at most 16 * 2^24 in size, so
+ * the residual functions above serve as they are; u is below 2^30, the Rice parameters are 0 .. 30 in five bits (method 01),
+ * and everything summed over a lane's run, not only over a block, needs 64 bits. No LPC. */
+constexpr unsigned FLAC_K_MAX_W = 30, FLAC_NK_W = 31;  /* Rice parameters 0 .. 30; 31 is the escape, never used */
+constexpr int32_t FLAC_S24_MIN = -8388608, FLAC_S24_MAX = 8388607;
+SAU_FLAC_HD bool flac_bits_ok(int bits) { return bits == 16 || bits == 24; }
+/* the most bytes a frame of n frames takes at `bits` per sample (16: flac_frame_bound) */
+SAU_FLAC_HD uint32_t flac_frame_bound_bits(uint32_t n, uint32_t channels, unsigned bits) {
+	return 15 + channels * (1 + (bits == 24 ? 3 : 2) * n);
+}
+SAU_FLAC_HD int32_t flac_cand_w(int32_t l, int32_t r, unsigned cand) {
+	switch (cand) {
+	case FLAC_CAND_L: return l;
+	case FLAC_CAND_R: return r;
+	case FLAC_CAND_M: return (l + r) >> 1; /* (arithmetic) */
+	default: return l - r;
+	}
+}
+SAU_FLAC_HD unsigned flac_cand_bps_w(unsigned cand) { return cand == FLAC_CAND_S ? 25 : 24; }
+/* flac_node_cost with fine[f * 31 + k], k = 0 .. 30 */
+SAU_FLAC_HD uint64_t flac_node_cost_w(const uint64_t *fine, unsigned fine_log2, unsigned p, unsigned part, uint32_t n, unsigned o, unsigned *k_out) {
+	const unsigned span = 1u << (fine_log2 - p), first = part * span;
+	const uint64_t count = (n >> p) - (part == 0 ? o : 0);
+	uint64_t best = ~0ull;
+	unsigned bk = 0;
+	for (unsigned k = 0; k < FLAC_NK_W; ++k) {
+		uint64_t s = 0;
+		for (unsigned f = 0; f < span; ++f) s += fine[(first + f) * FLAC_NK_W + k];
+		const uint64_t cost = s + (1 + k) * count;
+		if (cost < best) { best = cost; bk = k; }
+	}
+	*k_out = bk;
+	return best;
+}
+/* flac_finish_sub with 24 or 25 bits per sample and five bits per partition's parameter */
+SAU_FLAC_HD void flac_finish_sub_w(FlacSub *s, unsigned cand, uint32_t n, bool all_equal, unsigned o, unsigned fine_log2,
+		const uint64_t *node_cost, const uint8_t *node_k) {
+	const unsigned bps = flac_cand_bps_w(cand);
+	s->cand = (uint8_t)cand; s->order = 0; s->p = 0;
+	for (unsigned j = 0; j < FLAC_FINE; ++j) s->k[j] = 0;
+	for (unsigned j = 0; j < FLAC_LPC_MAX; ++j) s->q[j] = 0;
+	s->shift = 0; s->pad_[0] = s->pad_[1] = s->pad_[2] = 0;
+	if (all_equal) { s->type = FLAC_CONSTANT; s->bits = 8 + bps; return; }
+	uint64_t best = ~0ull;
+	unsigned bp = 0;
+	for (unsigned p = 0; p <= fine_log2; ++p) {
+		uint64_t c = 0;
+		for (unsigned j = 0; j < (1u << p); ++j) c += 5 + node_cost[flac_node_index(p, j)];
+		if (c < best) { best = c; bp = p; }
+	}
+	const uint64_t fixed = 8 + (uint64_t)bps * o + 6 + best, verbatim = 8 + (uint64_t)bps * n;
+	if (verbatim <= fixed) { s->type = FLAC_VERBATIM; s->bits = (uint32_t)verbatim; return; }
+	s->type = FLAC_FIXED; s->order = (uint8_t)o; s->p = (uint8_t)bp; s->bits = (uint32_t)fixed;
+	for (unsigned j = 0; j < (1u << bp); ++j) s->k[j] = node_k[flac_node_index(bp, j)];
+}
+/* flac_frame_header with the sample-size code of `bits`: 100 for 16, 110 for 24 (the CRC-8 covers it) */
+SAU_FLAC_HD uint32_t flac_frame_header_bits(uint32_t n, uint32_t block_frames, uint32_t assign, uint32_t number, unsigned bits, uint8_t *out /* [16] */) {
+	const uint32_t len = flac_frame_header(n, block_frames, assign, number, out);
+	if (bits == 24) {
+		out[3] = (uint8_t)((assign << 4) | (6u << 1));
+		uint32_t crc = 0;
+		for (uint32_t i = 0; i + 1 < len; ++i) crc = flac_crc8_update(crc, out[i]);
+		out[len - 1] = (uint8_t)crc;
+	}
+	return len;
+}
+
 } /* namespace sauflac */
 #endif

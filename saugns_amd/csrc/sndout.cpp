@@ -578,7 +578,261 @@ bool write_flac(const sauProgram *prg, uint32_t srate, const char *path, int cha
 	return ok;
 }
 
+/* The scaled FLAC writer: write_scaled's float runs on the file lattice, each run's device row fed with `gain` to a float-fed
+ * encoder of one stream (`bits` per sample) where that writer requantises and fetches; the file I/O is write_flac's. A backend
+ * without float output or without the encoder says so before there is a file. */
+bool write_flac_scaled(const sauProgram *prg, uint32_t srate, const char *path, int channels, uint32_t block_frames, int bits,
+		uint32_t max_lpc_order, float gain, Backend *backend /* owned */, uint64_t *frames_out, sauengine::FlacInfo *info_out, std::string &err) {
+	Engine *engine = Engine::create(&prg, 1, srate, backend, err);
+	if (!engine) return false;
+	const bool stereo = channels == 2;
+	const uint32_t B = sauflac::flac_block_frames(block_frames);
+	size_t call, chunk;
+	file_lattice(srate, call, chunk);
+	engine->set_call_len(call);
+	if (!engine->set_format(sauengine::SF_F32, err)) { delete engine; return false; }
+	sauengine::FlacEncoder *enc = backend->create_flac_f32(1, (uint32_t)channels, B, bits, max_lpc_order, err);
+	if (!enc) { delete engine; return false; }
+	const size_t slot_bytes = (chunk / B + 2) * (size_t)sauflac::flac_frame_bound_bits(B, (uint32_t)channels, (unsigned)bits);
+	uint8_t *host[2] = {(uint8_t *)backend->alloc_host(slot_bytes), (uint8_t *)backend->alloc_host(slot_bytes)};
+	FILE *f = nullptr;
+	bool ok = host[0] && host[1];
+	if (!ok) err = "out of page-locked memory";
+	uint8_t head[42];
+	sauengine::FlacInfo info{0, 0, 0, 0, 0};
+	if (ok) {
+		f = fopen(path, "wb");
+		if (!f) { err = std::string("couldn't open \"") + path + "\" for writing"; ok = false; }
+		else if (sauengine::flac_header_bits(srate, channels, B, bits, &info, head, sizeof head) != 42 || fwrite(head, 1, 42, f) != 42) { err = "write failed"; ok = false; }
+	}
+	size_t pending[2] = {0, 0};
+	int slot = 0;
+	bool more = ok;
+	while (ok && more) {
+		size_t len = 0;
+		ok = engine->run_f32(nullptr, chunk, stereo, &more, &len, err);
+		if (!ok) break;
+		const uint32_t n = (uint32_t)len;
+		const float *row = backend->device_pcm_f32(0);
+		if (!row) { err = "the backend keeps no float rows on the device"; ok = false; break; }
+		/* (the rounding happens in the feed, once, after the gain) */
+		ok = enc->feed_f32(row, backend->device_pcm_pitch(), &n, &gain, !more, err);
+		/* while this run renders and is encoded, the one before goes to the file */
+		const int other = slot ^ 1;
+		if (ok && pending[other]) {
+			if (fwrite(host[other], 1, pending[other], f) != pending[other]) { err = "write failed"; ok = false; }
+			pending[other] = 0;
+		}
+		if (ok) {
+			uint8_t *const bufs[1] = {host[slot]};
+			size_t got = 0;
+			ok = enc->read(bufs, &slot_bytes, &got, &info, false, err);
+			pending[slot] = got;
+		}
+		slot = other;
+	}
+	for (int s = 0; ok && s < 2; ++s) { /* oldest first: `slot` is the older of the two */
+		const int k = slot ^ s;
+		if (pending[k] && fwrite(host[k], 1, pending[k], f) != pending[k]) { err = "write failed"; ok = false; }
+		pending[k] = 0;
+	}
+	delete enc;
+	{ std::string e2; (void)backend->sync(e2); }
+	if (f) {
+		if (ok && (sauengine::flac_header_bits(srate, channels, B, bits, &info, head, sizeof head) != 42 || fseek(f, 0, SEEK_SET) != 0 ||
+		           fwrite(head, 1, 42, f) != 42)) { err = "write failed"; ok = false; }
+		const int ferr = ferror(f);
+		if ((fclose(f) != 0 || ferr) && ok) { err = "write failed"; ok = false; }
+	}
+	if (frames_out) *frames_out = info.frames;
+	if (ok && info_out) *info_out = info;
+	backend->free_host(host[0]);
+	backend->free_host(host[1]);
+	delete engine; /* owns the backend */
+	return ok;
+}
+
+/* The limited FLAC writer: write_limited's loop with float limited rows, each run's part of y[D, D + N) fed with gain 1 to a
+ * float-fed encoder from where it lies in the device row (D frames in for the first run: the feed needs float alignment only),
+ * the D-frame tail run fed too and as the finish; the file I/O is write_flac's. */
+bool write_flac_limited(const sauProgram *prg, uint32_t srate, const char *path, int channels, uint32_t block_frames, int bits,
+		uint32_t max_lpc_order, float pre_gain, float ceiling, Backend *backend /* owned */, uint64_t *frames_out,
+		sauengine::LimiterStats *stats_out, sauengine::FlacInfo *info_out, std::string &err) {
+	Engine *engine = Engine::create(&prg, 1, srate, backend, err);
+	if (!engine) return false;
+	const bool stereo = channels == 2;
+	const uint32_t B = sauflac::flac_block_frames(block_frames);
+	const size_t D = sauengine::limiter_latency(srate);
+	size_t call, chunk;
+	file_lattice(srate, call, chunk);
+	engine->set_call_len(call);
+	/* a backend without float output, without a limiter or without the encoder says so here, before there is a file */
+	if (!engine->set_format(sauengine::SF_F32, err) || !engine->begin_limited(pre_gain, ceiling, stereo, err)) { delete engine; return false; }
+	sauengine::FlacEncoder *enc = backend->create_flac_f32(1, (uint32_t)channels, B, bits, max_lpc_order, err);
+	if (!enc) { delete engine; return false; }
+	const size_t slot_frames = chunk > D ? chunk : D;
+	const size_t slot_bytes = (slot_frames / B + 2) * (size_t)sauflac::flac_frame_bound_bits(B, (uint32_t)channels, (unsigned)bits);
+	uint8_t *host[2] = {(uint8_t *)backend->alloc_host(slot_bytes), (uint8_t *)backend->alloc_host(slot_bytes)};
+	FILE *f = nullptr;
+	bool ok = host[0] && host[1];
+	if (!ok) err = "out of page-locked memory";
+	uint8_t head[42];
+	sauengine::FlacInfo info{0, 0, 0, 0, 0};
+	if (ok) {
+		f = fopen(path, "wb");
+		if (!f) { err = std::string("couldn't open \"") + path + "\" for writing"; ok = false; }
+		else if (sauengine::flac_header_bits(srate, channels, B, bits, &info, head, sizeof head) != 42 || fwrite(head, 1, 42, f) != 42) { err = "write failed"; ok = false; }
+	}
+	size_t pending[2] = {0, 0};
+	int slot = 0;
+	bool more = ok, tail = false;
+	uint64_t y_pos = 0, wanted = 0; /* limited frames made so far; the N frames rendered so far */
+	while (ok && !tail) {
+		tail = !more; /* behind the program's end: the one run for the limiter's tail, and the encoder's finish */
+		const size_t n = tail ? D : chunk;
+		size_t len = 0;
+		ok = engine->run_limited(nullptr, sauengine::SF_F32, false, pre_gain, ceiling, n, stereo, &more, &len, err);
+		if (!ok) break;
+		wanted += len;
+		/* the file is y[D, D + wanted): while the program runs that covers every frame of a run but the first D */
+		const uint64_t lo = y_pos > D ? y_pos : D, end = y_pos + n, hi = D + wanted < end ? D + wanted : end;
+		const uint32_t cnt = hi > lo ? (uint32_t)(hi - lo) : 0;
+		if (cnt || tail) {
+			const float *row = backend->device_limited_f32(0);
+			if (!row) { err = "the backend keeps no limited rows on the device"; ok = false; break; }
+			ok = enc->feed_f32(row + (cnt ? (size_t)(lo - y_pos) * (size_t)channels : 0), backend->device_limited_pitch(), &cnt, nullptr, tail, err);
+		}
+		y_pos = end;
+		const int other = slot ^ 1;
+		if (ok && pending[other]) {
+			if (fwrite(host[other], 1, pending[other], f) != pending[other]) { err = "write failed"; ok = false; }
+			pending[other] = 0;
+		}
+		if (ok) {
+			uint8_t *const bufs[1] = {host[slot]};
+			size_t got = 0;
+			ok = enc->read(bufs, &slot_bytes, &got, &info, false, err);
+			pending[slot] = got;
+		}
+		slot = other;
+	}
+	for (int s = 0; ok && s < 2; ++s) { /* oldest first */
+		const int k = slot ^ s;
+		if (pending[k] && fwrite(host[k], 1, pending[k], f) != pending[k]) { err = "write failed"; ok = false; }
+		pending[k] = 0;
+	}
+	if (ok && stats_out) ok = engine->limiter_stats(stats_out, false, err);
+	delete enc;
+	{ std::string e2; (void)backend->sync(e2); }
+	if (f) {
+		if (ok && (sauengine::flac_header_bits(srate, channels, B, bits, &info, head, sizeof head) != 42 || fseek(f, 0, SEEK_SET) != 0 ||
+		           fwrite(head, 1, 42, f) != 42)) { err = "write failed"; ok = false; }
+		const int ferr = ferror(f);
+		if ((fclose(f) != 0 || ferr) && ok) { err = "write failed"; ok = false; }
+	}
+	if (frames_out) *frames_out = info.frames;
+	if (ok && info_out) *info_out = info;
+	backend->free_host(host[0]);
+	backend->free_host(host[1]);
+	delete engine; /* owns the backend */
+	return ok;
+}
+
+/* what every FLAC writer of float runs refuses of its encoder's parameters */
+bool flac_f32_params_ok(int channels, uint32_t block_frames, int bits, uint32_t max_lpc_order) {
+	return sauengine::flac_params_ok(channels, block_frames) && sauflac::flac_bits_ok(bits) && max_lpc_order <= sauflac::FLAC_LPC_MAX &&
+	       !(bits == 24 && max_lpc_order);
+}
+
 } /* namespace */
+
+bool sauamd_internal::render_file_flac_f32(const sauProgram *prg, uint32_t srate, const char *path, int channels, uint32_t block_frames,
+		int bits, uint32_t max_lpc_order, float gain, const std::function<Backend *(std::string &)> &make_backend, uint64_t *frames_out,
+		sauAmdFlacInfo *info_out, std::string &err) {
+	if (frames_out) *frames_out = 0;
+	if (!prg || !path || !srate || srate > 655350u || !flac_f32_params_ok(channels, block_frames, bits, max_lpc_order) ||
+	    !(gain >= -FLT_MAX && gain <= FLT_MAX)) { /* (a NaN fails both comparisons) */
+		err = "bad argument";
+		return false;
+	}
+	Backend *backend = make_backend(err);
+	if (!backend) return false;
+	return write_flac_scaled(prg, srate, path, channels, block_frames, bits, max_lpc_order, gain, backend, frames_out,
+			(sauengine::FlacInfo *)info_out, err);
+}
+
+extern "C" bool sauAmd_render_file_flac_f32(const sauProgram *prg, uint32_t srate, const char *path, int channels, uint32_t block_frames,
+		int bits, uint32_t max_lpc_order, float gain, uint64_t *frames_out, sauAmdFlacInfo *info_out) {
+	std::string err;
+	bool ok = false;
+	try {
+		ok = sauamd_internal::render_file_flac_f32(prg, srate, path, channels, block_frames, bits, max_lpc_order, gain,
+				[](std::string &e) -> Backend * { return sauhip::create_hip_backend(e); }, frames_out, info_out, err);
+	} catch (const std::exception &ex) { /* (nothing C++ crosses the C ABI) */
+		err = std::string("internal error: ") + ex.what();
+	}
+	if (!ok) sauamd_internal::set_last_error("output", err);
+	return ok;
+}
+
+bool sauamd_internal::render_file_flac_loudness(const sauProgram *prg, uint32_t srate, const char *path, int channels, uint32_t block_frames,
+		int bits, uint32_t max_lpc_order, double target_lufs, float max_true_peak, bool limited,
+		const std::function<Backend *(std::string &)> &make_backend, uint64_t *frames_out, sauAmdLoudness *loud_out, float *gain_out,
+		sauAmdLimiterStats *stats_out, sauAmdFlacInfo *info_out, std::string &err) {
+	if (frames_out) *frames_out = 0;
+	if (!prg || !path || srate > 655350u || !flac_f32_params_ok(channels, block_frames, bits, max_lpc_order) ||
+	    !(target_lufs >= -DBL_MAX && target_lufs <= DBL_MAX) || !(max_true_peak > 0.f) || !(max_true_peak <= FLT_MAX) ||
+	    srate < sauengine::LOUD_MIN_RATE) { /* (a NaN fails every comparison) */
+		err = "bad argument";
+		return false;
+	}
+	Backend *first = make_backend(err);
+	if (!first) return false;
+	sauengine::Loudness ld;
+	if (!measure_program_loudness(prg, srate, channels == 2, first, ld, err)) return false;
+	if (loud_out) memcpy(loud_out, &ld, sizeof ld);
+	float gain = 1.0f;
+	if (!limited) { /* render_file_loudness's rule */
+		const float tp = ld.true_peak[0] > ld.true_peak[1] ? ld.true_peak[0] : ld.true_peak[1];
+		if (ld.integrated > -HUGE_VAL) {
+			gain = (float)pow(10.0, (target_lufs - ld.integrated) / 20.0);
+			if (tp * gain > max_true_peak) gain = max_true_peak / tp; /* the ceiling binds: one f32 division */
+		}
+		if (gain_out) *gain_out = gain;
+		if (!(gain >= -FLT_MAX && gain <= FLT_MAX)) { err = "bad argument: the gain to the target loudness is not finite"; return false; }
+		Backend *second = make_backend(err);
+		if (!second) return false;
+		return write_flac_scaled(prg, srate, path, channels, block_frames, bits, max_lpc_order, gain, second, frames_out,
+				(sauengine::FlacInfo *)info_out, err);
+	}
+	/* render_file_loudness_limited's rule: never lowered for the ceiling, the limiter holds that */
+	if (ld.integrated > -HUGE_VAL) gain = (float)pow(10.0, (target_lufs - ld.integrated) / 20.0);
+	if (gain_out) *gain_out = gain;
+	if (!(gain > 0.f) || !(gain <= FLT_MAX)) { err = "bad argument: the gain to the target loudness is not a finite positive float"; return false; }
+	Backend *second = make_backend(err);
+	if (!second) return false;
+	sauengine::LimiterStats st{0, 0, 1.0};
+	const bool ok = write_flac_limited(prg, srate, path, channels, block_frames, bits, max_lpc_order, gain, max_true_peak, second, frames_out,
+			&st, (sauengine::FlacInfo *)info_out, err);
+	if (ok && stats_out) memcpy(stats_out, &st, sizeof st);
+	return ok;
+}
+
+extern "C" bool sauAmd_render_file_flac_loudness(const sauProgram *prg, uint32_t srate, const char *path, int channels,
+		uint32_t block_frames, int bits, uint32_t max_lpc_order, double target_lufs, float max_true_peak, int limited,
+		uint64_t *frames_out, sauAmdLoudness *loud_out, float *gain_out, sauAmdLimiterStats *stats_out, sauAmdFlacInfo *info_out) {
+	std::string err;
+	bool ok = false;
+	try {
+		ok = sauamd_internal::render_file_flac_loudness(prg, srate, path, channels, block_frames, bits, max_lpc_order, target_lufs,
+				max_true_peak, limited != 0, [](std::string &e) -> Backend * { return sauhip::create_hip_backend(e); }, frames_out,
+				loud_out, gain_out, stats_out, info_out, err);
+	} catch (const std::exception &ex) { /* (nothing C++ crosses the C ABI) */
+		err = std::string("internal error: ") + ex.what();
+	}
+	if (!ok) sauamd_internal::set_last_error("output", err);
+	return ok;
+}
 
 bool sauamd_internal::render_file_normalized(const sauProgram *prg, uint32_t srate, const char *path, int format, int channels,
 		float target_peak, const std::function<Backend *(std::string &)> &make_backend, uint64_t *frames_out,

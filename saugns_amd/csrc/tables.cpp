@@ -564,4 +564,112 @@ size_t flac_encode_block_lpc(const int16_t *x, uint32_t n, int channels, uint32_
 	return d.bytes;
 }
 
+/* ---- 24 bits and float-fed encoders (include/saugns_amd.h, FLAC, "24 bits") ---- */
+size_t flac_header_bits(uint32_t srate, int channels, uint32_t block_frames, int bits, const FlacInfo *info, uint8_t *out, size_t cap) {
+	if (!sauflac::flac_bits_ok(bits)) return 0;
+	const size_t got = flac_header(srate, channels, block_frames, info, out, cap);
+	if (got == 42 && out && cap >= 42 && bits == 24) { /* bits per sample - 1: the low bit of byte 20, the high nibble of byte 21 */
+		out[20] = (uint8_t)((out[20] & 0xfeu) | (23u >> 4));
+		out[21] = (uint8_t)((out[21] & 0x0fu) | ((23u & 0xfu) << 4));
+	}
+	return got;
+}
+
+bool flac_quantize(const float *x, size_t n, float gain, int bits, int32_t *out) {
+	if (!sauflac::flac_bits_ok(bits) || (n && (!x || !out))) return false;
+	for (size_t i = 0; i < n; ++i) {
+		const float y = x[i] * gain; /* one f32 multiply, as flac_quant_kernel's */
+		out[i] = bits == 24 ? saudev::pcm24(y) : (int32_t)saudev::pcm16(y);
+	}
+	return true;
+}
+
+/* flac_encode_block's loops at 24 bits: what flac_analyze_wide_kernel and flac_write_wide_kernel make of one block */
+static size_t flac_encode_block_24(const int32_t *x, uint32_t n, unsigned ch, uint32_t B, uint32_t frame_number, uint8_t *out, size_t cap) {
+	using namespace sauflac;
+	const unsigned n_cand = ch == 2 ? 4 : 1, fine_log2 = n == B ? 4 : 0, F = 1u << fine_log2;
+	auto at = [&](unsigned c, int64_t i) -> int32_t { return i < 0 ? 0 : ch == 2 ? flac_cand_w(x[2 * i], x[2 * i + 1], c) : x[i]; };
+	auto resid = [&](unsigned c, unsigned o, uint32_t i) { return flac_residual(o, at(c, i), at(c, (int64_t)i - 1), at(c, (int64_t)i - 2), at(c, (int64_t)i - 3), at(c, (int64_t)i - 4)); };
+	FlacSub cand[4];
+	for (unsigned c = 0; c < n_cand; ++c) {
+		bool equal = true;
+		for (uint32_t i = 1; i < n; ++i) equal = equal && at(c, i) == at(c, 0);
+		uint64_t abs_sum[5] = {0, 0, 0, 0, 0};
+		for (uint32_t i = 4; i < n; ++i) {
+			int32_t r[5];
+			flac_residuals(at(c, i), at(c, i - 1), at(c, i - 2), at(c, i - 3), at(c, i - 4), r);
+			for (int o = 0; o < 5; ++o) abs_sum[o] += flac_abs(r[o]);
+		}
+		const unsigned o = flac_pick_order(n, abs_sum);
+		uint64_t fine[FLAC_FINE * FLAC_NK_W];
+		memset(fine, 0, sizeof fine);
+		const uint32_t plen = n / F; /* (F == 1 unless n == B, a multiple of 16) */
+		for (uint32_t i = o; i < n; ++i) {
+			const uint32_t u = flac_zigzag(resid(c, o, i));
+			for (unsigned k = 0; k < FLAC_NK_W; ++k) fine[(i / plen) * FLAC_NK_W + k] += u >> k;
+		}
+		uint64_t node_cost[FLAC_NODES];
+		uint8_t node_k[FLAC_NODES];
+		for (unsigned p = 0; p <= fine_log2; ++p)
+			for (unsigned j = 0; j < (1u << p); ++j) {
+				unsigned k;
+				node_cost[flac_node_index(p, j)] = flac_node_cost_w(fine, fine_log2, p, j, n, o, &k);
+				node_k[flac_node_index(p, j)] = (uint8_t)k;
+			}
+		flac_finish_sub_w(&cand[c], c, n, equal, o, fine_log2, node_cost, node_k);
+	}
+	FlacFrameDesc d;
+	flac_finish_frame(&d, cand, ch, n, B, frame_number);
+	if (!out || cap < d.bytes) return d.bytes;
+	memset(out, 0, d.bytes);
+	uint8_t hdr[16];
+	const uint32_t hl = flac_frame_header_bits(n, B, d.assign, frame_number, 24, hdr);
+	memcpy(out, hdr, hl);
+	FlacBits bw{out, (size_t)hl * 8};
+	for (unsigned si = 0; si < d.n_sub; ++si) {
+		const FlacSub &s = d.sub[si];
+		const unsigned c = s.cand, bps = flac_cand_bps_w(c);
+		const uint32_t mask = bps == 25 ? 0x1ffffffu : 0xffffffu;
+		bw.put(s.type == FLAC_CONSTANT ? 0u : s.type == FLAC_VERBATIM ? 2u : (uint32_t)(0x10u | (s.order << 1)), 8); /* 0 tttttt 0 */
+		if (s.type == FLAC_CONSTANT) bw.put((uint32_t)at(c, 0) & mask, bps);
+		else if (s.type == FLAC_VERBATIM) for (uint32_t i = 0; i < n; ++i) bw.put((uint32_t)at(c, i) & mask, bps);
+		else {
+			for (uint32_t i = 0; i < s.order; ++i) bw.put((uint32_t)at(c, i) & mask, bps);
+			bw.put(0x10u | s.p, 6); /* 01 pppp */
+			const uint32_t plen = n >> s.p;
+			for (uint32_t j = 0; j < (1u << s.p); ++j) {
+				const unsigned k = s.k[j];
+				bw.put(k, 5);
+				for (uint32_t i = j ? j * plen : s.order; i < (j + 1) * plen; ++i) {
+					const uint32_t u = flac_zigzag(resid(c, s.order, i));
+					bw.zeros(u >> k);
+					bw.put((1u << k) | (u & ((1u << k) - 1)), k + 1);
+				}
+			}
+		}
+	}
+	const size_t body = (bw.pos + 7) / 8;
+	if (body + 2 != d.bytes) return 0; /* (the analysis and the writer disagree: never) */
+	uint32_t crc = 0;
+	for (size_t i = 0; i < body; ++i) crc = flac_crc16_update(crc, out[i]);
+	out[body] = (uint8_t)(crc >> 8); out[body + 1] = (uint8_t)crc;
+	return d.bytes;
+}
+
+size_t flac_encode_block_s32(const int32_t *x, uint32_t n, int channels, uint32_t block_frames, uint32_t frame_number, int bits,
+		uint32_t max_lpc_order, uint8_t *out, size_t cap) {
+	using namespace sauflac;
+	const uint32_t B = flac_block_frames(block_frames);
+	if (!x || !B || !n || n > B || (channels != 1 && channels != 2) || frame_number > FLAC_MAX_BLOCKS || !flac_bits_ok(bits) ||
+	    max_lpc_order > FLAC_LPC_MAX || (bits == 24 && max_lpc_order)) return 0;
+	const size_t cnt = (size_t)n * (size_t)channels;
+	const int32_t lo = bits == 24 ? FLAC_S24_MIN : -32768, hi = bits == 24 ? FLAC_S24_MAX : 32767;
+	for (size_t i = 0; i < cnt; ++i)
+		if (x[i] < lo || x[i] > hi) return 0;
+	if (bits == 24) return flac_encode_block_24(x, n, (unsigned)channels, B, frame_number, out, cap);
+	std::vector<int16_t> s(cnt);
+	for (size_t i = 0; i < cnt; ++i) s[i] = (int16_t)x[i];
+	return flac_encode_block_lpc(s.data(), n, channels, B, frame_number, max_lpc_order, out, cap);
+}
+
 } /* namespace sauengine */
