@@ -576,7 +576,7 @@ SAU_AMD_API bool sauAmd_render_spectrum(const sauProgram *prg, uint32_t srate, i
  * are pending until a later feed completes the block or a finish makes them one last short block. At most 65535 rows per
  * encoder and 2^31 - 1 blocks per row.
  * Limits: no MD5 (the field is zeros: "not computed"), no seek table, no comments, no wasted-bits detection, no escape
- * partitions, no dither; LPC only on request (max_lpc_order, "The LPC mode" below), of order <= 8 with 12-bit coefficients, one
+ * partitions, no dither of its own (a quantiser's rows can be fed: "Dither and noise shaping" below); LPC only on request (max_lpc_order, "The LPC mode" below), of order <= 8 with 12-bit coefficients, one
  * precision and one window, and at 16 bits only: max_lpc_order > 0 with bits == 24 is a bad argument everywhere (its products
  * pass 32 bits, and the window scaling would pass 64). 24-bit output comes from float rows only ("24 bits" below). The
  * peak-normalised and oversampled writers have no FLAC variant; the fed encoders take any int16 or float device rows, decimated
@@ -792,6 +792,111 @@ SAU_AMD_API bool sauAmd_render_file_flac_f32(const sauProgram *prg, uint32_t sra
 SAU_AMD_API bool sauAmd_render_file_flac_loudness(const sauProgram *prg, uint32_t srate, const char *path, int channels,
 		uint32_t block_frames, int bits, uint32_t max_lpc_order, double target_lufs, float max_true_peak, int limited,
 		uint64_t *frames_out, sauAmdLoudness *loud_out, float *gain_out, sauAmdLimiterStats *stats_out, sauAmdFlacInfo *info_out);
+
+/* ---- Dither and noise shaping ------------------------------------------------------
+ * A quantiser stage for 16-bit output: float device rows in, int16 device rows of its own out, with TPDF dither and
+ * error-feedback noise shaping, reproducible bit for bit. Every other writer rounds pcm16(x * gain) bare: a tone below half an
+ * LSB becomes zeros and a fade becomes harmonic distortion. With TPDF dither the error is noise that does not depend on the
+ * signal, and a shaper moves that noise to where the ear is least sensitive.
+ *
+ * The spec: `dither` 0 (none) or 1 (TPDF); `taps` T = 0 .. 9 error-feedback coefficients coef[0 .. T), coef[0] on the most
+ * recent error; `seed` of the dither. Valid when dither <= 1, taps <= 9, every used coefficient is finite and the sum of
+ * |coef[j]| over the used taps is at most 64; anything else is a bad argument everywhere. The noise transfer function is
+ * 1 - sum(coef[j] z^-(j+1)).
+ *
+ * The dither of row r, channel c (0 or 1), frame i -- counted from the stream's start in 64 bits, never per feed -- with all
+ * integer arithmetic modulo 2^64:
+ *     seed_r = seed + 0xD1B54A32D192ED03 r
+ *     z = seed_r + 0x9E3779B97F4A7C15 (2 i + c + 1)
+ *     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  z = z ^ (z >> 31)
+ *     d = (float)((int32)(z >> 40) - (int32)((z >> 16) & 0xFFFFFF)) * 2^-24
+ * (splitmix64's output at a counter): exact, triangular on (-1, 1) LSB and a function of position only, so no result depends on
+ * how a sequence is cut into feeds. Without dither d = 0.
+ *
+ * One sample: y = x * gain in one f32 multiply, a NaN becomes -1, y is clamped to [-1, 1], s = (double)y * 32767.0 (exact).
+ * With e[j] the error j + 1 frames earlier on that channel of that row, zeros at the stream's start:
+ *     t = +0.0;  for j = T-1 down to 1: t = t + coef[j] * e[j]
+ *     w = T ? (s - t) - coef[0] * e[0] : s
+ *     q = rint(w + (double)d)       (ties to even)
+ *     e_new = q - w
+ * in f64, every product rounded before the sum it enters. The error comes from the unclamped q, so |e| < 1.5 and |w - s| < 96;
+ * the stored sample is q clamped to -32767 .. 32767, and a clamp that changes q is counted per channel. With dither 0 and
+ * taps 0 the stored sample is exactly pcm16(y) = sauAmd_flac_quantize(x, gain, 16): such a quantiser reproduces the existing
+ * writers' int16s.
+ *
+ * Dither and shaped noise are added after the gain, so a signal at full scale clips: at constant full scale with F9 (seed 7,
+ * row 0) the quantiser clamps 902 of 2000 samples. The stats say how often it happened; the caller leaves headroom (the shaped sets'
+ * noise reaches a few tens of LSB).
+ *
+ * Presets (dither 1): FLAT no taps; HP1 {1.0}; E3 {1.623, -0.982, 0.109}; E5 {2.033, -2.165, 1.959, -1.590, 0.6149};
+ * F9 {2.412, -3.370, 3.937, -4.174, 3.353, -2.205, 1.281, -0.569, 0.0847}. E3, E5 and F9 are the published psychoacoustic sets
+ * (PAPERS.md), designed for 44.1 kHz and accepted at any rate. E5's noise gain is 0.148 at DC and 9.36 at Nyquist.
+ *
+ * Out of scope: 24-bit dither, dither in the int16 runs of sauAmd_Batch_run, rate-specific shapers, a limited dithered writer. */
+typedef struct sauAmdDither {
+	uint64_t seed;
+	uint32_t dither;   /* 0 none, 1 TPDF */
+	uint32_t taps;     /* T, 0 .. 9 */
+	double coef[9];
+} sauAmdDither;
+typedef struct sauAmdDitherStats {
+	uint64_t frames;       /* fed since the last reset */
+	uint64_t clipped[2];   /* per channel: samples the clamp to -32767 .. 32767 changed */
+} sauAmdDitherStats;
+enum { SAU_AMD_DITHER_FLAT = 0, SAU_AMD_DITHER_HP1 = 1, SAU_AMD_DITHER_E3 = 2, SAU_AMD_DITHER_E5 = 3, SAU_AMD_DITHER_F9 = 4 };
+typedef struct sauAmdQuantizer sauAmdQuantizer;
+/* *out = the preset `shape` with TPDF dither of `seed` (unused coefficients zero). False for any other shape or out == NULL. */
+SAU_AMD_API bool sauAmd_dither_preset(int shape, uint64_t seed, sauAmdDither *out);
+/* The host restatement, from the same source as the kernels: out = what a quantiser makes of frames [first_frame,
+ * first_frame + frames) of its row `row`, `channels` interleaved. history: [channels][9] in and out, the errors 1 .. 9 frames
+ * back (NULL: zeros, and nothing is handed back); a spec without taps leaves it alone. clipped (may be NULL) gets this call's
+ * counts. False on an invalid spec, channels other than 1 or 2, a gain that is not finite, or a NULL x or out with frames > 0. */
+SAU_AMD_API bool sauAmd_dither_quantize(const float *x, size_t frames, int channels, float gain, const sauAmdDither *spec, uint64_t row,
+		uint64_t first_frame, double *history, int16_t *out, uint64_t clipped[2]);
+/* A quantiser of n_rows streams (1 .. 65535) of 1 or 2 channels on the batch's device and stream, independent of the batch's
+ * own runs. NULL (sauAmd_last_error) on a bad argument or on a backend without it. It must be destroyed before the batch.
+ * sauAmd_Quantizer_destroy(NULL) is allowed. */
+SAU_AMD_API sauAmdQuantizer *sauAmd_Batch_create_quantizer(sauAmdBatch *b, size_t n_rows, int channels, const sauAmdDither *spec);
+SAU_AMD_API void sauAmd_Quantizer_destroy(sauAmdQuantizer *q);
+/* Row r's next frames[r] float frames times gains[r] (NULL: 1.0f everywhere), read from rows + pitch_bytes * r, become the
+ * first frames[r] frames of the quantiser's own row r. The argument rules are sauAmd_Flac_feed_f32's: rows and pitch_bytes
+ * multiples of 4, the rows inside one allocation of the device, and a gain that is not finite is a bad argument that changes
+ * nothing. Queued on the batch's stream: it may directly follow the run that produced the rows. A feed waits for nothing on
+ * the host, except that one whose longest row is longer than that of every feed before it replaces the output rows with
+ * larger ones, which waits for the device once (as a float-fed encoder's rows do). */
+SAU_AMD_API bool sauAmd_Quantizer_feed(sauAmdQuantizer *q, const void *rows, size_t pitch_bytes, const uint32_t *frames /* [n_rows] */,
+		const float *gains /* [n_rows]; NULL: 1.0f */);
+/* The output rows: device address and pitch in bytes (NULL and 0 before the first feed with frames). The rows are 16-byte
+ * aligned and in one allocation, the pitch is a multiple of 256, and they are valid until the next feed: they can go straight
+ * into sauAmd_Flac_feed (int16-fed, every LPC order) or sauAmd_Batch_measure_rows on the same batch. */
+SAU_AMD_API const int16_t *sauAmd_Quantizer_rows(sauAmdQuantizer *q);
+SAU_AMD_API size_t sauAmd_Quantizer_pitch(sauAmdQuantizer *q);
+/* Wait for the batch's stream, then copy the last feed's frames of row r to bufs[r] (may be NULL where that feed gave row r
+ * no frames). */
+SAU_AMD_API bool sauAmd_Quantizer_read(sauAmdQuantizer *q, int16_t *const *bufs /* [n_rows] */);
+/* Wait for the batch's stream and report per row (out may be NULL). reset != 0 then restarts every stream at frame 0 with
+ * zero history and zero counts. */
+SAU_AMD_API bool sauAmd_Quantizer_stats(sauAmdQuantizer *q, sauAmdDitherStats *out /* [n_rows] */, int reset);
+/* Render prg into a 16-bit file through a quantiser: sauAmd_render_file_normalized's second pass with a sauAmd_Quantizer_feed
+ * of the run's device row (gain `gain`, row 0, the frames counted through the whole file) where that writer requantises; the
+ * int16s go through the two page-locked slots to the file. format is RAW, AU (the same values big-endian) or WAV;
+ * SAU_AMD_SNDFILE_WAV_F32 is a bad argument. Headers and frame counts are sauAmd_render_file's, and the samples are
+ * sauAmd_dither_quantize's of the floats sauAmd_render_file(.., SAU_AMD_SNDFILE_WAV_F32, ..) writes. The out pointers may be
+ * NULL. False with "bad argument" on a NULL pointer, channels other than 1 or 2, such a format, an invalid spec or a gain that
+ * is not finite, and on a backend without the quantiser or float output -- all before any file is created. */
+SAU_AMD_API bool sauAmd_render_file_dithered(const sauProgram *prg, uint32_t srate, const char *path, int format, int channels,
+		float gain, const sauAmdDither *spec, uint64_t *frames_out, sauAmdDitherStats *stats_out);
+/* ... into a 16-bit FLAC file: the float runs go through the quantiser into an int16-fed encoder of one stream
+ * (sauAmd_Batch_create_flac_lpc's parameters); the file I/O is sauAmd_render_file_flac's. The file decodes to the samples
+ * sauAmd_render_file_dithered writes. Refusals: that writer's and sauAmd_render_file_flac_lpc's, all before any file is created. */
+SAU_AMD_API bool sauAmd_render_file_flac_dithered(const sauProgram *prg, uint32_t srate, const char *path, int channels,
+		uint32_t block_frames, uint32_t max_lpc_order, float gain, const sauAmdDither *spec, uint64_t *frames_out,
+		sauAmdFlacInfo *info_out, sauAmdDitherStats *stats_out);
+/* The loudness-normalised writer through a quantiser: pass 1 and the gain rule are sauAmd_render_file_loudness's, pass 2 is
+ * sauAmd_render_file_dithered's with that gain. Refusals: those two writers', all before any file is created. */
+SAU_AMD_API bool sauAmd_render_file_loudness_dithered(const sauProgram *prg, uint32_t srate, const char *path, int format, int channels,
+		double target_lufs, float max_true_peak, const sauAmdDither *spec, uint64_t *frames_out, sauAmdLoudness *loud_out,
+		float *gain_out, sauAmdDitherStats *stats_out);
 
 #ifdef __cplusplus
 }

@@ -154,6 +154,43 @@ class FlacInfo(C.Structure):
 assert C.sizeof(FlacInfo) == 32
 
 
+class Dither(C.Structure):
+    """sauAmdDither (include/saugns_amd.h, section "Dither and noise shaping"): a quantiser's spec -- the dither's seed,
+    ``dither`` 0 (none) or 1 (TPDF), and ``taps`` error-feedback coefficients, coef[0] on the most recent error."""
+    _fields_ = [("seed", C.c_uint64), ("dither", C.c_uint32), ("taps", C.c_uint32), ("coef", C.c_double * 9)]
+
+    def __init__(self, seed=0, dither=0, coef=()):
+        super().__init__()
+        self.seed, self.dither, self.taps = int(seed) & (2**64 - 1), int(dither), len(coef)
+        for j, v in enumerate(list(coef)[:9]):
+            self.coef[j] = float(v)
+
+    def as_dict(self):
+        return {"seed": int(self.seed), "dither": int(self.dither), "taps": int(self.taps),
+                "coef": [float(v) for v in self.coef[:min(int(self.taps), 9)]]}
+
+    def __repr__(self):
+        return "Dither(%r)" % (self.as_dict(),)
+
+
+assert C.sizeof(Dither) == 88
+
+
+class DitherStats(C.Structure):
+    """sauAmdDitherStats: the frames a quantiser's row was fed and, per channel, the samples its clamp changed"""
+    _fields_ = [("frames", C.c_uint64), ("clipped", C.c_uint64 * 2)]
+
+    def as_dict(self):
+        return {"frames": int(self.frames), "clipped": [int(self.clipped[0]), int(self.clipped[1])]}
+
+    def __repr__(self):
+        return "DitherStats(%r)" % (self.as_dict(),)
+
+
+assert C.sizeof(DitherStats) == 24
+DITHER_FLAT, DITHER_HP1, DITHER_E3, DITHER_E5, DITHER_F9 = range(5)
+
+
 def _declare(L):
     """The C ABI of include/saugns_amd.h on a loaded library."""
     L.sau_create_Generator.restype = C.c_void_p
@@ -299,6 +336,36 @@ def _declare(L):
         L.sauAmd_render_file_flac.restype = C.c_bool
         L.sauAmd_render_file_flac.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_int, C.c_uint32, C.POINTER(C.c_uint64),
                                               C.POINTER(FlacInfo)]
+    if hasattr(L, "sauAmd_Batch_create_quantizer"):  # dither and noise shaping (SAU_AMD_LIB may name an older build)
+        L.sauAmd_dither_preset.restype = C.c_bool
+        L.sauAmd_dither_preset.argtypes = [C.c_int, C.c_uint64, C.POINTER(Dither)]
+        L.sauAmd_dither_quantize.restype = C.c_bool
+        L.sauAmd_dither_quantize.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.POINTER(Dither), C.c_uint64, C.c_uint64,
+                                             C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+        L.sauAmd_Batch_create_quantizer.restype = C.c_void_p
+        L.sauAmd_Batch_create_quantizer.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.POINTER(Dither)]
+        L.sauAmd_Quantizer_destroy.argtypes = [C.c_void_p]
+        L.sauAmd_Quantizer_feed.restype = C.c_bool
+        L.sauAmd_Quantizer_feed.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_float)]
+        L.sauAmd_Quantizer_rows.restype = C.c_void_p
+        L.sauAmd_Quantizer_rows.argtypes = [C.c_void_p]
+        L.sauAmd_Quantizer_pitch.restype = C.c_size_t
+        L.sauAmd_Quantizer_pitch.argtypes = [C.c_void_p]
+        L.sauAmd_Quantizer_read.restype = C.c_bool
+        L.sauAmd_Quantizer_read.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+        L.sauAmd_Quantizer_stats.restype = C.c_bool
+        L.sauAmd_Quantizer_stats.argtypes = [C.c_void_p, C.POINTER(DitherStats), C.c_int]
+        L.sauAmd_render_file_dithered.restype = C.c_bool
+        L.sauAmd_render_file_dithered.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_int, C.c_int, C.c_float, C.POINTER(Dither),
+                                                  C.POINTER(C.c_uint64), C.POINTER(DitherStats)]
+        L.sauAmd_render_file_flac_dithered.restype = C.c_bool
+        L.sauAmd_render_file_flac_dithered.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_int, C.c_uint32, C.c_uint32, C.c_float,
+                                                       C.POINTER(Dither), C.POINTER(C.c_uint64), C.POINTER(FlacInfo),
+                                                       C.POINTER(DitherStats)]
+        L.sauAmd_render_file_loudness_dithered.restype = C.c_bool
+        L.sauAmd_render_file_loudness_dithered.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_int, C.c_int, C.c_double, C.c_float,
+                                                           C.POINTER(Dither), C.POINTER(C.c_uint64), C.POINTER(Loudness),
+                                                           C.POINTER(C.c_float), C.POINTER(DitherStats)]
     if hasattr(L, "sauAmd_Batch_create_flac_lpc"):  # the encoder's LPC mode (SAU_AMD_LIB may name an older build)
         L.sauAmd_flac_encode_block_lpc.restype = C.c_size_t
         L.sauAmd_flac_encode_block_lpc.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
@@ -781,6 +848,63 @@ def render_file_flac(program, srate, path, channels=1, block_frames=0, backend=N
     return n.value, info
 
 
+def dither_preset(shape, seed=0):
+    """sauAmd_dither_preset: the Dither spec of a preset (DITHER_FLAT, _HP1, _E3, _E5, _F9) with TPDF dither of ``seed``"""
+    d = Dither()
+    if not lib().sauAmd_dither_preset(int(shape), int(seed) & (2**64 - 1), C.byref(d)):
+        raise ValueError("sauAmd_dither_preset refused shape %r" % (shape,))
+    return d
+
+
+def dither_quantize(x, channels, gain, spec, row=0, first_frame=0, history=None):
+    """sauAmd_dither_quantize: the host's restatement of a quantiser, from the same source as the kernels. x: float32 samples,
+    ``channels`` interleaved, the frames from ``first_frame`` on of the quantiser's row ``row``. ``history``: float64
+    [channels, 9], the errors 1 .. 9 frames back (None: zeros) -> (int16 samples, the history behind them, [clipped per
+    channel]). Raises ValueError on what the library refuses."""
+    x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+    frames = x.size // channels if channels in (1, 2) else 0
+    h = np.zeros((max(int(channels), 1), 9), np.float64) if history is None else np.array(history, np.float64).reshape(channels, 9)
+    out = np.zeros(x.size, np.int16)
+    cl = (C.c_uint64 * 2)()
+    if not lib().sauAmd_dither_quantize(x.ctypes.data, frames, int(channels), float(gain), C.byref(spec), int(row), int(first_frame),
+                                        h.ctypes.data, out.ctypes.data, cl):
+        raise ValueError("sauAmd_dither_quantize refused its arguments")
+    return out, h, [int(cl[0]), int(cl[1])]
+
+
+def render_file_dithered(program, srate, path, spec, fmt=SNDFILE_WAV, channels=1, gain=1.0):
+    """sauAmd_render_file_dithered: render a whole program in float32 into a 16-bit RAW, AU or WAV file, scaled by ``gain`` and
+    quantised on the device with the Dither ``spec`` -> (frames written, DitherStats as a dict)."""
+    n, st = C.c_uint64(), DitherStats()
+    L = _used(lib())
+    if not L.sauAmd_render_file_dithered(program.ptr, srate, os.fsencode(path), fmt, channels, float(gain), C.byref(spec),
+                                         C.byref(n), C.byref(st)):
+        raise RuntimeError("sauAmd_render_file_dithered failed: " + last_error(L))
+    return n.value, st.as_dict()
+
+
+def render_file_flac_dithered(program, srate, path, spec, channels=1, block_frames=0, max_lpc_order=0, gain=1.0):
+    """sauAmd_render_file_flac_dithered: the same samples into a 16-bit FLAC file, encoded on the device
+    -> (frames, FlacInfo, DitherStats as a dict)."""
+    n, info, st = C.c_uint64(), FlacInfo(), DitherStats()
+    L = _used(lib())
+    if not L.sauAmd_render_file_flac_dithered(program.ptr, srate, os.fsencode(path), channels, block_frames, _lpc_order(max_lpc_order),
+                                              float(gain), C.byref(spec), C.byref(n), C.byref(info), C.byref(st)):
+        raise RuntimeError("sauAmd_render_file_flac_dithered failed: " + last_error(L))
+    return n.value, info, st.as_dict()
+
+
+def render_file_loudness_dithered(program, srate, path, spec, fmt=SNDFILE_WAV, channels=1, target_lufs=-23.0, max_true_peak=1.0):
+    """sauAmd_render_file_loudness_dithered: render_file_loudness's measuring pass and gain, then render_file_dithered's pass
+    with that gain -> (frames written, Loudness of the render before the gain, the gain, DitherStats as a dict)."""
+    n, ld, gain, st = C.c_uint64(), Loudness(), C.c_float(), DitherStats()
+    L = _used(lib())
+    if not L.sauAmd_render_file_loudness_dithered(program.ptr, srate, os.fsencode(path), fmt, channels, target_lufs, max_true_peak,
+                                                  C.byref(spec), C.byref(n), C.byref(ld), C.byref(gain), C.byref(st)):
+        raise RuntimeError("sauAmd_render_file_loudness_dithered failed: " + last_error(L))
+    return n.value, ld, gain.value, st.as_dict()
+
+
 _flac24_hooks = None
 
 
@@ -1242,6 +1366,11 @@ class Batch:
         with 0 the encoder create_flac makes, by the other entry point"""
         return Flac(self, n_rows, channels, block_frames, max_lpc_order, lpc_entry=True)
 
+    def create_quantizer(self, n_rows, channels, spec):
+        """sauAmd_Batch_create_quantizer: a Quantizer of n_rows streams with the Dither ``spec`` on the batch's device and
+        stream. Close it before the batch."""
+        return Quantizer(self, n_rows, channels, spec)
+
     def device_pcm(self, stream):
         """Device address of the stream's int16 row of the last run; None after a float32 run."""
         return self._L.sauAmd_Batch_device_pcm(self._b, stream)
@@ -1399,6 +1528,66 @@ class Flac:
         if getattr(self, "_e", None):
             self._L.sauAmd_Flac_destroy(self._e)
             self._e = None
+            self._batch = None
+
+    def __del__(self):
+        self.close()
+
+
+class Quantizer:
+    """sauAmdQuantizer: the 16-bit quantiser stage with TPDF dither and error-feedback noise shaping (include/saugns_amd.h,
+    section "Dither and noise shaping"). ``feed`` takes row r's next frames[r] float frames from device memory, on the batch's
+    stream, and leaves int16 rows of the stage's own on the device (``rows``, ``pitch``); ``read`` waits and returns the last
+    feed's samples. Close it before its batch."""
+
+    def __init__(self, batch, n_rows, channels, spec):
+        self._L = batch._L
+        self.n_rows, self.channels = int(n_rows), int(channels)
+        self._last = [0] * self.n_rows
+        self._q = _used(self._L).sauAmd_Batch_create_quantizer(batch._b, self.n_rows, self.channels, C.byref(spec))
+        if not self._q:
+            raise RuntimeError("sauAmd_Batch_create_quantizer returned NULL: " + last_error(self._L))
+        self._batch = batch  # (the batch outlives the quantiser: its close() closes this one first)
+        batch._meters = getattr(batch, "_meters", []) + [weakref.ref(self)]
+
+    def feed(self, ptr, pitch, frames, gains=None):
+        """sauAmd_Quantizer_feed: row r's next frames[r] float frames from the device rows at `ptr`, `pitch` bytes apart, times
+        gains[r] (None: 1.0)."""
+        fr = (C.c_uint32 * self.n_rows)(*[int(f) for f in frames])
+        g = None if gains is None else (C.c_float * self.n_rows)(*[float(v) for v in gains])
+        if not _used(self._L).sauAmd_Quantizer_feed(self._q, ptr, pitch, fr, g):
+            raise RuntimeError("sauAmd_Quantizer_feed failed: " + last_error(self._L))
+        self._last = [int(f) for f in frames]
+
+    def rows(self):
+        """sauAmd_Quantizer_rows: the device address of the output rows (None before the first feed with frames)"""
+        return self._L.sauAmd_Quantizer_rows(self._q)
+
+    def pitch(self):
+        """sauAmd_Quantizer_pitch: the bytes between the output rows"""
+        return int(self._L.sauAmd_Quantizer_pitch(self._q))
+
+    def read(self):
+        """sauAmd_Quantizer_read -> the last feed's samples per row, a list of int16 arrays [frames[r] * channels]"""
+        bufs = [np.full(n * self.channels + 8, 0x5a5a, np.int16) for n in self._last]
+        ptrs = (C.c_void_p * self.n_rows)(*[b.ctypes.data for b in bufs])
+        if not _used(self._L).sauAmd_Quantizer_read(self._q, ptrs):
+            raise RuntimeError("sauAmd_Quantizer_read failed: " + last_error(self._L))
+        for b, n in zip(bufs, self._last):
+            assert (b[n * self.channels:] == 0x5a5a).all(), "a store behind the row's frames"
+        return [b[:n * self.channels].copy() for b, n in zip(bufs, self._last)]
+
+    def stats(self, reset=False):
+        """sauAmd_Quantizer_stats -> the rows' DitherStats as dicts; ``reset`` restarts every stream at frame 0"""
+        st = (DitherStats * self.n_rows)()
+        if not _used(self._L).sauAmd_Quantizer_stats(self._q, st, 1 if reset else 0):
+            raise RuntimeError("sauAmd_Quantizer_stats failed: " + last_error(self._L))
+        return [s.as_dict() for s in st]
+
+    def close(self):
+        if getattr(self, "_q", None):
+            self._L.sauAmd_Quantizer_destroy(self._q)
+            self._q = None
             self._batch = None
 
     def __del__(self):

@@ -769,6 +769,80 @@ extern "C" bool sauAmd_Flac_read(sauAmdFlac *e, uint8_t *const *bufs, const size
 	return false;
 }
 
+/* ---- the quantiser (include/saugns_amd.h, section "Dither and noise shaping") ---- */
+struct sauAmdQuantizer {
+	sauengine::Quantizer *q;
+};
+static_assert(sizeof(sauAmdDither) == 88 && sizeof(sauAmdDither) == sizeof(saudither::DitherSpec), "sauAmdDither is saudither::DitherSpec");
+static_assert(sizeof(sauAmdDitherStats) == sizeof(sauengine::DitherStats), "sauAmdDitherStats is sauengine::DitherStats");
+
+extern "C" bool sauAmd_dither_preset(int shape, uint64_t seed, sauAmdDither *out) {
+	return out && saudither::dither_preset(shape, seed, *(saudither::DitherSpec *)out);
+}
+extern "C" bool sauAmd_dither_quantize(const float *x, size_t frames, int channels, float gain, const sauAmdDither *spec, uint64_t row,
+		uint64_t first_frame, double *history, int16_t *out, uint64_t clipped[2]) {
+	return sauengine::dither_quantize(x, frames, channels, gain, (const saudither::DitherSpec *)spec, row, first_frame, history, out, clipped);
+}
+
+extern "C" sauAmdQuantizer *sauAmd_Batch_create_quantizer(sauAmdBatch *b, size_t n_rows, int channels, const sauAmdDither *spec) {
+	std::string err;
+	try {
+		if (!b || !n_rows || n_rows > saudither::DITHER_MAX_ROWS || (channels != 1 && channels != 2) || !spec ||
+		    !saudither::dither_spec_ok(*(const saudither::DitherSpec *)spec)) err = "bad argument";
+		else if (sauengine::Quantizer *q = b->engine->backend()->create_quantizer(n_rows, (uint32_t)channels, *(const saudither::DitherSpec *)spec, err))
+			return new sauAmdQuantizer{q};
+	} catch (const std::exception &ex) {
+		err = std::string("internal error: ") + ex.what();
+	}
+	report("dither", err);
+	return nullptr;
+}
+
+extern "C" void sauAmd_Quantizer_destroy(sauAmdQuantizer *q) {
+	if (!q) return;
+	delete q->q;
+	delete q;
+}
+
+extern "C" bool sauAmd_Quantizer_feed(sauAmdQuantizer *q, const void *rows, size_t pitch_bytes, const uint32_t *frames, const float *gains) {
+	std::string err;
+	try {
+		if (!q || !rows || !frames || ((uintptr_t)rows & 3u) || (pitch_bytes & 3u)) err = "bad argument";
+		else if (q->q->feed(rows, pitch_bytes, frames, gains, err)) return true;
+	} catch (const std::exception &ex) {
+		err = std::string("internal error: ") + ex.what();
+	}
+	report("dither", err);
+	return false;
+}
+
+extern "C" const int16_t *sauAmd_Quantizer_rows(sauAmdQuantizer *q) { return q ? q->q->rows() : nullptr; }
+extern "C" size_t sauAmd_Quantizer_pitch(sauAmdQuantizer *q) { return q ? q->q->pitch() : 0; }
+
+extern "C" bool sauAmd_Quantizer_read(sauAmdQuantizer *q, int16_t *const *bufs) {
+	std::string err;
+	try {
+		if (!q || !bufs) err = "bad argument";
+		else if (q->q->read(bufs, err)) return true;
+	} catch (const std::exception &ex) {
+		err = std::string("internal error: ") + ex.what();
+	}
+	report("dither", err);
+	return false;
+}
+
+extern "C" bool sauAmd_Quantizer_stats(sauAmdQuantizer *q, sauAmdDitherStats *out, int reset) {
+	std::string err;
+	try {
+		if (!q) err = "bad argument";
+		else if (q->q->stats((sauengine::DitherStats *)out, reset != 0, err)) return true;
+	} catch (const std::exception &ex) {
+		err = std::string("internal error: ") + ex.what();
+	}
+	report("dither", err);
+	return false;
+}
+
 extern "C" bool sauAmd_Batch_sync(sauAmdBatch *b) {
 	std::string err;
 	if (!b->engine->backend()->sync(err)) { report("batch", err); return false; }

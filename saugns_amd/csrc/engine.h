@@ -15,6 +15,7 @@
 #include "../../include/sau_abi.h"
 #include "sau_dev_types.h"
 #include "sau_flac.h"
+#include "sau_dither.h"
 #include <stddef.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -156,6 +157,41 @@ public:
 	/* wait for the stream; bytes_out[n_rows] the unread bytes; bufs (may be NULL): they are copied there and consumed, every
 	 * caps[r] has to suffice; info_out (may be NULL) [n_rows]; `reset`: new streams behind the read */
 	virtual bool read(uint8_t *const *bufs, const size_t *caps, size_t *bytes_out, FlacInfo *info_out, bool reset, std::string &err) = 0;
+};
+
+/* The 16-bit quantiser on the host (tables.cpp; include/saugns_amd.h, section "Dither and noise shaping"; the arithmetic is
+ * sau_dither.h's, which the kernels use too). DitherStats is sauAmdDitherStats. dither_quantize: row `row`'s frames
+ * [first_frame, first_frame + frames) as a quantiser makes them; history (may be NULL: zeros) [channels][9] in and out, left
+ * alone by a spec without taps; clipped (may be NULL) [2] is set to this call's counts. False on a bad spec, channels other
+ * than 1 or 2, a gain that is not finite or a NULL pointer with frames > 0. */
+struct DitherStats {
+	uint64_t frames;
+	uint64_t clipped[2];
+};
+static_assert(sizeof(DitherStats) == 24, "DitherStats is sauAmdDitherStats");
+bool dither_quantize(const float *x, size_t frames, int channels, float gain, const saudither::DitherSpec *spec, uint64_t row,
+		uint64_t first_frame, double *history, int16_t *out, uint64_t *clipped);
+
+/* A quantiser of a backend (Backend::create_quantizer): streams that are fed float rows and leave int16 rows of the stage's
+ * own on the device. Destroyed before its backend. */
+class Quantizer {
+public:
+	virtual ~Quantizer() {}
+	virtual size_t n_rows() const = 0;
+	virtual uint32_t channels() const = 0;
+	/* row r's next frames[r] float frames times gains[r] (NULL: 1.0f), from rows + pitch_bytes * r: device work on the backend's
+	 * stream, into the first frames[r] frames of the stage's row r */
+	virtual bool feed(const void *rows, size_t pitch_bytes, const uint32_t *frames, const float *gains, std::string &err) = 0;
+	/* the output rows: device address (16-byte aligned, one allocation) and pitch in bytes (a multiple of 256), valid until the
+	 * next feed; NULL and 0 before the first feed with frames */
+	virtual const int16_t *rows() const = 0;
+	virtual size_t pitch() const = 0;
+	/* wait for the stream, then the last feed's frames per row to bufs[r] (may be NULL where the row had none) */
+	virtual bool read(int16_t *const *bufs, std::string &err) = 0;
+	/* queue the copy of the first `bytes` bytes of row 0 out, like Backend::fetch_pcm_async (`slot`, wait_fetch): the file writers */
+	virtual bool fetch_async(void *dst, size_t bytes, int slot, std::string &err) = 0;
+	/* wait for the stream; out (may be NULL) [n_rows]; `reset`: every stream starts again at frame 0 with zero history */
+	virtual bool stats(DitherStats *out, bool reset, std::string &err) = 0;
 };
 
 /* Everything the backend needs to render one segment (no events inside). */
@@ -424,6 +460,11 @@ public:
 	virtual FlacEncoder *create_flac_f32(size_t n_rows, uint32_t channels, uint32_t block_frames, int bits, uint32_t max_lpc_order, std::string &err) {
 		(void)n_rows; (void)channels; (void)block_frames; (void)bits; (void)max_lpc_order;
 		err = "this backend has no float-fed FLAC encoder"; return nullptr;
+	}
+	/* A quantiser of n_rows streams on the backend's stream (include/saugns_amd.h, section "Dither and noise shaping"); the
+	 * arguments have been looked at. A backend without one refuses -- this default -- and nothing changes. */
+	virtual Quantizer *create_quantizer(size_t n_rows, uint32_t channels, const saudither::DitherSpec &spec, std::string &err) {
+		(void)n_rows; (void)channels; (void)spec; err = "this backend has no quantiser"; return nullptr;
 	}
 	/* the same from empty records on rows of `frames` frames each, synchronous; spectrogram_out (may be NULL): every segment's
 	 * (float)p[k], [n_rows][channels][S][N/2 + 1], refused when spectrogram_cap (in floats) does not suffice */

@@ -17,6 +17,7 @@
  *   k_flac.h        flac_analyze_kernel, flac_scan_kernel, flac_write_kernel, flac_carry_kernel (FLAC frames of fed int16 rows;
  *                   the <true> builds of the first and the third hold the LPC mode), flac_quant_kernel (a float-fed encoder's
  *                   rows), flac_analyze_wide_kernel, flac_write_wide_kernel, flac_carry_wide_kernel (24 bits: int32 samples)
+ *   k_dither.h      dither_flat_kernel, dither_shape_kernel (the 16-bit quantiser stage: TPDF dither, error-feedback noise shaping)
  *   launch_plan.h   (plain C++, no HIP) the tuning switches and every decision about a segment's launches: rows per pass, LDS
  *                   budgets, builds, grids, tasks, chain chunks, the mixer -- a plan per segment, testable without a GPU
  *   mix_overlap.h   (plain C++, no HIP) where the main stream waits for a final mixer that runs on the side stream
@@ -85,6 +86,7 @@ using namespace sauplan;
 #include "k_limiter.h"
 #include "k_spectrum.h"
 #include "k_flac.h"
+#include "k_dither.h"
 static_assert(MISC_BYTES == sizeof(Misc), "launch_plan.h plans the block loop's LDS with this size");
 
 /* ------------------------------------------------------------------------ */
@@ -2437,6 +2439,128 @@ public:
 		Flac *e = new Flac(this, n_rows, channels, block_frames, max_lpc_order, true, (uint32_t)bits);
 		if (!e->init(err)) { delete e; return nullptr; }
 		return e;
+	}
+
+	/* ---- the quantiser (k_dither.h; the geometry is launch_plan.h's plan_dither) ----
+	 * A quantiser is streams of its own on this backend's device and stream: a record per chain (history and clamp counts) and
+	 * the int16 rows of the feed at hand. Where a row stands is kept on the host and goes to the kernels with the feed's row
+	 * records, so a feed waits for nothing. */
+	class Quant : public sauengine::Quantizer {
+	public:
+		Quant(HipBackendImpl *be, size_t n_rows, uint32_t channels, const saudither::DitherSpec &spec)
+			: be_(be), n_(n_rows), ch_(channels), spec_(spec), pos_(n_rows, 0), last_(n_rows, 0) {}
+		~Quant() override { /* the buffers go back to the pool (member destructors): nothing may still be using them */
+			be_->use_device();
+			if (be_->stream_) { be_->join_mixer_quiet("dither"); (void)hipStreamSynchronize(be_->stream_); }
+		}
+		size_t n_rows() const override { return n_; }
+		uint32_t channels() const override { return ch_; }
+		bool init(std::string &err) {
+			if (!plan_dither(spec_.taps, ch_, n_, 0).ok) { err = "bad argument"; return false; }
+			if (!chains_.ensure(n_ * ch_, err) || !desc_.ensure(n_, err)) return false;
+			return clear(err);
+		}
+		bool clear(std::string &err) {
+			if (!be_->join_mixer("dither_clear", err)) return false;
+			HIP_OK(hipMemsetAsync(chains_.p, 0, n_ * ch_ * sizeof(saudither::DitherChain), be_->stream_));
+			std::fill(pos_.begin(), pos_.end(), 0);
+			return true;
+		}
+		/* every refusal comes before anything is queued or changed */
+		bool feed(const void *rows, size_t pitch, const uint32_t *frames, const float *gains, std::string &err) override {
+			be_->use_device();
+			if (!be_->join_mixer("dither_feed", err)) return false; /* (the rows fed may be the batch's PCM) */
+			if (!rows || !frames || ((uintptr_t)rows & 3u) || (pitch & 3u)) { err = "bad argument: rows and pitch_bytes must be multiples of 4"; return false; }
+			for (size_t r = 0; gains && r < n_; ++r)
+				if (!(gains[r] >= -FLT_MAX && gains[r] <= FLT_MAX)) { err = "bad argument: a gain is not finite"; return false; }
+			uint32_t longest = 0;
+			for (size_t r = 0; r < n_; ++r) longest = frames[r] > longest ? frames[r] : longest;
+			if (!longest) { std::fill(last_.begin(), last_.end(), 0); return true; } /* nothing changes, and the rows are not looked at */
+			const size_t row_bytes = (size_t)longest * ch_ * sizeof(float);
+			if (n_ > 1 && row_bytes > pitch) { err = "bad argument: rows longer than their pitch"; return false; }
+			/* the rows are read by kernels: they have to lie inside one allocation of this device */
+			if (!be_->lim_rows_inside(rows, pitch, n_, row_bytes, "rows", err)) return false;
+			const DitherPlan plan = plan_dither(spec_.taps, ch_, n_, longest);
+			if (!plan.ok) { err = "bad argument"; return false; }
+			if (!out_.ensure(n_ * plan.out_pitch, err)) return false;
+			std::vector<DitherRow> d(n_);
+			for (size_t r = 0; r < n_; ++r) {
+				d[r].first = pos_[r]; d[r].seed_r = saudither::dither_row_seed(spec_.seed, r);
+				d[r].frames = frames[r]; d[r].gain = gains ? gains[r] : 1.0f;
+			}
+			if (!be_->send(desc_.p, d.data(), n_ * sizeof(DitherRow), err)) return false;
+			DitherParams dp;
+			memset((void *)&dp, 0, sizeof dp);
+			dp.src = (const float *)rows; dp.src_pitch = pitch; dp.dst = (int16_t *)out_.p; dp.dst_pitch = plan.out_pitch;
+			dp.rows = desc_.p; dp.chains = chains_.p; dp.n_rows = (uint32_t)n_; dp.channels = ch_;
+			dp.dither = spec_.dither; dp.plain = saudither::dither_spec_plain(spec_) ? 1 : 0;
+			for (unsigned j = 0; j < saudither::DITHER_TAPS_MAX; ++j) dp.coef[j] = j < spec_.taps ? spec_.coef[j] : 0.0;
+			if (plan.shaped) hipLaunchKernelGGL(dither_shape_kernel, dim3(plan.shape_waves), dim3(DITHER_CHAINS), 0, be_->stream_, dp);
+			else hipLaunchKernelGGL(dither_flat_kernel, dim3(plan.flat_grid_x, plan.rows), dim3(256), 0, be_->stream_, dp);
+			HIP_OK(hipGetLastError());
+			for (size_t r = 0; r < n_; ++r) { pos_[r] += frames[r]; last_[r] = frames[r]; }
+			pitch_ = plan.out_pitch;
+			return true;
+		}
+		const int16_t *rows() const override { return pitch_ ? (const int16_t *)out_.p : nullptr; }
+		size_t pitch() const override { return pitch_; }
+		bool read(int16_t *const *bufs, std::string &err) override {
+			be_->use_device();
+			if (!be_->join_mixer("dither_read", err)) return false;
+			if (!bufs) { err = "bad argument"; return false; }
+			for (size_t r = 0; r < n_; ++r)
+				if (last_[r] && !bufs[r]) { err = "bad argument: no buffer for a row with frames"; return false; }
+			for (size_t r = 0; r < n_; ++r)
+				if (last_[r]) HIP_OK(hipMemcpyAsync(bufs[r], out_.p + pitch_ * r, (size_t)last_[r] * ch_ * sizeof(int16_t), hipMemcpyDeviceToHost, be_->stream_));
+			HIP_OK(hipStreamSynchronize(be_->stream_));
+			return true;
+		}
+		/* (the next feed's kernel is ordered behind this copy on the one stream: one set of rows serves both host slots) */
+		bool fetch_async(void *dst, size_t bytes, int slot, std::string &err) override {
+			slot &= 3;
+			be_->use_device();
+			if (!be_->join_mixer("dither_fetch_async", err)) return false;
+			if (bytes > (size_t)last_[0] * ch_ * sizeof(int16_t)) { err = "more bytes than were quantised"; return false; }
+			if (!be_->fetch_ev_[slot]) HIP_OK(hipEventCreateWithFlags(&be_->fetch_ev_[slot], hipEventDisableTiming));
+			HIP_OK(hipMemcpyAsync(dst, out_.p, bytes, hipMemcpyDeviceToHost, be_->stream_));
+			HIP_OK(hipEventRecord(be_->fetch_ev_[slot], be_->stream_));
+			return true;
+		}
+		bool stats(sauengine::DitherStats *out, bool reset, std::string &err) override {
+			be_->use_device();
+			if (!be_->join_mixer("dither_stats", err)) return false;
+			HIP_OK(hipStreamSynchronize(be_->stream_));
+			if (out) {
+				std::vector<saudither::DitherChain> c(n_ * ch_);
+				HIP_OK(hipMemcpy(c.data(), chains_.p, c.size() * sizeof(saudither::DitherChain), hipMemcpyDeviceToHost));
+				for (size_t r = 0; r < n_; ++r) {
+					out[r].frames = pos_[r];
+					out[r].clipped[0] = c[r * ch_].clipped;
+					out[r].clipped[1] = ch_ == 2 ? c[r * ch_ + 1].clipped : 0;
+				}
+			}
+			return reset ? clear(err) : true;
+		}
+	private:
+		HipBackendImpl *be_;
+		size_t n_;
+		uint32_t ch_;
+		saudither::DitherSpec spec_;
+		std::vector<uint64_t> pos_;          /* per row: frames fed */
+		std::vector<uint32_t> last_;         /* per row: frames of the last feed */
+		size_t pitch_ = 0;
+		DevBuf<saudither::DitherChain> chains_;
+		DevBuf<DitherRow> desc_;
+		DevBuf<unsigned char> out_;          /* the int16 rows of the feed at hand */
+	};
+	sauengine::Quantizer *create_quantizer(size_t n_rows, uint32_t channels, const saudither::DitherSpec &spec, std::string &err) override {
+		use_device();
+		if (!join_mixer("create_quantizer", err)) return nullptr;
+		if (!n_rows || (channels != 1 && channels != 2) || !saudither::dither_spec_ok(spec)) { err = "bad argument"; return nullptr; }
+		if (n_rows > saudither::DITHER_MAX_ROWS) { err = "bad argument: more than 65535 rows"; return nullptr; }
+		Quant *q = new Quant(this, n_rows, channels, spec);
+		if (!q->init(err)) { delete q; return nullptr; }
+		return q;
 	}
 
 	/* (whoever reads the rows through these pointers orders itself behind the main stream -- sync(), stream_handle() -- and so

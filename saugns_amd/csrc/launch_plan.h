@@ -1066,5 +1066,54 @@ inline FlacPlan plan_flac(uint32_t block_frames, uint32_t channels, size_t n_row
 	return p;
 }
 
+/* ---- the quantiser (k_dither.h; include/saugns_amd.h, section "Dither and noise shaping") ----
+ * Without taps a sample depends on its position only: dither_flat_kernel has flac_quant_kernel's geometry, four samples per
+ * thread. With taps a chain -- one channel of one row -- is a recurrence that cannot be cut in time: dither_shape_kernel gives a
+ * wave 64 chains, one per lane (64 mono rows or 32 stereo rows), and walks them through tiles of 64 frames staged in LDS
+ * frame-major: s as f64, the dither as f32 and in its place the sample on the way back, 12 bytes per sample. A frame's 64
+ * chains lie 64 + channels entries apart: the walking side (lanes a chain apart) reads consecutive entries, and the transposing
+ * side (lanes a frame apart) no longer meets it 64 ways on one bank. That is by the address arithmetic only -- in stereo the
+ * f64 stores may still meet two ways --, and no counter run has looked at it yet. */
+constexpr uint32_t DITHER_TILE = 64;   /* frames of a tile */
+constexpr uint32_t DITHER_CHAINS = 64; /* chains of a wave */
+/* what a feed tells the kernels of a row (uploaded as it stands) */
+struct DitherRow {
+	uint64_t first;    /* the stream's frames before this feed */
+	uint64_t seed_r;   /* sau_dither.h: dither_row_seed */
+	uint32_t frames;   /* of this feed */
+	float gain;
+};
+static_assert(sizeof(DitherRow) == 24, "DitherRow is uploaded as it stands");
+struct DitherPlan {
+	bool ok = false;          /* false: taps above 9, channels not 1 or 2, no row or more than 65535 */
+	bool shaped = false;      /* dither_shape_kernel; else dither_flat_kernel */
+	uint32_t rows = 0, channels = 0;
+	uint32_t flat_grid_x = 0; /* dither_flat_kernel: grid (this, rows) x 256; 0: no launch */
+	uint32_t shape_waves = 0; /* dither_shape_kernel: grid (this) x 64; 0: no launch */
+	uint32_t rows_per_wave = 0;
+	uint32_t tiles = 0;       /* of the feed's longest row */
+	uint32_t lds_stride = 0;  /* entries between a tile's frames */
+	size_t shape_lds = 0;     /* bytes of the tile and the wave's row records */
+	size_t out_pitch = 0;     /* bytes between the output rows: a multiple of 256 (0 for a feed without frames) */
+};
+inline DitherPlan plan_dither(uint32_t taps, uint32_t channels, size_t n_rows, uint32_t longest) {
+	DitherPlan p;
+	if (taps > saudither::DITHER_TAPS_MAX || (channels != 1 && channels != 2) || !n_rows || n_rows > saudither::DITHER_MAX_ROWS) return p;
+	p.shaped = taps != 0;
+	p.rows = (uint32_t)n_rows; p.channels = channels;
+	p.rows_per_wave = DITHER_CHAINS / channels;
+	p.lds_stride = DITHER_CHAINS + channels;
+	p.shape_lds = (size_t)DITHER_TILE * (DITHER_CHAINS + 2) * 12 + DITHER_CHAINS * sizeof(DitherRow);
+	p.tiles = (uint32_t)(((uint64_t)longest + DITHER_TILE - 1) / DITHER_TILE);
+	p.out_pitch = ((size_t)longest * channels * sizeof(int16_t) + 255) & ~(size_t)255;
+	if (longest) {
+		if (p.shaped) p.shape_waves = (uint32_t)((n_rows + p.rows_per_wave - 1) / p.rows_per_wave);
+		/* thread 0 of a row takes the samples ahead of the first 16-byte boundary, every other thread four */
+		else p.flat_grid_x = (uint32_t)(((uint64_t)longest * channels / 4 + 2 + 255) / 256);
+	}
+	p.ok = true;
+	return p;
+}
+
 } /* namespace sauplan */
 #endif

@@ -738,6 +738,170 @@ bool write_flac_limited(const sauProgram *prg, uint32_t srate, const char *path,
 	return ok;
 }
 
+/* The dithered writer: write_scaled's pass with a quantiser of one stream in place of requant_kernel -- each float run's
+ * device row fed with `gain`, the stage's int16 row fetched through the two page-locked slots. The quantiser's rows are in
+ * host order: an AU file's samples are swapped in the slot, behind the fetch. A backend without float output or without the
+ * quantiser says so before there is a file. The quantiser goes before the engine, which owns the backend. */
+bool write_dithered(const sauProgram *prg, uint32_t srate, const char *path, int format, int channels, float gain,
+		const saudither::DitherSpec &spec, Backend *backend /* owned */, uint64_t *frames_out, sauengine::DitherStats *stats_out, std::string &err) {
+	Engine *engine = Engine::create(&prg, 1, srate, backend, err);
+	if (!engine) return false;
+	const bool stereo = channels == 2;
+	size_t call, chunk;
+	file_lattice(srate, call, chunk);
+	engine->set_call_len(call);
+	if (!engine->set_format(sauengine::SF_F32, err)) { delete engine; return false; }
+	sauengine::Quantizer *q = backend->create_quantizer(1, (uint32_t)channels, spec, err);
+	if (!q) { delete engine; return false; }
+	const size_t frame_bytes = (size_t)channels * sizeof(int16_t);
+	void *host[2] = {backend->alloc_host(chunk * frame_bytes), backend->alloc_host(chunk * frame_bytes)};
+	SndOut out;
+	bool ok = host[0] && host[1];
+	if (!ok) err = "out of page-locked memory";
+	if (ok && !out.open(path, format, (uint16_t)channels, srate)) {
+		err = std::string("couldn't open \"") + path + "\" for writing";
+		ok = false;
+	}
+	const bool swap = format == SAU_AMD_SNDFILE_AU;
+	auto flush = [&](int k, size_t len) -> bool {
+		if (!backend->wait_fetch(k, err)) return false;
+		if (swap) {
+			int16_t *s = (int16_t *)host[k];
+			for (size_t i = 0; i < len * (size_t)channels; ++i) s[i] = saudev::pcm_swap(s[i]);
+		}
+		if (!out.write(host[k], len)) { err = "write failed"; return false; }
+		return true;
+	};
+	size_t pending[2] = {0, 0};
+	int slot = 0;
+	bool more = ok;
+	while (ok && more) {
+		size_t len = 0;
+		ok = engine->run_f32(nullptr, chunk, stereo, &more, &len, err);
+		if (!ok) break;
+		if (len) {
+			const uint32_t n = (uint32_t)len;
+			const float *row = backend->device_pcm_f32(0);
+			if (!row) { err = "the backend keeps no float rows on the device"; ok = false; break; }
+			/* (the rounding happens here, once, after the gain) */
+			ok = q->feed(row, backend->device_pcm_pitch(), &n, &gain, err) && q->fetch_async(host[slot], len * frame_bytes, slot, err);
+			pending[slot] = len;
+		}
+		const int other = slot ^ 1;
+		if (ok && pending[other]) {
+			ok = flush(other, pending[other]);
+			pending[other] = 0;
+		}
+		slot = other;
+	}
+	for (int s = 0; ok && s < 2; ++s) { /* oldest first */
+		const int k = slot ^ s;
+		if (pending[k]) {
+			ok = flush(k, pending[k]);
+			pending[k] = 0;
+		}
+	}
+	sauengine::DitherStats st{0, {0, 0}};
+	if (ok) ok = q->stats(&st, false, err);
+	delete q;
+	{ std::string e2; (void)backend->sync(e2); }
+	if (out.f && out.close() != 0 && ok) { err = "write failed"; ok = false; }
+	if (frames_out) *frames_out = out.frames;
+	if (ok && stats_out) *stats_out = st;
+	backend->free_host(host[0]);
+	backend->free_host(host[1]);
+	delete engine; /* owns the backend */
+	return ok;
+}
+
+/* The dithered FLAC writer: write_flac_scaled's float runs, each through a quantiser of one stream whose int16 row is fed to
+ * an int16-fed encoder where that writer feeds the floats; the file I/O is write_flac's. */
+bool write_flac_dithered(const sauProgram *prg, uint32_t srate, const char *path, int channels, uint32_t block_frames,
+		uint32_t max_lpc_order, float gain, const saudither::DitherSpec &spec, Backend *backend /* owned */, uint64_t *frames_out,
+		sauengine::FlacInfo *info_out, sauengine::DitherStats *stats_out, std::string &err) {
+	Engine *engine = Engine::create(&prg, 1, srate, backend, err);
+	if (!engine) return false;
+	const bool stereo = channels == 2;
+	const uint32_t B = sauflac::flac_block_frames(block_frames);
+	size_t call, chunk;
+	file_lattice(srate, call, chunk);
+	engine->set_call_len(call);
+	if (!engine->set_format(sauengine::SF_F32, err)) { delete engine; return false; }
+	sauengine::Quantizer *q = backend->create_quantizer(1, (uint32_t)channels, spec, err);
+	if (!q) { delete engine; return false; }
+	sauengine::FlacEncoder *enc = backend->create_flac_lpc(1, (uint32_t)channels, B, max_lpc_order, err);
+	if (!enc) { delete q; delete engine; return false; }
+	const size_t slot_bytes = (chunk / B + 2) * (size_t)sauflac::flac_frame_bound(B, (uint32_t)channels);
+	uint8_t *host[2] = {(uint8_t *)backend->alloc_host(slot_bytes), (uint8_t *)backend->alloc_host(slot_bytes)};
+	FILE *f = nullptr;
+	bool ok = host[0] && host[1];
+	if (!ok) err = "out of page-locked memory";
+	uint8_t head[42];
+	sauengine::FlacInfo info{0, 0, 0, 0, 0};
+	if (ok) {
+		f = fopen(path, "wb");
+		if (!f) { err = std::string("couldn't open \"") + path + "\" for writing"; ok = false; }
+		else if (sauengine::flac_header(srate, channels, B, &info, head, sizeof head) != 42 || fwrite(head, 1, 42, f) != 42) { err = "write failed"; ok = false; }
+	}
+	size_t pending[2] = {0, 0};
+	int slot = 0;
+	bool more = ok;
+	while (ok && more) {
+		size_t len = 0;
+		ok = engine->run_f32(nullptr, chunk, stereo, &more, &len, err);
+		if (!ok) break;
+		const uint32_t n = (uint32_t)len;
+		const float *row = backend->device_pcm_f32(0);
+		if (!row) { err = "the backend keeps no float rows on the device"; ok = false; break; }
+		ok = q->feed(row, backend->device_pcm_pitch(), &n, &gain, err);
+		if (ok) { /* (a feed without frames -- the finish behind the last run -- names rows but reads none) */
+			static const int16_t none[8] __attribute__((aligned(16))) = {0};
+			ok = n ? enc->feed(q->rows(), q->pitch(), &n, !more, err) : enc->feed(none, 16, &n, !more, err);
+		}
+		/* while this run renders and is encoded, the one before goes to the file */
+		const int other = slot ^ 1;
+		if (ok && pending[other]) {
+			if (fwrite(host[other], 1, pending[other], f) != pending[other]) { err = "write failed"; ok = false; }
+			pending[other] = 0;
+		}
+		if (ok) {
+			uint8_t *const bufs[1] = {host[slot]};
+			size_t got = 0;
+			ok = enc->read(bufs, &slot_bytes, &got, &info, false, err);
+			pending[slot] = got;
+		}
+		slot = other;
+	}
+	for (int s = 0; ok && s < 2; ++s) { /* oldest first: `slot` is the older of the two */
+		const int k = slot ^ s;
+		if (pending[k] && fwrite(host[k], 1, pending[k], f) != pending[k]) { err = "write failed"; ok = false; }
+		pending[k] = 0;
+	}
+	sauengine::DitherStats st{0, {0, 0}};
+	if (ok) ok = q->stats(&st, false, err);
+	delete enc;
+	delete q;
+	{ std::string e2; (void)backend->sync(e2); }
+	if (f) {
+		if (ok && (sauengine::flac_header(srate, channels, B, &info, head, sizeof head) != 42 || fseek(f, 0, SEEK_SET) != 0 ||
+		           fwrite(head, 1, 42, f) != 42)) { err = "write failed"; ok = false; }
+		const int ferr = ferror(f);
+		if ((fclose(f) != 0 || ferr) && ok) { err = "write failed"; ok = false; }
+	}
+	if (frames_out) *frames_out = info.frames;
+	if (ok && info_out) *info_out = info;
+	if (ok && stats_out) *stats_out = st;
+	backend->free_host(host[0]);
+	backend->free_host(host[1]);
+	delete engine; /* owns the backend */
+	return ok;
+}
+
+/* what the dithered writers refuse of a spec and a gain */
+bool dither_args_ok(const sauAmdDither *spec, float gain) {
+	return spec && saudither::dither_spec_ok(*(const saudither::DitherSpec *)spec) && gain >= -FLT_MAX && gain <= FLT_MAX;
+}
+
 /* what every FLAC writer of float runs refuses of its encoder's parameters */
 bool flac_f32_params_ok(int channels, uint32_t block_frames, int bits, uint32_t max_lpc_order) {
 	return sauengine::flac_params_ok(channels, block_frames) && sauflac::flac_bits_ok(bits) && max_lpc_order <= sauflac::FLAC_LPC_MAX &&
@@ -903,6 +1067,82 @@ extern "C" bool sauAmd_render_file_loudness(const sauProgram *prg, uint32_t srat
 	try {
 		ok = sauamd_internal::render_file_loudness(prg, srate, path, format, channels, target_lufs, max_true_peak,
 				[](std::string &e) -> Backend * { return sauhip::create_hip_backend(e); }, frames_out, loud_out, gain_out, err);
+	} catch (const std::exception &ex) { /* (nothing C++ crosses the C ABI) */
+		err = std::string("internal error: ") + ex.what();
+	}
+	if (!ok) sauamd_internal::set_last_error("output", err);
+	return ok;
+}
+
+/* ---- the dithered writers (include/saugns_amd.h, section "Dither and noise shaping"): every argument is looked at before a
+ * backend is made, and every refusal comes before any file is created ---- */
+extern "C" bool sauAmd_render_file_dithered(const sauProgram *prg, uint32_t srate, const char *path, int format, int channels,
+		float gain, const sauAmdDither *spec, uint64_t *frames_out, sauAmdDitherStats *stats_out) {
+	std::string err;
+	bool ok = false;
+	if (frames_out) *frames_out = 0;
+	try {
+		if (!prg || !path || (channels != 1 && channels != 2) || format < 0 || format > SAU_AMD_SNDFILE_WAV || !dither_args_ok(spec, gain))
+			err = "bad argument";
+		else if (Backend *backend = sauhip::create_hip_backend(err))
+			ok = write_dithered(prg, srate, path, format, channels, gain, *(const saudither::DitherSpec *)spec, backend, frames_out,
+					(sauengine::DitherStats *)stats_out, err);
+	} catch (const std::exception &ex) { /* (nothing C++ crosses the C ABI) */
+		err = std::string("internal error: ") + ex.what();
+	}
+	if (!ok) sauamd_internal::set_last_error("output", err);
+	return ok;
+}
+
+extern "C" bool sauAmd_render_file_flac_dithered(const sauProgram *prg, uint32_t srate, const char *path, int channels,
+		uint32_t block_frames, uint32_t max_lpc_order, float gain, const sauAmdDither *spec, uint64_t *frames_out,
+		sauAmdFlacInfo *info_out, sauAmdDitherStats *stats_out) {
+	std::string err;
+	bool ok = false;
+	if (frames_out) *frames_out = 0;
+	try {
+		if (!prg || !path || !srate || srate > 655350u || !sauengine::flac_params_ok(channels, block_frames) ||
+		    max_lpc_order > sauflac::FLAC_LPC_MAX || !dither_args_ok(spec, gain))
+			err = "bad argument";
+		else if (Backend *backend = sauhip::create_hip_backend(err))
+			ok = write_flac_dithered(prg, srate, path, channels, block_frames, max_lpc_order, gain, *(const saudither::DitherSpec *)spec,
+					backend, frames_out, (sauengine::FlacInfo *)info_out, (sauengine::DitherStats *)stats_out, err);
+	} catch (const std::exception &ex) { /* (nothing C++ crosses the C ABI) */
+		err = std::string("internal error: ") + ex.what();
+	}
+	if (!ok) sauamd_internal::set_last_error("output", err);
+	return ok;
+}
+
+extern "C" bool sauAmd_render_file_loudness_dithered(const sauProgram *prg, uint32_t srate, const char *path, int format, int channels,
+		double target_lufs, float max_true_peak, const sauAmdDither *spec, uint64_t *frames_out, sauAmdLoudness *loud_out,
+		float *gain_out, sauAmdDitherStats *stats_out) {
+	std::string err;
+	bool ok = false;
+	if (frames_out) *frames_out = 0;
+	try {
+		if (!prg || !path || (channels != 1 && channels != 2) || format < 0 || format > SAU_AMD_SNDFILE_WAV || !dither_args_ok(spec, 1.0f) ||
+		    !(target_lufs >= -DBL_MAX && target_lufs <= DBL_MAX) || !(max_true_peak > 0.f) || !(max_true_peak <= FLT_MAX) ||
+		    srate < sauengine::LOUD_MIN_RATE) /* (a NaN fails every comparison) */
+			err = "bad argument";
+		else if (Backend *first = sauhip::create_hip_backend(err)) {
+			sauengine::Loudness ld;
+			if (measure_program_loudness(prg, srate, channels == 2, first, ld, err)) {
+				if (loud_out) memcpy(loud_out, &ld, sizeof ld);
+				/* render_file_loudness's rule */
+				const float tp = ld.true_peak[0] > ld.true_peak[1] ? ld.true_peak[0] : ld.true_peak[1];
+				float gain = 1.0f;
+				if (ld.integrated > -HUGE_VAL) {
+					gain = (float)pow(10.0, (target_lufs - ld.integrated) / 20.0);
+					if (tp * gain > max_true_peak) gain = max_true_peak / tp; /* the ceiling binds: one f32 division */
+				}
+				if (gain_out) *gain_out = gain;
+				if (!(gain >= -FLT_MAX && gain <= FLT_MAX)) err = "bad argument: the gain to the target loudness is not finite";
+				else if (Backend *second = sauhip::create_hip_backend(err))
+					ok = write_dithered(prg, srate, path, format, channels, gain, *(const saudither::DitherSpec *)spec, second, frames_out,
+							(sauengine::DitherStats *)stats_out, err);
+			}
+		}
 	} catch (const std::exception &ex) { /* (nothing C++ crosses the C ABI) */
 		err = std::string("internal error: ") + ex.what();
 	}

@@ -14,6 +14,7 @@
  */
 #include "engine.h"
 #include <dlfcn.h>
+#include <float.h>
 #include <math.h>
 #include <string.h>
 
@@ -670,6 +671,37 @@ size_t flac_encode_block_s32(const int32_t *x, uint32_t n, int channels, uint32_
 	std::vector<int16_t> s(cnt);
 	for (size_t i = 0; i < cnt; ++i) s[i] = (int16_t)x[i];
 	return flac_encode_block_lpc(s.data(), n, channels, B, frame_number, max_lpc_order, out, cap);
+}
+
+/* ---- dither and noise shaping (include/saugns_amd.h, section "Dither and noise shaping"; the arithmetic is sau_dither.h's,
+ * which the kernels use too): what a quantiser makes of one row's frames [first_frame, first_frame + frames) ---- */
+bool dither_quantize(const float *x, size_t frames, int channels, float gain, const saudither::DitherSpec *spec, uint64_t row,
+		uint64_t first_frame, double *history, int16_t *out, uint64_t *clipped) {
+	using namespace saudither;
+	if ((channels != 1 && channels != 2) || !spec || !dither_spec_ok(*spec) || !(gain >= -FLT_MAX && gain <= FLT_MAX) ||
+	    (frames && (!x || !out))) return false;
+	if (clipped) clipped[0] = clipped[1] = 0;
+	const unsigned ch = (unsigned)channels, T = spec->taps;
+	if (dither_spec_plain(*spec)) { /* the existing rounding: nothing is clamped after it, and no state moves */
+		for (size_t i = 0; i < frames * ch; ++i) out[i] = saudev::pcm16(x[i] * gain);
+		return true;
+	}
+	const uint64_t seed_r = dither_row_seed(spec->seed, row);
+	for (unsigned c = 0; c < ch; ++c) {
+		double e[DITHER_TAPS_MAX] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+		if (history) memcpy(e, history + (size_t)c * DITHER_TAPS_MAX, sizeof e);
+		uint64_t clips = 0;
+		for (size_t i = 0; i < frames; ++i) {
+			const double s = dither_lsb(dither_scale(x[i * ch + c], gain));
+			const float d = spec->dither ? dither_tpdf(seed_r, first_frame + i, c) : 0.f;
+			bool cl;
+			out[i * ch + c] = (int16_t)dither_step(spec->coef, T, e, s, d, cl);
+			clips += cl ? 1 : 0;
+		}
+		if (history) memcpy(history + (size_t)c * DITHER_TAPS_MAX, e, sizeof e);
+		if (clipped) clipped[c] = clips;
+	}
+	return true;
 }
 
 } /* namespace sauengine */
