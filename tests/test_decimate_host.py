@@ -140,3 +140,14 @@ def test_plan_decimate_constants_are_what_the_gpu_tests_mirror():
     assert re.search(r"DECIM_TILE = 256;", hdr)
     import test_gpu_decimate as g
     assert g.DECIM_TILE == 256 and g.DECIM_TILE < 300 and 300 % g.DECIM_TILE != 0
+    # tests/test_gpu_decimate_rows.py sizes its runs by the tile, by the history (2 * DECIM_HALF output frames) and by the
+    # carry kernel's reach (four floats a thread): the same header, and engine.h for the half-length
+    assert re.search(r"DECIM_CARRY_THREADS = 256;", hdr)
+    assert re.search(r"DECIM_HALF = \(uint32_t\)sauengine::DECIM_HALF;", hdr)
+    eng = open(os.path.join(ROOT, "saugns_amd", "csrc", "engine.h")).read()
+    assert re.search(r"constexpr size_t DECIM_HALF = 32;", eng)
+    import test_gpu_decimate_rows as r
+    assert (r.DECIM_TILE, r.DECIM_HALF, r.DECIM_CARRY_THREADS) == (256, 32, 256) and r.H == g.H == H == r.DECIM_HALF
+    assert 2 * r.DECIM_HALF * 8 * 2 == 4 * r.DECIM_CARRY_THREADS  # K = 8 stereo fills the carry kernel to its last thread
+    for n in (r.DECIM_TILE - 1, r.DECIM_TILE, r.DECIM_TILE + 1, 2 * r.DECIM_TILE, 2 * r.DECIM_HALF - 1, 2 * r.DECIM_HALF, 2 * r.DECIM_HALF + 1):
+        assert n in r.RUNS

@@ -5,7 +5,8 @@ The reference is numpy applied to a SECOND batch's run_f32 output at srate * K -
 the oracle -- rendered in the same runs (a run is one call of the reference's block lattice), and it is the header's loop as it
 stands: float64, the taps the library exports, ascending j, acc = acc + h[j] * x64[m * K - j], then .astype(float32). numpy
 neither fuses the multiply into the add nor reorders the sum, so the comparison is by BYTES. The reference is asserted to
-hold no non-zero subnormal, so no denormal mode can come into it."""
+hold no non-zero subnormal, so no denormal mode can come into it -- subnormal, non-finite and full-scale samples, poison behind
+a stream's end and every kernel instantiation are tests/test_gpu_decimate_rows.py's, on rows of its own."""
 import functools
 import struct
 
@@ -24,9 +25,10 @@ KEYS = ["devtests__voice-reuse", "devtests__pm-addremaddrem"]  # 4 s; 2 s with a
 THIRD = "examples__tests__vibrato-pm"  # 2.1 s
 
 
-def decimate_ref(sa, x_hi, K, ch, n_out):
+def decimate_ref(sa, x_hi, K, ch, n_out, allow_subnormal=False):
     """the header's loop over x_hi (float32, interleaved, from the start of the sequence; +0 before it and behind its end)
-    -> n_out frames as float32"""
+    -> n_out frames as float32. allow_subnormal: the caller feeds crafted rows and compares subnormal results too
+    (tests/test_gpu_decimate_rows.py); everyone else's reference holds none."""
     h = sa.decimator_taps(K)
     L = len(h)
     x = np.asarray(x_hi, np.float32).reshape(-1, ch)
@@ -37,8 +39,9 @@ def decimate_ref(sa, x_hi, K, ch, n_out):
     for j in range(L):
         acc = acc + h[j] * xp[L - 1 - j:L - 1 - j + n_out * K:K]
     y = acc.astype(np.float32)
-    tiny = np.abs(y) < np.finfo(np.float32).tiny
-    assert not (tiny & (y != 0)).any(), "the reference holds a non-zero subnormal"
+    if not allow_subnormal:
+        tiny = np.abs(y) < np.finfo(np.float32).tiny
+        assert not (tiny & (y != 0)).any(), "the reference holds a non-zero subnormal"
     return y.reshape(-1)
 
 
@@ -195,34 +198,40 @@ HEADER = {0: 0, 1: 28, 2: 44, 3: 58}  # RAW, AU, WAV, WAV_F32
 
 
 @functools.lru_cache(maxsize=None)
-def _file_reference():
-    """sauAmd_render_file at RATE * 4 as float WAV -> its samples decimated on the host, H frames dropped, ceil(N / 4) kept"""
+def _file_reference(factor, channels):
+    """sauAmd_render_file at RATE * factor as float WAV -> its samples decimated on the host, H frames dropped,
+    ceil(N / factor) kept"""
     import tempfile
     import saugns_amd as sa
     prg = load_program(sa, KEYS[1])
     with tempfile.TemporaryDirectory() as t:
-        n_hi = sa.render_file(prg, RATE * 4, t + "/hi.wav", sa.api.SNDFILE_WAV_F32, 2)
+        n_hi = sa.render_file(prg, RATE * factor, t + "/hi.wav", sa.api.SNDFILE_WAV_F32, channels)
         x = np.frombuffer(open(t + "/hi.wav", "rb").read()[HEADER[3]:], "<f4")
-    assert len(x) == n_hi * 2 and n_hi == 2 * RATE * 4
-    keep = -(-n_hi // 4)
-    y = decimate_ref(sa, x, 4, 2, keep + H)[H * 2:]
+    assert len(x) == n_hi * channels and n_hi == 2 * RATE * factor
+    keep = -(-n_hi // factor)
+    y = decimate_ref(sa, x, factor, channels, keep + H)[H * channels:]
     y.setflags(write=False)
     return keep, y
 
 
-@pytest.mark.parametrize("fmt", [0, 1, 2, 3])
-def test_oversampled_files(sa, tmp_path, fmt):
-    keep, y = _file_reference()
+# factor 4 stereo in every format (ids as before); factors 2 and 8 mono in the int16 formats with a header: the big-endian one
+# (AU) and the little-endian one (WAV) -- decimate_kernel<2 and 8, int16_t, 1> with and without swap_bytes
+@pytest.mark.parametrize("factor,channels,fmt", [
+    pytest.param(4, 2, 0, id="0"), pytest.param(4, 2, 1, id="1"), pytest.param(4, 2, 2, id="2"), pytest.param(4, 2, 3, id="3"),
+    pytest.param(2, 1, 1, id="x2-mono-au"), pytest.param(2, 1, 2, id="x2-mono-wav"),
+    pytest.param(8, 1, 1, id="x8-mono-au"), pytest.param(8, 1, 2, id="x8-mono-wav")])
+def test_oversampled_files(sa, tmp_path, factor, channels, fmt):
+    keep, y = _file_reference(factor, channels)
     prg = load_program(sa, KEYS[1])
     path = str(tmp_path / "over.out")
-    assert sa.render_file_oversampled(prg, RATE, 4, path, fmt, 2) == keep
+    assert sa.render_file_oversampled(prg, RATE, factor, path, fmt, channels) == keep
     raw = open(path, "rb").read()
     head, data = raw[:HEADER[fmt]], raw[HEADER[fmt]:]
     if fmt == 3:
         want = y.astype("<f4").tobytes()
     else:
         want = quantise(y).astype(">i2" if fmt == 1 else "<i2").tobytes()
-    assert len(data) == len(want) == keep * 2 * (4 if fmt == 3 else 2)
+    assert len(data) == len(want) == keep * channels * (4 if fmt == 3 else 2)
     assert data == want
     if fmt == 1:
         assert head[:4] == b".snd" and struct.unpack(">I", head[16:20])[0] == RATE and struct.unpack(">I", head[8:12])[0] == keep
