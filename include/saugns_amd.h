@@ -575,7 +575,7 @@ SAU_AMD_API bool sauAmd_render_spectrum(const sauProgram *prg, uint32_t srate, i
  * 4096). Row r's block k covers its frames [k B, k B + B) and becomes FLAC frame number k; frames behind the last complete block
  * are pending until a later feed completes the block or a finish makes them one last short block. At most 65535 rows per
  * encoder and 2^31 - 1 blocks per row.
- * Limits: no MD5 (the field is zeros: "not computed"), no seek table, no comments, no wasted-bits detection, no escape
+ * Limits: MD5 only on request ("MD5" below), no seek table, no comments, no wasted-bits detection, no escape
  * partitions, no dither of its own (a quantiser's rows can be fed: "Dither and noise shaping" below); LPC only on request (max_lpc_order, "The LPC mode" below), of order <= 8 with 12-bit coefficients, one
  * precision and one window, and at 16 bits only: max_lpc_order > 0 with bits == 24 is a bad argument everywhere (its products
  * pass 32 bits, and the window scaling would pass 64). 24-bit output comes from float rows only ("24 bits" below). The
@@ -586,7 +586,7 @@ SAU_AMD_API bool sauAmd_render_spectrum(const sauProgram *prg, uint32_t srate, i
  * The header (42 bytes): "fLaC"; one metadata block header, 80 00 00 22 (last = 1, type 0, length 34); STREAMINFO:
  *   min blocksize 16 bits = B; max blocksize 16 = B; min framesize 24 and max framesize 24 from the record (0 before any
  *   frame); sample rate 20; channels - 1 in 3; bits per sample - 1 in 5 = 15; total samples 36 = the record's frames; MD5 128
- *   bits of zeros.
+ *   bits of zeros ("not computed"), or the digest ("MD5" below).
  * A frame's header:
  *   FF F8 (the sync code, reserved 0, fixed block size);
  *   4 bits block size code: 8 + log2(B / 256) for a block of B frames; 0111 for any other length n (also for n <= 256), and
@@ -690,6 +690,17 @@ SAU_AMD_API bool sauAmd_render_spectrum(const sauProgram *prg, uint32_t srate, i
  * sauAmd_flac_encode_block_s32 restates one such frame on the host. The bytes are a function of the fed floats, the gains and
  * (B, channels, bits, M) only, never of how the sequence was cut into feeds.
  *
+ * MD5. STREAMINFO's MD5 field is zeros unless it is asked for: sauAmd_Flac_set_md5 on a fed encoder, sauAmd_set_flac_file_md5
+ * for the file writers. Off, every byte and every launch is what it is without this paragraph. On, the encoder keeps the MD5
+ * (RFC 1321) of each row's unencoded samples (RFC 9639 section 8.2) on the device, where the samples are: the samples that the
+ * analysis sees -- behind a float-fed encoder's quantiser, behind a dither quantiser upstream --, in stream order, channels
+ * interleaved L, R whatever assignment the frames chose, each sample as a signed little-endian integer of 2 bytes (16 bits) or 3
+ * bytes (24 bits). An empty stream has the digest of the empty message, d41d8cd98f00b204e9800998ecf8427e. It is 32-bit integer
+ * arithmetic throughout: the digest is a function of the samples only, never of how the sequence was cut into feeds. A whole
+ * block is a multiple of 64 bytes, so the running state of four words per row is all that is carried between feeds; a finish
+ * hashes the short block, if there is one, and the padding, and leaves the 16 bytes, which sauAmd_Flac_md5 fetches.
+ * sauAmd_flac_md5 restates it on the host, and sauAmd_flac_header_md5 writes the header with the field filled in.
+ *
  * The worst case of a feed is that bound summed over the blocks it completes. Unread output lives on the device: a feed whose
  * worst case would bring the unread total above 1 GiB is refused; read first. (Until a read has fetched the frames' sizes, a
  * feed counts in that total with its worst case.) */
@@ -764,6 +775,24 @@ SAU_AMD_API size_t sauAmd_flac_encode_block_s32(const int32_t *x, uint32_t n, in
 /* The quantiser on the host: out[i] = what a float-fed encoder of `bits` makes of x[i] with `gain`. False for bits other than 16
  * or 24, or a NULL pointer with n > 0. */
 SAU_AMD_API bool sauAmd_flac_quantize(const float *x, size_t n, float gain, int bits, int32_t *out);
+/* MD5 (the text's "MD5"). sauAmd_Flac_set_md5: on != 0 turns an encoder's MD5 on, 0 off; allowed only while every stream stands
+ * at its start -- nothing fed since creation or since the last read with reset --, otherwise false with "bad argument" and
+ * nothing changed. The setting outlives resets, which put the running states back to MD5's initial value. sauAmd_Flac_md5: waits
+ * for the batch's stream; out[n_rows][16] the rows' digests when MD5 is on and a finish has closed the rows (before a read with
+ * reset), otherwise false with "bad argument" and nothing written. */
+SAU_AMD_API bool sauAmd_Flac_set_md5(sauAmdFlac *e, int on);
+SAU_AMD_API bool sauAmd_Flac_md5(sauAmdFlac *e, uint8_t *out /* [n_rows][16] */);
+/* sauAmd_flac_header_bits's bytes with bytes 26 .. 41, the MD5 field, replaced by md5[16] (NULL: zeros). */
+SAU_AMD_API size_t sauAmd_flac_header_md5(uint32_t srate, int channels, uint32_t block_frames, int bits, const sauAmdFlacInfo *info,
+		const uint8_t md5[16], uint8_t *out, size_t cap);
+/* The host restatement: the digest of n_samples interleaved samples of `bits` per sample. False for bits other than 16 or 24, a
+ * sample that does not fit `bits`, or a NULL pointer (x with n_samples > 0, or out). */
+SAU_AMD_API bool sauAmd_flac_md5(const int32_t *x, size_t n_samples, int bits, uint8_t out[16]);
+/* The FLAC file writers' process-wide default (atomic; initially 0): returns the previous value. Every sauAmd_render_file_flac*
+ * writer reads it once at entry. On, the writer turns its encoder's MD5 on, fetches the digest behind the last read and writes
+ * it into the header it rewrites at the end; every other byte of the file is the same. A backend whose encoder has no MD5 then
+ * gives "bad argument" before any file is created. Off, a writer does what it does without this switch. */
+SAU_AMD_API int sauAmd_set_flac_file_md5(int on);
 /* A float-fed encoder: sauAmd_Batch_create_flac_lpc's rules, and bits 16 or 24; 24 with max_lpc_order > 0 is a bad argument. */
 SAU_AMD_API sauAmdFlac *sauAmd_Batch_create_flac_f32(sauAmdBatch *b, size_t n_rows, int channels, uint32_t block_frames, int bits,
 		uint32_t max_lpc_order);

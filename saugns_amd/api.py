@@ -375,6 +375,18 @@ def _declare(L):
         L.sauAmd_render_file_flac_lpc.restype = C.c_bool
         L.sauAmd_render_file_flac_lpc.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_int, C.c_uint32, C.c_uint32,
                                                   C.POINTER(C.c_uint64), C.POINTER(FlacInfo)]
+    if hasattr(L, "sauAmd_Flac_set_md5"):  # the encoder's MD5 (SAU_AMD_LIB may name an older build)
+        L.sauAmd_Flac_set_md5.restype = C.c_bool
+        L.sauAmd_Flac_set_md5.argtypes = [C.c_void_p, C.c_int]
+        L.sauAmd_Flac_md5.restype = C.c_bool
+        L.sauAmd_Flac_md5.argtypes = [C.c_void_p, C.c_void_p]
+        L.sauAmd_flac_header_md5.restype = C.c_size_t
+        L.sauAmd_flac_header_md5.argtypes = [C.c_uint32, C.c_int, C.c_uint32, C.c_int, C.POINTER(FlacInfo), C.c_void_p, C.c_void_p,
+                                             C.c_size_t]
+        L.sauAmd_flac_md5.restype = C.c_bool
+        L.sauAmd_flac_md5.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+        L.sauAmd_set_flac_file_md5.restype = C.c_int
+        L.sauAmd_set_flac_file_md5.argtypes = [C.c_int]
     if hasattr(L, "sauAmd_Batch_create_flac_f32"):  # 24 bits and float-fed encoders (SAU_AMD_LIB may name an older build)
         L.sauAmd_flac_header_bits.restype = C.c_size_t
         L.sauAmd_flac_header_bits.argtypes = [C.c_uint32, C.c_int, C.c_uint32, C.c_int, C.POINTER(FlacInfo), C.c_void_p, C.c_size_t]
@@ -755,19 +767,39 @@ def use_flac_hooks(path):
     return _flac_hooks
 
 
-def flac_header(srate, channels, block_frames, info=None, bits=None):
+def flac_header(srate, channels, block_frames, info=None, bits=None, md5=None):
     """sauAmd_flac_header, or with ``bits`` (16 or 24) sauAmd_flac_header_bits: the 42 bytes ahead of the frames ("fLaC", the
     metadata block header, STREAMINFO) for a record (a FlacInfo, a dict of its fields, or None: an empty one); b"" for arguments
-    that are refused."""
+    that are refused. With ``md5`` (16 bytes) sauAmd_flac_header_md5: the same with the MD5 field filled in (bits None: 16)."""
     if isinstance(info, dict):
         info = FlacInfo(**info)
     out = (C.c_uint8 * 42)()
     ref = C.byref(info) if info is not None else None
-    if bits is None:
+    if md5 is not None:
+        md5 = bytes(md5)
+        if len(md5) != 16:
+            raise ValueError("an MD5 digest is 16 bytes")
+        n = lib().sauAmd_flac_header_md5(srate, channels, block_frames, 16 if bits is None else int(bits), ref, md5, out, 42)
+    elif bits is None:
         n = lib().sauAmd_flac_header(srate, channels, block_frames, ref, out, 42)
     else:
         n = lib().sauAmd_flac_header_bits(srate, channels, block_frames, int(bits), ref, out, 42)
     return bytes(out) if n == 42 else b""
+
+
+def flac_md5(samples, bits):
+    """sauAmd_flac_md5: the MD5 of the interleaved samples as an encoder of ``bits`` (16 or 24) per sample with MD5 on makes it
+    -> 16 bytes (None when the library refuses the bits or a sample that does not fit them)"""
+    x = np.ascontiguousarray(samples, np.int32).reshape(-1)
+    out = (C.c_uint8 * 16)()
+    ok = lib().sauAmd_flac_md5(x.ctypes.data if x.size else None, x.size, int(bits), out)
+    return bytes(out) if ok else None
+
+
+def set_flac_file_md5(on):
+    """sauAmd_set_flac_file_md5: the process-wide switch that makes the FLAC file writers fill STREAMINFO's MD5 field
+    -> the previous value"""
+    return int(lib().sauAmd_set_flac_file_md5(1 if on else 0))
 
 
 def flac_quantize(x, gain=1.0, bits=24):
@@ -1499,6 +1531,20 @@ class Flac:
         g = None if gains is None else (C.c_float * self.n_rows)(*[float(v) for v in gains])
         if not _used(self._L).sauAmd_Flac_feed_f32(self._e, ptr, pitch, fr, g, 1 if finish else 0):
             raise RuntimeError("sauAmd_Flac_feed_f32 failed: " + last_error(self._L))
+
+    def set_md5(self, on=True):
+        """sauAmd_Flac_set_md5: keep the MD5 of every row's unencoded samples; only while every stream stands at its start"""
+        if not _used(self._L).sauAmd_Flac_set_md5(self._e, 1 if on else 0):
+            raise RuntimeError("sauAmd_Flac_set_md5 failed: " + last_error(self._L))
+
+    def md5(self):
+        """sauAmd_Flac_md5 -> the rows' digests as a list of 16-byte objects; behind a finish, with MD5 on"""
+        out = np.full(16 * self.n_rows + 8, 0xa5, np.uint8)
+        if not _used(self._L).sauAmd_Flac_md5(self._e, out.ctypes.data):
+            assert (out == 0xa5).all(), "a refused md5() has written"
+            raise RuntimeError("sauAmd_Flac_md5 failed: " + last_error(self._L))
+        assert (out[16 * self.n_rows:] == 0xa5).all(), "a store behind the digests"
+        return [bytes(out[16 * r:16 * r + 16]) for r in range(self.n_rows)]
 
     def unread(self):
         """sauAmd_Flac_read without buffers -> (the unread bytes per row as a list, the rows' FlacInfo as dicts)"""

@@ -769,6 +769,37 @@ extern "C" bool sauAmd_Flac_read(sauAmdFlac *e, uint8_t *const *bufs, const size
 	return false;
 }
 
+/* ---- MD5 of the unencoded samples (include/saugns_amd.h, FLAC, "MD5"; sauAmd_set_flac_file_md5 stands with the writers) ---- */
+extern "C" bool sauAmd_Flac_set_md5(sauAmdFlac *e, int on) {
+	std::string err;
+	try {
+		if (!e) err = "bad argument";
+		else if (e->enc->set_md5(on != 0, err)) return true;
+	} catch (const std::exception &ex) {
+		err = std::string("internal error: ") + ex.what();
+	}
+	report("flac", err);
+	return false;
+}
+extern "C" bool sauAmd_Flac_md5(sauAmdFlac *e, uint8_t *out) {
+	std::string err;
+	try {
+		if (!e || !out) err = "bad argument";
+		else if (e->enc->md5(out, err)) return true;
+	} catch (const std::exception &ex) {
+		err = std::string("internal error: ") + ex.what();
+	}
+	report("flac", err);
+	return false;
+}
+extern "C" size_t sauAmd_flac_header_md5(uint32_t srate, int channels, uint32_t block_frames, int bits, const sauAmdFlacInfo *info,
+		const uint8_t md5[16], uint8_t *out, size_t cap) {
+	return sauengine::flac_header_md5(srate, channels, block_frames, bits, (const sauengine::FlacInfo *)info, md5, out, cap);
+}
+extern "C" bool sauAmd_flac_md5(const int32_t *x, size_t n_samples, int bits, uint8_t out[16]) {
+	return sauengine::flac_md5(x, n_samples, bits, out);
+}
+
 /* ---- the quantiser (include/saugns_amd.h, section "Dither and noise shaping") ---- */
 struct sauAmdQuantizer {
 	sauengine::Quantizer *q;

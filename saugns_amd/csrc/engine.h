@@ -135,6 +135,12 @@ size_t flac_header_bits(uint32_t srate, int channels, uint32_t block_frames, int
 size_t flac_encode_block_s32(const int32_t *x, uint32_t n, int channels, uint32_t block_frames, uint32_t frame_number, int bits,
 		uint32_t max_lpc_order, uint8_t *out, size_t cap);
 bool flac_quantize(const float *x, size_t n, float gain, int bits, int32_t *out);
+/* MD5 (the header's "MD5"; the arithmetic is sau_md5.h's). flac_header_md5: flac_header_bits with STREAMINFO's MD5 field, bytes
+ * 26 .. 41, taken from md5 (NULL: zeros). flac_md5: the digest of n interleaved samples of `bits` (16 or 24) per sample as the
+ * device makes it; false for other bits, a sample that does not fit them or a NULL pointer with n > 0. */
+size_t flac_header_md5(uint32_t srate, int channels, uint32_t block_frames, int bits, const FlacInfo *info, const uint8_t md5[16],
+		uint8_t *out, size_t cap);
+bool flac_md5(const int32_t *x, size_t n, int bits, uint8_t out[16]);
 inline bool flac_params_ok(int channels, uint32_t block_frames) {
 	return (channels == 1 || channels == 2) && sauflac::flac_block_frames(block_frames) != 0;
 }
@@ -157,6 +163,12 @@ public:
 	/* wait for the stream; bytes_out[n_rows] the unread bytes; bufs (may be NULL): they are copied there and consumed, every
 	 * caps[r] has to suffice; info_out (may be NULL) [n_rows]; `reset`: new streams behind the read */
 	virtual bool read(uint8_t *const *bufs, const size_t *caps, size_t *bytes_out, FlacInfo *info_out, bool reset, std::string &err) = 0;
+	/* the MD5 of the unencoded samples (the header's "MD5"), off until asked for. set_md5: only while every stream stands at its
+	 * start -- nothing fed since creation or since the last read with reset --, else a bad argument; the setting outlives resets.
+	 * md5: waits for the stream; out[n_rows][16] the digests when MD5 is on and a finish has closed the rows, else false with a
+	 * bad argument and nothing written. */
+	virtual bool set_md5(bool on, std::string &err) { (void)on; err = "bad argument: this backend's FLAC encoder has no MD5"; return false; }
+	virtual bool md5(uint8_t *out, std::string &err) { (void)out; err = "bad argument: this backend's FLAC encoder has no MD5"; return false; }
 };
 
 /* The 16-bit quantiser on the host (tables.cpp; include/saugns_amd.h, section "Dither and noise shaping"; the arithmetic is

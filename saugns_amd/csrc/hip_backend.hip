@@ -17,6 +17,7 @@
  *   k_flac.h        flac_analyze_kernel, flac_scan_kernel, flac_write_kernel, flac_carry_kernel (FLAC frames of fed int16 rows;
  *                   the <true> builds of the first and the third hold the LPC mode), flac_quant_kernel (a float-fed encoder's
  *                   rows), flac_analyze_wide_kernel, flac_write_wide_kernel, flac_carry_wide_kernel (24 bits: int32 samples)
+ *   k_md5.h         flac_md5_kernel, flac_md5_wide_kernel (the MD5 of an encoder's unencoded samples, a wave per row; opt-in)
  *   k_dither.h      dither_flat_kernel, dither_shape_kernel (the 16-bit quantiser stage: TPDF dither, error-feedback noise shaping)
  *   launch_plan.h   (plain C++, no HIP) the tuning switches and every decision about a segment's launches: rows per pass, LDS
  *                   budgets, builds, grids, tasks, chain chunks, the mixer -- a plan per segment, testable without a GPU
@@ -49,6 +50,7 @@
 #include "hip_backend.h"
 #include "launch_plan.h"
 #include "sau_dev_ops.h"
+#include "sau_md5.h"
 #include <float.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -86,6 +88,7 @@ using namespace sauplan;
 #include "k_limiter.h"
 #include "k_spectrum.h"
 #include "k_flac.h"
+#include "k_md5.h"
 #include "k_dither.h"
 static_assert(MISC_BYTES == sizeof(Misc), "launch_plan.h plans the block loop's LDS with this size");
 
@@ -2229,9 +2232,31 @@ public:
 		bool clear(std::string &err) {
 			if (!be_->join_mixer("flac_clear", err)) return false;
 			HIP_OK(hipMemsetAsync(stats_.p, 0, n_ * sizeof(FlacStats), be_->stream_));
+			if (md5_on_ && !md5_reset(err)) return false;
 			std::fill(pos_.begin(), pos_.end(), 0);
 			std::fill(blocks_.begin(), blocks_.end(), 0);
 			closed_ = false;
+			return true;
+		}
+		/* MD5 (k_md5.h): a running state of four words and a digest per row, and the row's byte count for a finish */
+		bool set_md5(bool on, std::string &err) override {
+			be_->use_device();
+			if (closed_) { err = "bad argument: the streams are not at their start (read with reset first)"; return false; }
+			for (size_t r = 0; r < n_; ++r)
+				if (pos_[r]) { err = "bad argument: the streams are not at their start (read with reset first)"; return false; }
+			if (on) {
+				if (!md5_state_.ensure(4 * n_, err) || !md5_digest_.ensure(4 * n_, err) || !md5_desc_.ensure(n_, err)) return false;
+				if (!be_->join_mixer("flac_set_md5", err) || !md5_reset(err)) return false;
+			}
+			md5_on_ = on;
+			return true;
+		}
+		bool md5(uint8_t *out, std::string &err) override {
+			be_->use_device();
+			if (!md5_on_ || !closed_ || !out) { err = !out ? "bad argument" : !md5_on_ ? "bad argument: MD5 is off (set_md5)" : "bad argument: the streams are not finished"; return false; }
+			if (!be_->join_mixer("flac_md5", err)) return false;
+			HIP_OK(hipStreamSynchronize(be_->stream_));
+			HIP_OK(hipMemcpy(out, md5_digest_.p, 16 * n_, hipMemcpyDeviceToHost));
 			return true;
 		}
 		bool feed(const void *rows, size_t pitch, const uint32_t *frames, bool finish, std::string &err) override {
@@ -2281,6 +2306,12 @@ public:
 			const size_t q_pitch = ((size_t)longest * ch_ * (wide ? sizeof(int32_t) : sizeof(int16_t)) + 255) & ~(size_t)255;
 			if (f32_ && longest && !qrows_.ensure(n_ * q_pitch, err)) return false;
 			if (!be_->send(desc_.p, d.data(), n_ * sizeof(FlacRow), err)) return false;
+			const bool md5_now = md5_on_ && (plan.jobs || finish); /* (a finish that completes no block still pads) */
+			if (md5_now) {
+				std::vector<FlacMd5Row> m(n_);
+				for (size_t r = 0; r < n_; ++r) m[r].total = (pos_[r] + frames[r]) * ch_ * (wide ? 3 : 2);
+				if (!be_->send(md5_desc_.p, m.data(), n_ * sizeof(FlacMd5Row), err)) return false;
+			}
 			hipStream_t st = be_->stream_;
 			if (f32_ && longest) {
 				std::vector<FlacQuantRow> q(n_);
@@ -2301,6 +2332,11 @@ public:
 			fp.pend = pend_[cur_].p; fp.pend_next = pend_[cur_ ^ 1].p; fp.pend_pitch = plan.pend_pitch;
 			fp.frames = frames_.p; fp.stats = stats_.p;
 			fp.B = B_; fp.channels = ch_; fp.n_rows = (uint32_t)n_; fp.jobs = plan.jobs; fp.max_lpc = M_;
+			FlacMd5Params mp; /* (reads what the analysis reads: the rows at hand and the pending frames ahead of the carry) */
+			memset((void *)&mp, 0, sizeof mp);
+			mp.rows = rows; mp.row_pitch = pitch; mp.desc = desc_.p; mp.pend = pend_[cur_].p; mp.pend_pitch = plan.pend_pitch;
+			mp.md5 = md5_desc_.p; mp.state = md5_state_.p; mp.digest = md5_digest_.p;
+			mp.B = B_; mp.channels = ch_; mp.n_rows = (uint32_t)n_; mp.finish = finish ? 1 : 0;
 			if (wide) { /* the sibling kernels of int32 samples; flac_scan_kernel is the same */
 				FlacWideParams wp;
 				memset((void *)&wp, 0, sizeof wp);
@@ -2315,6 +2351,10 @@ public:
 					hipLaunchKernelGGL(flac_scan_kernel, dim3(plan.rows), dim3(FLAC_THREADS), 0, st, fp);
 					HIP_OK(hipGetLastError());
 					hipLaunchKernelGGL(flac_write_wide_kernel, dim3(plan.jobs), dim3(FLAC_THREADS), plan.write_lds, st, wp);
+					HIP_OK(hipGetLastError());
+				}
+				if (md5_now) {
+					hipLaunchKernelGGL(flac_md5_wide_kernel, dim3(plan.rows), dim3(64), 0, st, mp);
 					HIP_OK(hipGetLastError());
 				}
 				if (!finish) {
@@ -2333,6 +2373,10 @@ public:
 				HIP_OK(hipGetLastError());
 				if (M_) hipLaunchKernelGGL(flac_write_kernel<true>, dim3(plan.jobs), dim3(FLAC_THREADS), plan.write_lds, st, fp);
 				else hipLaunchKernelGGL(flac_write_kernel<false>, dim3(plan.jobs), dim3(FLAC_THREADS), plan.write_lds, st, fp);
+				HIP_OK(hipGetLastError());
+			}
+			if (md5_now) {
+				hipLaunchKernelGGL(flac_md5_kernel, dim3(plan.rows), dim3(64), 0, st, mp);
 				HIP_OK(hipGetLastError());
 			}
 			if (!finish) { /* (behind a finish nothing is pending) */
@@ -2395,6 +2439,12 @@ public:
 			return true;
 		}
 	private:
+		/* every row's running state back to MD5's initial value, on the stream */
+		bool md5_reset(std::string &err) {
+			std::vector<uint32_t> s(4 * n_);
+			for (size_t r = 0; r < n_; ++r) saumd5::md5_init(&s[4 * r]);
+			return be_->send(md5_state_.p, s.data(), s.size() * sizeof(uint32_t), err);
+		}
 		struct Chunk { /* one feed's output */
 			DevBuf<uint8_t> out;
 			DevBuf<uint32_t> row_bytes;  /* [rows]: flac_scan_kernel's word on them */
@@ -2416,6 +2466,9 @@ public:
 		DevBuf<FlacFrameDesc> frames_;
 		DevBuf<unsigned char> qrows_;        /* a float-fed encoder's quantised rows of the feed at hand */
 		DevBuf<FlacQuantRow> qdesc_;
+		bool md5_on_ = false;                /* set_md5: flac_md5_kernel runs behind the write kernel */
+		DevBuf<uint32_t> md5_state_, md5_digest_; /* [rows][4] each */
+		DevBuf<FlacMd5Row> md5_desc_;
 		int cur_ = 0;
 	};
 	sauengine::FlacEncoder *create_flac(size_t n_rows, uint32_t channels, uint32_t block_frames, std::string &err) override {

@@ -19,6 +19,7 @@
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
+#include <atomic>
 #include <exception>
 #include <string>
 
@@ -503,6 +504,12 @@ bool measure_spectrum(const sauProgram *prg, uint32_t srate, int factor, int cha
 	return ok;
 }
 
+/* The FLAC file writers' process-wide MD5 switch (include/saugns_amd.h, FLAC, "MD5"): every writer below reads it once, where it
+ * begins. On: the writer turns its encoder's MD5 on -- a backend whose encoder has none refuses there, before there is a file
+ * --, fetches the digest behind the last read and puts it into the header it rewrites at the end. Off: nothing differs. */
+static std::atomic<int> g_flac_file_md5{0};
+static bool flac_file_md5() { return g_flac_file_md5.load(std::memory_order_relaxed) != 0; }
+
 /* The FLAC writer: render_file_over's int16 runs (no byte swap) on the same lattice, each run's device row fed to an encoder
  * of one stream where that writer fetches it, the last feed a finish. A read brings the run's frames into a page-locked slot;
  * the slot before it goes to the file once the next run has been queued, so the file is written while the device renders.
@@ -519,13 +526,15 @@ bool write_flac(const sauProgram *prg, uint32_t srate, const char *path, int cha
 	/* a backend without an encoder says so here, before there is a file */
 	sauengine::FlacEncoder *enc = backend->create_flac_lpc(1, (uint32_t)channels, B, max_lpc_order, err);
 	if (!enc) { delete engine; return false; }
+	const bool md5 = flac_file_md5();
+	if (md5 && !enc->set_md5(true, err)) { delete enc; delete engine; return false; }
 	/* what a run can come to: the blocks it completes, with what was pending, and a last short one, each at its bound */
 	const size_t slot_bytes = (chunk / B + 2) * (size_t)sauflac::flac_frame_bound(B, (uint32_t)channels);
 	uint8_t *host[2] = {(uint8_t *)backend->alloc_host(slot_bytes), (uint8_t *)backend->alloc_host(slot_bytes)};
 	FILE *f = nullptr;
 	bool ok = host[0] && host[1];
 	if (!ok) err = "out of page-locked memory";
-	uint8_t head[42];
+	uint8_t head[42], digest[16];
 	sauengine::FlacInfo info{0, 0, 0, 0, 0};
 	if (ok) {
 		f = fopen(path, "wb");
@@ -562,10 +571,11 @@ bool write_flac(const sauProgram *prg, uint32_t srate, const char *path, int cha
 		if (pending[k] && fwrite(host[k], 1, pending[k], f) != pending[k]) { err = "write failed"; ok = false; }
 		pending[k] = 0;
 	}
+	if (ok && md5) ok = enc->md5(digest, err); /* (the last feed was the finish, and nothing has reset the stream) */
 	delete enc;
 	{ std::string e2; (void)backend->sync(e2); }
 	if (f) {
-		if (ok && (sauengine::flac_header(srate, channels, B, &info, head, sizeof head) != 42 || fseek(f, 0, SEEK_SET) != 0 ||
+		if (ok && (sauengine::flac_header_md5(srate, channels, B, 16, &info, md5 ? digest : nullptr, head, sizeof head) != 42 || fseek(f, 0, SEEK_SET) != 0 ||
 		           fwrite(head, 1, 42, f) != 42)) { err = "write failed"; ok = false; }
 		const int ferr = ferror(f);
 		if ((fclose(f) != 0 || ferr) && ok) { err = "write failed"; ok = false; }
@@ -593,12 +603,14 @@ bool write_flac_scaled(const sauProgram *prg, uint32_t srate, const char *path, 
 	if (!engine->set_format(sauengine::SF_F32, err)) { delete engine; return false; }
 	sauengine::FlacEncoder *enc = backend->create_flac_f32(1, (uint32_t)channels, B, bits, max_lpc_order, err);
 	if (!enc) { delete engine; return false; }
+	const bool md5 = flac_file_md5();
+	if (md5 && !enc->set_md5(true, err)) { delete enc; delete engine; return false; }
 	const size_t slot_bytes = (chunk / B + 2) * (size_t)sauflac::flac_frame_bound_bits(B, (uint32_t)channels, (unsigned)bits);
 	uint8_t *host[2] = {(uint8_t *)backend->alloc_host(slot_bytes), (uint8_t *)backend->alloc_host(slot_bytes)};
 	FILE *f = nullptr;
 	bool ok = host[0] && host[1];
 	if (!ok) err = "out of page-locked memory";
-	uint8_t head[42];
+	uint8_t head[42], digest[16];
 	sauengine::FlacInfo info{0, 0, 0, 0, 0};
 	if (ok) {
 		f = fopen(path, "wb");
@@ -636,10 +648,11 @@ bool write_flac_scaled(const sauProgram *prg, uint32_t srate, const char *path, 
 		if (pending[k] && fwrite(host[k], 1, pending[k], f) != pending[k]) { err = "write failed"; ok = false; }
 		pending[k] = 0;
 	}
+	if (ok && md5) ok = enc->md5(digest, err); /* (the last feed was the finish, and nothing has reset the stream) */
 	delete enc;
 	{ std::string e2; (void)backend->sync(e2); }
 	if (f) {
-		if (ok && (sauengine::flac_header_bits(srate, channels, B, bits, &info, head, sizeof head) != 42 || fseek(f, 0, SEEK_SET) != 0 ||
+		if (ok && (sauengine::flac_header_md5(srate, channels, B, bits, &info, md5 ? digest : nullptr, head, sizeof head) != 42 || fseek(f, 0, SEEK_SET) != 0 ||
 		           fwrite(head, 1, 42, f) != 42)) { err = "write failed"; ok = false; }
 		const int ferr = ferror(f);
 		if ((fclose(f) != 0 || ferr) && ok) { err = "write failed"; ok = false; }
@@ -670,13 +683,15 @@ bool write_flac_limited(const sauProgram *prg, uint32_t srate, const char *path,
 	if (!engine->set_format(sauengine::SF_F32, err) || !engine->begin_limited(pre_gain, ceiling, stereo, err)) { delete engine; return false; }
 	sauengine::FlacEncoder *enc = backend->create_flac_f32(1, (uint32_t)channels, B, bits, max_lpc_order, err);
 	if (!enc) { delete engine; return false; }
+	const bool md5 = flac_file_md5();
+	if (md5 && !enc->set_md5(true, err)) { delete enc; delete engine; return false; }
 	const size_t slot_frames = chunk > D ? chunk : D;
 	const size_t slot_bytes = (slot_frames / B + 2) * (size_t)sauflac::flac_frame_bound_bits(B, (uint32_t)channels, (unsigned)bits);
 	uint8_t *host[2] = {(uint8_t *)backend->alloc_host(slot_bytes), (uint8_t *)backend->alloc_host(slot_bytes)};
 	FILE *f = nullptr;
 	bool ok = host[0] && host[1];
 	if (!ok) err = "out of page-locked memory";
-	uint8_t head[42];
+	uint8_t head[42], digest[16];
 	sauengine::FlacInfo info{0, 0, 0, 0, 0};
 	if (ok) {
 		f = fopen(path, "wb");
@@ -722,10 +737,11 @@ bool write_flac_limited(const sauProgram *prg, uint32_t srate, const char *path,
 		pending[k] = 0;
 	}
 	if (ok && stats_out) ok = engine->limiter_stats(stats_out, false, err);
+	if (ok && md5) ok = enc->md5(digest, err); /* (the last feed was the finish, and nothing has reset the stream) */
 	delete enc;
 	{ std::string e2; (void)backend->sync(e2); }
 	if (f) {
-		if (ok && (sauengine::flac_header_bits(srate, channels, B, bits, &info, head, sizeof head) != 42 || fseek(f, 0, SEEK_SET) != 0 ||
+		if (ok && (sauengine::flac_header_md5(srate, channels, B, bits, &info, md5 ? digest : nullptr, head, sizeof head) != 42 || fseek(f, 0, SEEK_SET) != 0 ||
 		           fwrite(head, 1, 42, f) != 42)) { err = "write failed"; ok = false; }
 		const int ferr = ferror(f);
 		if ((fclose(f) != 0 || ferr) && ok) { err = "write failed"; ok = false; }
@@ -831,12 +847,14 @@ bool write_flac_dithered(const sauProgram *prg, uint32_t srate, const char *path
 	if (!q) { delete engine; return false; }
 	sauengine::FlacEncoder *enc = backend->create_flac_lpc(1, (uint32_t)channels, B, max_lpc_order, err);
 	if (!enc) { delete q; delete engine; return false; }
+	const bool md5 = flac_file_md5();
+	if (md5 && !enc->set_md5(true, err)) { delete enc; delete q; delete engine; return false; }
 	const size_t slot_bytes = (chunk / B + 2) * (size_t)sauflac::flac_frame_bound(B, (uint32_t)channels);
 	uint8_t *host[2] = {(uint8_t *)backend->alloc_host(slot_bytes), (uint8_t *)backend->alloc_host(slot_bytes)};
 	FILE *f = nullptr;
 	bool ok = host[0] && host[1];
 	if (!ok) err = "out of page-locked memory";
-	uint8_t head[42];
+	uint8_t head[42], digest[16];
 	sauengine::FlacInfo info{0, 0, 0, 0, 0};
 	if (ok) {
 		f = fopen(path, "wb");
@@ -879,11 +897,12 @@ bool write_flac_dithered(const sauProgram *prg, uint32_t srate, const char *path
 	}
 	sauengine::DitherStats st{0, {0, 0}};
 	if (ok) ok = q->stats(&st, false, err);
+	if (ok && md5) ok = enc->md5(digest, err); /* (the last feed was the finish, and nothing has reset the stream) */
 	delete enc;
 	delete q;
 	{ std::string e2; (void)backend->sync(e2); }
 	if (f) {
-		if (ok && (sauengine::flac_header(srate, channels, B, &info, head, sizeof head) != 42 || fseek(f, 0, SEEK_SET) != 0 ||
+		if (ok && (sauengine::flac_header_md5(srate, channels, B, 16, &info, md5 ? digest : nullptr, head, sizeof head) != 42 || fseek(f, 0, SEEK_SET) != 0 ||
 		           fwrite(head, 1, 42, f) != 42)) { err = "write failed"; ok = false; }
 		const int ferr = ferror(f);
 		if ((fclose(f) != 0 || ferr) && ok) { err = "write failed"; ok = false; }
@@ -909,6 +928,8 @@ bool flac_f32_params_ok(int channels, uint32_t block_frames, int bits, uint32_t 
 }
 
 } /* namespace */
+
+extern "C" int sauAmd_set_flac_file_md5(int on) { return g_flac_file_md5.exchange(on ? 1 : 0, std::memory_order_relaxed); }
 
 bool sauamd_internal::render_file_flac_f32(const sauProgram *prg, uint32_t srate, const char *path, int channels, uint32_t block_frames,
 		int bits, uint32_t max_lpc_order, float gain, const std::function<Backend *(std::string &)> &make_backend, uint64_t *frames_out,

@@ -13,6 +13,7 @@
  *   3. the strict-order builder below.
  */
 #include "engine.h"
+#include "sau_md5.h"
 #include <dlfcn.h>
 #include <float.h>
 #include <math.h>
@@ -582,6 +583,33 @@ bool flac_quantize(const float *x, size_t n, float gain, int bits, int32_t *out)
 		const float y = x[i] * gain; /* one f32 multiply, as flac_quant_kernel's */
 		out[i] = bits == 24 ? saudev::pcm24(y) : (int32_t)saudev::pcm16(y);
 	}
+	return true;
+}
+
+/* ---- MD5 (include/saugns_amd.h, FLAC, "MD5"): what flac_md5_kernel makes of a stream's samples, with sau_md5.h's steps ---- */
+size_t flac_header_md5(uint32_t srate, int channels, uint32_t block_frames, int bits, const FlacInfo *info, const uint8_t md5[16],
+		uint8_t *out, size_t cap) {
+	const size_t got = flac_header_bits(srate, channels, block_frames, bits, info, out, cap);
+	if (got == 42 && out && cap >= 42 && md5) memcpy(out + 26, md5, 16);
+	return got;
+}
+
+bool flac_md5(const int32_t *x, size_t n, int bits, uint8_t out[16]) {
+	using namespace saumd5;
+	if (!sauflac::flac_bits_ok(bits) || !out || (n && !x)) return false;
+	const int32_t lo = bits == 24 ? -(1 << 23) : -32768, hi = bits == 24 ? (1 << 23) - 1 : 32767;
+	for (size_t i = 0; i < n; ++i)
+		if (x[i] < lo || x[i] > hi) return false;
+	const auto at = [x](unsigned long long i) -> int32_t { return x[i]; };
+	const unsigned long long total = (unsigned long long)n * (bits == 24 ? 3 : 2), whole = total / 64;
+	uint32_t s[4], w[16];
+	md5_init(s);
+	for (unsigned long long c = 0; c <= whole; ++c) { /* the last round: what is left, and the padding */
+		for (unsigned k = 0; k < 16; ++k) w[k] = bits == 24 ? md5_word24(at, 16 * c + k, n) : md5_word16(at, 16 * c + k, n);
+		if (c < whole) md5_chunk(s, w);
+		else md5_finish(s, w, total);
+	}
+	md5_digest(s, out);
 	return true;
 }
 
