@@ -14,9 +14,9 @@
  *   k_loudness.h    loud_chunk_kernel, loud_scan_kernel, truepeak_kernel, loud_finish_kernel, loud_carry_kernel (BS.1770 loudness, true peak)
  *   k_limiter.h     lim_env_kernel, lim_gain_kernel, lim_finish_kernel, lim_carry_kernel (the look-ahead true-peak limiter)
  *   k_spectrum.h    spec_segment_kernel, spec_finish_kernel, spec_carry_kernel (Welch power spectra of fed rows)
- *   k_flac.h        flac_analyze_kernel, flac_scan_kernel, flac_write_kernel, flac_carry_kernel (FLAC frames of fed int16 rows;
- *                   the <true> builds of the first and the third hold the LPC mode), flac_quant_kernel (a float-fed encoder's
- *                   rows), flac_analyze_wide_kernel, flac_write_wide_kernel, flac_carry_wide_kernel (24 bits: int32 samples)
+ *   k_flac.h        flac_analyze_kernel, flac_scan_kernel, flac_write_kernel, flac_carry_kernel (FLAC frames of fed rows, built
+ *                   for int16 and for int32 samples: FlacS16, FlacS32; the <FlacS16, true> builds of the first and the third
+ *                   hold the LPC mode), flac_quant_kernel (a float-fed encoder's rows)
  *   k_md5.h         flac_md5_kernel, flac_md5_wide_kernel (the MD5 of an encoder's unencoded samples, a wave per row; opt-in)
  *   k_dither.h      dither_flat_kernel, dither_shape_kernel (the 16-bit quantiser stage: TPDF dither, error-feedback noise shaping)
  *   launch_plan.h   (plain C++, no HIP) the tuning switches and every decision about a segment's launches: rows per pass, LDS
@@ -2328,63 +2328,43 @@ public:
 			}
 			FlacParams fp;
 			memset((void *)&fp, 0, sizeof fp);
-			fp.rows = (const int16_t *)rows; fp.row_pitch = pitch; fp.desc = desc_.p;
+			fp.rows = rows; fp.row_pitch = pitch; fp.desc = desc_.p;
 			fp.pend = pend_[cur_].p; fp.pend_next = pend_[cur_ ^ 1].p; fp.pend_pitch = plan.pend_pitch;
 			fp.frames = frames_.p; fp.stats = stats_.p;
 			fp.B = B_; fp.channels = ch_; fp.n_rows = (uint32_t)n_; fp.jobs = plan.jobs; fp.max_lpc = M_;
+			if (plan.jobs) { fp.out = c->out.p; fp.row_bytes = c->row_bytes.p; }
 			FlacMd5Params mp; /* (reads what the analysis reads: the rows at hand and the pending frames ahead of the carry) */
 			memset((void *)&mp, 0, sizeof mp);
 			mp.rows = rows; mp.row_pitch = pitch; mp.desc = desc_.p; mp.pend = pend_[cur_].p; mp.pend_pitch = plan.pend_pitch;
 			mp.md5 = md5_desc_.p; mp.state = md5_state_.p; mp.digest = md5_digest_.p;
 			mp.B = B_; mp.channels = ch_; mp.n_rows = (uint32_t)n_; mp.finish = finish ? 1 : 0;
-			if (wide) { /* the sibling kernels of int32 samples; flac_scan_kernel is the same */
-				FlacWideParams wp;
-				memset((void *)&wp, 0, sizeof wp);
-				wp.rows = (const int32_t *)rows; wp.row_pitch = pitch; wp.desc = desc_.p;
-				wp.pend = (const int32_t *)pend_[cur_].p; wp.pend_next = (int32_t *)pend_[cur_ ^ 1].p; wp.pend_pitch = plan.pend_pitch;
-				wp.frames = frames_.p;
-				wp.B = B_; wp.channels = ch_; wp.n_rows = (uint32_t)n_; wp.jobs = plan.jobs;
+			/* the feed's launches at one width (k_flac.h: FlacS16, FlacS32); flac_scan_kernel is the same for both */
+			auto launch = [&](auto w, auto md5_kernel) -> bool {
+				typedef decltype(w) W;
 				if (plan.jobs) {
-					wp.out = fp.out = c->out.p; fp.row_bytes = c->row_bytes.p;
-					hipLaunchKernelGGL(flac_analyze_wide_kernel, dim3(plan.jobs), dim3(plan.analyze_threads), plan.analyze_lds, st, wp);
+					/* (max_lpc_order 0 runs the kernels without the LPC mode's code: the encoder as it was before that mode) */
+					auto analyze = flac_analyze_kernel<W, false>, write = flac_write_kernel<W, false>;
+					if constexpr (W::BITS == 16)
+						if (M_) { analyze = flac_analyze_kernel<W, true>; write = flac_write_kernel<W, true>; }
+					hipLaunchKernelGGL(analyze, dim3(plan.jobs), dim3(plan.analyze_threads), plan.analyze_lds, st, fp);
 					HIP_OK(hipGetLastError());
 					hipLaunchKernelGGL(flac_scan_kernel, dim3(plan.rows), dim3(FLAC_THREADS), 0, st, fp);
 					HIP_OK(hipGetLastError());
-					hipLaunchKernelGGL(flac_write_wide_kernel, dim3(plan.jobs), dim3(FLAC_THREADS), plan.write_lds, st, wp);
+					hipLaunchKernelGGL(write, dim3(plan.jobs), dim3(FLAC_THREADS), plan.write_lds, st, fp);
 					HIP_OK(hipGetLastError());
 				}
 				if (md5_now) {
-					hipLaunchKernelGGL(flac_md5_wide_kernel, dim3(plan.rows), dim3(64), 0, st, mp);
+					hipLaunchKernelGGL(md5_kernel, dim3(plan.rows), dim3(64), 0, st, mp);
 					HIP_OK(hipGetLastError());
 				}
-				if (!finish) {
-					hipLaunchKernelGGL(flac_carry_wide_kernel, dim3((uint32_t)((plan.pend_pitch + FLAC_THREADS - 1) / FLAC_THREADS), plan.rows), dim3(FLAC_THREADS), 0, st, wp);
+				if (!finish) { /* (behind a finish nothing is pending) */
+					hipLaunchKernelGGL(flac_carry_kernel<W>, dim3((uint32_t)((plan.pend_pitch + FLAC_THREADS - 1) / FLAC_THREADS), plan.rows), dim3(FLAC_THREADS), 0, st, fp);
 					HIP_OK(hipGetLastError());
 					cur_ ^= 1;
 				}
-			} else {
-			if (plan.jobs) {
-				fp.out = c->out.p; fp.row_bytes = c->row_bytes.p;
-				/* (max_lpc_order 0 runs the kernels without the LPC mode's code: the encoder as it was before that mode) */
-				if (M_) hipLaunchKernelGGL(flac_analyze_kernel<true>, dim3(plan.jobs), dim3(plan.analyze_threads), plan.analyze_lds, st, fp);
-				else hipLaunchKernelGGL(flac_analyze_kernel<false>, dim3(plan.jobs), dim3(plan.analyze_threads), plan.analyze_lds, st, fp);
-				HIP_OK(hipGetLastError());
-				hipLaunchKernelGGL(flac_scan_kernel, dim3(plan.rows), dim3(FLAC_THREADS), 0, st, fp);
-				HIP_OK(hipGetLastError());
-				if (M_) hipLaunchKernelGGL(flac_write_kernel<true>, dim3(plan.jobs), dim3(FLAC_THREADS), plan.write_lds, st, fp);
-				else hipLaunchKernelGGL(flac_write_kernel<false>, dim3(plan.jobs), dim3(FLAC_THREADS), plan.write_lds, st, fp);
-				HIP_OK(hipGetLastError());
-			}
-			if (md5_now) {
-				hipLaunchKernelGGL(flac_md5_kernel, dim3(plan.rows), dim3(64), 0, st, mp);
-				HIP_OK(hipGetLastError());
-			}
-			if (!finish) { /* (behind a finish nothing is pending) */
-				hipLaunchKernelGGL(flac_carry_kernel, dim3((uint32_t)((plan.pend_pitch + FLAC_THREADS - 1) / FLAC_THREADS), plan.rows), dim3(FLAC_THREADS), 0, st, fp);
-				HIP_OK(hipGetLastError());
-				cur_ ^= 1;
-			}
-			}
+				return true;
+			};
+			if (!(wide ? launch(FlacS32(), flac_md5_wide_kernel) : launch(FlacS16(), flac_md5_kernel))) return false;
 			for (size_t r = 0; r < n_; ++r) { pos_[r] += frames[r]; blocks_[r] += d[r].n_blocks; }
 			if (c) chunks_.push_back(std::move(c));
 			bound_ += plan.worst;

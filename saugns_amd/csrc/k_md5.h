@@ -28,7 +28,7 @@ struct FlacMd5Params {
 	const void *rows;         /* the rows the analysis reads: int16, or int32 for the wide kernel */
 	size_t row_pitch;         /* bytes between them */
 	const FlacRow *desc;      /* [n_rows] (launch_plan.h) */
-	const void *pend;         /* [n_rows][pend_pitch], as FlacParams::pend or FlacWideParams::pend */
+	const void *pend;         /* [n_rows][pend_pitch], as FlacParams::pend */
 	size_t pend_pitch;        /* samples */
 	const FlacMd5Row *md5;    /* [n_rows] */
 	uint32_t *state;          /* [n_rows][4] */

@@ -1023,7 +1023,7 @@ inline FlacRow plan_flac_row(uint64_t pos, uint32_t frames, uint32_t B, bool fin
 /* the worst case of a row's feed (include/saugns_amd.h, FLAC: the bound of every block it completes, summed) */
 inline uint64_t flac_row_worst(const FlacRow &r, uint32_t B, uint32_t channels, unsigned bits = 16) {
 	if (!r.n_blocks) return 0;
-	return (uint64_t)(r.n_blocks - 1) * sauflac::flac_frame_bound_bits(B, channels, bits) + sauflac::flac_frame_bound_bits(r.last_n, channels, bits);
+	return (uint64_t)(r.n_blocks - 1) * sauflac::flac_frame_bound(B, channels, bits) + sauflac::flac_frame_bound(r.last_n, channels, bits);
 }
 struct FlacPlan {
 	bool ok = false;           /* false: B or channels not allowed, no row or more than 65535, a block number beyond 2^31 - 1, a feed
@@ -1046,7 +1046,7 @@ inline FlacPlan plan_flac(uint32_t block_frames, uint32_t channels, size_t n_row
 	p.B = B; p.rows = (uint32_t)n_rows; p.channels = channels;
 	p.analyze_threads = channels == 2 ? 256 : 64;
 	p.analyze_lds = (size_t)(B + B / 32) * sizeof(uint32_t) * (bits == 24 ? channels : 1);
-	p.write_lds = p.analyze_lds + ((size_t)sauflac::flac_frame_bound_bits(B, channels, bits) / 4 + 2) * sizeof(uint32_t);
+	p.write_lds = p.analyze_lds + ((size_t)sauflac::flac_frame_bound(B, channels, bits) / 4 + 2) * sizeof(uint32_t);
 	p.pend_pitch = (size_t)B * channels;
 	uint64_t jobs = 0, out = 0;
 	for (size_t r = 0; rows && r < n_rows; ++r) {

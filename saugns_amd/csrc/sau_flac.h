@@ -20,8 +20,17 @@ namespace sauflac {
 constexpr uint32_t FLAC_MAX_ROWS = 65535;
 constexpr uint64_t FLAC_MAX_BLOCKS = 0x7fffffffull;  /* per row: the frame number's six bytes hold 31 bits */
 constexpr uint64_t FLAC_MAX_UNREAD = 1ull << 30;     /* bytes of unread output on the device */
-constexpr unsigned FLAC_K_MAX = 14, FLAC_NK = 15;    /* Rice parameters 0 .. 14; 15 is the escape, never used */
+constexpr unsigned FLAC_K_MAX = 14, FLAC_NK = 15;    /* 16 bits: Rice parameters 0 .. 14; 15 is the escape, never used */
 constexpr unsigned FLAC_FINE = 16, FLAC_NODES = 31;  /* finest partitions of a whole block; (p, partition) pairs for p = 0 .. 4 */
+/* The two sample widths (include/saugns_amd.h, FLAC, "24 bits"). 16: int16 samples, the side channel takes 17 bits, u is below
+ * 2^21, the Rice parameters are 0 .. 14 in four bits each (method 00). 24: int32 samples in -2^23 .. 2^23 - 1, the side channel
+ * takes 25 bits; a FIXED residual is at most 16 * 2^24 in size, so the residual functions below serve both; u is below 2^30, the
+ * parameters are 0 .. 30 in five bits (method 01), and everything summed over a lane's run, not only over a block, needs 64
+ * bits. The LPC mode is 16-bit only. */
+constexpr int32_t FLAC_S24_MIN = -8388608, FLAC_S24_MAX = 8388607;
+SAU_FLAC_HD bool flac_bits_ok(int bits) { return bits == 16 || bits == 24; }
+SAU_FLAC_HD constexpr unsigned flac_k_width(unsigned bits) { return bits == 24 ? 5 : 4; } /* bits of a partition's parameter */
+SAU_FLAC_HD constexpr unsigned flac_nk(unsigned bits) { return (1u << flac_k_width(bits)) - 1; } /* parameters tried: FLAC_NK or 31 */
 enum : uint8_t { FLAC_CONSTANT = 0, FLAC_VERBATIM = 1, FLAC_FIXED = 2, FLAC_LPC = 3 };
 constexpr unsigned FLAC_LPC_MAX = 8, FLAC_LPC_PREC = 12; /* max_lpc_order's largest value; bits of a quantised coefficient */
 enum : uint8_t { FLAC_CAND_L = 0, FLAC_CAND_R = 1, FLAC_CAND_M = 2, FLAC_CAND_S = 3 };
@@ -31,8 +40,8 @@ SAU_FLAC_HD uint32_t flac_block_frames(uint32_t b) {
 	if (b == 0) return 4096;
 	return (b == 256 || b == 512 || b == 1024 || b == 2048 || b == 4096) ? b : 0;
 }
-/* the most bytes a frame of n frames takes: 13 header bytes, every channel verbatim, the CRC-16 */
-SAU_FLAC_HD uint32_t flac_frame_bound(uint32_t n, uint32_t channels) { return 15 + channels * (1 + 2 * n); }
+/* the most bytes a frame of n frames takes at `bits` per sample: 13 header bytes, every channel verbatim, the CRC-16 */
+SAU_FLAC_HD uint32_t flac_frame_bound(uint32_t n, uint32_t channels, unsigned bits) { return 15 + channels * (1 + bits / 8 * n); }
 
 /* What a block's choices come to for one channel: kind, order, partition order and the partitions' Rice parameters. */
 struct FlacSub {
@@ -58,10 +67,8 @@ struct FlacFrameDesc {
 };
 static_assert(sizeof(FlacFrameDesc) == 104, "FlacFrameDesc is read by the kernels as it stands");
 
-/* a frame as one word: the left (or only) sample in the low half, the right one in the high half */
-SAU_FLAC_HD uint32_t flac_pack(int16_t l, int16_t r) { return (uint32_t)(uint16_t)l | ((uint32_t)(uint16_t)r << 16); }
-SAU_FLAC_HD int32_t flac_cand(uint32_t w, unsigned cand) {
-	const int32_t l = (int16_t)(uint16_t)(w & 0xffffu), r = (int16_t)(uint16_t)(w >> 16);
+/* a candidate channel's sample from the frame's two */
+SAU_FLAC_HD int32_t flac_cand(int32_t l, int32_t r, unsigned cand) {
 	switch (cand) {
 	case FLAC_CAND_L: return l;
 	case FLAC_CAND_R: return r;
@@ -69,7 +76,10 @@ SAU_FLAC_HD int32_t flac_cand(uint32_t w, unsigned cand) {
 	default: return l - r;
 	}
 }
-SAU_FLAC_HD unsigned flac_cand_bps(unsigned cand) { return cand == FLAC_CAND_S ? 17 : 16; }
+/* a 16-bit frame as one word: the left (or only) sample in the low half, the right one in the high half */
+SAU_FLAC_HD uint32_t flac_pack(int16_t l, int16_t r) { return (uint32_t)(uint16_t)l | ((uint32_t)(uint16_t)r << 16); }
+SAU_FLAC_HD int32_t flac_cand(uint32_t w, unsigned cand) { return flac_cand((int16_t)(uint16_t)(w & 0xffffu), (int16_t)(uint16_t)(w >> 16), cand); }
+SAU_FLAC_HD unsigned flac_cand_bps(unsigned cand, unsigned bits) { return cand == FLAC_CAND_S ? bits + 1 : bits; }
 
 /* the residuals of all five orders from s_i .. s_{i-4} */
 SAU_FLAC_HD void flac_residuals(int32_t s0, int32_t s1, int32_t s2, int32_t s3, int32_t s4, int32_t r[5]) {
@@ -101,16 +111,17 @@ SAU_FLAC_HD unsigned flac_pick_order(uint32_t n, const uint64_t abs_sum[5]) {
 	return best;
 }
 
-/* node (p, part) of a block of n frames whose finest sums are fine[f * 15 + k] = the sum of u >> k over fine partition f
- * (f < 2^fine_log2; fine_log2 = 4 for a whole block, 0 otherwise): the least cost over k, the lowest k on ties */
-SAU_FLAC_HD uint64_t flac_node_cost(const uint64_t *fine, unsigned fine_log2, unsigned p, unsigned part, uint32_t n, unsigned o, unsigned *k_out) {
+/* node (p, part) of a block of n frames whose finest sums are fine[f * nk + k] = the sum of u >> k over fine partition f
+ * (f < 2^fine_log2; fine_log2 = 4 for a whole block, 0 otherwise; nk = flac_nk(bits)): the least cost over k, the lowest k on ties */
+SAU_FLAC_HD uint64_t flac_node_cost(const uint64_t *fine, unsigned nk, unsigned fine_log2, unsigned p, unsigned part, uint32_t n, unsigned o,
+		unsigned *k_out) {
 	const unsigned span = 1u << (fine_log2 - p), first = part * span;
 	const uint64_t count = (n >> p) - (part == 0 ? o : 0);
 	uint64_t best = ~0ull;
 	unsigned bk = 0;
-	for (unsigned k = 0; k < FLAC_NK; ++k) {
+	for (unsigned k = 0; k < nk; ++k) {
 		uint64_t s = 0;
-		for (unsigned f = 0; f < span; ++f) s += fine[(first + f) * FLAC_NK + k];
+		for (unsigned f = 0; f < span; ++f) s += fine[(first + f) * nk + k];
 		const uint64_t cost = s + (1 + k) * count;
 		if (cost < best) { best = cost; bk = k; }
 	}
@@ -120,10 +131,11 @@ SAU_FLAC_HD uint64_t flac_node_cost(const uint64_t *fine, unsigned fine_log2, un
 SAU_FLAC_HD unsigned flac_node_index(unsigned p, unsigned part) { return (1u << p) - 1 + part; }
 
 /* From the nodes' costs and parameters (those of p = 0 .. fine_log2) to the channel's record: the partition order with the
- * least cost (the lowest on ties), FIXED against VERBATIM (VERBATIM on ties). all_equal: CONSTANT whatever the rest. */
+ * least cost (the lowest on ties), FIXED against VERBATIM (VERBATIM on ties). all_equal: CONSTANT whatever the rest. `bits`
+ * gives the sample's size and the four or five bits of a partition's parameter. */
 SAU_FLAC_HD void flac_finish_sub(FlacSub *s, unsigned cand, uint32_t n, bool all_equal, unsigned o, unsigned fine_log2,
-		const uint64_t *node_cost, const uint8_t *node_k) {
-	const unsigned bps = flac_cand_bps(cand);
+		const uint64_t *node_cost, const uint8_t *node_k, unsigned bits) {
+	const unsigned bps = flac_cand_bps(cand, bits);
 	s->cand = (uint8_t)cand; s->order = 0; s->p = 0;
 	for (unsigned j = 0; j < FLAC_FINE; ++j) s->k[j] = 0;
 	for (unsigned j = 0; j < FLAC_LPC_MAX; ++j) s->q[j] = 0;
@@ -133,10 +145,10 @@ SAU_FLAC_HD void flac_finish_sub(FlacSub *s, unsigned cand, uint32_t n, bool all
 	unsigned bp = 0;
 	for (unsigned p = 0; p <= fine_log2; ++p) {
 		uint64_t c = 0;
-		for (unsigned j = 0; j < (1u << p); ++j) c += 4 + node_cost[flac_node_index(p, j)];
+		for (unsigned j = 0; j < (1u << p); ++j) c += flac_k_width(bits) + node_cost[flac_node_index(p, j)];
 		if (c < best) { best = c; bp = p; }
 	}
-	const uint64_t fixed = 8 + (uint64_t)bps * o + 6 + best, verbatim = 8 + (uint64_t)bps * n;
+	const uint64_t fixed =8 + (uint64_t)bps * o + 6 + best, verbatim = 8 + (uint64_t)bps * n;
 	if (verbatim <= fixed) { s->type = FLAC_VERBATIM; s->bits = (uint32_t)verbatim; return; }
 	s->type = FLAC_FIXED; s->order = (uint8_t)o; s->p = (uint8_t)bp; s->bits = (uint32_t)fixed;
 	for (unsigned j = 0; j < (1u << bp); ++j) s->k[j] = node_k[flac_node_index(bp, j)];
@@ -231,7 +243,7 @@ SAU_FLAC_HD unsigned flac_lpc_pick_order(uint32_t mask, const uint64_t *abs_sum 
 SAU_FLAC_HD void flac_lpc_choose(FlacSub *s, uint32_t n, unsigned m, const int16_t *q, unsigned shift, unsigned fine_log2,
 		const uint64_t *node_cost, const uint8_t *node_k) {
 	if (s->type == FLAC_CONSTANT) return;
-	const unsigned bps = flac_cand_bps(s->cand);
+	const unsigned bps = flac_cand_bps(s->cand, 16);
 	uint64_t best = ~0ull;
 	unsigned bp = 0;
 	for (unsigned p = 0; p <= fine_log2; ++p) {
@@ -307,14 +319,15 @@ SAU_FLAC_HD uint32_t flac_crc16_advance(uint32_t crc, uint32_t bytes) {
 	return crc;
 }
 
-/* the frame header, CRC-8 included -> its length (at most 13). assign: the channel assignment's four bits. */
-SAU_FLAC_HD uint32_t flac_frame_header(uint32_t n, uint32_t block_frames, uint32_t assign, uint32_t number, uint8_t *out /* [16] */) {
+/* the frame header, CRC-8 included -> its length (at most 13). assign: the channel assignment's four bits; the sample-size
+ * code of `bits` is 100 for 16, 110 for 24. */
+SAU_FLAC_HD uint32_t flac_frame_header(uint32_t n, uint32_t block_frames, uint32_t assign, uint32_t number, unsigned bits, uint8_t *out /* [16] */) {
 	uint32_t len = 0;
 	out[len++] = 0xff; out[len++] = 0xf8;
 	uint32_t code = 7;
 	if (n == block_frames) { code = 8; for (uint32_t b = 256; b < block_frames; b <<= 1) ++code; }
 	out[len++] = (uint8_t)(code << 4);
-	out[len++] = (uint8_t)((assign << 4) | (4u << 1));
+	out[len++] = (uint8_t)((assign << 4) | ((bits == 24 ? 6u : 4u) << 1));
 	const uint32_t ul = flac_utf8_len(number);
 	if (ul == 1) out[len++] = (uint8_t)number;
 	else {
@@ -325,74 +338,6 @@ SAU_FLAC_HD uint32_t flac_frame_header(uint32_t n, uint32_t block_frames, uint32
 	uint32_t crc = 0;
 	for (uint32_t i = 0; i < len; ++i) crc = flac_crc8_update(crc, out[i]);
 	out[len++] = (uint8_t)crc;
-	return len;
-}
-
-/* ---- the 24-bit format (include/saugns_amd.h, FLAC, "24 bits"): what differs from the 16-bit arithmetic above ----
- * Samples are int32 in -2^23 .. 2^23 - 1; the side channel takes 25 bits. A FIXED residual is at most 16 * 2^24 in size, so
- * the residual functions above serve as they are; u is below 2^30, the Rice parameters are 0 .. 30 in five bits (method 01),
- * and everything summed over a lane's run, not only over a block, needs 64 bits. No LPC. */
-constexpr unsigned FLAC_K_MAX_W = 30, FLAC_NK_W = 31;  /* Rice parameters 0 .. 30; 31 is the escape, never used */
-constexpr int32_t FLAC_S24_MIN = -8388608, FLAC_S24_MAX = 8388607;
-SAU_FLAC_HD bool flac_bits_ok(int bits) { return bits == 16 || bits == 24; }
-/* the most bytes a frame of n frames takes at `bits` per sample (16: flac_frame_bound) */
-SAU_FLAC_HD uint32_t flac_frame_bound_bits(uint32_t n, uint32_t channels, unsigned bits) {
-	return 15 + channels * (1 + (bits == 24 ? 3 : 2) * n);
-}
-SAU_FLAC_HD int32_t flac_cand_w(int32_t l, int32_t r, unsigned cand) {
-	switch (cand) {
-	case FLAC_CAND_L: return l;
-	case FLAC_CAND_R: return r;
-	case FLAC_CAND_M: return (l + r) >> 1; /* (arithmetic) */
-	default: return l - r;
-	}
-}
-SAU_FLAC_HD unsigned flac_cand_bps_w(unsigned cand) { return cand == FLAC_CAND_S ? 25 : 24; }
-/* flac_node_cost with fine[f * 31 + k], k = 0 .. 30 */
-SAU_FLAC_HD uint64_t flac_node_cost_w(const uint64_t *fine, unsigned fine_log2, unsigned p, unsigned part, uint32_t n, unsigned o, unsigned *k_out) {
-	const unsigned span = 1u << (fine_log2 - p), first = part * span;
-	const uint64_t count = (n >> p) - (part == 0 ? o : 0);
-	uint64_t best = ~0ull;
-	unsigned bk = 0;
-	for (unsigned k = 0; k < FLAC_NK_W; ++k) {
-		uint64_t s = 0;
-		for (unsigned f = 0; f < span; ++f) s += fine[(first + f) * FLAC_NK_W + k];
-		const uint64_t cost = s + (1 + k) * count;
-		if (cost < best) { best = cost; bk = k; }
-	}
-	*k_out = bk;
-	return best;
-}
-/* flac_finish_sub with 24 or 25 bits per sample and five bits per partition's parameter */
-SAU_FLAC_HD void flac_finish_sub_w(FlacSub *s, unsigned cand, uint32_t n, bool all_equal, unsigned o, unsigned fine_log2,
-		const uint64_t *node_cost, const uint8_t *node_k) {
-	const unsigned bps = flac_cand_bps_w(cand);
-	s->cand = (uint8_t)cand; s->order = 0; s->p = 0;
-	for (unsigned j = 0; j < FLAC_FINE; ++j) s->k[j] = 0;
-	for (unsigned j = 0; j < FLAC_LPC_MAX; ++j) s->q[j] = 0;
-	s->shift = 0; s->pad_[0] = s->pad_[1] = s->pad_[2] = 0;
-	if (all_equal) { s->type = FLAC_CONSTANT; s->bits = 8 + bps; return; }
-	uint64_t best = ~0ull;
-	unsigned bp = 0;
-	for (unsigned p = 0; p <= fine_log2; ++p) {
-		uint64_t c = 0;
-		for (unsigned j = 0; j < (1u << p); ++j) c += 5 + node_cost[flac_node_index(p, j)];
-		if (c < best) { best = c; bp = p; }
-	}
-	const uint64_t fixed = 8 + (uint64_t)bps * o + 6 + best, verbatim = 8 + (uint64_t)bps * n;
-	if (verbatim <= fixed) { s->type = FLAC_VERBATIM; s->bits = (uint32_t)verbatim; return; }
-	s->type = FLAC_FIXED; s->order = (uint8_t)o; s->p = (uint8_t)bp; s->bits = (uint32_t)fixed;
-	for (unsigned j = 0; j < (1u << bp); ++j) s->k[j] = node_k[flac_node_index(bp, j)];
-}
-/* flac_frame_header with the sample-size code of `bits`: 100 for 16, 110 for 24 (the CRC-8 covers it) */
-SAU_FLAC_HD uint32_t flac_frame_header_bits(uint32_t n, uint32_t block_frames, uint32_t assign, uint32_t number, unsigned bits, uint8_t *out /* [16] */) {
-	const uint32_t len = flac_frame_header(n, block_frames, assign, number, out);
-	if (bits == 24) {
-		out[3] = (uint8_t)((assign << 4) | (6u << 1));
-		uint32_t crc = 0;
-		for (uint32_t i = 0; i + 1 < len; ++i) crc = flac_crc8_update(crc, out[i]);
-		out[len - 1] = (uint8_t)crc;
-	}
 	return len;
 }
 

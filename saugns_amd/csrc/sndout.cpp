@@ -529,7 +529,7 @@ bool write_flac(const sauProgram *prg, uint32_t srate, const char *path, int cha
 	const bool md5 = flac_file_md5();
 	if (md5 && !enc->set_md5(true, err)) { delete enc; delete engine; return false; }
 	/* what a run can come to: the blocks it completes, with what was pending, and a last short one, each at its bound */
-	const size_t slot_bytes = (chunk / B + 2) * (size_t)sauflac::flac_frame_bound(B, (uint32_t)channels);
+	const size_t slot_bytes = (chunk / B + 2) * (size_t)sauflac::flac_frame_bound(B, (uint32_t)channels, 16);
 	uint8_t *host[2] = {(uint8_t *)backend->alloc_host(slot_bytes), (uint8_t *)backend->alloc_host(slot_bytes)};
 	FILE *f = nullptr;
 	bool ok = host[0] && host[1];
@@ -605,7 +605,7 @@ bool write_flac_scaled(const sauProgram *prg, uint32_t srate, const char *path, 
 	if (!enc) { delete engine; return false; }
 	const bool md5 = flac_file_md5();
 	if (md5 && !enc->set_md5(true, err)) { delete enc; delete engine; return false; }
-	const size_t slot_bytes = (chunk / B + 2) * (size_t)sauflac::flac_frame_bound_bits(B, (uint32_t)channels, (unsigned)bits);
+	const size_t slot_bytes = (chunk / B + 2) * (size_t)sauflac::flac_frame_bound(B, (uint32_t)channels, (unsigned)bits);
 	uint8_t *host[2] = {(uint8_t *)backend->alloc_host(slot_bytes), (uint8_t *)backend->alloc_host(slot_bytes)};
 	FILE *f = nullptr;
 	bool ok = host[0] && host[1];
@@ -686,7 +686,7 @@ bool write_flac_limited(const sauProgram *prg, uint32_t srate, const char *path,
 	const bool md5 = flac_file_md5();
 	if (md5 && !enc->set_md5(true, err)) { delete enc; delete engine; return false; }
 	const size_t slot_frames = chunk > D ? chunk : D;
-	const size_t slot_bytes = (slot_frames / B + 2) * (size_t)sauflac::flac_frame_bound_bits(B, (uint32_t)channels, (unsigned)bits);
+	const size_t slot_bytes = (slot_frames / B + 2) * (size_t)sauflac::flac_frame_bound(B, (uint32_t)channels, (unsigned)bits);
 	uint8_t *host[2] = {(uint8_t *)backend->alloc_host(slot_bytes), (uint8_t *)backend->alloc_host(slot_bytes)};
 	FILE *f = nullptr;
 	bool ok = host[0] && host[1];
@@ -849,7 +849,7 @@ bool write_flac_dithered(const sauProgram *prg, uint32_t srate, const char *path
 	if (!enc) { delete q; delete engine; return false; }
 	const bool md5 = flac_file_md5();
 	if (md5 && !enc->set_md5(true, err)) { delete enc; delete q; delete engine; return false; }
-	const size_t slot_bytes = (chunk / B + 2) * (size_t)sauflac::flac_frame_bound(B, (uint32_t)channels);
+	const size_t slot_bytes = (chunk / B + 2) * (size_t)sauflac::flac_frame_bound(B, (uint32_t)channels, 16);
 	uint8_t *host[2] = {(uint8_t *)backend->alloc_host(slot_bytes), (uint8_t *)backend->alloc_host(slot_bytes)};
 	FILE *f = nullptr;
 	bool ok = host[0] && host[1];

@@ -438,20 +438,13 @@ size_t flac_header(uint32_t srate, int channels, uint32_t block_frames, const Fl
 	return 42;
 }
 
-size_t flac_encode_block(const int16_t *x, uint32_t n, int channels, uint32_t block_frames, uint32_t frame_number, uint8_t *out, size_t cap) {
-	return flac_encode_block_lpc(x, n, channels, block_frames, frame_number, 0, out, cap);
-}
-
-size_t flac_encode_block_lpc(const int16_t *x, uint32_t n, int channels, uint32_t block_frames, uint32_t frame_number, uint32_t max_lpc_order,
+/* One block of n frames of int32 samples, already checked: B a block size, n in 1 .. B, every sample within `bits`, M the LPC
+ * mode's largest order (0 at 24 bits). */
+static size_t flac_encode_block_any(const int32_t *x, uint32_t n, unsigned ch, uint32_t B, uint32_t frame_number, unsigned bits, unsigned M,
 		uint8_t *out, size_t cap) {
 	using namespace sauflac;
-	const uint32_t B = flac_block_frames(block_frames);
-	if (!x || !B || !n || n > B || (channels != 1 && channels != 2) || frame_number > FLAC_MAX_BLOCKS || max_lpc_order > FLAC_LPC_MAX) return 0;
-	const unsigned M = max_lpc_order;
-	const unsigned ch = (unsigned)channels, n_cand = ch == 2 ? 4 : 1, fine_log2 = n == B ? 4 : 0, F = 1u << fine_log2;
-	uint32_t *w = new uint32_t[n];
-	for (uint32_t i = 0; i < n; ++i) w[i] = ch == 2 ? flac_pack(x[2 * i], x[2 * i + 1]) : flac_pack(x[i], 0);
-	auto at = [&](unsigned c, int64_t i) -> int32_t { return i >= 0 ? flac_cand(w[i], c) : 0; };
+	const unsigned n_cand = ch == 2 ? 4 : 1, fine_log2 = n == B ? 4 : 0, F = 1u << fine_log2, nk = flac_nk(bits);
+	auto at = [&](unsigned c, int64_t i) -> int32_t { return i < 0 ? 0 : ch == 2 ? flac_cand(x[2 * i], x[2 * i + 1], c) : x[i]; };
 	auto resid = [&](unsigned c, unsigned o, uint32_t i) { return flac_residual(o, at(c, i), at(c, (int64_t)i - 1), at(c, (int64_t)i - 2), at(c, (int64_t)i - 3), at(c, (int64_t)i - 4)); };
 	auto resid_lpc = [&](unsigned c, const int16_t *q, unsigned m, unsigned shift, uint32_t i) { /* (i >= m) */
 		int32_t sum = 0;
@@ -462,7 +455,7 @@ size_t flac_encode_block_lpc(const int16_t *x, uint32_t n, int channels, uint32_
 		for (unsigned p = 0; p <= fine_log2; ++p)
 			for (unsigned j = 0; j < (1u << p); ++j) {
 				unsigned k;
-				node_cost[flac_node_index(p, j)] = flac_node_cost(fine, fine_log2, p, j, n, o, &k);
+				node_cost[flac_node_index(p, j)] = flac_node_cost(fine, nk, fine_log2, p, j, n, o, &k);
 				node_k[flac_node_index(p, j)] = (uint8_t)k;
 			}
 	};
@@ -477,17 +470,17 @@ size_t flac_encode_block_lpc(const int16_t *x, uint32_t n, int channels, uint32_
 			for (int o = 0; o < 5; ++o) abs_sum[o] += flac_abs(r[o]);
 		}
 		const unsigned o = flac_pick_order(n, abs_sum);
-		uint64_t fine[FLAC_FINE * FLAC_NK];
+		uint64_t fine[FLAC_FINE * flac_nk(24)]; /* [f * nk + k] */
 		memset(fine, 0, sizeof fine);
 		const uint32_t plen = n / F; /* (F == 1 unless n == B, a multiple of 16) */
 		for (uint32_t i = o; i < n; ++i) {
 			const uint32_t u = flac_zigzag(resid(c, o, i));
-			for (unsigned k = 0; k < FLAC_NK; ++k) fine[(i / plen) * FLAC_NK + k] += u >> k;
+			for (unsigned k = 0; k < nk; ++k) fine[(i / plen) * nk + k] += u >> k;
 		}
 		uint64_t node_cost[FLAC_NODES];
 		uint8_t node_k[FLAC_NODES];
 		nodes(fine, fine_log2, o, node_cost, node_k);
-		flac_finish_sub(&cand[c], c, n, equal, o, fine_log2, node_cost, node_k);
+		flac_finish_sub(&cand[c], c, n, equal, o, fine_log2, node_cost, node_k, bits);
 		if (!M || n != B || equal) continue;
 		/* the LPC mode: the windowed autocorrelation in integers, the orders' coefficients, the order, its partitions */
 		unsigned log2B = 0;
@@ -511,28 +504,28 @@ size_t flac_encode_block_lpc(const int16_t *x, uint32_t n, int channels, uint32_
 			if (mask & (1u << (m - 1)))
 				for (uint32_t i = M; i < n; ++i) lpc_abs[m - 1] += flac_abs(resid_lpc(c, q + (m - 1) * FLAC_LPC_MAX, m, shift[m - 1], i));
 		}
-		const unsigned m = flac_lpc_pick_order(mask, lpc_abs, n, M, flac_cand_bps(c));
+		const unsigned m = flac_lpc_pick_order(mask, lpc_abs, n, M, flac_cand_bps(c, bits));
 		if (!m) continue;
 		memset(fine, 0, sizeof fine);
 		for (uint32_t i = m; i < n; ++i) {
 			const uint32_t u = flac_zigzag(resid_lpc(c, q + (m - 1) * FLAC_LPC_MAX, m, shift[m - 1], i));
-			for (unsigned k = 0; k < FLAC_NK; ++k) fine[(i / plen) * FLAC_NK + k] += u >> k;
+			for (unsigned k = 0; k < nk; ++k) fine[(i / plen) * nk + k] += u >> k;
 		}
 		nodes(fine, fine_log2, m, node_cost, node_k);
 		flac_lpc_choose(&cand[c], n, m, q + (m - 1) * FLAC_LPC_MAX, shift[m - 1], fine_log2, node_cost, node_k);
 	}
 	FlacFrameDesc d;
 	flac_finish_frame(&d, cand, ch, n, B, frame_number);
-	if (!out || cap < d.bytes) { delete[] w; return d.bytes; }
+	if (!out || cap < d.bytes) return d.bytes;
 	memset(out, 0, d.bytes);
 	uint8_t hdr[16];
-	const uint32_t hl = flac_frame_header(n, B, d.assign, frame_number, hdr);
+	const uint32_t hl = flac_frame_header(n, B, d.assign, frame_number, bits, hdr);
 	memcpy(out, hdr, hl);
 	FlacBits bw{out, (size_t)hl * 8};
 	for (unsigned si = 0; si < d.n_sub; ++si) {
 		const FlacSub &s = d.sub[si];
-		const unsigned c = s.cand, bps = flac_cand_bps(c);
-		const uint32_t mask = bps == 17 ? 0x1ffffu : 0xffffu;
+		const unsigned c = s.cand, bps = flac_cand_bps(c, bits);
+		const uint32_t mask = (1u << bps) - 1;
 		bw.put(s.type == FLAC_CONSTANT ? 0u : s.type == FLAC_VERBATIM ? 2u : s.type == FLAC_LPC ? (uint32_t)(0x40u | ((s.order - 1u) << 1)) :
 				(uint32_t)(0x10u | (s.order << 1)), 8); /* 0 tttttt 0 */
 		if (s.type == FLAC_CONSTANT) bw.put((uint32_t)at(c, 0) & mask, bps);
@@ -544,11 +537,11 @@ size_t flac_encode_block_lpc(const int16_t *x, uint32_t n, int channels, uint32_
 				bw.put(s.shift, 5);
 				for (uint32_t i = 0; i < s.order; ++i) bw.put((uint32_t)s.q[i] & 0xfffu, FLAC_LPC_PREC);
 			}
-			bw.put(s.p, 6); /* 00 pppp */
+			bw.put((bits == 24 ? 0x10u : 0u) | s.p, 6); /* 00 pppp, or 01 pppp where the parameters take five bits */
 			const uint32_t plen = n >> s.p;
 			for (uint32_t j = 0; j < (1u << s.p); ++j) {
 				const unsigned k = s.k[j];
-				bw.put(k, 4);
+				bw.put(k, flac_k_width(bits));
 				for (uint32_t i = j ? j * plen : s.order; i < (j + 1) * plen; ++i) {
 					const uint32_t u = flac_zigzag(s.type == FLAC_LPC ? resid_lpc(c, s.q, s.order, s.shift, i) : resid(c, s.order, i));
 					bw.zeros(u >> k);
@@ -557,13 +550,25 @@ size_t flac_encode_block_lpc(const int16_t *x, uint32_t n, int channels, uint32_
 			}
 		}
 	}
-	delete[] w;
 	const size_t body = (bw.pos + 7) / 8;
 	if (body + 2 != d.bytes) return 0; /* (the analysis and the writer disagree: never) */
 	uint32_t crc = 0;
 	for (size_t i = 0; i < body; ++i) crc = flac_crc16_update(crc, out[i]);
 	out[body] = (uint8_t)(crc >> 8); out[body + 1] = (uint8_t)crc;
 	return d.bytes;
+}
+
+size_t flac_encode_block(const int16_t *x, uint32_t n, int channels, uint32_t block_frames, uint32_t frame_number, uint8_t *out, size_t cap) {
+	return flac_encode_block_lpc(x, n, channels, block_frames, frame_number, 0, out, cap);
+}
+
+size_t flac_encode_block_lpc(const int16_t *x, uint32_t n, int channels, uint32_t block_frames, uint32_t frame_number, uint32_t max_lpc_order,
+		uint8_t *out, size_t cap) {
+	using namespace sauflac;
+	const uint32_t B = flac_block_frames(block_frames);
+	if (!x || !B || !n || n > B || (channels != 1 && channels != 2) || frame_number > FLAC_MAX_BLOCKS || max_lpc_order > FLAC_LPC_MAX) return 0;
+	const std::vector<int32_t> s(x, x + (size_t)n * (size_t)channels);
+	return flac_encode_block_any(s.data(), n, (unsigned)channels, B, frame_number, 16, max_lpc_order, out, cap);
 }
 
 /* ---- 24 bits and float-fed encoders (include/saugns_amd.h, FLAC, "24 bits") ---- */
@@ -613,78 +618,6 @@ bool flac_md5(const int32_t *x, size_t n, int bits, uint8_t out[16]) {
 	return true;
 }
 
-/* flac_encode_block's loops at 24 bits: what flac_analyze_wide_kernel and flac_write_wide_kernel make of one block */
-static size_t flac_encode_block_24(const int32_t *x, uint32_t n, unsigned ch, uint32_t B, uint32_t frame_number, uint8_t *out, size_t cap) {
-	using namespace sauflac;
-	const unsigned n_cand = ch == 2 ? 4 : 1, fine_log2 = n == B ? 4 : 0, F = 1u << fine_log2;
-	auto at = [&](unsigned c, int64_t i) -> int32_t { return i < 0 ? 0 : ch == 2 ? flac_cand_w(x[2 * i], x[2 * i + 1], c) : x[i]; };
-	auto resid = [&](unsigned c, unsigned o, uint32_t i) { return flac_residual(o, at(c, i), at(c, (int64_t)i - 1), at(c, (int64_t)i - 2), at(c, (int64_t)i - 3), at(c, (int64_t)i - 4)); };
-	FlacSub cand[4];
-	for (unsigned c = 0; c < n_cand; ++c) {
-		bool equal = true;
-		for (uint32_t i = 1; i < n; ++i) equal = equal && at(c, i) == at(c, 0);
-		uint64_t abs_sum[5] = {0, 0, 0, 0, 0};
-		for (uint32_t i = 4; i < n; ++i) {
-			int32_t r[5];
-			flac_residuals(at(c, i), at(c, i - 1), at(c, i - 2), at(c, i - 3), at(c, i - 4), r);
-			for (int o = 0; o < 5; ++o) abs_sum[o] += flac_abs(r[o]);
-		}
-		const unsigned o = flac_pick_order(n, abs_sum);
-		uint64_t fine[FLAC_FINE * FLAC_NK_W];
-		memset(fine, 0, sizeof fine);
-		const uint32_t plen = n / F; /* (F == 1 unless n == B, a multiple of 16) */
-		for (uint32_t i = o; i < n; ++i) {
-			const uint32_t u = flac_zigzag(resid(c, o, i));
-			for (unsigned k = 0; k < FLAC_NK_W; ++k) fine[(i / plen) * FLAC_NK_W + k] += u >> k;
-		}
-		uint64_t node_cost[FLAC_NODES];
-		uint8_t node_k[FLAC_NODES];
-		for (unsigned p = 0; p <= fine_log2; ++p)
-			for (unsigned j = 0; j < (1u << p); ++j) {
-				unsigned k;
-				node_cost[flac_node_index(p, j)] = flac_node_cost_w(fine, fine_log2, p, j, n, o, &k);
-				node_k[flac_node_index(p, j)] = (uint8_t)k;
-			}
-		flac_finish_sub_w(&cand[c], c, n, equal, o, fine_log2, node_cost, node_k);
-	}
-	FlacFrameDesc d;
-	flac_finish_frame(&d, cand, ch, n, B, frame_number);
-	if (!out || cap < d.bytes) return d.bytes;
-	memset(out, 0, d.bytes);
-	uint8_t hdr[16];
-	const uint32_t hl = flac_frame_header_bits(n, B, d.assign, frame_number, 24, hdr);
-	memcpy(out, hdr, hl);
-	FlacBits bw{out, (size_t)hl * 8};
-	for (unsigned si = 0; si < d.n_sub; ++si) {
-		const FlacSub &s = d.sub[si];
-		const unsigned c = s.cand, bps = flac_cand_bps_w(c);
-		const uint32_t mask = bps == 25 ? 0x1ffffffu : 0xffffffu;
-		bw.put(s.type == FLAC_CONSTANT ? 0u : s.type == FLAC_VERBATIM ? 2u : (uint32_t)(0x10u | (s.order << 1)), 8); /* 0 tttttt 0 */
-		if (s.type == FLAC_CONSTANT) bw.put((uint32_t)at(c, 0) & mask, bps);
-		else if (s.type == FLAC_VERBATIM) for (uint32_t i = 0; i < n; ++i) bw.put((uint32_t)at(c, i) & mask, bps);
-		else {
-			for (uint32_t i = 0; i < s.order; ++i) bw.put((uint32_t)at(c, i) & mask, bps);
-			bw.put(0x10u | s.p, 6); /* 01 pppp */
-			const uint32_t plen = n >> s.p;
-			for (uint32_t j = 0; j < (1u << s.p); ++j) {
-				const unsigned k = s.k[j];
-				bw.put(k, 5);
-				for (uint32_t i = j ? j * plen : s.order; i < (j + 1) * plen; ++i) {
-					const uint32_t u = flac_zigzag(resid(c, s.order, i));
-					bw.zeros(u >> k);
-					bw.put((1u << k) | (u & ((1u << k) - 1)), k + 1);
-				}
-			}
-		}
-	}
-	const size_t body = (bw.pos + 7) / 8;
-	if (body + 2 != d.bytes) return 0; /* (the analysis and the writer disagree: never) */
-	uint32_t crc = 0;
-	for (size_t i = 0; i < body; ++i) crc = flac_crc16_update(crc, out[i]);
-	out[body] = (uint8_t)(crc >> 8); out[body + 1] = (uint8_t)crc;
-	return d.bytes;
-}
-
 size_t flac_encode_block_s32(const int32_t *x, uint32_t n, int channels, uint32_t block_frames, uint32_t frame_number, int bits,
 		uint32_t max_lpc_order, uint8_t *out, size_t cap) {
 	using namespace sauflac;
@@ -695,10 +628,7 @@ size_t flac_encode_block_s32(const int32_t *x, uint32_t n, int channels, uint32_
 	const int32_t lo = bits == 24 ? FLAC_S24_MIN : -32768, hi = bits == 24 ? FLAC_S24_MAX : 32767;
 	for (size_t i = 0; i < cnt; ++i)
 		if (x[i] < lo || x[i] > hi) return 0;
-	if (bits == 24) return flac_encode_block_24(x, n, (unsigned)channels, B, frame_number, out, cap);
-	std::vector<int16_t> s(cnt);
-	for (size_t i = 0; i < cnt; ++i) s[i] = (int16_t)x[i];
-	return flac_encode_block_lpc(s.data(), n, channels, B, frame_number, max_lpc_order, out, cap);
+	return flac_encode_block_any(x, n, (unsigned)channels, B, frame_number, (unsigned)bits, max_lpc_order, out, cap);
 }
 
 /* ---- dither and noise shaping (include/saugns_amd.h, section "Dither and noise shaping"; the arithmetic is sau_dither.h's,
