@@ -577,8 +577,10 @@ SAU_AMD_API bool sauAmd_render_spectrum(const sauProgram *prg, uint32_t srate, i
  * encoder and 2^31 - 1 blocks per row.
  * Limits: MD5 only on request ("MD5" below), no seek table, no comments, no wasted-bits detection, no escape
  * partitions, no dither of its own (a quantiser's rows can be fed: "Dither and noise shaping" below); LPC only on request (max_lpc_order, "The LPC mode" below), of order <= 8 with 12-bit coefficients, one
- * precision and one window, and at 16 bits only: max_lpc_order > 0 with bits == 24 is a bad argument everywhere (its products
- * pass 32 bits, and the window scaling would pass 64). 24-bit output comes from float rows only ("24 bits" below). The
+ * precision and one window. At 24 bits the LPC mode has entry points of its own, whose names end in _lpc24 ("LPC at 24 bits"
+ * below); the entry points that take `bits` -- sauAmd_flac_encode_block_s32, sauAmd_Batch_create_flac_f32,
+ * sauAmd_render_file_flac_f32, sauAmd_render_file_flac_loudness -- refuse max_lpc_order > 0 with bits == 24 as a bad argument,
+ * as they always have. 24-bit output comes from float rows only ("24 bits" below). The
  * peak-normalised and oversampled writers have no FLAC variant; the fed encoders take any int16 or float device rows, decimated
  * ones included.
  *
@@ -686,9 +688,30 @@ SAU_AMD_API bool sauAmd_render_spectrum(const sauProgram *prg, uint32_t srate, i
  *   Rule 4: FIXED costs 8 + bps * o + 6 + cost(p), VERBATIM 8 + bps * n, with those bps.
  *   Unchanged: P = 4 for whole blocks, the order rule (sums of |r| over i >= 4, in 64 bits), the stereo rule and every tie.
  *   A frame is at most 15 + channels * (1 + 3 n) bytes. A code's non-zero part is at most 31 bits: the stop bit and k low bits.
- *   No LPC (Limits).
+ *   No LPC through these entry points (Limits); "LPC at 24 bits" below has it.
  * sauAmd_flac_encode_block_s32 restates one such frame on the host. The bytes are a function of the fed floats, the gains and
  * (B, channels, bits, M) only, never of how the sequence was cut into feeds.
+ *
+ * LPC at 24 bits. The entry points whose names end in _lpc24 -- sauAmd_flac_encode_block_lpc24, sauAmd_Batch_create_flac_lpc24,
+ * sauAmd_render_file_flac_lpc24, sauAmd_render_file_flac_loudness_lpc24 -- make 24-bit streams with max_lpc_order M in 0 .. 8;
+ * M = 0 is "24 bits" above and nothing else, byte for byte and launch for launch. Everything in "The LPC mode", steps 1 to 10,
+ * holds with bps 24, or 25 for a side channel, and with the 24-bit residual coding: method 01, 5-bit Rice parameters
+ * k = 0 .. 30, a partition costing 5 plus its least cost. Whole blocks only, as at 16 bits. The differences:
+ *   Step 1: ws[j] = (s[j] W[j]) >> 11, the product in 64-bit integers. |s| <= 2^24 and W <= 4095, so |ws| < 2^25 as at 16
+ *     bits, and step 2's bounds (a product below 2^50, a sum below 2^62) stay as written.
+ *   Step 5b (new), after the quantisation of order m: S = the sum of |q[j]| over j < m. The order is no candidate for this
+ *     channel candidate when (S << (bps - 1)) >> shift >= 2^30, computed in 64-bit integers. This is the only place where the
+ *     candidate orders depend on bps. It makes step 6 safe on every input: a prediction is at most that quantity + 1 in size,
+ *     so |r_i| < 2^30 + 2^24 + 1 < 2^31 -- a residual fits int32, as RFC 9639 requires, and its u fits uint32. It fires at a
+ *     sum of |c[j]| of about 64 for a side channel and 128 otherwise, far above what ordinary material gives.
+ *   Step 6: the sum of q[j] s_{i-1-j} is in 64-bit integers (below 2^39 in size), >> shift is arithmetic on that, and the
+ *     residual is then narrowed to 32 bits.
+ *   Step 7: est's k runs over 0 .. 30; the order term is m (bps + 12) with these bps.
+ *   Steps 8 to 10: rule 3 as in "24 bits" (k = 0 .. 30, 5 bits a parameter); the cost formula of step 9 is unchanged; the
+ *     subframe is step 10's with its residual section in method 01: 01, the partition order, 5-bit parameters, the codes.
+ * An LPC residual's u may take all 32 bits ("u is below 2^30" is said of FIXED only). A code's non-zero part is still at most
+ * 31 bits, the stop bit and k <= 30 low bits, and the frame bound 15 + channels * (1 + 3 n) holds: LPC is taken only where it
+ * is cheaper, so no frame is longer than with M = 0. The 16-bit rules have no step 5b and no other change.
  *
  * MD5. STREAMINFO's MD5 field is zeros unless it is asked for: sauAmd_Flac_set_md5 on a fed encoder, sauAmd_set_flac_file_md5
  * for the file writers. Off, every byte and every launch is what it is without this paragraph. On, the encoder keeps the MD5
@@ -768,8 +791,8 @@ SAU_AMD_API bool sauAmd_render_file_flac_lpc(const sauProgram *prg, uint32_t sra
 SAU_AMD_API size_t sauAmd_flac_header_bits(uint32_t srate, int channels, uint32_t block_frames, int bits, const sauAmdFlacInfo *info,
 		uint8_t *out, size_t cap);
 /* The host restatement for int32 samples. bits == 16: every sample must fit int16, and the bytes are
- * sauAmd_flac_encode_block_lpc's. bits == 24: every sample must lie in -2^23 .. 2^23 - 1 and max_lpc_order must be 0. Otherwise,
- * and for other bits, 0. */
+ * sauAmd_flac_encode_block_lpc's. bits == 24: every sample must lie in -2^23 .. 2^23 - 1, and this entry point refuses
+ * max_lpc_order > 0 (sauAmd_flac_encode_block_lpc24 takes it). Otherwise, and for other bits, 0. */
 SAU_AMD_API size_t sauAmd_flac_encode_block_s32(const int32_t *x, uint32_t n, int channels, uint32_t block_frames, uint32_t frame_number,
 		int bits, uint32_t max_lpc_order, uint8_t *out, size_t cap);
 /* The quantiser on the host: out[i] = what a float-fed encoder of `bits` makes of x[i] with `gain`. False for bits other than 16
@@ -793,7 +816,8 @@ SAU_AMD_API bool sauAmd_flac_md5(const int32_t *x, size_t n_samples, int bits, u
  * it into the header it rewrites at the end; every other byte of the file is the same. A backend whose encoder has no MD5 then
  * gives "bad argument" before any file is created. Off, a writer does what it does without this switch. */
 SAU_AMD_API int sauAmd_set_flac_file_md5(int on);
-/* A float-fed encoder: sauAmd_Batch_create_flac_lpc's rules, and bits 16 or 24; 24 with max_lpc_order > 0 is a bad argument. */
+/* A float-fed encoder: sauAmd_Batch_create_flac_lpc's rules, and bits 16 or 24; this entry point refuses 24 with
+ * max_lpc_order > 0 as a bad argument (sauAmd_Batch_create_flac_lpc24 takes it). */
 SAU_AMD_API sauAmdFlac *sauAmd_Batch_create_flac_f32(sauAmdBatch *b, size_t n_rows, int channels, uint32_t block_frames, int bits,
 		uint32_t max_lpc_order);
 /* sauAmd_Flac_feed for a float-fed encoder: row r's next frames[r] float frames times gains[r] (gains NULL: 1.0f everywhere; a
@@ -808,8 +832,8 @@ SAU_AMD_API bool sauAmd_Flac_feed_f32(sauAmdFlac *e, const void *rows, size_t pi
  * sauAmd_Flac_feed_f32 of the run's device row (gain `gain`) where that writer requantises and fetches; the file I/O is
  * sauAmd_render_file_flac's. The file decodes to the quantiser's values of x * gain for the floats x that
  * sauAmd_render_file(.., SAU_AMD_SNDFILE_WAV_F32, ..) writes. False with "bad argument" on what sauAmd_render_file_flac_lpc
- * refuses, bits other than 16 or 24, 24 with max_lpc_order > 0, a gain that is not finite, and on a backend without the encoder
- * or float output -- all before any file is created. */
+ * refuses, bits other than 16 or 24, 24 with max_lpc_order > 0 (this writer refuses it; sauAmd_render_file_flac_lpc24 takes it), a
+ * gain that is not finite, and on a backend without the encoder or float output -- all before any file is created. */
 SAU_AMD_API bool sauAmd_render_file_flac_f32(const sauProgram *prg, uint32_t srate, const char *path, int channels, uint32_t block_frames,
 		int bits, uint32_t max_lpc_order, float gain, uint64_t *frames_out, sauAmdFlacInfo *info_out);
 /* The loudness-normalised writers with FLAC output. Pass 1 is sauAmd_render_file_loudness's. limited == 0: the gain follows that
@@ -820,6 +844,25 @@ SAU_AMD_API bool sauAmd_render_file_flac_f32(const sauProgram *prg, uint32_t sra
  * created. The out pointers may be NULL; stats_out is written only when limited. */
 SAU_AMD_API bool sauAmd_render_file_flac_loudness(const sauProgram *prg, uint32_t srate, const char *path, int channels,
 		uint32_t block_frames, int bits, uint32_t max_lpc_order, double target_lufs, float max_true_peak, int limited,
+		uint64_t *frames_out, sauAmdLoudness *loud_out, float *gain_out, sauAmdLimiterStats *stats_out, sauAmdFlacInfo *info_out);
+
+/* ---- LPC at 24 bits (the paragraph of that name above) ---- */
+/* The host restatement for int32 samples in -2^23 .. 2^23 - 1 with max_lpc_order 0 .. 8: sauAmd_flac_encode_block_s32's rules
+ * for its other arguments, and with max_lpc_order 0 its bytes at bits == 24. 0 on a bad argument. */
+SAU_AMD_API size_t sauAmd_flac_encode_block_lpc24(const int32_t *x, uint32_t n, int channels, uint32_t block_frames, uint32_t frame_number,
+		uint32_t max_lpc_order, uint8_t *out, size_t cap);
+/* A float-fed encoder of 24 bits per sample in the LPC mode with max_lpc_order (0 .. 8; above 8 is a bad argument: NULL). It is
+ * fed with sauAmd_Flac_feed_f32, read with sauAmd_Flac_read, and sauAmd_Flac_set_md5, sauAmd_Flac_md5 and sauAmd_Flac_destroy
+ * serve it too. With 0 it is sauAmd_Batch_create_flac_f32(.., 24, 0): the same bytes from the same launches. */
+SAU_AMD_API sauAmdFlac *sauAmd_Batch_create_flac_lpc24(sauAmdBatch *b, size_t n_rows, int channels, uint32_t block_frames, uint32_t max_lpc_order);
+/* sauAmd_render_file_flac_f32 at 24 bits with that encoder: the same refusals (max_lpc_order above 8 among them), all before any
+ * file is created; sauAmd_set_flac_file_md5 applies. The file decodes to the same samples as with max_lpc_order 0, has as many
+ * frames and none of them is longer. */
+SAU_AMD_API bool sauAmd_render_file_flac_lpc24(const sauProgram *prg, uint32_t srate, const char *path, int channels, uint32_t block_frames,
+		uint32_t max_lpc_order, float gain, uint64_t *frames_out, sauAmdFlacInfo *info_out);
+/* sauAmd_render_file_flac_loudness at 24 bits with that encoder, both its variants: that writer's argument list without `bits`. */
+SAU_AMD_API bool sauAmd_render_file_flac_loudness_lpc24(const sauProgram *prg, uint32_t srate, const char *path, int channels,
+		uint32_t block_frames, uint32_t max_lpc_order, double target_lufs, float max_true_peak, int limited,
 		uint64_t *frames_out, sauAmdLoudness *loud_out, float *gain_out, sauAmdLimiterStats *stats_out, sauAmdFlacInfo *info_out);
 
 /* ---- Dither and noise shaping ------------------------------------------------------

@@ -7,7 +7,7 @@ from .api import (Batch, Flac, FlacInfo, Generator, Levels, LimiterStats, Loudne
                   decimator_latency, decimator_taps, get_piluts, last_error, lib, limiter_latency, limiter_window,
                   loudness_filter, loudness_gate, render_file, render_file_flac, flac_encode_block, flac_header, flac_encode_block_s32, flac_quantize,
                   flac_md5, set_flac_file_md5,
-                  render_file_flac_f32, render_file_flac_loudness, render_file_loudness, render_file_loudness_limited,
+                  render_file_flac_f32, render_file_flac_loudness, flac_encode_block_lpc24, render_file_flac_lpc24, render_file_flac_loudness_lpc24, render_file_loudness, render_file_loudness_limited,
                   render_file_normalized, render_file_oversampled, render_spectrum, set_piluts, spectrum_twiddles, spectrum_window,
                   truepeak_taps,
                   Dither, DitherStats, Quantizer, DITHER_FLAT, DITHER_HP1, DITHER_E3, DITHER_E5, DITHER_F9, dither_preset, dither_quantize,

@@ -387,6 +387,19 @@ def _declare(L):
         L.sauAmd_flac_md5.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
         L.sauAmd_set_flac_file_md5.restype = C.c_int
         L.sauAmd_set_flac_file_md5.argtypes = [C.c_int]
+    if hasattr(L, "sauAmd_Batch_create_flac_lpc24"):  # LPC at 24 bits (SAU_AMD_LIB may name an older build)
+        L.sauAmd_flac_encode_block_lpc24.restype = C.c_size_t
+        L.sauAmd_flac_encode_block_lpc24.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                                     C.c_size_t]
+        L.sauAmd_Batch_create_flac_lpc24.restype = C.c_void_p
+        L.sauAmd_Batch_create_flac_lpc24.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.c_uint32]
+        L.sauAmd_render_file_flac_lpc24.restype = C.c_bool
+        L.sauAmd_render_file_flac_lpc24.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_int, C.c_uint32, C.c_uint32, C.c_float,
+                                                    C.POINTER(C.c_uint64), C.POINTER(FlacInfo)]
+        L.sauAmd_render_file_flac_loudness_lpc24.restype = C.c_bool
+        L.sauAmd_render_file_flac_loudness_lpc24.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_int, C.c_uint32, C.c_uint32,
+                                                             C.c_double, C.c_float, C.c_int, C.POINTER(C.c_uint64), C.POINTER(Loudness),
+                                                             C.POINTER(C.c_float), C.POINTER(LimiterStats), C.POINTER(FlacInfo)]
     if hasattr(L, "sauAmd_Batch_create_flac_f32"):  # 24 bits and float-fed encoders (SAU_AMD_LIB may name an older build)
         L.sauAmd_flac_header_bits.restype = C.c_size_t
         L.sauAmd_flac_header_bits.argtypes = [C.c_uint32, C.c_int, C.c_uint32, C.c_int, C.POINTER(FlacInfo), C.c_void_p, C.c_size_t]
@@ -829,6 +842,23 @@ def flac_encode_block_s32(x, channels, block_frames, frame_number, bits=24, max_
     return bytes(out)
 
 
+def flac_encode_block_lpc24(x, channels, block_frames, frame_number, max_lpc_order=0):
+    """sauAmd_flac_encode_block_lpc24: the host's restatement of one 24-bit frame in the LPC mode ("LPC at 24 bits") from
+    interleaved int32 samples -> bytes (b"" when the arguments are refused)"""
+    x = np.ascontiguousarray(x, np.int32)
+    n = len(x) // max(int(channels), 1)
+    L = lib()
+
+    def call(out, cap):
+        return L.sauAmd_flac_encode_block_lpc24(x.ctypes.data, n, channels, block_frames, frame_number, _lpc_order(max_lpc_order), out, cap)
+    size = call(None, 0)
+    if not size:
+        return b""
+    out = (C.c_uint8 * size)()
+    assert call(out, size) == size
+    return bytes(out)
+
+
 def _lpc_order(max_lpc_order):
     """0 .. 2^32 - 1 as the library takes it (it refuses what is above 8); anything else is refused here the same way"""
     m = int(max_lpc_order)
@@ -1002,6 +1032,29 @@ def render_file_flac_loudness(program, srate, path, channels=1, block_frames=0, 
                                                               1 if limited else 0, backends[0], backends[1], C.byref(n))
     if not ok:
         raise RuntimeError("sauAmd_render_file_flac_loudness failed: " + last_error(L))
+    return n.value, ld, gain.value, (st if limited else None), info
+
+
+def render_file_flac_lpc24(program, srate, path, channels=1, block_frames=0, max_lpc_order=0, gain=1.0):
+    """sauAmd_render_file_flac_lpc24: render_file_flac_f32 at 24 bits with the encoder of "LPC at 24 bits" -> (frames, FlacInfo)"""
+    n, info = C.c_uint64(), FlacInfo()
+    L = _used(lib())
+    if not L.sauAmd_render_file_flac_lpc24(program.ptr, srate, os.fsencode(path), channels, block_frames, _lpc_order(max_lpc_order),
+                                           gain, C.byref(n), C.byref(info)):
+        raise RuntimeError("sauAmd_render_file_flac_lpc24 failed: " + last_error(L))
+    return n.value, info
+
+
+def render_file_flac_loudness_lpc24(program, srate, path, channels=1, block_frames=0, max_lpc_order=0, target_lufs=-23.0,
+                                    max_true_peak=1.0, limited=False):
+    """sauAmd_render_file_flac_loudness_lpc24: render_file_flac_loudness at 24 bits with the encoder of "LPC at 24 bits"
+    -> (frames, Loudness, gain, LimiterStats or None, FlacInfo)"""
+    n, ld, gain, st, info = C.c_uint64(), Loudness(), C.c_float(), LimiterStats(), FlacInfo()
+    L = _used(lib())
+    if not L.sauAmd_render_file_flac_loudness_lpc24(program.ptr, srate, os.fsencode(path), channels, block_frames,
+                                                    _lpc_order(max_lpc_order), target_lufs, max_true_peak, 1 if limited else 0,
+                                                    C.byref(n), C.byref(ld), C.byref(gain), C.byref(st), C.byref(info)):
+        raise RuntimeError("sauAmd_render_file_flac_loudness_lpc24 failed: " + last_error(L))
     return n.value, ld, gain.value, (st if limited else None), info
 
 
@@ -1393,6 +1446,11 @@ class Batch:
         rows and per-row gains. Close it before the batch."""
         return Flac(self, n_rows, channels, block_frames, max_lpc_order, bits=bits)
 
+    def create_flac_lpc24(self, n_rows, channels, block_frames=0, max_lpc_order=0):
+        """sauAmd_Batch_create_flac_lpc24: a float-fed Flac encoder of 24 bits per sample in the LPC mode ("LPC at 24 bits");
+        fed, read and closed like create_flac_f32's. Close it before the batch."""
+        return Flac(self, n_rows, channels, block_frames, max_lpc_order, bits=24, lpc24=True)
+
     def create_flac_lpc(self, n_rows, channels, block_frames=0, max_lpc_order=0):
         """(tests) sauAmd_Batch_create_flac_lpc whatever max_lpc_order is -- create_flac reaches it only with an order above 0 --:
         with 0 the encoder create_flac makes, by the other entry point"""
@@ -1498,13 +1556,17 @@ class Flac:
     row r's next frames[r] frames from device memory, on the batch's stream; ``read`` waits and returns the rows' encoded bytes.
     Close it before its batch."""
 
-    def __init__(self, batch, n_rows, channels, block_frames=0, max_lpc_order=0, lpc_entry=False, bits=None):
+    def __init__(self, batch, n_rows, channels, block_frames=0, max_lpc_order=0, lpc_entry=False, bits=None, lpc24=False):
         self._L = batch._L
         self.n_rows, self.channels, self.block_frames = int(n_rows), int(channels), int(block_frames)
         self.max_lpc_order = _lpc_order(max_lpc_order)
         self.bits = None if bits is None else int(bits)  # (None: fed int16 rows; 16 or 24: fed float rows)
         entry = "sauAmd_Batch_create_flac_lpc" if self.max_lpc_order or lpc_entry else "sauAmd_Batch_create_flac"
-        if self.bits is not None:
+        if lpc24:  # (bits is 24)
+            entry = "sauAmd_Batch_create_flac_lpc24"
+            self._e = _used(self._L).sauAmd_Batch_create_flac_lpc24(batch._b, self.n_rows, self.channels, self.block_frames,
+                                                                    self.max_lpc_order)
+        elif self.bits is not None:
             entry = "sauAmd_Batch_create_flac_f32"
             self._e = _used(self._L).sauAmd_Batch_create_flac_f32(batch._b, self.n_rows, self.channels, self.block_frames,
                                                                   self.bits, self.max_lpc_order)

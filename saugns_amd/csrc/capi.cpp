@@ -745,6 +745,30 @@ extern "C" sauAmdFlac *sauAmd_Batch_create_flac_f32(sauAmdBatch *b, size_t n_row
 	return nullptr;
 }
 
+/* ---- LPC at 24 bits (include/saugns_amd.h, FLAC, "LPC at 24 bits"): the entry points above keep refusing (24, M > 0) ---- */
+extern "C" size_t sauAmd_flac_encode_block_lpc24(const int32_t *x, uint32_t n, int channels, uint32_t block_frames, uint32_t frame_number,
+		uint32_t max_lpc_order, uint8_t *out, size_t cap) {
+	try {
+		return sauengine::flac_encode_block_lpc24(x, n, channels, block_frames, frame_number, max_lpc_order, out, cap);
+	} catch (const std::exception &) { /* (nothing C++ crosses the C ABI) */
+		return 0;
+	}
+}
+
+extern "C" sauAmdFlac *sauAmd_Batch_create_flac_lpc24(sauAmdBatch *b, size_t n_rows, int channels, uint32_t block_frames, uint32_t max_lpc_order) {
+	std::string err;
+	try {
+		if (!b || !n_rows || n_rows > sauflac::FLAC_MAX_ROWS || !sauengine::flac_params_ok(channels, block_frames) ||
+		    max_lpc_order > sauflac::FLAC_LPC_MAX) err = "bad argument";
+		else if (sauengine::FlacEncoder *e = b->engine->backend()->create_flac_lpc24(n_rows, (uint32_t)channels, block_frames, max_lpc_order, err))
+			return new sauAmdFlac{e};
+	} catch (const std::exception &ex) {
+		err = std::string("internal error: ") + ex.what();
+	}
+	report("flac", err);
+	return nullptr;
+}
+
 extern "C" bool sauAmd_Flac_feed_f32(sauAmdFlac *e, const void *rows, size_t pitch_bytes, const uint32_t *frames, const float *gains, int finish) {
 	std::string err;
 	try {

@@ -63,6 +63,15 @@ bool render_file_flac_loudness(const sauProgram *prg, uint32_t srate, const char
 		uint32_t max_lpc_order, double target_lufs, float max_true_peak, bool limited,
 		const std::function<sauengine::Backend *(std::string &)> &make_backend, uint64_t *frames_out, sauAmdLoudness *loud_out,
 		float *gain_out, sauAmdLimiterStats *stats_out, sauAmdFlacInfo *info_out, std::string &err);
+/* sauAmd_render_file_flac_lpc24's and sauAmd_render_file_flac_loudness_lpc24's bodies (sndout.cpp): the two above at 24 bits over
+ * Backend::create_flac_lpc24's encoder, max_lpc_order 0 .. 8 */
+bool render_file_flac_lpc24(const sauProgram *prg, uint32_t srate, const char *path, int channels, uint32_t block_frames,
+		uint32_t max_lpc_order, float gain, const std::function<sauengine::Backend *(std::string &)> &make_backend, uint64_t *frames_out,
+		sauAmdFlacInfo *info_out, std::string &err);
+bool render_file_flac_loudness_lpc24(const sauProgram *prg, uint32_t srate, const char *path, int channels, uint32_t block_frames,
+		uint32_t max_lpc_order, double target_lufs, float max_true_peak, bool limited,
+		const std::function<sauengine::Backend *(std::string &)> &make_backend, uint64_t *frames_out, sauAmdLoudness *loud_out,
+		float *gain_out, sauAmdLimiterStats *stats_out, sauAmdFlacInfo *info_out, std::string &err);
 /* the thread's sauAmd_last_error text (capi.cpp), with the line on stderr */
 void set_last_error(const char *where, const std::string &err);
 } /* namespace sauamd_internal */

@@ -135,6 +135,10 @@ size_t flac_header_bits(uint32_t srate, int channels, uint32_t block_frames, int
 size_t flac_encode_block_s32(const int32_t *x, uint32_t n, int channels, uint32_t block_frames, uint32_t frame_number, int bits,
 		uint32_t max_lpc_order, uint8_t *out, size_t cap);
 bool flac_quantize(const float *x, size_t n, float gain, int bits, int32_t *out);
+/* LPC at 24 bits (the header's paragraph of that name): one frame of int32 samples in -2^23 .. 2^23 - 1 with the LPC mode's
+ * max_lpc_order (0 .. 8; 0: flac_encode_block_s32's bytes at 24 bits) -- else 0. */
+size_t flac_encode_block_lpc24(const int32_t *x, uint32_t n, int channels, uint32_t block_frames, uint32_t frame_number, uint32_t max_lpc_order,
+		uint8_t *out, size_t cap);
 /* MD5 (the header's "MD5"; the arithmetic is sau_md5.h's). flac_header_md5: flac_header_bits with STREAMINFO's MD5 field, bytes
  * 26 .. 41, taken from md5 (NULL: zeros). flac_md5: the digest of n interleaved samples of `bits` (16 or 24) per sample as the
  * device makes it; false for other bits, a sample that does not fit them or a NULL pointer with n > 0. */
@@ -472,6 +476,12 @@ public:
 	virtual FlacEncoder *create_flac_f32(size_t n_rows, uint32_t channels, uint32_t block_frames, int bits, uint32_t max_lpc_order, std::string &err) {
 		(void)n_rows; (void)channels; (void)block_frames; (void)bits; (void)max_lpc_order;
 		err = "this backend has no float-fed FLAC encoder"; return nullptr;
+	}
+	/* A float-fed encoder of 24 bits per sample with the LPC mode's max_lpc_order (0 .. 8; the header's "LPC at 24 bits"). 0 is
+	 * create_flac_f32 at 24 bits; this default refuses every other value, as create_flac_lpc's does. */
+	virtual FlacEncoder *create_flac_lpc24(size_t n_rows, uint32_t channels, uint32_t block_frames, uint32_t max_lpc_order, std::string &err) {
+		if (!max_lpc_order) return create_flac_f32(n_rows, channels, block_frames, 24, 0, err);
+		err = "this backend's FLAC encoder has no LPC mode at 24 bits"; return nullptr;
 	}
 	/* A quantiser of n_rows streams on the backend's stream (include/saugns_amd.h, section "Dither and noise shaping"); the
 	 * arguments have been looked at. A backend without one refuses -- this default -- and nothing changes. */

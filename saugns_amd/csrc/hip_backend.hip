@@ -15,7 +15,7 @@
  *   k_limiter.h     lim_env_kernel, lim_gain_kernel, lim_finish_kernel, lim_carry_kernel (the look-ahead true-peak limiter)
  *   k_spectrum.h    spec_segment_kernel, spec_finish_kernel, spec_carry_kernel (Welch power spectra of fed rows)
  *   k_flac.h        flac_analyze_kernel, flac_scan_kernel, flac_write_kernel, flac_carry_kernel (FLAC frames of fed rows, built
- *                   for int16 and for int32 samples: FlacS16, FlacS32; the <FlacS16, true> builds of the first and the third
+ *                   for int16 and for int32 samples: FlacS16, FlacS32; the <.., true> builds of the first and the third
  *                   hold the LPC mode), flac_quant_kernel (a float-fed encoder's rows)
  *   k_md5.h         flac_md5_kernel, flac_md5_wide_kernel (the MD5 of an encoder's unencoded samples, a wave per row; opt-in)
  *   k_dither.h      dither_flat_kernel, dither_shape_kernel (the 16-bit quantiser stage: TPDF dither, error-feedback noise shaping)
@@ -2344,8 +2344,7 @@ public:
 				if (plan.jobs) {
 					/* (max_lpc_order 0 runs the kernels without the LPC mode's code: the encoder as it was before that mode) */
 					auto analyze = flac_analyze_kernel<W, false>, write = flac_write_kernel<W, false>;
-					if constexpr (W::BITS == 16)
-						if (M_) { analyze = flac_analyze_kernel<W, true>; write = flac_write_kernel<W, true>; }
+					if (M_) { analyze = flac_analyze_kernel<W, true>; write = flac_write_kernel<W, true>; }
 					hipLaunchKernelGGL(analyze, dim3(plan.jobs), dim3(plan.analyze_threads), plan.analyze_lds, st, fp);
 					HIP_OK(hipGetLastError());
 					hipLaunchKernelGGL(flac_scan_kernel, dim3(plan.rows), dim3(FLAC_THREADS), 0, st, fp);
@@ -2464,10 +2463,19 @@ public:
 		return e;
 	}
 	sauengine::FlacEncoder *create_flac_f32(size_t n_rows, uint32_t channels, uint32_t block_frames, int bits, uint32_t max_lpc_order, std::string &err) override {
+		return create_flac_float(n_rows, channels, block_frames, bits, max_lpc_order, false, err);
+	}
+	/* the float-fed encoder of 24 bits in the LPC mode (the header's "LPC at 24 bits"); order 0 is create_flac_f32's encoder */
+	sauengine::FlacEncoder *create_flac_lpc24(size_t n_rows, uint32_t channels, uint32_t block_frames, uint32_t max_lpc_order, std::string &err) override {
+		return create_flac_float(n_rows, channels, block_frames, 24, max_lpc_order, true, err);
+	}
+	/* (lpc24: asked for through create_flac_lpc24 -- create_flac_f32 keeps refusing an order at 24 bits) */
+	sauengine::FlacEncoder *create_flac_float(size_t n_rows, uint32_t channels, uint32_t block_frames, int bits, uint32_t max_lpc_order, bool lpc24,
+			std::string &err) {
 		use_device();
 		if (!join_mixer("create_flac", err)) return nullptr;
 		if (!sauengine::flac_params_ok((int)channels, block_frames) || !n_rows || !sauflac::flac_bits_ok(bits) || max_lpc_order > sauflac::FLAC_LPC_MAX) { err = "bad argument"; return nullptr; }
-		if (bits == 24 && max_lpc_order) { err = "bad argument: no LPC mode at 24 bits"; return nullptr; }
+		if (bits == 24 && max_lpc_order && !lpc24) { err = "bad argument: no LPC mode at 24 bits"; return nullptr; }
 		if (n_rows > sauflac::FLAC_MAX_ROWS) { err = "bad argument: more than 65535 rows"; return nullptr; }
 		Flac *e = new Flac(this, n_rows, channels, block_frames, max_lpc_order, true, (uint32_t)bits);
 		if (!e->init(err)) { delete e; return nullptr; }

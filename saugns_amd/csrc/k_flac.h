@@ -22,8 +22,8 @@
  *       float-fed encoder's rows, into rows of the encoder's own, ahead of the other kernels. A source row need only be
  *       float-aligned: thread 0 takes the samples ahead of the row's first 16-byte boundary one by one, every other thread
  *       four from a 16-byte load, the row's end again one by one.
- * The LPC mode (the header's "The LPC mode", max_lpc_order > 0; 16 bits only) is a second build of the first and the third
- * kernel, flac_analyze_kernel<FlacS16, true> and flac_write_kernel<FlacS16, true>; the <.., false> builds hold none of its
+ * The LPC mode (the header's "The LPC mode" and "LPC at 24 bits", max_lpc_order > 0) is a second build of the first and the third
+ * kernel at either width, flac_analyze_kernel<W, true> and flac_write_kernel<W, true>; the <.., false> builds hold none of its
  * code and are what an encoder of order 0 launches. In the analysis of a whole block the candidate's wave goes on behind the
  * FIXED choice (flac_analyze_lpc): the windowed autocorrelation in 64-bit integers, a lane a run of n / 64 frames, the shares
  * added by the xor-shuffle sum; the Levinson-Durbin recursion and the quantisation of every order in f64 on lane 0, serial, in
@@ -44,7 +44,12 @@
  *   - the Rice parameters are 0 .. 30 with five bits each (method 01), s_fine is [4][16 * 31];
  *   - samples take 24 or 25 bits in the frame, whose header says so and whose bound is larger;
  *   - the analysis takes 8.25 B bytes (stereo) + 17 KiB: 51 KiB at B = 4096; the writer 8.25 B + the frame's bound: 57 KiB;
- *   - no LPC mode. */
+ *   - the LPC build's analysis adds FlacLpcLds, 1.1 KiB: 33792 + 17200 + 1104 = 52096 bytes at B = 4096 stereo, the most any
+ *     kernel here takes and under the 64 KiB a workgroup may have (launch_plan.h: FLAC_ANALYZE_STATIC_LDS);
+ *   - in the LPC mode the window product is 64-bit (>> 11), the coefficient sum is 64-bit (below 2^39), and lane 0 takes the
+ *     orders that step 5b excludes out of the mask (flac_lpc_guard) before the barrier that publishes it; a residual then is
+ *     below 2^31 in size and its u takes 32 bits, which the 64-bit sums, flac_put's 32-bit field and the writer's bit counts
+ *     (a subframe is cheaper than its verbatim form, below 2^18 bits) all hold. */
 #ifndef SAU_K_FLAC_H
 #define SAU_K_FLAC_H
 
@@ -90,10 +95,12 @@ __device__ __forceinline__ int32_t flac_at(const uint32_t *s_w, const unsigned c
  * coding method's two bits, the type of a lane's sums over its run, and how a block lies in LDS:
  *   lds_words  the words of a staged block; lds_words(B, 1) is R0, where the second array begins if there is one;
  *   stage      block j of the row's feed, n frames, into s_w: a pending frame, or one of the fed row;
- *   at         candidate c's sample i (0 below the block's start). c is the same for a whole wave. */
+ *   at         candidate c's sample i (0 below the block's start). c is the same for a whole wave.
+ *   at_in      the same for an i that is inside the block: no look at its sign. */
 struct FlacS16 { /* a frame is one word, L | R << 16 */
 	typedef int16_t sample_t;
 	typedef uint32_t run_t; /* (a lane's share fits 32 bits: at most 64 values below 2^21) */
+	typedef int32_t acc_t;  /* the LPC mode's sum of q[j] * s_{i-1-j}: below 2^30 */
 	static constexpr unsigned BITS = 16, NK = flac_nk(16), K_BITS = flac_k_width(16), METHOD = 0;
 	static __device__ __forceinline__ unsigned lds_words(const unsigned B, const unsigned channels) { return B + (B >> 5); }
 	static __device__ __forceinline__ void stage(const FlacParams &P, const FlacRow &d, const unsigned row, const unsigned j, const unsigned n,
@@ -112,10 +119,12 @@ struct FlacS16 { /* a frame is one word, L | R << 16 */
 		}
 	}
 	static __device__ __forceinline__ int32_t at(const uint32_t *s_w, const unsigned R0, const unsigned c, const int i) { return flac_at(s_w, c, i); }
+	static __device__ __forceinline__ int32_t at_in(const uint32_t *s_w, const unsigned R0, const unsigned c, const unsigned i) { return flac_cand(s_w[flac_ix(i)], c); }
 };
 struct FlacS32 { /* L (or the one channel) at s_w, R at s_w + R0; mono has c == 0 only and no R array */
 	typedef int32_t sample_t;
 	typedef unsigned long long run_t; /* (64 values of up to 2^28, of u up to 2^30) */
+	typedef int64_t acc_t;  /* the LPC mode's sum of q[j] * s_{i-1-j}: below 2^39 */
 	static constexpr unsigned BITS = 24, NK = flac_nk(24), K_BITS = flac_k_width(24), METHOD = 1;
 	static __device__ __forceinline__ unsigned lds_words(const unsigned B, const unsigned channels) { return (B + (B >> 5)) * channels; }
 	static __device__ __forceinline__ void stage(const FlacParams &P, const FlacRow &d, const unsigned row, const unsigned j, const unsigned n,
@@ -140,6 +149,12 @@ struct FlacS32 { /* L (or the one channel) at s_w, R at s_w + R0; mono has c == 
 		if (c == FLAC_CAND_R) return (int32_t)s_w[R0 + x];
 		return flac_cand((int32_t)s_w[x], (int32_t)s_w[R0 + x], c);
 	}
+	static __device__ __forceinline__ int32_t at_in(const uint32_t *s_w, const unsigned R0, const unsigned c, const unsigned i) {
+		const unsigned x = flac_ix(i);
+		if (c == FLAC_CAND_L) return (int32_t)s_w[x];
+		if (c == FLAC_CAND_R) return (int32_t)s_w[R0 + x];
+		return flac_cand((int32_t)s_w[x], (int32_t)s_w[R0 + x], c);
+	}
 };
 
 __device__ __forceinline__ unsigned long long flac_wave_sum(unsigned long long v, const int steps) {
@@ -148,9 +163,11 @@ __device__ __forceinline__ unsigned long long flac_wave_sum(unsigned long long v
 }
 
 /* the sum of q[j] * s_{i-1-j}, j < m (i >= m): the coefficients are read from LDS, where a run-time index costs nothing */
-__device__ __forceinline__ int32_t flac_lpc_sum(const uint32_t *s_w, const unsigned c, const int16_t *q, const unsigned m, const unsigned i) {
-	int32_t sum = 0;
-	for (unsigned j = 0; j < m; ++j) sum += (int32_t)q[j] * flac_cand(s_w[flac_ix(i - 1 - j)], c);
+template <typename W>
+__device__ __forceinline__ typename W::acc_t flac_lpc_sum(const uint32_t *s_w, const unsigned R0, const unsigned c, const int16_t *q, const unsigned m,
+		const unsigned i) {
+	typename W::acc_t sum = 0;
+	for (unsigned j = 0; j < m; ++j) sum += (typename W::acc_t)q[j] * W::at_in(s_w, R0, c, i - 1 - j);
 	return sum;
 }
 
@@ -159,7 +176,9 @@ __device__ __forceinline__ int32_t flac_lpc_sum(const uint32_t *s_w, const unsig
  * frames, the window's value computed where it is used, products and sums in 64-bit integers, the lanes' shares added by the
  * xor-shuffle sum --, steps 3 to 5 on lane 0 with the orders' coefficient tables left in LDS, the sums of |r| of all
  * candidate orders in one walk of the lane's run, the chosen order's sums of u >> k per finest partition (64 bits: an LPC
- * residual may take 32), the nodes' costs, and the choice against what flac_finish_sub has left in s_cand[c]. */
+ * residual may take 32), the nodes' costs, and the choice against what flac_finish_sub has left in s_cand[c]. At 24 bits the
+ * samples come through W::at (M and S are formed where they are read), the coefficient sums are 64-bit, and lane 0 applies
+ * step 5b to the mask. */
 struct FlacLpcLds {
 	double r[4][FLAC_LPC_MAX + 1];
 	double a[4][FLAC_LPC_MAX];
@@ -167,9 +186,13 @@ struct FlacLpcLds {
 	uint8_t shift[4][FLAC_LPC_MAX];
 	uint32_t mask[4];
 };
-__device__ __forceinline__ void flac_analyze_lpc(const FlacParams &P, const uint32_t *s_w, FlacLpcLds &L, uint64_t (*s_fine)[FLAC_FINE * FLAC_NK],
-		uint64_t (*s_node_cost)[32], uint8_t (*s_node_k)[32], FlacSub *s_cand, const unsigned c, const unsigned lane, const bool equal) {
-	const unsigned n = P.B, M = P.max_lpc, log2B = 31 - __clz((int)P.B), bps = flac_cand_bps(c, 16);
+static_assert(sizeof(FlacLpcLds) == FLAC_LPC_LDS, "launch_plan.h counts FlacLpcLds in the analysis' LDS");
+template <typename W>
+__device__ __forceinline__ void flac_analyze_lpc(const FlacParams &P, const uint32_t *s_w, const unsigned R0, FlacLpcLds &L,
+		uint64_t (*s_fine)[FLAC_FINE * W::NK], uint64_t (*s_node_cost)[32], uint8_t (*s_node_k)[32], FlacSub *s_cand, const unsigned c,
+		const unsigned lane, const bool equal) {
+	typedef typename W::acc_t acc_t;
+	const unsigned n = P.B, M = P.max_lpc, log2B = 31 - __clz((int)P.B), bps = flac_cand_bps(c, W::BITS);
 	const unsigned run = n >> 6, i0 = lane * run;
 	/* steps 1 and 2 */
 	long long R[FLAC_LPC_MAX + 1];
@@ -179,9 +202,9 @@ __device__ __forceinline__ void flac_analyze_lpc(const FlacParams &P, const uint
 		int32_t h[FLAC_LPC_MAX + 1]; /* h[l] = ws[i - l] */
 #pragma unroll
 		for (unsigned l = 1; l <= FLAC_LPC_MAX; ++l)
-			h[l] = i0 + 1 >= l + 1 ? flac_lpc_windowed(flac_at(s_w, c, (int)(i0 - l)), flac_lpc_window(i0 - l, n, log2B)) : 0;
+			h[l] = i0 + 1 >= l + 1 ? flac_lpc_windowed(W::at(s_w, R0, c, (int)(i0 - l)), flac_lpc_window(i0 - l, n, log2B), W::BITS) : 0;
 		for (unsigned i = i0; i < i0 + run; ++i) {
-			h[0] = flac_lpc_windowed(flac_at(s_w, c, (int)i), flac_lpc_window(i, n, log2B));
+			h[0] = flac_lpc_windowed(W::at(s_w, R0, c, (int)i), flac_lpc_window(i, n, log2B), W::BITS);
 #pragma unroll
 			for (unsigned l = 0; l <= FLAC_LPC_MAX; ++l) R[l] += (long long)h[0] * h[l]; /* (h[l] is 0 where i < l; orders above M are not read) */
 #pragma unroll
@@ -199,6 +222,7 @@ __device__ __forceinline__ void flac_analyze_lpc(const FlacParams &P, const uint
 #pragma unroll
 			for (unsigned l = 0; l <= FLAC_LPC_MAX; ++l) L.r[c][l] = (double)(R[l] >> g);
 			mask = flac_lpc_orders(L.r[c], M, L.a[c], L.q[c], L.shift[c]);
+			if (W::BITS == 24) mask = flac_lpc_guard(mask, L.q[c], L.shift[c], bps); /* step 5b */
 		}
 		L.mask[c] = mask;
 	}
@@ -210,16 +234,16 @@ __device__ __forceinline__ void flac_analyze_lpc(const FlacParams &P, const uint
 	for (unsigned m = 1; m <= FLAC_LPC_MAX; ++m) A[m - 1] = 0;
 	if (mask)
 		for (unsigned i = i0 > M ? i0 : M; i < i0 + run; ++i) {
-			const int32_t s0 = flac_at(s_w, c, (int)i);
+			const int32_t s0 = W::at(s_w, R0, c, (int)i);
 			int32_t hs[FLAC_LPC_MAX];
 #pragma unroll
-			for (unsigned j = 0; j < FLAC_LPC_MAX; ++j) hs[j] = j < M ? flac_at(s_w, c, (int)(i - 1 - j)) : 0;
+			for (unsigned j = 0; j < FLAC_LPC_MAX; ++j) hs[j] = j < M ? W::at(s_w, R0, c, (int)(i - 1 - j)) : 0;
 #pragma unroll
 			for (unsigned m = 1; m <= FLAC_LPC_MAX; ++m)
 				if (mask & (1u << (m - 1))) {
-					int32_t sum = 0;
+					acc_t sum = 0;
 #pragma unroll
-					for (unsigned j = 0; j < m; ++j) sum += (int32_t)L.q[c][(m - 1) * FLAC_LPC_MAX + j] * hs[j];
+					for (unsigned j = 0; j < m; ++j) sum += (acc_t)L.q[c][(m - 1) * FLAC_LPC_MAX + j] * hs[j];
 					A[m - 1] += flac_abs(flac_lpc_residual(s0, sum, L.shift[c][m - 1]));
 				}
 		}
@@ -231,43 +255,42 @@ __device__ __forceinline__ void flac_analyze_lpc(const FlacParams &P, const uint
 #pragma unroll
 		for (unsigned t = 1; t <= FLAC_LPC_MAX; ++t)
 			if (mask & (1u << (t - 1))) {
-				const uint64_t e = flac_lpc_est(A[t - 1], n, M, t, bps);
+				const uint64_t e = flac_lpc_est_nk<W::NK>(A[t - 1], n, M, t, bps);
 				if (e < least) { least = e; m = t; }
 			}
 	}
 	/* step 8: the chosen order's sums of u >> k per finest partition */
-	unsigned long long f64[FLAC_NK];
+	unsigned long long f64[W::NK];
 #pragma unroll
-	for (unsigned k = 0; k < FLAC_NK; ++k) f64[k] = 0;
+	for (unsigned k = 0; k < W::NK; ++k) f64[k] = 0;
 	/* (m == 0, no candidate order: q and shift are then order 1's places, which nobody may have written -- they are not used;
 	 * the lanes still store their zero sums and reach the barriers with the other waves) */
 	const int16_t *q = &L.q[c][(m ? m - 1 : 0) * FLAC_LPC_MAX];
 	const unsigned shift = L.shift[c][m ? m - 1 : 0];
 	if (m)
 		for (unsigned i = i0 > m ? i0 : m; i < i0 + run; ++i) {
-			const uint32_t u = flac_zigzag(flac_lpc_residual(flac_at(s_w, c, (int)i), flac_lpc_sum(s_w, c, q, m, i), shift));
+			const uint32_t u = flac_zigzag(flac_lpc_residual(W::at(s_w, R0, c, (int)i), flac_lpc_sum<W>(s_w, R0, c, q, m, i), shift));
 #pragma unroll
-			for (unsigned k = 0; k < FLAC_NK; ++k) f64[k] += u >> k;
+			for (unsigned k = 0; k < W::NK; ++k) f64[k] += u >> k;
 		}
 #pragma unroll
-	for (unsigned k = 0; k < FLAC_NK; ++k) {
+	for (unsigned k = 0; k < W::NK; ++k) {
 		const unsigned long long s = flac_wave_sum(f64[k], 2);
-		if ((lane & 3) == 0) s_fine[c][(lane >> 2) * FLAC_NK + k] = s;
+		if ((lane & 3) == 0) s_fine[c][(lane >> 2) * W::NK + k] = s;
 	}
 	__syncthreads();
 	if (m && lane < FLAC_NODES) {
 		const unsigned p = 31 - __clz((int)(lane + 1)), part = lane + 1 - (1u << p);
 		unsigned k;
-		s_node_cost[c][lane] = flac_node_cost(s_fine[c], FLAC_NK, 4, p, part, n, m, &k);
+		s_node_cost[c][lane] = flac_node_cost(s_fine[c], W::NK, 4, p, part, n, m, &k);
 		s_node_k[c][lane] = (uint8_t)k;
 	}
 	__syncthreads();
-	if (m && lane == 0) flac_lpc_choose(&s_cand[c], n, m, q, shift, 4, s_node_cost[c], s_node_k[c]);
+	if (m && lane == 0) flac_lpc_choose(&s_cand[c], n, m, q, shift, 4, s_node_cost[c], s_node_k[c], W::BITS);
 }
 
 template <typename W, bool LPC>
 __global__ __launch_bounds__(256) void flac_analyze_kernel(const FlacParams P) {
-	static_assert(!LPC || W::BITS == 16, "the LPC mode is 16-bit only");
 	extern __shared__ uint32_t flac_lds[];
 	__shared__ uint64_t s_fine[4][FLAC_FINE * W::NK];
 	__shared__ uint64_t s_node_cost[4][32];
@@ -346,7 +369,7 @@ __global__ __launch_bounds__(256) void flac_analyze_kernel(const FlacParams P) {
 	__syncthreads();
 	if constexpr (LPC) if (n == P.B) { /* (the same for the whole workgroup) */
 		__shared__ FlacLpcLds s_lpc;
-		flac_analyze_lpc(P, s_w, s_lpc, s_fine, s_node_cost, s_node_k, s_cand, c, lane, equal);
+		flac_analyze_lpc<W>(P, s_w, R0, s_lpc, s_fine, s_node_cost, s_node_k, s_cand, c, lane, equal);
 		__syncthreads();
 	}
 	if (threadIdx.x == 0) flac_finish_frame(&P.frames[job], s_cand, P.channels, n, P.B, (uint32_t)(d.block0 + j));
@@ -408,14 +431,13 @@ __device__ __forceinline__ uint32_t flac_byte(const uint32_t *s_f, const uint32_
 template <typename W, bool LPC>
 __device__ __forceinline__ int32_t flac_sub_residual(const uint32_t *s_w, const unsigned R0, const FlacSub &s, const unsigned c, const unsigned o,
 		const unsigned i) {
-	if (LPC && s.type == FLAC_LPC) return flac_lpc_residual(flac_at(s_w, c, (int)i), flac_lpc_sum(s_w, c, s.q, o, i), s.shift);
+	if (LPC && s.type == FLAC_LPC) return flac_lpc_residual(W::at(s_w, R0, c, (int)i), flac_lpc_sum<W>(s_w, R0, c, s.q, o, i), s.shift);
 	return flac_residual(o, W::at(s_w, R0, c, (int)i), W::at(s_w, R0, c, (int)i - 1), W::at(s_w, R0, c, (int)i - 2), W::at(s_w, R0, c, (int)i - 3),
 			W::at(s_w, R0, c, (int)i - 4));
 }
 
 template <typename W, bool LPC>
 __global__ __launch_bounds__(FLAC_THREADS) void flac_write_kernel(const FlacParams P) {
-	static_assert(!LPC || W::BITS == 16, "the LPC mode is 16-bit only");
 	extern __shared__ uint32_t flac_lds[];
 	__shared__ uint32_t s_scan[4], s_crc;
 	__shared__ FlacFrameDesc s_fd; /* (in LDS: its fields are picked by index) */

@@ -1025,6 +1025,16 @@ inline uint64_t flac_row_worst(const FlacRow &r, uint32_t B, uint32_t channels, 
 	if (!r.n_blocks) return 0;
 	return (uint64_t)(r.n_blocks - 1) * sauflac::flac_frame_bound(B, channels, bits) + sauflac::flac_frame_bound(r.last_n, channels, bits);
 }
+/* flac_analyze_kernel's static LDS beside the staged block (k_flac.h): the finest partitions' sums [4][16 * nk] of 8 bytes, the
+ * nodes' costs and parameters [4][32], the four candidates' records, and in the LPC build FlacLpcLds -- counted for every
+ * encoder, whatever its order. With the staged block it has to fit the 64 KiB of a workgroup: 52096 bytes at 24 bits, B = 4096,
+ * stereo. */
+constexpr size_t FLAC_LPC_LDS = 4 * ((sauflac::FLAC_LPC_MAX + 1) * 8 + sauflac::FLAC_LPC_MAX * 8 + sauflac::FLAC_LPC_MAX * sauflac::FLAC_LPC_MAX * 2 +
+		sauflac::FLAC_LPC_MAX + 4);
+constexpr size_t FLAC_LDS_MAX = 65536;
+constexpr size_t flac_analyze_static_lds(unsigned bits) {
+	return 4 * sauflac::FLAC_FINE * sauflac::flac_nk(bits) * 8 + 4 * 32 * 8 + 4 * 32 + 4 * sizeof(sauflac::FlacSub) + FLAC_LPC_LDS;
+}
 struct FlacPlan {
 	bool ok = false;           /* false: B or channels not allowed, no row or more than 65535, a block number beyond 2^31 - 1, a feed
 	                            * with more than FLAC_MAX_JOBS blocks or a worst case above FLAC_MAX_UNREAD */
@@ -1047,6 +1057,7 @@ inline FlacPlan plan_flac(uint32_t block_frames, uint32_t channels, size_t n_row
 	p.analyze_threads = channels == 2 ? 256 : 64;
 	p.analyze_lds = (size_t)(B + B / 32) * sizeof(uint32_t) * (bits == 24 ? channels : 1);
 	p.write_lds = p.analyze_lds + ((size_t)sauflac::flac_frame_bound(B, channels, bits) / 4 + 2) * sizeof(uint32_t);
+	if (p.analyze_lds + flac_analyze_static_lds(bits) > FLAC_LDS_MAX) return p; /* (never, for the sizes allowed) */
 	p.pend_pitch = (size_t)B * channels;
 	uint64_t jobs = 0, out = 0;
 	for (size_t r = 0; rows && r < n_rows; ++r) {

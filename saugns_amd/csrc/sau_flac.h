@@ -26,7 +26,8 @@ constexpr unsigned FLAC_FINE = 16, FLAC_NODES = 31;  /* finest partitions of a w
  * 2^21, the Rice parameters are 0 .. 14 in four bits each (method 00). 24: int32 samples in -2^23 .. 2^23 - 1, the side channel
  * takes 25 bits; a FIXED residual is at most 16 * 2^24 in size, so the residual functions below serve both; u is below 2^30, the
  * parameters are 0 .. 30 in five bits (method 01), and everything summed over a lane's run, not only over a block, needs 64
- * bits. The LPC mode is 16-bit only. */
+ * bits. In the LPC mode ("LPC at 24 bits") the window product and the coefficient sum are 64-bit, and a residual is below 2^31
+ * in size -- flac_lpc_guard sees to that --, so its u takes all 32 bits: nothing behind an LPC residual may rely on 2^30. */
 constexpr int32_t FLAC_S24_MIN = -8388608, FLAC_S24_MAX = 8388607;
 SAU_FLAC_HD bool flac_bits_ok(int bits) { return bits == 16 || bits == 24; }
 SAU_FLAC_HD constexpr unsigned flac_k_width(unsigned bits) { return bits == 24 ? 5 : 4; } /* bits of a partition's parameter */
@@ -157,12 +158,16 @@ SAU_FLAC_HD void flac_finish_sub(FlacSub *s, unsigned cand, uint32_t n, bool all
 /* ---- the LPC mode (include/saugns_amd.h, FLAC, "The LPC mode": the steps' numbers are those of that text) ----
  * Sums over a block are integers, so whoever adds them in whatever order gets the same; the floating-point steps are a short
  * serial sequence of IEEE f64 operations in a stated order (the build is -ffp-contract=off), done by one lane or one thread. */
-/* step 1: the window's value at j, 0 .. 4095, and a windowed sample (|s| < 2^17: the product fits 32 bits) */
+/* step 1: the window's value at j, 0 .. 4095, and a windowed sample (|s| < 2^17: the product fits 32 bits; at 24 bits |s| <= 2^24,
+ * the product is 64-bit and the shift 11, so |ws| < 2^25 at both widths) */
 SAU_FLAC_HD int32_t flac_lpc_window(uint32_t j, uint32_t B, unsigned log2B) {
 	const int32_t d = (int32_t)(2 * j + 1) - (int32_t)B;
 	return (int32_t)((B * B - (uint32_t)(d * d)) >> (2 * log2B - 12));
 }
 SAU_FLAC_HD int32_t flac_lpc_windowed(int32_t s, int32_t w) { return (s * w) >> 3; }
+SAU_FLAC_HD int32_t flac_lpc_windowed(int32_t s, int32_t w, unsigned bits) {
+	return bits == 24 ? (int32_t)(((int64_t)s * w) >> 11) : flac_lpc_windowed(s, w);
+}
 /* step 3: the least shift that brings R[0] below 2^53 */
 SAU_FLAC_HD unsigned flac_lpc_f64_shift(int64_t r0) {
 	unsigned g = 0;
@@ -216,39 +221,62 @@ SAU_FLAC_HD uint32_t flac_lpc_orders(const double *r, unsigned M, double *a, int
 	}
 	return mask;
 }
-/* step 6 from the sum of q[j] * s_{i-1-j} */
+/* step 5b ("LPC at 24 bits"): the mask without the orders whose prediction could pass 2^30 in size -- S = the sum of |q[j]|,
+ * j < m; order m goes when (S << (bps - 1)) >> shift >= 2^30 (S < 2^15 and bps <= 25: below 2^40). Integers only, so host
+ * and device agree; the 16-bit rules have no such step and never come here. */
+SAU_FLAC_HD uint32_t flac_lpc_guard(uint32_t mask, const int16_t *q /* [(m - 1) * 8 + j] */, const uint8_t *shift /* [m - 1] */, unsigned bps) {
+	for (unsigned m = 1; m <= FLAC_LPC_MAX; ++m)
+		if (mask & (1u << (m - 1))) {
+			uint64_t S = 0;
+			for (unsigned j = 0; j < m; ++j) {
+				const int32_t v = q[(m - 1) * FLAC_LPC_MAX + j];
+				S += (uint64_t)(v < 0 ? -v : v);
+			}
+			if (((S << (bps - 1)) >> shift[m - 1]) >= (1ull << 30)) mask &= ~(1u << (m - 1));
+		}
+	return mask;
+}
+/* step 6 from the sum of q[j] * s_{i-1-j}: in 32 bits at 16 bits per sample; at 24 the sum is 64-bit (below 2^39 in size) and
+ * the residual, below 2^31 in size behind flac_lpc_guard, is narrowed */
 SAU_FLAC_HD int32_t flac_lpc_residual(int32_t s0, int32_t sum, unsigned shift) { return s0 - (sum >> shift); }
-/* step 7: what order m is estimated to cost, from A_m */
-SAU_FLAC_HD uint64_t flac_lpc_est(uint64_t abs_sum, uint32_t n, unsigned M, unsigned m, unsigned bps) {
+SAU_FLAC_HD int32_t flac_lpc_residual(int32_t s0, int64_t sum, unsigned shift) { return (int32_t)((int64_t)s0 - (sum >> shift)); }
+/* step 7: what order m is estimated to cost, from A_m; nk = flac_nk(bits), the parameters tried. The kernels name nk at compile
+ * time (the 16-bit build's loop is then the one it always had); the host hands it in. */
+template <unsigned NK>
+SAU_FLAC_HD uint64_t flac_lpc_est_nk(uint64_t abs_sum, uint32_t n, unsigned M, unsigned m, unsigned bps) {
 	uint64_t best = ~0ull;
-	for (unsigned k = 0; k < FLAC_NK; ++k) {
+	for (unsigned k = 0; k < NK; ++k) {
 		const uint64_t c = (uint64_t)(1 + k) * (n - M) + ((2 * abs_sum) >> k);
 		if (c < best) best = c;
 	}
 	return best + (uint64_t)m * (bps + FLAC_LPC_PREC);
 }
+SAU_FLAC_HD uint64_t flac_lpc_est(uint64_t abs_sum, uint32_t n, unsigned M, unsigned m, unsigned bps, unsigned nk) {
+	return nk == flac_nk(24) ? flac_lpc_est_nk<flac_nk(24)>(abs_sum, n, M, m, bps) : flac_lpc_est_nk<FLAC_NK>(abs_sum, n, M, m, bps);
+}
 /* the candidate order with the least estimate, the lowest on ties; 0 when there is none */
-SAU_FLAC_HD unsigned flac_lpc_pick_order(uint32_t mask, const uint64_t *abs_sum /* [m - 1] */, uint32_t n, unsigned M, unsigned bps) {
+SAU_FLAC_HD unsigned flac_lpc_pick_order(uint32_t mask, const uint64_t *abs_sum /* [m - 1] */, uint32_t n, unsigned M, unsigned bps, unsigned nk) {
 	unsigned best = 0;
 	uint64_t least = ~0ull;
 	for (unsigned m = 1; m <= M; ++m)
 		if (mask & (1u << (m - 1))) {
-			const uint64_t e = flac_lpc_est(abs_sum[m - 1], n, M, m, bps);
+			const uint64_t e = flac_lpc_est(abs_sum[m - 1], n, M, m, bps, nk);
 			if (e < least) { least = e; best = m; }
 		}
 	return best;
 }
 /* steps 8 and 9 on a record flac_finish_sub has left as VERBATIM or FIXED (the cheaper of the two, VERBATIM on ties): LPC of
- * order m takes its place where it costs less. node_cost, node_k: the nodes of the LPC residual's partitions (o = m). */
+ * order m takes its place where it costs less. node_cost, node_k: the nodes of the LPC residual's partitions (o = m). `bits`
+ * gives the sample's size and the four or five bits of a partition's parameter, as in flac_finish_sub. */
 SAU_FLAC_HD void flac_lpc_choose(FlacSub *s, uint32_t n, unsigned m, const int16_t *q, unsigned shift, unsigned fine_log2,
-		const uint64_t *node_cost, const uint8_t *node_k) {
+		const uint64_t *node_cost, const uint8_t *node_k, unsigned bits) {
 	if (s->type == FLAC_CONSTANT) return;
-	const unsigned bps = flac_cand_bps(s->cand, 16);
+	const unsigned bps = flac_cand_bps(s->cand, bits);
 	uint64_t best = ~0ull;
 	unsigned bp = 0;
 	for (unsigned p = 0; p <= fine_log2; ++p) {
 		uint64_t c = 0;
-		for (unsigned j = 0; j < (1u << p); ++j) c += 4 + node_cost[flac_node_index(p, j)];
+		for (unsigned j = 0; j < (1u << p); ++j) c += flac_k_width(bits) + node_cost[flac_node_index(p, j)];
 		if (c < best) { best = c; bp = p; }
 	}
 	const uint64_t lpc = 8 + (uint64_t)bps * m + 4 + 5 + (uint64_t)FLAC_LPC_PREC * m + 6 + best;

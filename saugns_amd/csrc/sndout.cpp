@@ -592,7 +592,8 @@ bool write_flac(const sauProgram *prg, uint32_t srate, const char *path, int cha
  * encoder of one stream (`bits` per sample) where that writer requantises and fetches; the file I/O is write_flac's. A backend
  * without float output or without the encoder says so before there is a file. */
 bool write_flac_scaled(const sauProgram *prg, uint32_t srate, const char *path, int channels, uint32_t block_frames, int bits,
-		uint32_t max_lpc_order, float gain, Backend *backend /* owned */, uint64_t *frames_out, sauengine::FlacInfo *info_out, std::string &err) {
+		uint32_t max_lpc_order, float gain, Backend *backend /* owned */, uint64_t *frames_out, sauengine::FlacInfo *info_out, std::string &err,
+		bool lpc24 = false /* the encoder of "LPC at 24 bits" (bits is 24) */) {
 	Engine *engine = Engine::create(&prg, 1, srate, backend, err);
 	if (!engine) return false;
 	const bool stereo = channels == 2;
@@ -601,7 +602,8 @@ bool write_flac_scaled(const sauProgram *prg, uint32_t srate, const char *path, 
 	file_lattice(srate, call, chunk);
 	engine->set_call_len(call);
 	if (!engine->set_format(sauengine::SF_F32, err)) { delete engine; return false; }
-	sauengine::FlacEncoder *enc = backend->create_flac_f32(1, (uint32_t)channels, B, bits, max_lpc_order, err);
+	sauengine::FlacEncoder *enc = lpc24 ? backend->create_flac_lpc24(1, (uint32_t)channels, B, max_lpc_order, err) :
+			backend->create_flac_f32(1, (uint32_t)channels, B, bits, max_lpc_order, err);
 	if (!enc) { delete engine; return false; }
 	const bool md5 = flac_file_md5();
 	if (md5 && !enc->set_md5(true, err)) { delete enc; delete engine; return false; }
@@ -670,7 +672,7 @@ bool write_flac_scaled(const sauProgram *prg, uint32_t srate, const char *path, 
  * the D-frame tail run fed too and as the finish; the file I/O is write_flac's. */
 bool write_flac_limited(const sauProgram *prg, uint32_t srate, const char *path, int channels, uint32_t block_frames, int bits,
 		uint32_t max_lpc_order, float pre_gain, float ceiling, Backend *backend /* owned */, uint64_t *frames_out,
-		sauengine::LimiterStats *stats_out, sauengine::FlacInfo *info_out, std::string &err) {
+		sauengine::LimiterStats *stats_out, sauengine::FlacInfo *info_out, std::string &err, bool lpc24 = false /* as write_flac_scaled's */) {
 	Engine *engine = Engine::create(&prg, 1, srate, backend, err);
 	if (!engine) return false;
 	const bool stereo = channels == 2;
@@ -681,7 +683,8 @@ bool write_flac_limited(const sauProgram *prg, uint32_t srate, const char *path,
 	engine->set_call_len(call);
 	/* a backend without float output, without a limiter or without the encoder says so here, before there is a file */
 	if (!engine->set_format(sauengine::SF_F32, err) || !engine->begin_limited(pre_gain, ceiling, stereo, err)) { delete engine; return false; }
-	sauengine::FlacEncoder *enc = backend->create_flac_f32(1, (uint32_t)channels, B, bits, max_lpc_order, err);
+	sauengine::FlacEncoder *enc = lpc24 ? backend->create_flac_lpc24(1, (uint32_t)channels, B, max_lpc_order, err) :
+			backend->create_flac_f32(1, (uint32_t)channels, B, bits, max_lpc_order, err);
 	if (!enc) { delete engine; return false; }
 	const bool md5 = flac_file_md5();
 	if (md5 && !enc->set_md5(true, err)) { delete enc; delete engine; return false; }
@@ -931,19 +934,46 @@ bool flac_f32_params_ok(int channels, uint32_t block_frames, int bits, uint32_t 
 
 extern "C" int sauAmd_set_flac_file_md5(int on) { return g_flac_file_md5.exchange(on ? 1 : 0, std::memory_order_relaxed); }
 
-bool sauamd_internal::render_file_flac_f32(const sauProgram *prg, uint32_t srate, const char *path, int channels, uint32_t block_frames,
-		int bits, uint32_t max_lpc_order, float gain, const std::function<Backend *(std::string &)> &make_backend, uint64_t *frames_out,
-		sauAmdFlacInfo *info_out, std::string &err) {
+/* render_file_flac_f32's body, and with lpc24 render_file_flac_lpc24's: 24 bits, any order up to 8 */
+static bool flac_f32_file(const sauProgram *prg, uint32_t srate, const char *path, int channels, uint32_t block_frames,
+		int bits, uint32_t max_lpc_order, float gain, bool lpc24, const std::function<Backend *(std::string &)> &make_backend,
+		uint64_t *frames_out, sauAmdFlacInfo *info_out, std::string &err) {
 	if (frames_out) *frames_out = 0;
-	if (!prg || !path || !srate || srate > 655350u || !flac_f32_params_ok(channels, block_frames, bits, max_lpc_order) ||
-	    !(gain >= -FLT_MAX && gain <= FLT_MAX)) { /* (a NaN fails both comparisons) */
+	if (!prg || !path || !srate || srate > 655350u || !flac_f32_params_ok(channels, block_frames, bits, lpc24 ? 0 : max_lpc_order) ||
+	    max_lpc_order > sauflac::FLAC_LPC_MAX || !(gain >= -FLT_MAX && gain <= FLT_MAX)) { /* (a NaN fails both comparisons) */
 		err = "bad argument";
 		return false;
 	}
 	Backend *backend = make_backend(err);
 	if (!backend) return false;
 	return write_flac_scaled(prg, srate, path, channels, block_frames, bits, max_lpc_order, gain, backend, frames_out,
-			(sauengine::FlacInfo *)info_out, err);
+			(sauengine::FlacInfo *)info_out, err, lpc24);
+}
+
+bool sauamd_internal::render_file_flac_f32(const sauProgram *prg, uint32_t srate, const char *path, int channels, uint32_t block_frames,
+		int bits, uint32_t max_lpc_order, float gain, const std::function<Backend *(std::string &)> &make_backend, uint64_t *frames_out,
+		sauAmdFlacInfo *info_out, std::string &err) {
+	return flac_f32_file(prg, srate, path, channels, block_frames, bits, max_lpc_order, gain, false, make_backend, frames_out, info_out, err);
+}
+
+bool sauamd_internal::render_file_flac_lpc24(const sauProgram *prg, uint32_t srate, const char *path, int channels, uint32_t block_frames,
+		uint32_t max_lpc_order, float gain, const std::function<Backend *(std::string &)> &make_backend, uint64_t *frames_out,
+		sauAmdFlacInfo *info_out, std::string &err) {
+	return flac_f32_file(prg, srate, path, channels, block_frames, 24, max_lpc_order, gain, true, make_backend, frames_out, info_out, err);
+}
+
+extern "C" bool sauAmd_render_file_flac_lpc24(const sauProgram *prg, uint32_t srate, const char *path, int channels, uint32_t block_frames,
+		uint32_t max_lpc_order, float gain, uint64_t *frames_out, sauAmdFlacInfo *info_out) {
+	std::string err;
+	bool ok = false;
+	try {
+		ok = sauamd_internal::render_file_flac_lpc24(prg, srate, path, channels, block_frames, max_lpc_order, gain,
+				[](std::string &e) -> Backend * { return sauhip::create_hip_backend(e); }, frames_out, info_out, err);
+	} catch (const std::exception &ex) { /* (nothing C++ crosses the C ABI) */
+		err = std::string("internal error: ") + ex.what();
+	}
+	if (!ok) sauamd_internal::set_last_error("output", err);
+	return ok;
 }
 
 extern "C" bool sauAmd_render_file_flac_f32(const sauProgram *prg, uint32_t srate, const char *path, int channels, uint32_t block_frames,
@@ -960,13 +990,14 @@ extern "C" bool sauAmd_render_file_flac_f32(const sauProgram *prg, uint32_t srat
 	return ok;
 }
 
-bool sauamd_internal::render_file_flac_loudness(const sauProgram *prg, uint32_t srate, const char *path, int channels, uint32_t block_frames,
-		int bits, uint32_t max_lpc_order, double target_lufs, float max_true_peak, bool limited,
+/* render_file_flac_loudness's body, and with lpc24 render_file_flac_loudness_lpc24's */
+static bool flac_loudness_file(const sauProgram *prg, uint32_t srate, const char *path, int channels, uint32_t block_frames,
+		int bits, uint32_t max_lpc_order, double target_lufs, float max_true_peak, bool limited, bool lpc24,
 		const std::function<Backend *(std::string &)> &make_backend, uint64_t *frames_out, sauAmdLoudness *loud_out, float *gain_out,
 		sauAmdLimiterStats *stats_out, sauAmdFlacInfo *info_out, std::string &err) {
 	if (frames_out) *frames_out = 0;
-	if (!prg || !path || srate > 655350u || !flac_f32_params_ok(channels, block_frames, bits, max_lpc_order) ||
-	    !(target_lufs >= -DBL_MAX && target_lufs <= DBL_MAX) || !(max_true_peak > 0.f) || !(max_true_peak <= FLT_MAX) ||
+	if (!prg || !path || srate > 655350u || !flac_f32_params_ok(channels, block_frames, bits, lpc24 ? 0 : max_lpc_order) ||
+	    max_lpc_order > sauflac::FLAC_LPC_MAX || !(target_lufs >= -DBL_MAX && target_lufs <= DBL_MAX) || !(max_true_peak > 0.f) || !(max_true_peak <= FLT_MAX) ||
 	    srate < sauengine::LOUD_MIN_RATE) { /* (a NaN fails every comparison) */
 		err = "bad argument";
 		return false;
@@ -988,7 +1019,7 @@ bool sauamd_internal::render_file_flac_loudness(const sauProgram *prg, uint32_t 
 		Backend *second = make_backend(err);
 		if (!second) return false;
 		return write_flac_scaled(prg, srate, path, channels, block_frames, bits, max_lpc_order, gain, second, frames_out,
-				(sauengine::FlacInfo *)info_out, err);
+				(sauengine::FlacInfo *)info_out, err, lpc24);
 	}
 	/* render_file_loudness_limited's rule: never lowered for the ceiling, the limiter holds that */
 	if (ld.integrated > -HUGE_VAL) gain = (float)pow(10.0, (target_lufs - ld.integrated) / 20.0);
@@ -998,8 +1029,40 @@ bool sauamd_internal::render_file_flac_loudness(const sauProgram *prg, uint32_t 
 	if (!second) return false;
 	sauengine::LimiterStats st{0, 0, 1.0};
 	const bool ok = write_flac_limited(prg, srate, path, channels, block_frames, bits, max_lpc_order, gain, max_true_peak, second, frames_out,
-			&st, (sauengine::FlacInfo *)info_out, err);
+			&st, (sauengine::FlacInfo *)info_out, err, lpc24);
 	if (ok && stats_out) memcpy(stats_out, &st, sizeof st);
+	return ok;
+}
+
+bool sauamd_internal::render_file_flac_loudness(const sauProgram *prg, uint32_t srate, const char *path, int channels, uint32_t block_frames,
+		int bits, uint32_t max_lpc_order, double target_lufs, float max_true_peak, bool limited,
+		const std::function<Backend *(std::string &)> &make_backend, uint64_t *frames_out, sauAmdLoudness *loud_out, float *gain_out,
+		sauAmdLimiterStats *stats_out, sauAmdFlacInfo *info_out, std::string &err) {
+	return flac_loudness_file(prg, srate, path, channels, block_frames, bits, max_lpc_order, target_lufs, max_true_peak, limited, false,
+			make_backend, frames_out, loud_out, gain_out, stats_out, info_out, err);
+}
+
+bool sauamd_internal::render_file_flac_loudness_lpc24(const sauProgram *prg, uint32_t srate, const char *path, int channels,
+		uint32_t block_frames, uint32_t max_lpc_order, double target_lufs, float max_true_peak, bool limited,
+		const std::function<Backend *(std::string &)> &make_backend, uint64_t *frames_out, sauAmdLoudness *loud_out, float *gain_out,
+		sauAmdLimiterStats *stats_out, sauAmdFlacInfo *info_out, std::string &err) {
+	return flac_loudness_file(prg, srate, path, channels, block_frames, 24, max_lpc_order, target_lufs, max_true_peak, limited, true,
+			make_backend, frames_out, loud_out, gain_out, stats_out, info_out, err);
+}
+
+extern "C" bool sauAmd_render_file_flac_loudness_lpc24(const sauProgram *prg, uint32_t srate, const char *path, int channels,
+		uint32_t block_frames, uint32_t max_lpc_order, double target_lufs, float max_true_peak, int limited,
+		uint64_t *frames_out, sauAmdLoudness *loud_out, float *gain_out, sauAmdLimiterStats *stats_out, sauAmdFlacInfo *info_out) {
+	std::string err;
+	bool ok = false;
+	try {
+		ok = sauamd_internal::render_file_flac_loudness_lpc24(prg, srate, path, channels, block_frames, max_lpc_order, target_lufs,
+				max_true_peak, limited != 0, [](std::string &e) -> Backend * { return sauhip::create_hip_backend(e); }, frames_out,
+				loud_out, gain_out, stats_out, info_out, err);
+	} catch (const std::exception &ex) { /* (nothing C++ crosses the C ABI) */
+		err = std::string("internal error: ") + ex.what();
+	}
+	if (!ok) sauamd_internal::set_last_error("output", err);
 	return ok;
 }
 

@@ -439,14 +439,20 @@ size_t flac_header(uint32_t srate, int channels, uint32_t block_frames, const Fl
 }
 
 /* One block of n frames of int32 samples, already checked: B a block size, n in 1 .. B, every sample within `bits`, M the LPC
- * mode's largest order (0 at 24 bits). */
+ * mode's largest order. At 24 bits the LPC mode (the header's "LPC at 24 bits") runs only with lpc24, which
+ * flac_encode_block_lpc24 alone sets; without it M is 0 there. */
 static size_t flac_encode_block_any(const int32_t *x, uint32_t n, unsigned ch, uint32_t B, uint32_t frame_number, unsigned bits, unsigned M,
-		uint8_t *out, size_t cap) {
+		uint8_t *out, size_t cap, bool lpc24 = false) {
 	using namespace sauflac;
 	const unsigned n_cand = ch == 2 ? 4 : 1, fine_log2 = n == B ? 4 : 0, F = 1u << fine_log2, nk = flac_nk(bits);
 	auto at = [&](unsigned c, int64_t i) -> int32_t { return i < 0 ? 0 : ch == 2 ? flac_cand(x[2 * i], x[2 * i + 1], c) : x[i]; };
 	auto resid = [&](unsigned c, unsigned o, uint32_t i) { return flac_residual(o, at(c, i), at(c, (int64_t)i - 1), at(c, (int64_t)i - 2), at(c, (int64_t)i - 3), at(c, (int64_t)i - 4)); };
 	auto resid_lpc = [&](unsigned c, const int16_t *q, unsigned m, unsigned shift, uint32_t i) { /* (i >= m) */
+		if (bits == 24) { /* (the sum is below 2^39 in size, the residual below 2^31 behind step 5b) */
+			int64_t sum = 0;
+			for (unsigned j = 0; j < m; ++j) sum += (int64_t)q[j] * at(c, (int64_t)i - 1 - j);
+			return flac_lpc_residual(at(c, i), sum, shift);
+		}
 		int32_t sum = 0;
 		for (unsigned j = 0; j < m; ++j) sum += (int32_t)q[j] * at(c, (int64_t)i - 1 - j);
 		return flac_lpc_residual(at(c, i), sum, shift);
@@ -481,7 +487,7 @@ static size_t flac_encode_block_any(const int32_t *x, uint32_t n, unsigned ch, u
 		uint8_t node_k[FLAC_NODES];
 		nodes(fine, fine_log2, o, node_cost, node_k);
 		flac_finish_sub(&cand[c], c, n, equal, o, fine_log2, node_cost, node_k, bits);
-		if (!M || n != B || equal) continue;
+		if (!M || n != B || equal || (bits == 24 && !lpc24)) continue;
 		/* the LPC mode: the windowed autocorrelation in integers, the orders' coefficients, the order, its partitions */
 		unsigned log2B = 0;
 		while ((1u << log2B) < B) ++log2B;
@@ -489,7 +495,7 @@ static size_t flac_encode_block_any(const int32_t *x, uint32_t n, unsigned ch, u
 		for (unsigned l = 0; l <= M; ++l) {
 			R[l] = 0;
 			for (uint32_t i = l; i < n; ++i)
-				R[l] += (int64_t)flac_lpc_windowed(at(c, i), flac_lpc_window(i, B, log2B)) * flac_lpc_windowed(at(c, i - l), flac_lpc_window(i - l, B, log2B));
+				R[l] += (int64_t)flac_lpc_windowed(at(c, i), flac_lpc_window(i, B, log2B), bits) * flac_lpc_windowed(at(c, i - l), flac_lpc_window(i - l, B, log2B), bits);
 		}
 		if (R[0] == 0) continue;
 		const unsigned g = flac_lpc_f64_shift(R[0]);
@@ -497,14 +503,15 @@ static size_t flac_encode_block_any(const int32_t *x, uint32_t n, unsigned ch, u
 		for (unsigned l = 0; l <= M; ++l) r[l] = (double)(R[l] >> g);
 		int16_t q[FLAC_LPC_MAX * FLAC_LPC_MAX];
 		uint8_t shift[FLAC_LPC_MAX];
-		const uint32_t mask = flac_lpc_orders(r, M, a, q, shift);
+		uint32_t mask = flac_lpc_orders(r, M, a, q, shift);
+		if (bits == 24) mask = flac_lpc_guard(mask, q, shift, flac_cand_bps(c, bits)); /* step 5b */
 		uint64_t lpc_abs[FLAC_LPC_MAX];
 		for (unsigned m = 1; m <= M; ++m) {
 			lpc_abs[m - 1] = 0;
 			if (mask & (1u << (m - 1)))
 				for (uint32_t i = M; i < n; ++i) lpc_abs[m - 1] += flac_abs(resid_lpc(c, q + (m - 1) * FLAC_LPC_MAX, m, shift[m - 1], i));
 		}
-		const unsigned m = flac_lpc_pick_order(mask, lpc_abs, n, M, flac_cand_bps(c, bits));
+		const unsigned m = flac_lpc_pick_order(mask, lpc_abs, n, M, flac_cand_bps(c, bits), nk);
 		if (!m) continue;
 		memset(fine, 0, sizeof fine);
 		for (uint32_t i = m; i < n; ++i) {
@@ -512,7 +519,7 @@ static size_t flac_encode_block_any(const int32_t *x, uint32_t n, unsigned ch, u
 			for (unsigned k = 0; k < nk; ++k) fine[(i / plen) * nk + k] += u >> k;
 		}
 		nodes(fine, fine_log2, m, node_cost, node_k);
-		flac_lpc_choose(&cand[c], n, m, q + (m - 1) * FLAC_LPC_MAX, shift[m - 1], fine_log2, node_cost, node_k);
+		flac_lpc_choose(&cand[c], n, m, q + (m - 1) * FLAC_LPC_MAX, shift[m - 1], fine_log2, node_cost, node_k, bits);
 	}
 	FlacFrameDesc d;
 	flac_finish_frame(&d, cand, ch, n, B, frame_number);
@@ -629,6 +636,19 @@ size_t flac_encode_block_s32(const int32_t *x, uint32_t n, int channels, uint32_
 	for (size_t i = 0; i < cnt; ++i)
 		if (x[i] < lo || x[i] > hi) return 0;
 	return flac_encode_block_any(x, n, (unsigned)channels, B, frame_number, (unsigned)bits, max_lpc_order, out, cap);
+}
+
+/* LPC at 24 bits: the one entry point that runs flac_encode_block_any's LPC mode on 24-bit samples; flac_encode_block_s32 keeps
+ * refusing (24, M > 0) */
+size_t flac_encode_block_lpc24(const int32_t *x, uint32_t n, int channels, uint32_t block_frames, uint32_t frame_number, uint32_t max_lpc_order,
+		uint8_t *out, size_t cap) {
+	using namespace sauflac;
+	const uint32_t B = flac_block_frames(block_frames);
+	if (!x || !B || !n || n > B || (channels != 1 && channels != 2) || frame_number > FLAC_MAX_BLOCKS || max_lpc_order > FLAC_LPC_MAX) return 0;
+	const size_t cnt = (size_t)n * (size_t)channels;
+	for (size_t i = 0; i < cnt; ++i)
+		if (x[i] < FLAC_S24_MIN || x[i] > FLAC_S24_MAX) return 0;
+	return flac_encode_block_any(x, n, (unsigned)channels, B, frame_number, 24, max_lpc_order, out, cap, true);
 }
 
 /* ---- dither and noise shaping (include/saugns_amd.h, section "Dither and noise shaping"; the arithmetic is sau_dither.h's,
