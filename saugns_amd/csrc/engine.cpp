@@ -263,7 +263,8 @@ bool Engine::rebuild_plans(std::string &err) {
 						    chk.wave_mask != wmask || chk.n_fast != sp.n_fast || chk.n_fast_full != sp.n_fast_full ||
 						    chk.n_slots != sp.n_slots || chk.n_main != sp.n_main || chk.no_fast != sp.no_fast ||
 						    chk.static_block != sp.static_block || chk.selfmod != sp.selfmod || chk.n_chain != sp.n_chain ||
-						    chk.n_osc != sp.n_osc || chk.has_camods != sp.has_camods || chk.carr_local != sp.carr_local || chk.wide != sp.wide) {
+						    chk.n_osc != sp.n_osc || chk.has_camods != sp.has_camods || chk.carr_local != sp.carr_local || chk.wide != sp.wide ||
+						    chk.wave_only != sp.wave_only) {
 							err = "plan cache: a cached plan differs from a fresh compile (SAU_AMD_PLAN_CHECK)";
 							return false;
 						}
@@ -274,6 +275,7 @@ bool Engine::rebuild_plans(std::string &err) {
 					vn.plan.n_fast = sp.n_fast; vn.plan.n_fast_full = sp.n_fast_full; vn.plan.wave_mask = wmask;
 					vn.plan.has_camods = sp.has_camods; vn.plan.no_fast = sp.no_fast; vn.plan.static_block = sp.static_block;
 					vn.plan.selfmod = sp.selfmod; vn.plan.n_chain = sp.n_chain; vn.plan.n_osc = sp.n_osc; vn.plan.wide = sp.wide;
+					vn.plan.wave_only = sp.wave_only;
 					vn.plan.ras_cub = false;
 					for (uint32_t id : shape_ids_) if (st.ops[id].ras_cub_seen) vn.plan.ras_cub = true;
 					vn.plan.n_steps = (uint32_t)sp.steps.size();
@@ -387,6 +389,7 @@ bool Engine::render_segment(uint32_t len, uint32_t offset, bool stereo, std::str
 	uint32_t n_main = 1, n_fpool = 0, max_ops = 1, n_pan = 0, max_steps = 1, n_fast = 1, n_fast_full = 0;
 	uint64_t wave_mask = 0;
 	bool maybe_block = false, serial = false, may_scan = false, maybe_cub = false;
+	bool wave_only = true; /* (every active voice so far: SegmentDesc.wave_only) */
 	uint32_t sum_levels = 0, n_chain_rows = 0, n_chain_slots = 0, n_inc_rows = 0, n_look_rows = 0, n_may_scan = 0;
 	bool chain_rows_padded = false;
 	for (size_t s = 0; s < streams_.size(); ++s) {
@@ -453,6 +456,7 @@ bool Engine::render_segment(uint32_t len, uint32_t offset, bool stereo, std::str
 			bool voice_block = vn.plan.static_block; /* this voice may leave the closed-form path */
 			if (vn.plan.static_block || vn.plan.no_fast) maybe_block = true;
 			if (vn.plan.selfmod) serial = true;
+			if (!vn.plan.wave_only) wave_only = false;
 			if (vn.plan.ras_cub && loop_tails_) maybe_cub = true;
 			for (uint32_t id : vn.plan.op_ids) {
 				OpMirror &m = st.ops[id];
@@ -564,6 +568,8 @@ bool Engine::render_segment(uint32_t len, uint32_t offset, bool stereo, std::str
 	seg.n_look_rows = n_look_rows;
 	seg.n_may_scan = n_may_scan;
 	seg.chain_rows_padded = chain_rows_padded;
+	/* (maybe_block: a sweep, an operator that runs out of time inside the segment, a carrier that ends before its voice) */
+	seg.wave_only = wave_only && !maybe_block && !may_scan;
 	return backend_->render(seg, err);
 }
 

@@ -247,6 +247,10 @@ struct SegmentDesc {
 	uint32_t n_may_scan = 0;  /* voices that may have running-sum phases this segment (the device decides: analyze_kernel) */
 	uint32_t n_chain_slots = 0; /* lanes of the chain kernels' waves the voices' chain_slot/n_chain span (>= n_chain_rows) */
 	bool chain_rows_padded = false; /* some of the n_chain_slots lanes belong to no voice (kinds of R feedback chains begin waves of their own) */
+	/* every active voice's steps are W oscillators with one amplitude value each: no amplitude modulators, no sweep ever given to
+	 * an operator, nothing layered, no R, N or A operator, no line step, no operator that runs out inside the segment.
+	 * Conservative (false wherever the host cannot be sure): the lane-major inner launch's wave-only instantiation */
+	bool wave_only = false;
 };
 
 /* Bytes a backend has for the rows of a segment's feedback chains (8 B per chain and frame; the engine cuts segments with
@@ -535,6 +539,11 @@ struct VoicePlan {
 	bool static_block = false;     /* graph has FM / feedback / R / filtered noise: block loop */
 	bool selfmod = false;          /* a self-modulation amount has modulators of its own */
 	bool ras_cub = false;          /* an R operator that was ever given `cub` segments */
+	/* every step evaluates a W oscillator that takes its amplitude from its own line and was never given a sweep, replaces its
+	 * output (nothing layered) and reads no amplitude, self-modulation or frequency-scaled PM block, or is that operator's
+	 * unforced frequency line (one value on the closed-form path: FM forces it and is a static_block). A function of
+	 * what the plan cache's key holds (plan.cpp: voice_plan_shape): types, list uses and counts, the sticky sweep marks */
+	bool wave_only = false;
 	uint32_t n_chain = 0;          /* oscillator steps that may run a feedback recurrence (step_may_chain) */
 	uint32_t n_osc = 0;            /* W and R oscillator steps (their phase increments may be saved between passes) */
 };

@@ -262,9 +262,10 @@ static bool raise_lds_attr(const void *fn, size_t lds, int dev, std::string &err
  * the look-back build at 8: round 5, where the lean buffer numbering leaves LDS for them), the look-back build that mixes
  * few-voice streams (round 6: FastParams.tail_ok), the builds with the loop tails of `cub` R segments, the inner launch of the
  * 12-row build (k_fast_voice.h: INNER), its lane-major form (k_fast_group_lm.h) and that form for launches of one table
- * (round 10: fk_entry's TAB0; only in a -DFK_LM_TAB0=1 build -- by default every launch takes the form that adds the table's base).
+ * (round 10: fk_entry's TAB0; only in a -DFK_LM_TAB0=1 build -- by default every launch takes the form that adds the table's base),
+ * and the lane-major form for launches of wave oscillators with constant amplitude only (round 11: fast_kernel's WONLY).
  * (The table's order is the order the instantiations take in the code object.) */
-enum : unsigned { FK_WIDE = 1, FK_TAIL = 2, FK_CUB = 4, FK_INNER = 8, FK_LANEMAJOR = 16, FK_TAB0 = 32 };
+enum : unsigned { FK_WIDE = 1, FK_TAIL = 2, FK_CUB = 4, FK_INNER = 8, FK_LANEMAJOR = 16, FK_TAB0 = 32, FK_WONLY = 64 };
 static const void *fast_kernel_fn(int build, uint32_t rows, unsigned form) {
 	struct Entry { int build; uint32_t rows; unsigned form; const void *fn; };
 #define FK(build, form, ...) {build, FK_ROWS(__VA_ARGS__), form, (const void *)fast_kernel<__VA_ARGS__>}
@@ -280,6 +281,9 @@ static const void *fast_kernel_fn(int build, uint32_t rows, unsigned form) {
 		FK(0, FK_WIDE | FK_INNER | FK_LANEMAJOR, 12, 0, false, true, false, true, true), FK(0, FK_WIDE | FK_INNER, 12, 0, false, true, false, true),
 #if FK_LM_TAB0
 		FK(0, FK_WIDE | FK_INNER | FK_LANEMAJOR | FK_TAB0, 12, 0, false, true, false, true, true, true),
+#endif
+#if FK_LM_WONLY
+		FK(0, FK_WIDE | FK_INNER | FK_LANEMAJOR | FK_WONLY, 12, 0, false, true, false, true, true, false, true),
 #endif
 		FK(0, FK_CUB, (int)FAST_CUB_ROWS, 0, true)};
 #undef FK
@@ -1151,7 +1155,10 @@ public:
 #else
 			const bool tab0 = false;
 #endif
-			const void *ik = fast_kernel_fn(0, 12, FK_WIDE | FK_INNER | (lm ? FK_LANEMAJOR : 0u) | (tab0 ? FK_TAB0 : 0u));
+			/* (wave oscillators with constant amplitude only, by the planner's word: the instantiation that holds nothing else. A
+			 * one-table build's launches of one table keep that instantiation: it is an A/B build, and has no third copy) */
+			const bool wonly = FK_LM_WONLY && lm && k.inner_wonly && !tab0;
+			const void *ik = fast_kernel_fn(0, 12, FK_WIDE | FK_INNER | (lm ? FK_LANEMAJOR : 0u) | (tab0 ? FK_TAB0 : 0u) | (wonly ? FK_WONLY : 0u));
 			if (!ik) { err = "no inner instantiation of fast_kernel for this form"; return false; }
 			const size_t lds = k.inner_lds();
 			FastParams ep = fp;
@@ -1164,7 +1171,7 @@ public:
 			if (!raise_lds_attr(ik, lds, dev_, err)) return false;
 			if (fp.inmix_flags && !pcm_hazard(err)) return false; /* (the inner launch mixes tiles into the PCM itself) */
 			HIP_OK(hipLaunchKernel(ik, dim3(k.grid), dim3(1024), iargs, lds, stream_));
-			if (inner_report_) fprintf(stderr, "[sau-amd] inner: %s, %u voices, %u tables%s\n", lm ? "lane-major" : "row-major", seg.n_voices, k.tabs.n, tab0 ? ", tab0" : "");
+			if (inner_report_) fprintf(stderr, "[sau-amd] inner: %s, %u voices, %u tables%s\n", lm ? "lane-major" : "row-major", seg.n_voices, k.tabs.n, tab0 ? ", tab0" : wonly ? ", wonly" : "");
 		} else {
 			/* (a closed-form segment that did not take the two launches, and what kept it from them) */
 			if (inner_report_) fprintf(stderr, "[sau-amd] inner: none (rows %u, wide %d, chunks %u), %u voices\n", k.rows, k.wide_cf ? 1 : 0, fp.dyn_chunks, seg.n_voices);

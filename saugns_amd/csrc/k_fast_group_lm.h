@@ -8,7 +8,9 @@
  * lane l both writes and reads it, and the launch only takes segments whose voices share ONE buffer (launch_plan.h:
  * plan_closed_form), so every *_off that is not ~0u names that block. The launch's LDS holds the tables and nothing else.
  * The arithmetic and its order are k_fast_group.h's with EDGE false, SCAN 0, REPAIR false, CUB false; only what reaches a frame's
- * neighbour differs. In scope: everything fast_voice has defined up to its row-group loop, plus cg. */
+ * neighbour differs. In scope: everything fast_voice has defined up to its row-group loop, plus cg.
+ * WONLY (round 11, fast_voice's flag): the same file as the instantiation for banks of wave oscillators with constant amplitude --
+ * every branch such a step does not take is compiled out (`!WONLY && ...`), and the general instantiation's code is what it was. */
 		const int j0 = l * T;                              /* this lane's first frame of the group, relative */
 		const int t0 = (int)(cg * GF) - (int)H + j0;       /* ... and in the segment: register k holds frame t0 + k */
 		/* which registers hold frames of the group's own (lead-in: j < H -- the first lanes' first registers): bit k */
@@ -55,7 +57,7 @@
 			/* (the step's own copy of t0: t0 + 1 ... t0 + T - 1, which only the ramps, N and R read, were computed ahead of the step
 			 * loop and held in T - 1 registers across it -- registers the block now needs) */
 			int t0s = t0;
-			asm volatile("" : "+v"(t0s));
+			if (!WONLY) asm volatile("" : "+v"(t0s)); /* (the wave-only instantiation has no reader of it) */
 			{
 				/* A step that needs a second block -- a buffer beyond the first, PM beside FPM, a range list's blend or envelope, a pan
 				 * block -- is not this form's. The host does not send such a segment here (launch_plan.h: plan_closed_form); should a
@@ -63,6 +65,19 @@
 				/* (off + 1: 0 none, 1 the first buffer, more another one -- in integers: as booleans these tests became vector code) */
 				const uint32_t o1 = f.out_off + 1u, p1 = f.pm_off + 1u, q1 = f.fpm_off + 1u, a1 = f.amp_off + 1u;
 				uint32_t two = 0;
+				if (WONLY) {
+					/* The wave-only instantiation (k_fast_voice.h: fast_kernel's WONLY) holds W oscillator steps with one amplitude
+					 * value -- and the same step standing still (k_decode.h makes it a constant source, type OT_AMP) --, the plain
+					 * combine and ST_VOICE. Anything else -- an amplitude block or ramp, a layered or enveloped combine,
+					 * frequency-scaled PM, an R or N operator, a line, a blend -- and the voice goes to the block loop. The host
+					 * sends no such segment here (launch_plan.h: FastPlan.inner_wonly). */
+					/* (the type in integers too: OT_WAVE and OT_AMP are the two values without a bit beside OT_WAVE's) */
+					static_assert(OT_AMP == 0 && OT_WAVE == 2, "the types as bits");
+					const uint32_t ty = f.type & 0xff & ~(uint32_t)OT_WAVE;
+					if (kind == ST_OSC) two = o1 | p1 | ((a1 | q1 | (flags & (SF_WAVE_ENV | SF_LAYER)) | (f.ramp & 1u) | ty) << 1);
+					else if (kind == ST_VOICE) two = o1 | (p1 << 1);
+					else two = 2u;
+				} else
 				if (kind == ST_OSC) two = o1 | a1 | (p1 + q1) | (flags & SF_WAVE_ENV);
 				else if (kind == ST_LINE) two = o1;
 				else if (kind == ST_VOICE) two = o1 | (p1 << 1);
@@ -75,7 +90,7 @@
 				const bool to_voice = ((f.kind >> 16) & OX_VOICE) != 0;
 				float s[T];
 				if (type == OT_WAVE) {
-					const bool has_pm = f.pm_off != ~0u, has_fpm = f.fpm_off != ~0u;
+					const bool has_pm = f.pm_off != ~0u, has_fpm = !WONLY && f.fpm_off != ~0u; /* (WONLY: no frequency-scaled PM -- it would keep pm_offset32 and the frequency registers in the general path) */
 					/* this operator's values are defined from relative frame p_min on */
 					const int p_min = (int)H - (int)(f.kind >> 24) + 1;
 					/* which of this lane's registers hold frames the operator defines (j >= p_min): bit k -- per-lane masks, where
@@ -86,13 +101,31 @@
 					if (FK_COMMON && f.tab >= 0 && !has_fpm && !(f.ramp & 2)) {
 						/* the common case, straight-line: table in LDS, plain PM or none */
 						uint32_t ph[T];
-						{
+						bool ok = true;
+						if (WONLY && FK_LM_WONLY_ADD3) {
+							/* (round 11) A PM operator's phase in ONE add a sample: base + k inc + offset, a three-operand add whose
+							 * second operand, the multiple of the wave-uniform increment, is a scalar register -- where acc += inc and
+							 * then ph += offset are two vector adds a sample. Mod 2^32 either way: the same phases. Without PM one
+							 * add a sample, as before. */
+							const uint32_t base = f.phase0 + f.inc * (uint32_t)(t0 + 1);
+							if (has_pm) {
+								bool big = false;
+#pragma unroll
+								for (int k = 0; k < T; ++k) big |= !(fabsf(blk[k]) < 0x1p20f);
+								ok = !__any(big);
+#pragma unroll
+								for (int k = 0; k < T; ++k) ph[k] = base + (uint32_t)k * f.inc + rint32w_p31_small(blk[k]);
+							} else { /* (as a sum of k inc here too the compiler made 64-bit multiply-adds of most of them) */
+								uint32_t acc = base;
+#pragma unroll
+								for (int k = 0; k < T; ++k) { ph[k] = acc; acc += f.inc; }
+							}
+						} else {
 							uint32_t acc = f.phase0 + f.inc * (uint32_t)(t0 + 1);
 #pragma unroll
 							for (int k = 0; k < T; ++k) { ph[k] = acc; acc += f.inc; }
 						}
-						bool ok = true;
-						if (has_pm) {
+						if (!(WONLY && FK_LM_WONLY_ADD3) && has_pm) {
 							float pm[T];
 							bool big = false;
 #pragma unroll
@@ -335,7 +368,7 @@
 							}
 						}
 					}
-				} else if (type == OT_RASEG) {
+				} else if (!WONLY && type == OT_RASEG) {
 					/* rasg.h:165-222 + 692-743: frame t reads the counter cp0 + inc * t (+ PM) */
 					const bool rate2x = (f.type >> 17) & 1;
 					const float phase_scale = rate2x ? 0x1p31f * 2 : 0x1p31f;
@@ -356,7 +389,7 @@
 						ras_split(cp, cyc, phf);
 						s[k] = ras_sample(rp, cyc, phf, true, false);
 					}
-				} else if (type == OT_NOISE) {
+				} else if (!WONLY && type == OT_NOISE) {
 					const uint32_t nz = (f.type >> 8) & 0xff;
 					const uint32_t n0 = f.phase0;
 #pragma unroll
@@ -379,11 +412,27 @@
 					for (int k = 0; k < T; ++k) s[k] = f.fc;
 				}
 				/* amplitude and combine: generator.c:384-440 */
+				if (WONLY && FK_LM_WONLY_INPLACE) {
+					/* (round 11) one amplitude value and the plain combine, the products written where they go: to the row store
+					 * of the step that feeds the voice, else over the block's registers -- whose old values no later code of this
+					 * step reads here, where the general instantiation may still layer onto them or read them as amplitudes
+					 * and so keeps them beside the new ones */
+					if (to_voice) {
+						float x[T];
+#pragma unroll
+						for (int k = 0; k < T; ++k) x[k] = s[k] * f.ac;
+						store_row(vrow, x, true);
+					} else {
+#pragma unroll
+						for (int k = 0; k < T; ++k) blk[k] = s[k] * f.ac;
+					}
+					continue;
+				}
 				float r[T];
-				if (f.amp_off != ~0u) {
+				if (!WONLY && f.amp_off != ~0u) {
 #pragma unroll
 					for (int k = 0; k < T; ++k) r[k] = blk[k];
-				} else if (f.ramp & 1) { /* amplitude ramp in progress, sau/line.c:65-281 */
+				} else if (!WONLY && (f.ramp & 1)) { /* amplitude ramp in progress, sau/line.c:65-281 */
 					const FastLine fl = load_line_uniform(flines + si);
 #pragma unroll
 					for (int k = 0; k < T; ++k) r[k] = fast_line_value(fl, t0s + k);
@@ -391,7 +440,7 @@
 #pragma unroll
 					for (int k = 0; k < T; ++k) r[k] = f.ac;
 				}
-				if (layer) {
+				if (!WONLY && layer) {
 #pragma unroll
 					for (int k = 0; k < T; ++k) r[k] = mix_combine(blk[k], s[k], r[k], false, true);
 				} else {
@@ -404,7 +453,7 @@
 #pragma unroll
 					for (int k = 0; k < T; ++k) blk[k] = r[k];
 				}
-			} else if (kind == ST_LINE) {
+			} else if (!WONLY && kind == ST_LINE) {
 				/* held line: v0 (sau/line.c:435-442) */
 				if (f.ramp) {
 					FastLine fl;

@@ -155,7 +155,8 @@ __device__ __forceinline__ FastStep load_step_uniform(const FastStep *p) {
  * need it (the same code with the running-sum branches compiled in was 27 %
  * slower on them), and a kernel that may meet both kinds holds both copies. */
 template <int T, int SCAN, bool REPAIR = false, bool CUB = false, bool WIDE = false, int SPLIT = 0 /* 1: three loops, 2: the groups between only, 3: the same in the lane-major form */, bool TAIL = false,
-		bool TAB0 = false /* SPLIT 3: the launch has one table, at LDS address 0 */>
+		bool TAB0 = false /* SPLIT 3: the launch has one table, at LDS address 0 */,
+		bool WONLY = false /* SPLIT 3: wave oscillators with constant amplitude only (k_fast_group_lm.h) */>
 __device__ __forceinline__ void fast_voice(const FastParams &P, const uint32_t v, const FastInfo &fi,
 		float *slots, unsigned long long *carry, const uint32_t tabs /* LDS address of the launch's table blocks */, const int l,
 		const uint32_t wpv, const uint32_t cstart, unsigned long long *lring = nullptr,
@@ -533,9 +534,16 @@ __device__ __forceinline__ void inmix_after(const InmixArgs &A, const uint32_t k
  * both forms in one kernel, spilled 175 vector registers at 12 rows. */
 /* LM (round 7): the INNER build's groups in the lane-major form (k_fast_group_lm.h); the row-major one stays for A/B (SAU_AMD_NO_LANEMAJOR) */
 /* TAB0 (round 10): the lane-major form for launches that stage one table -- its LDS address is the index alone (fk_entry) */
-template <int T, int SCAN, bool CUB = false, bool WIDE = false, bool TAIL = false, bool INNER = false, bool LM = false, bool TAB0 = false>
+/* WONLY (round 11): the lane-major form that holds only what a bank of plain wave-oscillator chains takes -- OT_WAVE steps with
+ * one amplitude value, the plain combine, ST_VOICE -- for launches the host knows to be such (launch_plan.h:
+ * FastPlan.inner_wonly). The general instantiation is an interpreter of every operator kind: 84736 bytes of code and 35 scalar
+ * registers spilled to lanes across a step loop that config 3 runs one branch of. A step of any other shape: one scalar test,
+ * and the voice goes to the block loop (k_fast_group_lm.h) */
+template <int T, int SCAN, bool CUB = false, bool WIDE = false, bool TAIL = false, bool INNER = false, bool LM = false, bool TAB0 = false,
+		bool WONLY = false>
 __global__ void FK_ATTR fast_kernel(FastParams P) {
 	static_assert(!TAB0 || LM, "the one-table address form exists for the lane-major inner build");
+	static_assert(!WONLY || LM, "the wave-only form exists for the lane-major inner build");
 	static_assert(!INNER || (SCAN == 0 && WIDE && T == 12 && !CUB && !TAIL), "the inner-groups-only form exists for the 12-row wide closed-form build");
 	static_assert(!LM || INNER, "the lane-major form exists for the inner-groups-only build");
 	static_assert(!WIDE || ((SCAN == 0 || SCAN == 2) && !CUB), "only the closed-form and the look-back builds have a wide-table form");
@@ -604,7 +612,7 @@ __global__ void FK_ATTR fast_kernel(FastParams P) {
 			const uint32_t vi = task / K;
 			const uint32_t v = P.split_cf ? P.vlists[vi] : vi;
 			const FastInfo fi = P.info[v];
-			fast_voice<T, 0, false, CUB, WIDE, SPLIT, false, TAB0>(P, v, fi, slots, carry, tabs, l, 1u, 0u, nullptr, task - vi * K, K);
+			fast_voice<T, 0, false, CUB, WIDE, SPLIT, false, TAB0, WONLY>(P, v, fi, slots, carry, tabs, l, 1u, 0u, nullptr, task - vi * K, K);
 			if (!CUB && mixing) {
 				const InmixArgs A = inmix_args(NVc);
 				inmix_after(A, task - vi * K, vi, l);

@@ -112,6 +112,10 @@ struct Tuning {
 	bool inmix_dry = false;      /* SAU_AMD_INMIX_DRY: timing aid (FastParams.inmix_flags bit 4) */
 	bool inner = true;           /* the 12-row wide closed-form build as two launches, edges and inner groups (SAU_AMD_NO_INNER: one) */
 	bool lanemajor = true;       /* ... its groups between in the lane-major form (SAU_AMD_NO_LANEMAJOR: row-major) */
+	bool inner_wonly = true;     /* ... in the wave-only instantiation where the segment says every voice is wave oscillators with constant
+	                              * amplitude (SegmentDesc.wave_only; SAU_AMD_NO_INNER_WONLY: the general instantiation, for A/B and tests) */
+	bool inner_wonly_force = false; /* SAU_AMD_INNER_WONLY_FORCE (tests): ... whatever the segment says -- the kernel's own guard then sends
+	                              * every voice that is not of that shape to the block loop */
 	bool duo = true;             /* closed-form and look-back voices of a segment in one launch where there are plenty of both (SAU_AMD_NO_DUO: two launches) */
 	uint32_t duo_lw = 0, duo_prio = 0; /* SAU_AMD_DUO_LW (4 bits), SAU_AMD_DUO_PRIO (1: none, 2: 1, 3: 2 (default), 4: 3): FastParams.look_wpv_flags */
 	bool tailmix = false;        /* SAU_AMD_TAILMIX: the look-back launch mixes few-voice streams itself. Exact (357 GPU tests with it on), and
@@ -189,6 +193,8 @@ inline Tuning tuning_from_env(const char *(*env)(const char *)) {
 	t.inmix_dry = !off("SAU_AMD_INMIX_DRY");
 	t.inner = off("SAU_AMD_NO_INNER");
 	t.lanemajor = off("SAU_AMD_NO_LANEMAJOR");
+	t.inner_wonly = off("SAU_AMD_NO_INNER_WONLY");
+	t.inner_wonly_force = !off("SAU_AMD_INNER_WONLY_FORCE");
 	t.duo = off("SAU_AMD_NO_DUO");
 	if (const char *lw = env("SAU_AMD_DUO_LW")) t.duo_lw = (uint32_t)atoi(lw) & 15u;
 	if (const char *pr = env("SAU_AMD_DUO_PRIO")) t.duo_prio = (uint32_t)atoi(pr) & 7u;
@@ -435,6 +441,22 @@ inline uint32_t magic_quotient(uint32_t q, MagicDiv d) {
 #define FK_LM_AHEAD 1
 #endif
 constexpr bool FK_LM_SHORT_TASKS = FK_LM_ONE_PHASE_SET && FK_LM_AHEAD;
+/* Round 11, the wave-only instantiation of that launch (k_fast_voice.h: fast_kernel's WONLY; FastPlan.inner_wonly) and the two
+ * forms inside it, each behind a macro of its own for A/B (python saugns_amd/build.py --variant NAME DEFS...):
+ * FK_LM_WONLY          the instantiation exists and the host picks it (0: every lane-major launch takes the general one)
+ * FK_LM_WONLY_ADD3     a PM operator's phases in one three-operand add a sample, base + k inc + offset, the multiples of the
+ *                      increment on the scalar side (0: acc += inc, then ph += offset)
+ * FK_LM_WONLY_INPLACE  (off: measured, within noise) amplitude and combine written straight to the block's registers or to the row
+ *                      store (0: through r[] -- in the small kernel the compiler drops that copy itself: the same counts) */
+#ifndef FK_LM_WONLY
+#define FK_LM_WONLY 1
+#endif
+#ifndef FK_LM_WONLY_ADD3
+#define FK_LM_WONLY_ADD3 1
+#endif
+#ifndef FK_LM_WONLY_INPLACE
+#define FK_LM_WONLY_INPLACE 0
+#endif
 enum Inner : uint32_t { INNER_NONE = 0, INNER_ROW_MAJOR = 1, INNER_LANE_MAJOR = 2 };
 enum Mixer : uint32_t { MIX_NONE = 0, MIX_FEW_F32, MIX_F32, MIX_FEW, MIX_64, MIX_256 };
 
@@ -483,6 +505,7 @@ struct FastPlan {
 	MagicDiv div;
 	Inner inner = INNER_NONE;
 	bool inner_tab0 = false;   /* the lane-major inner launch stages ONE table: the instantiation that reads it at LDS address 0 */
+	bool inner_wonly = false;  /* ... every voice is wave oscillators with constant amplitude: the instantiation that holds nothing else */
 	Tasks tasks, tasks_cf, tasks_cub;
 	uint32_t groups = 0, groups_cf = 0;
 	uint32_t grid = 1, grid_cf = 1, grid_look = 1, grid_edge = 1, grid_cub = 1, grid_repair = 1;
@@ -698,6 +721,11 @@ inline void plan_closed_form(FastPlan &p, const SegmentDesc &seg, const Tuning &
 	/* (round 10) ... and a lane-major launch of one table has that table at LDS address 0: the kernel whose table address is the
 	 * index alone (k_fast_voice.h: fk_entry's TAB0). Two tables or more: the form that adds the table's base. */
 	p.inner_tab0 = p.inner == INNER_LANE_MAJOR && p.tabs.n == 1;
+	/* (round 11) ... and one whose voices are all wave oscillators with constant amplitude, by the engine's conservative word
+	 * (SegmentDesc.wave_only), takes the instantiation that holds only that (k_fast_voice.h: fast_kernel's WONLY). A voice of
+	 * another shape in such a launch would still be rendered right -- the kernel sends it to the block loop -- but slowly:
+	 * tests/test_inner_wonly_plan.py holds the flag against the decoded steps. */
+	p.inner_wonly = FK_LM_WONLY && p.inner == INNER_LANE_MAJOR && ((tun.inner_wonly && seg.wave_only) || tun.inner_wonly_force);
 	if (FK_LM_SHORT_TASKS && p.inmix && p.inner == INNER_LANE_MAJOR) p.inmix_flags = (p.inmix_flags & ~(15u << 8)) | ((tun.inmix_at_lm & 15u) << 8);
 	p.grid_edge = wave_grid(2ull * seg.n_voices, dev.fk_grid); /* (two tasks a voice: its first group, its last) */
 }

@@ -375,6 +375,19 @@ bool compile_voice_plan(const std::vector<OpMirror> &ops, uint32_t carrier,
 			}
 		}
 	}
+	/* wave oscillators with constant amplitude and nothing else (VoicePlan.wave_only): from the steps and from what the plan
+	 * cache's key holds of the operators -- their types, the sweep marks, the pm_a line */
+	out.wave_only = !out.wide && !out.no_fast && !out.static_block && !out.has_camods && !out.steps.empty();
+	for (const Step &st : out.steps) {
+		if (!out.wave_only) break;
+		/* (an operator's frequency line comes as a step of its own into a frequency slot, which the closed-form path reads as
+		 * one value: FM, which forces the block, is a static_block, and a frequency sweep is a sweep) */
+		if (st.kind == ST_LINE && st.which == L_FREQ && !(st.flags & SF_FORCE) && st.out >= FSLOT_BASE) continue;
+		if (st.kind != ST_OSC || (st.flags & (SF_LAYER | SF_WAVE_ENV)) || (st.freq != NO_SLOT && st.freq < FSLOT_BASE) || st.fpm != NO_SLOT ||
+		    st.amp != NO_SLOT || st.sm != NO_SLOT || st.op >= out.op_ids.size()) { out.wave_only = false; break; }
+		const OpMirror &om = ops[out.op_ids[st.op]];
+		if (om.type != SAU_POPT_N_wave || om.goal_seen || (om.line_set & (1u << L_PMA))) out.wave_only = false;
+	}
 	out.fast_ids.assign(out.steps.size(), FastIds());
 	out.fast_ids_full.assign(out.steps.size(), FastIds());
 	out.n_fast = out.n_fast_full = 0xffffffffu;
