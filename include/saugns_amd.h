@@ -575,7 +575,7 @@ SAU_AMD_API bool sauAmd_render_spectrum(const sauProgram *prg, uint32_t srate, i
  * 4096). Row r's block k covers its frames [k B, k B + B) and becomes FLAC frame number k; frames behind the last complete block
  * are pending until a later feed completes the block or a finish makes them one last short block. At most 65535 rows per
  * encoder and 2^31 - 1 blocks per row.
- * Limits: MD5 only on request ("MD5" below), no seek table, no comments, no wasted-bits detection, no escape
+ * Limits: MD5 only on request ("MD5" below), a decoder for these streams only ("Verify" below), no seek table, no comments, no wasted-bits detection, no escape
  * partitions, no dither of its own (a quantiser's rows can be fed: "Dither and noise shaping" below); LPC only on request (max_lpc_order, "The LPC mode" below), of order <= 8 with 12-bit coefficients, one
  * precision and one window. At 24 bits the LPC mode has entry points of its own, whose names end in _lpc24 ("LPC at 24 bits"
  * below); the entry points that take `bits` -- sauAmd_flac_encode_block_s32, sauAmd_Batch_create_flac_f32,
@@ -724,6 +724,37 @@ SAU_AMD_API bool sauAmd_render_spectrum(const sauProgram *prg, uint32_t srate, i
  * hashes the short block, if there is one, and the padding, and leaves the 16 bytes, which sauAmd_Flac_md5 fetches.
  * sauAmd_flac_md5 restates it on the host, and sauAmd_flac_header_md5 writes the header with the field filled in.
  *
+ * Verify. The library can read back what it writes: a strict decoder of exactly the frames stated above, and nothing else --
+ * no variable block size, no other LPC precision or order, no escape partitions, no wasted bits, no third channel, no scan for a
+ * sync code. sauAmd_flac_decode_block decodes one frame on the host; the same source decodes on the device. A frame is checked
+ * in stream order and the first failure gives the status (SAU_AMD_FLAC_DEC_*):
+ *   LENGTH    the data ends inside the frame (only the frame bound's bytes are ever looked at);
+ *   SYNC      not FF F8;
+ *   HEADER    a block size code that is neither 0111 nor B's, a sample rate code other than 0000, a channel assignment other
+ *             than 0, 1, 8, 9, 10 or one that does not go with `channels`, a sample size code other than that of `bits`, the
+ *             reserved bit, a code 0111 whose n is not below B;
+ *   NUMBER    a frame number that is malformed, not in its shortest form, or not the expected one;
+ *   CRC8      the header's CRC-8;
+ *   SUBFRAME  a subframe's padding bit, a type other than CONSTANT, VERBATIM, FIXED 0 .. 4 (no order above n) or LPC 1 .. 8
+ *             (only where n == B), the wasted-bits flag, an LPC precision field other than 1011 or a negative shift;
+ *   RESIDUAL  a coding method other than the width's own, a partition order above 4 or above 0 in a short block, a Rice
+ *             parameter above 14 (16 bits) or 30 (24 bits), the escape among them, a code whose u passes 32 bits;
+ *   PADDING   a non-zero bit ahead of the byte boundary;
+ *   CRC16     the frame's CRC-16;
+ *   RANGE     a restored L or R beyond `bits`;
+ *   MISMATCH  (verify only) the frame decoded, but not to the block's samples, length or size.
+ * The inverses: r = (u >> 1) for an even u, -((u + 1) >> 1) for an odd one; a FIXED sample is its residual plus the
+ * prediction the residual formula subtracts; an LPC sample is r_i + ((the sum of q[j] s_{i-1-j}) >> shift), the sum in 32 bits
+ * at 16 bits per sample and in 64 at 24; left/side: R = L - S; side/right: L = S + R; mid/side: m = (M << 1) | (S & 1),
+ * L = (m + S) >> 1, R = (m - S) >> 1.
+ * The verify mode is off unless asked for: sauAmd_Flac_set_verify on a fed encoder, sauAmd_set_flac_file_verify for the file
+ * writers. Off, every byte and every launch is what it is without this paragraph. On, every feed decodes each frame it made
+ * where the encoder left it, on the device, behind the kernel that wrote it and ahead of the one that moves the pending
+ * frames, and compares the result with the samples the analysis saw -- the fed rows and the pending frames; no PCM is fetched.
+ * The expected frame number and length come from the feed's plan, not from what the analysis left. Per row the encoder keeps
+ * the blocks checked, the bad ones, and the lowest bad block with its status (integer atomics: no order enters), which
+ * sauAmd_Flac_verify fetches; a read with reset clears them, the setting stays. The encoded bytes are the same on or off.
+ *
  * The worst case of a feed is that bound summed over the blocks it completes. Unread output lives on the device: a feed whose
  * worst case would bring the unread total above 1 GiB is refused; read first. (Until a read has fetched the frames' sizes, a
  * feed counts in that total with its worst case.) */
@@ -816,6 +847,42 @@ SAU_AMD_API bool sauAmd_flac_md5(const int32_t *x, size_t n_samples, int bits, u
  * it into the header it rewrites at the end; every other byte of the file is the same. A backend whose encoder has no MD5 then
  * gives "bad argument" before any file is created. Off, a writer does what it does without this switch. */
 SAU_AMD_API int sauAmd_set_flac_file_md5(int on);
+/* The decoder and the verify mode (the text's "Verify"). */
+enum {
+	SAU_AMD_FLAC_DEC_OK = 0, SAU_AMD_FLAC_DEC_LENGTH = 1, SAU_AMD_FLAC_DEC_SYNC = 2, SAU_AMD_FLAC_DEC_HEADER = 3,
+	SAU_AMD_FLAC_DEC_NUMBER = 4, SAU_AMD_FLAC_DEC_CRC8 = 5, SAU_AMD_FLAC_DEC_SUBFRAME = 6, SAU_AMD_FLAC_DEC_RESIDUAL = 7,
+	SAU_AMD_FLAC_DEC_PADDING = 8, SAU_AMD_FLAC_DEC_CRC16 = 9, SAU_AMD_FLAC_DEC_RANGE = 10, SAU_AMD_FLAC_DEC_MISMATCH = 11,
+	SAU_AMD_FLAC_DEC_BAD_ARGUMENT = 255
+};
+/* The host restatement of the decoder: the one frame that begins at data, a frame of `channels`, block_frames and `bits` as the
+ * encoders above make it, numbered frame_number. Returns the frame's size in bytes with *status_out == SAU_AMD_FLAC_DEC_OK,
+ * *n_out its frames and out[n * channels] its samples, interleaved. Otherwise 0 with the status, *n_out == 0 and nothing
+ * promised about out; a bad argument -- channels, block_frames, bits, a frame_number of 2^31 or more, a NULL pointer -- or
+ * cap_frames < n gives 0 with SAU_AMD_FLAC_DEC_BAD_ARGUMENT. data[len] and beyond are never read. */
+SAU_AMD_API size_t sauAmd_flac_decode_block(const uint8_t *data, size_t len, int channels, uint32_t block_frames, int bits,
+		uint32_t frame_number, int32_t *out /* [cap_frames * channels], interleaved */, size_t cap_frames, uint32_t *n_out, int *status_out);
+typedef struct sauAmdFlacVerify {
+	uint64_t blocks;              /* frames decoded since the last reset */
+	uint64_t bad_blocks;
+	uint64_t first_bad_block;     /* valid when bad_blocks > 0 */
+	uint32_t first_status, pad_;  /* SAU_AMD_FLAC_DEC_*; 0 when bad_blocks == 0 */
+} sauAmdFlacVerify;
+#ifdef __cplusplus
+static_assert(sizeof(sauAmdFlacVerify) == 32, "sauAmdFlacVerify is 32 bytes");
+#else
+_Static_assert(sizeof(sauAmdFlacVerify) == 32, "sauAmdFlacVerify is 32 bytes");
+#endif
+/* sauAmd_Flac_set_verify: sauAmd_Flac_set_md5's rules -- only while every stream stands at its start, otherwise false with
+ * "bad argument" and nothing changed; the setting outlives resets, which clear the records. sauAmd_Flac_verify: waits for the
+ * batch's stream; out[n_rows] the rows' records; false with "bad argument" when verify is off. */
+SAU_AMD_API bool sauAmd_Flac_set_verify(sauAmdFlac *e, int on);
+SAU_AMD_API bool sauAmd_Flac_verify(sauAmdFlac *e, sauAmdFlacVerify *out /* [n_rows] */);
+/* The FLAC file writers' process-wide default (atomic; initially 0): returns the previous value. Every sauAmd_render_file_flac*
+ * writer reads it once at entry. On, the writer turns its encoder's verify on and fetches the record behind the last read; with
+ * bad_blocks > 0 it returns false and sauAmd_last_error names the block and the status, the file closed as written, for
+ * inspection. Every byte of the file is the same on or off. A backend whose encoder has no verify mode then gives "bad
+ * argument" before any file is created. */
+SAU_AMD_API int sauAmd_set_flac_file_verify(int on);
 /* A float-fed encoder: sauAmd_Batch_create_flac_lpc's rules, and bits 16 or 24; this entry point refuses 24 with
  * max_lpc_order > 0 as a bad argument (sauAmd_Batch_create_flac_lpc24 takes it). */
 SAU_AMD_API sauAmdFlac *sauAmd_Batch_create_flac_f32(sauAmdBatch *b, size_t n_rows, int channels, uint32_t block_frames, int bits,

@@ -154,6 +154,21 @@ class FlacInfo(C.Structure):
 assert C.sizeof(FlacInfo) == 32
 
 
+class FlacVerify(C.Structure):
+    """sauAmdFlacVerify: what a verifying encoder has checked of a stream since the last reset"""
+    _fields_ = [("blocks", C.c_uint64), ("bad_blocks", C.c_uint64), ("first_bad_block", C.c_uint64), ("first_status", C.c_uint32),
+                ("pad_", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "pad_"}
+
+    def __repr__(self):
+        return "FlacVerify(%r)" % (self.as_dict(),)
+
+
+assert C.sizeof(FlacVerify) == 32
+
+
 class Dither(C.Structure):
     """sauAmdDither (include/saugns_amd.h, section "Dither and noise shaping"): a quantiser's spec -- the dither's seed,
     ``dither`` 0 (none) or 1 (TPDF), and ``taps`` error-feedback coefficients, coef[0] on the most recent error."""
@@ -387,6 +402,16 @@ def _declare(L):
         L.sauAmd_flac_md5.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
         L.sauAmd_set_flac_file_md5.restype = C.c_int
         L.sauAmd_set_flac_file_md5.argtypes = [C.c_int]
+    if hasattr(L, "sauAmd_flac_decode_block"):  # the decoder and the verify mode (SAU_AMD_LIB may name an older build)
+        L.sauAmd_flac_decode_block.restype = C.c_size_t
+        L.sauAmd_flac_decode_block.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.c_int, C.c_uint32, C.c_void_p, C.c_size_t,
+                                               C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
+        L.sauAmd_Flac_set_verify.restype = C.c_bool
+        L.sauAmd_Flac_set_verify.argtypes = [C.c_void_p, C.c_int]
+        L.sauAmd_Flac_verify.restype = C.c_bool
+        L.sauAmd_Flac_verify.argtypes = [C.c_void_p, C.POINTER(FlacVerify)]
+        L.sauAmd_set_flac_file_verify.restype = C.c_int
+        L.sauAmd_set_flac_file_verify.argtypes = [C.c_int]
     if hasattr(L, "sauAmd_Batch_create_flac_lpc24"):  # LPC at 24 bits (SAU_AMD_LIB may name an older build)
         L.sauAmd_flac_encode_block_lpc24.restype = C.c_size_t
         L.sauAmd_flac_encode_block_lpc24.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
@@ -813,6 +838,37 @@ def set_flac_file_md5(on):
     """sauAmd_set_flac_file_md5: the process-wide switch that makes the FLAC file writers fill STREAMINFO's MD5 field
     -> the previous value"""
     return int(lib().sauAmd_set_flac_file_md5(1 if on else 0))
+
+
+def set_flac_file_verify(on):
+    """sauAmd_set_flac_file_verify: the process-wide switch that makes the FLAC file writers decode every frame they made on the
+    device and hold it against the samples (include/saugns_amd.h, FLAC, "Verify") -> the previous value"""
+    return int(lib().sauAmd_set_flac_file_verify(1 if on else 0))
+
+
+# sauAmd_flac_decode_block's statuses (SAU_AMD_FLAC_DEC_*)
+FLAC_DEC_OK, FLAC_DEC_LENGTH, FLAC_DEC_SYNC, FLAC_DEC_HEADER, FLAC_DEC_NUMBER, FLAC_DEC_CRC8, FLAC_DEC_SUBFRAME, FLAC_DEC_RESIDUAL, \
+    FLAC_DEC_PADDING, FLAC_DEC_CRC16, FLAC_DEC_RANGE, FLAC_DEC_MISMATCH = range(12)
+FLAC_DEC_BAD_ARGUMENT = 255
+FLAC_DEC_NAMES = ("OK", "LENGTH", "SYNC", "HEADER", "NUMBER", "CRC8", "SUBFRAME", "RESIDUAL", "PADDING", "CRC16", "RANGE", "MISMATCH")
+
+
+def flac_decode_block(data, channels, block_frames, bits, frame_number, cap_frames=None):
+    """sauAmd_flac_decode_block: the host's restatement of the decoder on the one frame that begins at ``data`` (bytes; the library
+    is handed a buffer of exactly that length) -> (status, the frame's size in bytes, int32 samples [n, channels]); size 0 and no
+    samples unless the status is FLAC_DEC_OK. ``cap_frames`` (tests): the room to state instead of block_frames'."""
+    data = bytes(data)
+    buf = (C.c_uint8 * max(len(data), 1)).from_buffer_copy(data if data else b"\0")
+    B = int(block_frames) if int(block_frames) in (256, 512, 1024, 2048, 4096) else 4096
+    cap = B if cap_frames is None else int(cap_frames)
+    out = np.zeros((max(cap, 1), max(int(channels), 1)), np.int32)
+    n, st = C.c_uint32(0), C.c_int(-1)
+    size = lib().sauAmd_flac_decode_block(buf if data else None, len(data), int(channels), int(block_frames), int(bits), int(frame_number),
+                                          out.ctypes.data if cap else None, cap, C.byref(n), C.byref(st))
+    if st.value != FLAC_DEC_OK:
+        assert size == 0 and n.value == 0, "a refused frame with a size or a length"
+        return st.value, 0, None
+    return st.value, int(size), out[:n.value].copy()
 
 
 def flac_quantize(x, gain=1.0, bits=24):
@@ -1598,6 +1654,19 @@ class Flac:
         """sauAmd_Flac_set_md5: keep the MD5 of every row's unencoded samples; only while every stream stands at its start"""
         if not _used(self._L).sauAmd_Flac_set_md5(self._e, 1 if on else 0):
             raise RuntimeError("sauAmd_Flac_set_md5 failed: " + last_error(self._L))
+
+    def set_verify(self, on=True):
+        """sauAmd_Flac_set_verify: decode every frame behind the kernel that wrote it and hold it against the samples; only while
+        every stream stands at its start"""
+        if not _used(self._L).sauAmd_Flac_set_verify(self._e, 1 if on else 0):
+            raise RuntimeError("sauAmd_Flac_set_verify failed: " + last_error(self._L))
+
+    def verify(self):
+        """sauAmd_Flac_verify -> the rows' records as dicts (blocks, bad_blocks, first_bad_block, first_status); with verify on"""
+        out = (FlacVerify * self.n_rows)()
+        if not _used(self._L).sauAmd_Flac_verify(self._e, out):
+            raise RuntimeError("sauAmd_Flac_verify failed: " + last_error(self._L))
+        return [v.as_dict() for v in out]
 
     def md5(self):
         """sauAmd_Flac_md5 -> the rows' digests as a list of 16-byte objects; behind a finish, with MD5 on"""

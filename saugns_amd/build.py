@@ -8,9 +8,9 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libsaugns_amd.so")
 SOURCES = ["capi.cpp", "engine.cpp", "plan.cpp", "tables.cpp", "program_io.cpp", "sndout.cpp", "bank_builder.cpp",
            "hip_backend.hip"]
-HEADERS = ["engine.h", "hip_backend.h", "capi_internal.h", "sau_flac.h", "sau_md5.h", "sau_dither.h", "sau_dev_math.h", "sau_dev_ops.h", "launch_plan.h", "mix_overlap.h",
+HEADERS = ["engine.h", "hip_backend.h", "capi_internal.h", "sau_flac.h", "sau_flac_dec.h", "sau_md5.h", "sau_dither.h", "sau_dev_math.h", "sau_dev_ops.h", "launch_plan.h", "mix_overlap.h",
            "k_common.h", "k_wave_scan.h", "k_block_loop.h", "k_fast_types.h", "k_analyze.h", "k_decode.h", "k_fast_voice.h", "k_fast_group.h", "k_fast_group_lm.h",
-           "k_chain.h", "k_finish.h", "k_levels.h", "k_decimate.h", "k_loudness.h", "k_limiter.h", "k_spectrum.h", "k_flac.h", "k_md5.h", "k_dither.h",  # parts of hip_backend.hip
+           "k_chain.h", "k_finish.h", "k_levels.h", "k_decimate.h", "k_loudness.h", "k_limiter.h", "k_spectrum.h", "k_flac.h", "k_flac_dec.h", "k_md5.h", "k_dither.h",  # parts of hip_backend.hip
            "sau_dev_types.h", "../../include/sau_abi.h", "../../include/saugns_amd.h"]
 # -ffp-contract=off: the arithmetic contract forbids FMA contraction
 FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-std=c++17",

@@ -3,6 +3,7 @@
 #include "engine.h"
 #include "hip_backend.h"
 #include "capi_internal.h"
+#include "sau_flac_dec.h"
 #include <stdio.h>
 #include <string.h>
 #include <stddef.h>
@@ -822,6 +823,43 @@ extern "C" size_t sauAmd_flac_header_md5(uint32_t srate, int channels, uint32_t 
 }
 extern "C" bool sauAmd_flac_md5(const int32_t *x, size_t n_samples, int bits, uint8_t out[16]) {
 	return sauengine::flac_md5(x, n_samples, bits, out);
+}
+
+/* ---- the decoder and the verify mode (include/saugns_amd.h, FLAC, "Verify"; sauAmd_set_flac_file_verify stands with the
+ * writers) ---- */
+static_assert(sizeof(sauAmdFlacVerify) == sizeof(sauengine::FlacVerify), "sauAmdFlacVerify is sauengine::FlacVerify");
+static_assert(SAU_AMD_FLAC_DEC_MISMATCH == (int)sauflac::FLAC_DEC_MISMATCH && SAU_AMD_FLAC_DEC_BAD_ARGUMENT == (int)sauflac::FLAC_DEC_BAD_ARGUMENT,
+		"the public statuses are sauflac::FlacDecStatus");
+extern "C" size_t sauAmd_flac_decode_block(const uint8_t *data, size_t len, int channels, uint32_t block_frames, int bits, uint32_t frame_number,
+		int32_t *out, size_t cap_frames, uint32_t *n_out, int *status_out) {
+	try {
+		return sauengine::flac_decode_block(data, len, channels, block_frames, bits, frame_number, out, cap_frames, n_out, status_out);
+	} catch (const std::exception &) { /* (nothing C++ crosses the C ABI) */
+		if (status_out) *status_out = SAU_AMD_FLAC_DEC_BAD_ARGUMENT;
+		return 0;
+	}
+}
+extern "C" bool sauAmd_Flac_set_verify(sauAmdFlac *e, int on) {
+	std::string err;
+	try {
+		if (!e) err = "bad argument";
+		else if (e->enc->set_verify(on != 0, err)) return true;
+	} catch (const std::exception &ex) {
+		err = std::string("internal error: ") + ex.what();
+	}
+	report("flac", err);
+	return false;
+}
+extern "C" bool sauAmd_Flac_verify(sauAmdFlac *e, sauAmdFlacVerify *out) {
+	std::string err;
+	try {
+		if (!e || !out) err = "bad argument";
+		else if (e->enc->verify((sauengine::FlacVerify *)out, err)) return true;
+	} catch (const std::exception &ex) {
+		err = std::string("internal error: ") + ex.what();
+	}
+	report("flac", err);
+	return false;
 }
 
 /* ---- the quantiser (include/saugns_amd.h, section "Dither and noise shaping") ---- */

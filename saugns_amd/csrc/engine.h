@@ -145,6 +145,18 @@ size_t flac_encode_block_lpc24(const int32_t *x, uint32_t n, int channels, uint3
 size_t flac_header_md5(uint32_t srate, int channels, uint32_t block_frames, int bits, const FlacInfo *info, const uint8_t md5[16],
 		uint8_t *out, size_t cap);
 bool flac_md5(const int32_t *x, size_t n, int bits, uint8_t out[16]);
+/* The decoder (the header's "Verify"; the arithmetic is sau_flac_dec.h's, which flac_decode_kernel uses too): the one frame that
+ * begins at data, of the encoders' own making -> its size with *status_out == FLAC_DEC_OK, *n_out its frames and
+ * out[n * channels] its samples; otherwise 0 with the status (sauflac::FlacDecStatus; FLAC_DEC_BAD_ARGUMENT for a bad argument
+ * or cap_frames < n). data[len] and beyond are never read. */
+size_t flac_decode_block(const uint8_t *data, size_t len, int channels, uint32_t block_frames, int bits, uint32_t frame_number, int32_t *out,
+		size_t cap_frames, uint32_t *n_out, int *status_out);
+/* What a verifying encoder keeps per row (FlacEncoder::verify): sauAmdFlacVerify. */
+struct FlacVerify {
+	uint64_t blocks, bad_blocks, first_bad_block;
+	uint32_t first_status, pad_;
+};
+static_assert(sizeof(FlacVerify) == 32, "FlacVerify is sauAmdFlacVerify");
 inline bool flac_params_ok(int channels, uint32_t block_frames) {
 	return (channels == 1 || channels == 2) && sauflac::flac_block_frames(block_frames) != 0;
 }
@@ -173,6 +185,10 @@ public:
 	 * bad argument and nothing written. */
 	virtual bool set_md5(bool on, std::string &err) { (void)on; err = "bad argument: this backend's FLAC encoder has no MD5"; return false; }
 	virtual bool md5(uint8_t *out, std::string &err) { (void)out; err = "bad argument: this backend's FLAC encoder has no MD5"; return false; }
+	/* the verify mode (the header's "Verify"), off until asked for. set_verify: set_md5's rules. verify: waits for the stream;
+	 * out[n_rows] the rows' records since the last reset; false with a bad argument when verify is off. */
+	virtual bool set_verify(bool on, std::string &err) { (void)on; err = "bad argument: this backend's FLAC encoder has no verify mode"; return false; }
+	virtual bool verify(FlacVerify *out, std::string &err) { (void)out; err = "bad argument: this backend's FLAC encoder has no verify mode"; return false; }
 };
 
 /* The 16-bit quantiser on the host (tables.cpp; include/saugns_amd.h, section "Dither and noise shaping"; the arithmetic is

@@ -17,6 +17,8 @@
  *   k_flac.h        flac_analyze_kernel, flac_scan_kernel, flac_write_kernel, flac_carry_kernel (FLAC frames of fed rows, built
  *                   for int16 and for int32 samples: FlacS16, FlacS32; the <.., true> builds of the first and the third
  *                   hold the LPC mode), flac_quant_kernel (a float-fed encoder's rows)
+ *   k_flac_dec.h    flac_decode_kernel (a frame of the encoder's back into samples, stored or held against the originals: the
+ *                   verify mode; opt-in)
  *   k_md5.h         flac_md5_kernel, flac_md5_wide_kernel (the MD5 of an encoder's unencoded samples, a wave per row; opt-in)
  *   k_dither.h      dither_flat_kernel, dither_shape_kernel (the 16-bit quantiser stage: TPDF dither, error-feedback noise shaping)
  *   launch_plan.h   (plain C++, no HIP) the tuning switches and every decision about a segment's launches: rows per pass, LDS
@@ -51,6 +53,7 @@
 #include "launch_plan.h"
 #include "sau_dev_ops.h"
 #include "sau_md5.h"
+#include "sau_flac_dec.h"
 #include <float.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -89,6 +92,7 @@ using namespace sauplan;
 #include "k_spectrum.h"
 #include "k_flac.h"
 #include "k_md5.h"
+#include "k_flac_dec.h"
 #include "k_dither.h"
 static_assert(MISC_BYTES == sizeof(Misc), "launch_plan.h plans the block loop's LDS with this size");
 
@@ -2240,6 +2244,7 @@ public:
 			if (!be_->join_mixer("flac_clear", err)) return false;
 			HIP_OK(hipMemsetAsync(stats_.p, 0, n_ * sizeof(FlacStats), be_->stream_));
 			if (md5_on_ && !md5_reset(err)) return false;
+			if (verify_on_ && !verify_reset(err)) return false;
 			std::fill(pos_.begin(), pos_.end(), 0);
 			std::fill(blocks_.begin(), blocks_.end(), 0);
 			closed_ = false;
@@ -2264,6 +2269,34 @@ public:
 			if (!be_->join_mixer("flac_md5", err)) return false;
 			HIP_OK(hipStreamSynchronize(be_->stream_));
 			HIP_OK(hipMemcpy(out, md5_digest_.p, 16 * n_, hipMemcpyDeviceToHost));
+			return true;
+		}
+		/* the verify mode (k_flac_dec.h): a record of three words per row */
+		bool set_verify(bool on, std::string &err) override {
+			be_->use_device();
+			if (closed_) { err = "bad argument: the streams are not at their start (read with reset first)"; return false; }
+			for (size_t r = 0; r < n_; ++r)
+				if (pos_[r]) { err = "bad argument: the streams are not at their start (read with reset first)"; return false; }
+			if (on) {
+				if (!verify_rec_.ensure(n_, err)) return false;
+				if (!be_->join_mixer("flac_set_verify", err) || !verify_reset(err)) return false;
+			}
+			verify_on_ = on;
+			return true;
+		}
+		bool verify(sauengine::FlacVerify *out, std::string &err) override {
+			be_->use_device();
+			if (!verify_on_ || !out) { err = !out ? "bad argument" : "bad argument: verify is off (set_verify)"; return false; }
+			if (!be_->join_mixer("flac_verify", err)) return false;
+			HIP_OK(hipStreamSynchronize(be_->stream_));
+			std::vector<FlacVerifyRec> rec(n_);
+			HIP_OK(hipMemcpy(rec.data(), verify_rec_.p, n_ * sizeof(FlacVerifyRec), hipMemcpyDeviceToHost));
+			for (size_t r = 0; r < n_; ++r) {
+				const bool bad = rec[r].bad_blocks != 0;
+				out[r].blocks = rec[r].blocks; out[r].bad_blocks = rec[r].bad_blocks;
+				out[r].first_bad_block = bad ? rec[r].first >> 8 : 0;
+				out[r].first_status = bad ? (uint32_t)(rec[r].first & 0xffu) : 0; out[r].pad_ = 0;
+			}
 			return true;
 		}
 		bool feed(const void *rows, size_t pitch, const uint32_t *frames, bool finish, std::string &err) override {
@@ -2359,6 +2392,13 @@ public:
 					hipLaunchKernelGGL(write, dim3(plan.jobs), dim3(FLAC_THREADS), plan.write_lds, st, fp);
 					HIP_OK(hipGetLastError());
 				}
+				if (verify_on_ && plan.jobs) { /* behind the writer, ahead of the carry: the rows and the pending frames are the analysis' */
+					FlacDecArgs da;
+					memset((void *)&da, 0, sizeof da);
+					da.rec = verify_rec_.p;
+					hipLaunchKernelGGL((flac_decode_kernel<W, true>), dim3(plan.jobs), dim3(FLAC_THREADS), plan_flac_decode_lds(B_, ch_, bits_), st, fp, da);
+					HIP_OK(hipGetLastError());
+				}
 				if (md5_now) {
 					hipLaunchKernelGGL(md5_kernel, dim3(plan.rows), dim3(64), 0, st, mp);
 					HIP_OK(hipGetLastError());
@@ -2431,6 +2471,12 @@ public:
 			for (size_t r = 0; r < n_; ++r) saumd5::md5_init(&s[4 * r]);
 			return be_->send(md5_state_.p, s.data(), s.size() * sizeof(uint32_t), err);
 		}
+		/* every row's record back to nothing checked, on the stream */
+		bool verify_reset(std::string &err) {
+			const FlacVerifyRec none = {0, 0, ~0ull};
+			const std::vector<FlacVerifyRec> rec(n_, none);
+			return be_->send(verify_rec_.p, rec.data(), n_ * sizeof(FlacVerifyRec), err);
+		}
 		struct Chunk { /* one feed's output */
 			DevBuf<uint8_t> out;
 			DevBuf<uint32_t> row_bytes;  /* [rows]: flac_scan_kernel's word on them */
@@ -2455,6 +2501,8 @@ public:
 		bool md5_on_ = false;                /* set_md5: flac_md5_kernel runs behind the write kernel */
 		DevBuf<uint32_t> md5_state_, md5_digest_; /* [rows][4] each */
 		DevBuf<FlacMd5Row> md5_desc_;
+		bool verify_on_ = false;             /* set_verify: flac_decode_kernel<W, true> runs behind the write kernel */
+		DevBuf<FlacVerifyRec> verify_rec_;   /* [rows] */
 		int cur_ = 0;
 	};
 	sauengine::FlacEncoder *create_flac(size_t n_rows, uint32_t channels, uint32_t block_frames, std::string &err) override {

@@ -1105,6 +1105,17 @@ inline FlacPlan plan_flac(uint32_t block_frames, uint32_t channels, size_t n_row
 	return p;
 }
 
+/* flac_decode_kernel's dynamic LDS (k_flac_dec.h; grid (jobs) x FLAC_THREADS, the jobs of the feed's plan): a word per sample of
+ * the block, then the frame's bytes at their bound, rounded up to a word -- 57364 bytes at 24 bits, B = 4096, stereo. Beside it
+ * the kernel has FLAC_DECODE_STATIC_LDS bytes at most of its own. 0: sizes that are not allowed. */
+constexpr size_t FLAC_DECODE_STATIC_LDS = 256;
+inline size_t plan_flac_decode_lds(uint32_t block_frames, uint32_t channels, unsigned bits) {
+	const uint32_t B = sauflac::flac_block_frames(block_frames);
+	if (!B || (channels != 1 && channels != 2) || !sauflac::flac_bits_ok((int)bits)) return 0;
+	const size_t lds = (size_t)B * channels * sizeof(int32_t) + (((size_t)sauflac::flac_frame_bound(B, channels, bits) + 3) & ~(size_t)3);
+	return lds + FLAC_DECODE_STATIC_LDS <= FLAC_LDS_MAX ? lds : 0;
+}
+
 /* ---- the quantiser (k_dither.h; include/saugns_amd.h, section "Dither and noise shaping") ----
  * Without taps a sample depends on its position only: dither_flat_kernel has flac_quant_kernel's geometry, four samples per
  * thread. With taps a chain -- one channel of one row -- is a recurrence that cannot be cut in time: dither_shape_kernel gives a

@@ -509,6 +509,20 @@ bool measure_spectrum(const sauProgram *prg, uint32_t srate, int factor, int cha
  * --, fetches the digest behind the last read and puts it into the header it rewrites at the end. Off: nothing differs. */
 static std::atomic<int> g_flac_file_md5{0};
 static bool flac_file_md5() { return g_flac_file_md5.load(std::memory_order_relaxed) != 0; }
+/* ... and their verify switch ("Verify"), its exact twin: on, the writer turns its encoder's verify mode on and fetches the
+ * record behind the last read; a bad block makes the writer fail once the file is complete and closed. */
+static std::atomic<int> g_flac_file_verify{0};
+static bool flac_file_verify() { return g_flac_file_verify.load(std::memory_order_relaxed) != 0; }
+/* false: the record could not be fetched (err); bad: what to say of the first bad block, empty when there is none */
+static bool flac_file_verified(sauengine::FlacEncoder *enc, std::string &bad, std::string &err) {
+	static const char *const names[] = {"OK", "LENGTH", "SYNC", "HEADER", "NUMBER", "CRC8", "SUBFRAME", "RESIDUAL", "PADDING", "CRC16", "RANGE", "MISMATCH"};
+	sauengine::FlacVerify v{0, 0, 0, 0, 0};
+	if (!enc->verify(&v, err)) return false;
+	if (v.bad_blocks)
+		bad = "FLAC verify failed: " + std::to_string(v.bad_blocks) + " of " + std::to_string(v.blocks) + " blocks bad, the first block " +
+			std::to_string(v.first_bad_block) + " with status " + std::to_string(v.first_status) + " (" + (v.first_status < 12 ? names[v.first_status] : "?") + ")";
+	return true;
+}
 
 /* The FLAC writer: render_file_over's int16 runs (no byte swap) on the same lattice, each run's device row fed to an encoder
  * of one stream where that writer fetches it, the last feed a finish. A read brings the run's frames into a page-locked slot;
@@ -526,8 +540,9 @@ bool write_flac(const sauProgram *prg, uint32_t srate, const char *path, int cha
 	/* a backend without an encoder says so here, before there is a file */
 	sauengine::FlacEncoder *enc = backend->create_flac_lpc(1, (uint32_t)channels, B, max_lpc_order, err);
 	if (!enc) { delete engine; return false; }
-	const bool md5 = flac_file_md5();
-	if (md5 && !enc->set_md5(true, err)) { delete enc; delete engine; return false; }
+	const bool md5 = flac_file_md5(), verify = flac_file_verify();
+	std::string bad; /* (verify: the first bad block, if there is one) */
+	if ((md5 && !enc->set_md5(true, err)) || (verify && !enc->set_verify(true, err))) { delete enc; delete engine; return false; }
 	/* what a run can come to: the blocks it completes, with what was pending, and a last short one, each at its bound */
 	const size_t slot_bytes = (chunk / B + 2) * (size_t)sauflac::flac_frame_bound(B, (uint32_t)channels, 16);
 	uint8_t *host[2] = {(uint8_t *)backend->alloc_host(slot_bytes), (uint8_t *)backend->alloc_host(slot_bytes)};
@@ -572,6 +587,7 @@ bool write_flac(const sauProgram *prg, uint32_t srate, const char *path, int cha
 		pending[k] = 0;
 	}
 	if (ok && md5) ok = enc->md5(digest, err); /* (the last feed was the finish, and nothing has reset the stream) */
+	if (ok && verify) ok = flac_file_verified(enc, bad, err);
 	delete enc;
 	{ std::string e2; (void)backend->sync(e2); }
 	if (f) {
@@ -580,6 +596,7 @@ bool write_flac(const sauProgram *prg, uint32_t srate, const char *path, int cha
 		const int ferr = ferror(f);
 		if ((fclose(f) != 0 || ferr) && ok) { err = "write failed"; ok = false; }
 	}
+	if (ok && !bad.empty()) { err = bad; ok = false; } /* (the file is complete and closed as written, for inspection) */
 	if (frames_out) *frames_out = info.frames;
 	if (ok && info_out) *info_out = info;
 	backend->free_host(host[0]);
@@ -605,8 +622,9 @@ bool write_flac_scaled(const sauProgram *prg, uint32_t srate, const char *path, 
 	sauengine::FlacEncoder *enc = lpc24 ? backend->create_flac_lpc24(1, (uint32_t)channels, B, max_lpc_order, err) :
 			backend->create_flac_f32(1, (uint32_t)channels, B, bits, max_lpc_order, err);
 	if (!enc) { delete engine; return false; }
-	const bool md5 = flac_file_md5();
-	if (md5 && !enc->set_md5(true, err)) { delete enc; delete engine; return false; }
+	const bool md5 = flac_file_md5(), verify = flac_file_verify();
+	std::string bad; /* (verify: the first bad block, if there is one) */
+	if ((md5 && !enc->set_md5(true, err)) || (verify && !enc->set_verify(true, err))) { delete enc; delete engine; return false; }
 	const size_t slot_bytes = (chunk / B + 2) * (size_t)sauflac::flac_frame_bound(B, (uint32_t)channels, (unsigned)bits);
 	uint8_t *host[2] = {(uint8_t *)backend->alloc_host(slot_bytes), (uint8_t *)backend->alloc_host(slot_bytes)};
 	FILE *f = nullptr;
@@ -651,6 +669,7 @@ bool write_flac_scaled(const sauProgram *prg, uint32_t srate, const char *path, 
 		pending[k] = 0;
 	}
 	if (ok && md5) ok = enc->md5(digest, err); /* (the last feed was the finish, and nothing has reset the stream) */
+	if (ok && verify) ok = flac_file_verified(enc, bad, err);
 	delete enc;
 	{ std::string e2; (void)backend->sync(e2); }
 	if (f) {
@@ -659,6 +678,7 @@ bool write_flac_scaled(const sauProgram *prg, uint32_t srate, const char *path, 
 		const int ferr = ferror(f);
 		if ((fclose(f) != 0 || ferr) && ok) { err = "write failed"; ok = false; }
 	}
+	if (ok && !bad.empty()) { err = bad; ok = false; } /* (the file is complete and closed as written, for inspection) */
 	if (frames_out) *frames_out = info.frames;
 	if (ok && info_out) *info_out = info;
 	backend->free_host(host[0]);
@@ -686,8 +706,9 @@ bool write_flac_limited(const sauProgram *prg, uint32_t srate, const char *path,
 	sauengine::FlacEncoder *enc = lpc24 ? backend->create_flac_lpc24(1, (uint32_t)channels, B, max_lpc_order, err) :
 			backend->create_flac_f32(1, (uint32_t)channels, B, bits, max_lpc_order, err);
 	if (!enc) { delete engine; return false; }
-	const bool md5 = flac_file_md5();
-	if (md5 && !enc->set_md5(true, err)) { delete enc; delete engine; return false; }
+	const bool md5 = flac_file_md5(), verify = flac_file_verify();
+	std::string bad; /* (verify: the first bad block, if there is one) */
+	if ((md5 && !enc->set_md5(true, err)) || (verify && !enc->set_verify(true, err))) { delete enc; delete engine; return false; }
 	const size_t slot_frames = chunk > D ? chunk : D;
 	const size_t slot_bytes = (slot_frames / B + 2) * (size_t)sauflac::flac_frame_bound(B, (uint32_t)channels, (unsigned)bits);
 	uint8_t *host[2] = {(uint8_t *)backend->alloc_host(slot_bytes), (uint8_t *)backend->alloc_host(slot_bytes)};
@@ -741,6 +762,7 @@ bool write_flac_limited(const sauProgram *prg, uint32_t srate, const char *path,
 	}
 	if (ok && stats_out) ok = engine->limiter_stats(stats_out, false, err);
 	if (ok && md5) ok = enc->md5(digest, err); /* (the last feed was the finish, and nothing has reset the stream) */
+	if (ok && verify) ok = flac_file_verified(enc, bad, err);
 	delete enc;
 	{ std::string e2; (void)backend->sync(e2); }
 	if (f) {
@@ -749,6 +771,7 @@ bool write_flac_limited(const sauProgram *prg, uint32_t srate, const char *path,
 		const int ferr = ferror(f);
 		if ((fclose(f) != 0 || ferr) && ok) { err = "write failed"; ok = false; }
 	}
+	if (ok && !bad.empty()) { err = bad; ok = false; } /* (the file is complete and closed as written, for inspection) */
 	if (frames_out) *frames_out = info.frames;
 	if (ok && info_out) *info_out = info;
 	backend->free_host(host[0]);
@@ -850,8 +873,9 @@ bool write_flac_dithered(const sauProgram *prg, uint32_t srate, const char *path
 	if (!q) { delete engine; return false; }
 	sauengine::FlacEncoder *enc = backend->create_flac_lpc(1, (uint32_t)channels, B, max_lpc_order, err);
 	if (!enc) { delete q; delete engine; return false; }
-	const bool md5 = flac_file_md5();
-	if (md5 && !enc->set_md5(true, err)) { delete enc; delete q; delete engine; return false; }
+	const bool md5 = flac_file_md5(), verify = flac_file_verify();
+	std::string bad; /* (verify: the first bad block, if there is one) */
+	if ((md5 && !enc->set_md5(true, err)) || (verify && !enc->set_verify(true, err))) { delete enc; delete q; delete engine; return false; }
 	const size_t slot_bytes = (chunk / B + 2) * (size_t)sauflac::flac_frame_bound(B, (uint32_t)channels, 16);
 	uint8_t *host[2] = {(uint8_t *)backend->alloc_host(slot_bytes), (uint8_t *)backend->alloc_host(slot_bytes)};
 	FILE *f = nullptr;
@@ -901,6 +925,7 @@ bool write_flac_dithered(const sauProgram *prg, uint32_t srate, const char *path
 	sauengine::DitherStats st{0, {0, 0}};
 	if (ok) ok = q->stats(&st, false, err);
 	if (ok && md5) ok = enc->md5(digest, err); /* (the last feed was the finish, and nothing has reset the stream) */
+	if (ok && verify) ok = flac_file_verified(enc, bad, err);
 	delete enc;
 	delete q;
 	{ std::string e2; (void)backend->sync(e2); }
@@ -910,6 +935,7 @@ bool write_flac_dithered(const sauProgram *prg, uint32_t srate, const char *path
 		const int ferr = ferror(f);
 		if ((fclose(f) != 0 || ferr) && ok) { err = "write failed"; ok = false; }
 	}
+	if (ok && !bad.empty()) { err = bad; ok = false; } /* (the file is complete and closed as written, for inspection) */
 	if (frames_out) *frames_out = info.frames;
 	if (ok && info_out) *info_out = info;
 	if (ok && stats_out) *stats_out = st;
@@ -933,6 +959,7 @@ bool flac_f32_params_ok(int channels, uint32_t block_frames, int bits, uint32_t 
 } /* namespace */
 
 extern "C" int sauAmd_set_flac_file_md5(int on) { return g_flac_file_md5.exchange(on ? 1 : 0, std::memory_order_relaxed); }
+extern "C" int sauAmd_set_flac_file_verify(int on) { return g_flac_file_verify.exchange(on ? 1 : 0, std::memory_order_relaxed); }
 
 /* render_file_flac_f32's body, and with lpc24 render_file_flac_lpc24's: 24 bits, any order up to 8 */
 static bool flac_f32_file(const sauProgram *prg, uint32_t srate, const char *path, int channels, uint32_t block_frames,

@@ -14,6 +14,7 @@
  */
 #include "engine.h"
 #include "sau_md5.h"
+#include "sau_flac_dec.h"
 #include <dlfcn.h>
 #include <float.h>
 #include <math.h>
@@ -649,6 +650,28 @@ size_t flac_encode_block_lpc24(const int32_t *x, uint32_t n, int channels, uint3
 	for (size_t i = 0; i < cnt; ++i)
 		if (x[i] < FLAC_S24_MIN || x[i] > FLAC_S24_MAX) return 0;
 	return flac_encode_block_any(x, n, (unsigned)channels, B, frame_number, 24, max_lpc_order, out, cap, true);
+}
+
+/* ---- the decoder (include/saugns_amd.h, FLAC, "Verify"; the arithmetic is sau_flac_dec.h's, which flac_decode_kernel uses
+ * too): the one frame that begins at data ---- */
+size_t flac_decode_block(const uint8_t *data, size_t len, int channels, uint32_t block_frames, int bits, uint32_t frame_number, int32_t *out,
+		size_t cap_frames, uint32_t *n_out, int *status_out) {
+	using namespace sauflac;
+	const uint32_t B = flac_block_frames(block_frames);
+	if (n_out) *n_out = 0;
+	if (!status_out) return 0;
+	*status_out = FLAC_DEC_BAD_ARGUMENT;
+	if ((len && !data) || !B || (channels != 1 && channels != 2) || !flac_bits_ok(bits) || frame_number > FLAC_MAX_BLOCKS || !n_out ||
+	    (cap_frames && !out)) return 0;
+	std::vector<int32_t> ch((size_t)B * 2);
+	FlacDecFrame f;
+	/* (one pass: flac_decode_frame writes no frame at or behind cap_frames, and nothing is promised about out on a failure) */
+	const int st = flac_decode_frame(data, len, (uint32_t)channels, B, (unsigned)bits, frame_number, ch.data(), ch.data() + B, &f, out, cap_frames);
+	if (st == FLAC_DEC_OK && cap_frames < f.n) return 0;
+	*status_out = st;
+	if (st != FLAC_DEC_OK) return 0;
+	*n_out = f.n;
+	return f.bytes;
 }
 
 /* ---- dither and noise shaping (include/saugns_amd.h, section "Dither and noise shaping"; the arithmetic is sau_dither.h's,
